@@ -11,8 +11,9 @@ rate is measured separately and reported next to `value`, never as it):
   (HIP), ResNet-18 on the 128 crops (fp32 MFMA implicit GEMM), temporal
   Conv1d/MLP head + log-softmax + argmax (HIP) -> pa_record per (frame,
   fighter). A timed step runs `--inner-repeat` such clips back to back so that
-  the driver's 20 steps time ~0.6 s instead of 0.03 s; `ms_per_step` stays the
-  time of ONE 64-frame clip (timed region / (steps x inner_repeat)).
+  the driver's 20 steps time ~0.6 s instead of 0.03 s; `ms_per_step` is the
+  time of one such step (timed region / steps), `ms_per_clip` the time of ONE
+  64-frame clip (timed region / (steps x inner_repeat)).
 * N > 1 (or `--clip-frames F`): configs[3], ONE F = 8192-frame clip sharded
   frame-parallel over the ranks (strong scaling): each rank holds, crops and
   runs the backbone on its 8192/N frames in chunks of 64, the 27-frame feature
@@ -24,6 +25,11 @@ Prints ONE JSON line on rank 0 (contract in the task prompt) with `roofline`
 (dominant kernel family, timed with HIP events on the launch stream in a second
 pass right after the timed region) and `cpu_baseline` (the CPU oracle,
 reference-literal shape, on a bounded sample, N=1 only).
+
+`--dump-outputs DIR` writes what the last timed step returned -- the records
+decoded as Engine.decode_records does (char_id, action_id, prob, status) and
+the log-probabilities -- as DIR/<name>.npy in float32 / float64, so that two
+builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -153,6 +159,8 @@ def compact_line(result):
     cfg = result.get("config", {})
     out = {k: result.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                       "vs_baseline", "dtype", "data")}
+    if "ms_per_clip" in result:
+        out["ms_per_clip"] = result["ms_per_clip"]
     out["metric"] = out["metric"].split(" (")[0] if out.get("metric") else None
     out["config"] = {"workload": (cfg.get("workload") or "").split(", 2 fighters")[0], "parallelism": cfg.get("parallelism"),
                      "lanes": cfg.get("lanes"), "ingest": "raw BGR frames resident in HBM"}
@@ -214,6 +222,33 @@ def emit(result):
             pass
     print(full, file=sys.stderr, flush=True)
     print(compact_line(result), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def caller_outputs(rec, lp):
+    """The timed path's result as its caller reads it: the records through Engine.decode_records and the log-probabilities,
+    every array float32 (prob, logp) or float64 (the integer fields, exact)."""
+    out = {k: (v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in Engine.decode_records(rec).items()}
+    out["logp"] = lp.cpu().numpy()
+    return out
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy. The arrays share their first axis (frame numbers); should they pass
+    `limit_bytes` together, the same fixed, seeded sample of rows is written of each, and the row numbers as rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit_bytes:
+        keep = max(int(n * limit_bytes // (total + 8 * n)), 1)
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def emulated_fp32_side(sd, frames, boxes, n_clip, height, width, S, DELTA, device, quality):
@@ -892,7 +927,7 @@ def main():
                     help="configs[3]: ONE clip of this many frames sharded over the ranks (strong scaling); default 8192 when "
                     "--gpus > 1, off (configs[1]: a 64-frame clip per step) when --gpus 1; 0 = a --frames clip per rank (weak scaling)")
     ap.add_argument("--inner-repeat", type=int, default=20,
-                    help="configs[1]/[2] only: clips per timed step (ms_per_step stays per clip)")
+                    help="configs[1]/[2] only: clips per timed step (ms_per_clip = ms_per_step / inner_repeat)")
     ap.add_argument("--f4-windows", type=int, default=64, help="--workload rnn | resformer: windows per call")
     ap.add_argument("--workload", default="clip", choices=["clip", "mixed", "rnn", "resformer", "detect", "chain"],
                     help="clip = the headline / configs[1-3] workloads; mixed = BASELINE.json configs[4] (mixed-resolution stream, "
@@ -927,7 +962,13 @@ def main():
     ap.add_argument("--no-calibrate", action="store_true", help="(default since round 6; kept so that scripts/hw_queues.sh's command lines still parse)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "emulated_f32"],
                     help="f32 = the headline (reference arithmetic); bf16 = BASELINE.json configs[2]'s conv path, reported under its own dtype, never as the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="clip workload: write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "clip":
+        ap.error("--dump-outputs: the clip workload only")
 
     if args.workload == "mixed":
         return bench_mixed(args)
@@ -1017,6 +1058,9 @@ def main():
         dt = float(t.item())
     n_calls = args.steps * repeat       # step() calls in the timed region
     n_clips = n_calls * kb              # clips they processed
+    if args.dump_outputs and rank == 0:   # before the kernel pass below reuses the result buffers
+        names = dump_outputs(args.dump_outputs, caller_outputs(rec, lp))
+        print(f"--dump-outputs: {', '.join(names)} -> {args.dump_outputs}", file=sys.stderr, flush=True)
     # ---- kernel pass: clips again with every launch bracketed by HIP events on the launch stream
     # (pa_profile_enable). Kept out of the timed region because the event pairs serialise
     # neighbouring kernels and cost ~10 % throughput; its own wall time is reported as
@@ -1055,8 +1099,8 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(1000.0 * dt / n_clips, 4),
-            "ms_per_timed_step": round(1000.0 * dt / args.steps, 4),
+            "ms_per_step": round(1000.0 * dt / args.steps, 4),
+            "ms_per_clip": round(1000.0 * dt / n_clips, 4),
             "profiled_ms_per_step": round(1000.0 * dt_prof / prof_clips, 4) if dt_prof else None,
             "higher_is_better": True,
             "scaling": "strong" if long_clip else "weak",
@@ -1076,7 +1120,7 @@ def main():
                 "frames_per_backbone_batch": n_batch,
                 "crops_per_backbone_batch": n_batch * F,
                 "inner_repeat": repeat * kb,
-                "inner_repeat_note": "clips per timed step; ms_per_step = timed region / (steps x inner_repeat) = one clip",
+                "inner_repeat_note": "clips per timed step; ms_per_step = timed region / steps, ms_per_clip = timed region / (steps x inner_repeat)",
                 "parallelism": f"frame-parallel x{world}" if world > 1 else "single GPU",
                 "pipeline": (f"{args.lanes} lanes: independent clips alternate over {args.lanes} engines (own activation buffers, own HIP stream), "
                              "so one clip's launch ramps / kernel tails run under another clip's steady state; inside a lane the crop stage "
@@ -1169,7 +1213,7 @@ def main():
                 for s in stats
             }
             result["kernels_note"] = ("HIP-event times of a separate pass on ONE stream (profiled_ms_per_step is that pass's wall time per clip); "
-                                      "the timed region runs two lanes, whose kernels overlap across clips, so the families' sum may exceed ms_per_step"
+                                      "the timed region runs two lanes, whose kernels overlap across clips, so the families' sum may exceed ms_per_clip"
                                       if lanes is not None else "HIP-event times of a separate pass on one stream")
             pre = by.get("preprocess_crops")
             if pre and pre["total_ms"] > 0:

@@ -65,7 +65,7 @@ def test_compact_line_carries_the_judged_scalars_and_fits_the_drivers_tail():
     note = "x" * 4000
     full = {
         "metric": "1080p frames/sec end-to-end (decode->labels; 'decode' here = ingest of raw BGR frames already resident in HBM)",
-        "value": 63445.1, "unit": "frames/s", "n_gpus": 1, "steps": 20, "warmup": 3, "ms_per_step": 1.0087, "higher_is_better": True,
+        "value": 63445.1, "unit": "frames/s", "n_gpus": 1, "steps": 20, "warmup": 3, "ms_per_step": 1.0087, "ms_per_clip": 0.0504, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "configs[1]: 64 x 1080x1920 BGR frames per GPU per clip, 2 fighters/frame, " + note, "parallelism": "single GPU",
                    "lanes": 2, "lane_stream_calibration": {"rates": [1.0] * 6, "note": note}},
@@ -85,6 +85,7 @@ def test_compact_line_carries_the_judged_scalars_and_fits_the_drivers_tail():
     assert len(line) < 1800 and "\n" not in line
     d = json.loads(line)
     assert d["value"] == 63445.1 and d["ms_per_step"] == 1.0087 and d["dtype"] == "f32" and d["metric"].startswith("1080p frames/sec")
+    assert d["ms_per_clip"] == 0.0504
     assert d["config"]["workload"].startswith("configs[1]: 64 x 1080x1920")
     assert d["roofline"]["frac"] == 0.5455 and d["roofline"]["algorithmic_frac"] == 1.0259 and d["roofline"]["traffic"] == 71300000
     assert d["cpu_baseline"]["cores"] == 128 and d["cpu_baseline"]["kind"] == "port"
@@ -119,3 +120,47 @@ def test_driver_scale_command_shape_on_two_ranks():
     assert d["config"]["workload"] and d["scaling"] in ("strong", "weak")
     # (rank 0 asserts that every record of the clip arrived and every log-probability is finite before it prints the line:
     # bench.py, "sanity: results are finite and complete" -- a non-finite label fails the child, not this parse)
+
+
+def test_steps_and_dump_outputs_are_checked_before_any_gpu_call(monkeypatch):
+    """--steps 0 would time nothing; --dump-outputs belongs to the clip workload: both are refused while parsing."""
+    bench = _bench()
+    import torch
+
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *_: (_ for _ in ()).throw(AssertionError("GPU touched")))
+    for argv in (["--steps", "0"], ["--workload", "detect", "--dump-outputs", "out"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2, argv
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """--dump-outputs: the decoded records and the log-probabilities as float arrays, the integer fields exact; past the size
+    limit the same seeded sample of rows of every array, and the row numbers."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    rng = np.random.default_rng(3)
+    rec = np.zeros((40, 2, 4), np.int32)
+    rec[..., 0] = rng.integers(0, 80, (40, 2))
+    rec[..., 1] = rng.integers(0, 63, (40, 2))
+    rec[..., 2] = rng.random((40, 2)).astype(np.float32).view(np.int32)
+    rec[..., 3] = rng.integers(-3, 2, (40, 2))
+    lp = rng.standard_normal((40, 2, 63)).astype(np.float32)
+    outs = bench.caller_outputs(torch.from_numpy(rec), torch.from_numpy(lp))
+    names = bench.dump_outputs(str(tmp_path / "all"), outs)
+    assert names == ["action_id", "char_id", "logp", "prob", "status"]
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["char_id"], rec[..., 0]) and np.array_equal(got["action_id"], rec[..., 1])
+    assert np.array_equal(got["status"], rec[..., 3]) and np.array_equal(got["prob"], rec[..., 2].view(np.float32))
+    assert np.array_equal(got["logp"], lp)
+    limit = 4096
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outs, limit_bytes=limit)
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "s1").iterdir()) <= limit   # (128 bytes: an .npy header)
+    rows = np.load(tmp_path / "s1" / "rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 40 and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "logp.npy"), lp[rows])

@@ -100,18 +100,40 @@ def test_detection_network_against_the_oracle(engine, dtype):
 ARBITER_CASES = ((720, 1280, 3, 5), (1080, 1920, 2, 5), (270, 480, 5, 9))   # scripts/yolov5_parity.py's
 
 
+def _arbiter_bars():
+    """tests/golden/yolov5_arbiter_bars.json: (h, w, n, seed) -> {"boxes": .., "scores": ..}, the fp32 oracle's distance to the
+    float64 run in the record the 2.5x bar was set on."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "yolov5_arbiter_bars.json")) as f:
+        cases = json.load(f)["cases"]
+    return {(c["h"], c["w"], c["n"], c["seed"]): c for c in cases}
+
+
+def test_arbiter_bars_cover_the_arbiter_cases():
+    bars = _arbiter_bars()
+    assert set(bars) == set(ARBITER_CASES)
+    assert all(0 < bars[c]["boxes"] < 2e-2 and 0 < bars[c]["scores"] < 2e-5 for c in ARBITER_CASES)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["f32", "emulated_f32"])
 def test_detection_network_against_a_float64_arbiter(dtype):
     """the box bar BOX_TOL_PX is a distance to the fp32 ORACLE, which is itself 9e-3 px from the truth.
     This ties the device to an arbiter instead -- a float64 run of the same oracle graph on the same weights: the device's rows
     may be at most 2.5x as far from it as the fp32 oracle's rows are (measured 1.2-2.2x for the exact path whose stride-1 3x3
-    convolutions run as Winograd; profiles/r06_yolov5_parity.txt names the layers). Both compute dtypes."""
+    convolutions run as Winograd; profiles/r06_yolov5_parity.txt names the layers). Both compute dtypes.
+
+    The fp32 oracle's distance is the stored one of that record (tests/golden/yolov5_arbiter_bars.json): a live fp32 CPU run
+    lands elsewhere on every host -- its convolution library, instruction set and thread count pick the summation order
+    (5.8e-3 to 1.2e-2 px for the 1080p case on one host) -- while the float64 arbiter does not. The live figure is printed."""
     import torch
 
     from oracle import yolov5 as oy
     from playaid_core_amd.yolov5 import YoloV5Detector
 
+    bars = _arbiter_bars()
     sd = synth.make_yolov5s_state_dict()
     sd64 = {k: torch.from_numpy(np.asarray(v)).double() for k, v in sd.items()}
     det = YoloV5Detector(sd, NC, NET, max_images=5, compute_dtype=dtype)
@@ -125,8 +147,10 @@ def test_detection_network_against_a_float64_arbiter(dtype):
             w32 = oy.forward(x, sd, NC).numpy().astype(np.float64)
             w64 = oy.forward(x.double(), sd64, NC).numpy()
             for name, sl in (("boxes", slice(0, 4)), ("scores", slice(4, None))):
-                dev, o32 = np.abs(got[..., sl] - w64[..., sl]).max(), np.abs(w32[..., sl] - w64[..., sl]).max()
-                print(f"{dtype} {n} x {h}x{w} {name}: device-f64 {dev:.2e}, oracle32-f64 {o32:.2e} ({dev / o32:.2f}x)")
+                dev, live = np.abs(got[..., sl] - w64[..., sl]).max(), np.abs(w32[..., sl] - w64[..., sl]).max()
+                o32 = bars[(h, w, n, seed)][name]
+                print(f"{dtype} {n} x {h}x{w} {name}: device-f64 {dev:.2e}, oracle32-f64 {o32:.2e} ({dev / o32:.2f}x; "
+                      f"this host's fp32 oracle {live:.2e})")
                 assert dev <= 2.5 * o32, (dtype, h, w, name, dev, o32)
     finally:
         det.close()
