@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 11
+#define PA_ABI_VERSION 12
 #define PA_WEIGHT_MAGIC 0x31574150 /* "PAW1" */
 #define PA_LSTM_MAGIC 0x314c4150   /* "PAL1" */
 #define PA_ENCODER_MAGIC 0x31454150 /* "PAE1" */
@@ -517,6 +517,22 @@ int pa_crop_resize_width(pa_engine* e, const uint8_t* frames, int32_t n, int32_t
  * float32[n_crops,PA_FEATURE_STRIDE] (device), the engine's resnet18 output per crop (fc included; an
  * engine built from a state dict whose fc rows 300..999 are zero yields the 300 features and zeros). */
 int pa_backbone_windows(pa_engine* e, const float* x, int32_t n_crops, float* feats, void* stream);
+
+/* Test aid (ABI 12): the intermediate activations of the backbone. Enqueues exactly what pa_backbone_windows enqueues for
+ * n_crops (1..max_crops crops, one chunk: same kernels, tiles, split-K, fused branches and knobs), stops after `stage`
+ * and copies that stage's buffer, zero border included, to `out` (device, >= the stage's bytes). Storage type: bf16
+ * bits (2 bytes) for stages 0-17 of a PA_DTYPE_BF16 engine, float32 everywhere else.
+ *   0: model input x0 [n][134][134][4]          1: stem + BatchNorm + ReLU + max-pool [n][34][34][64]
+ *   2..17: the sixteen 3x3 convolutions in engine order (layer1.0.conv1, layer1.0.conv2, layer1.1.conv1, ...,
+ *          layer4.1.conv2), each [n][hw+2][hw+2][cout]
+ *   18: avgpool float32 [n][512]                19: fc float32 [n][PA_FEATURE_STRIDE]
+ * aux (device, may be NULL): at the layerX.0.conv2 stages of layers 2-4 (7, 11, 15) the stored 1x1/2 downsample branch
+ * the convolution read as its residual, in the layout and type of `out` (no bias: the conv's bias holds both). Where the
+ * engine stores no branch at such a stage (fused into the conv's K) a non-NULL aux is refused; elsewhere it is unused.
+ * PA_ERR_INVALID_ARG for a stage out of range, n_crops outside 1..max_crops or a buffer too small. */
+#define PA_TRACE_STAGES 20
+int pa_backbone_trace(pa_engine* e, const float* x, int32_t n_crops, int32_t stage, void* out, size_t out_bytes, void* aux,
+                      size_t aux_bytes, void* stream);
 
 /* The recurrent head. blob: int32 header {PA_LSTM_MAGIC, 1, input_dim, hidden_dim, num_layers, num_actions, 0, 0},
  * then float32 per layer l: weight_ih_l [4H, in_l], weight_hh_l [4H, H], bias_ih_l [4H], bias_hh_l [4H] (torch

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PA_LIB_PATH: load a differently built library (e.g. the ablation build used by scripts/)
 LIB_PATH = os.environ.get("PA_LIB_PATH") or os.path.join(HERE, "libplayaid_hip.so")
 
-PA_ABI_VERSION = 11
+PA_ABI_VERSION = 12
 PA_DTYPE_F32 = 0
 PA_DTYPE_BF16 = 1
 PA_DTYPE_EMULATED_F32 = 2
@@ -21,6 +21,7 @@ PA_WEIGHT_MAGIC = 0x31574150
 PA_LSTM_MAGIC = 0x314C4150
 PA_ENCODER_MAGIC = 0x31454150
 PA_FEATURE_STRIDE = 1024
+PA_TRACE_STAGES = 20
 
 PA_OK = 0
 PA_ERR_INVALID_ARG = -1
@@ -155,6 +156,7 @@ SYMBOLS = [
     ("pa_stream_gate_open", C.c_int, [_P]),
     ("pa_stream_sync", C.c_int, [_P, _P]),
     ("pa_backbone_windows", C.c_int, [_P, _P, C.c_int32, _P, _P]),
+    ("pa_backbone_trace", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, C.c_size_t, _P]),
     ("pa_lstm_blob_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("pa_lstm_create", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(_P)]),
     ("pa_lstm_destroy", None, [_P]),

@@ -108,7 +108,7 @@ struct pa_engine {
     float* slab = nullptr;
     size_t slab_floats = 0;
     float* wino_tickets = nullptr;  // int32[2][WINO_TICKETS], zero between launches: split-K tickets of the Winograd kernel, one set per half batch
-    std::vector<ConvLayer> convs;  // stem + 19 convs
+    std::vector<ConvLayer> convs;  // stem + the sixteen 3x3 convs (a block-0 downsample belongs to its conv2's entry)
     ConvLayer fc;
     float* stem_wgt_bf16 = nullptr;  // bf16 path: the folded stem weights [64][224] as bf16
     float* c1 = nullptr;  // stem output [max_crops][66][66][64] (only the unfused stem + pool fallback writes it)
@@ -536,7 +536,10 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
     return PA_OK;
 }
 
-int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, float* feats_out, size_t slab_off, hipStream_t s) {
+// stop: the last trace stage to run (pa_backbone_trace: 1 = stem + pool, 2..17 = convs[1..16], 18 = avgpool); anything
+// larger runs the whole backbone
+int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, float* feats_out, size_t slab_off, hipStream_t s,
+                      int stop = PA_TRACE_STAGES) {
     int rc;
     ConvLayer stem = e->convs[0];
     stem.in = const_cast<float*>(x_in);  // x_in / feats_out are the caller's bases: crop0 is applied by run_conv
@@ -600,6 +603,7 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
         if ((rc = stem_part(crop0, ncrops, s))) return rc;
         if ((rc = pool_part(crop0, ncrops, s))) return rc;
     }
+    if (stop <= 1) return PA_OK;
     // PA_DS_SIDE=1 (A/B): the 1x1/2 branch GEMM of a block (layers 2-4: ~10 us each, a few dozen tiles) is
     // launched on the side stream BEFORE the block's stride-2 opener instead of between the opener and conv2 -- both read the block
     // input, so the small GEMM runs under the opener and conv2 only waits for an event
@@ -623,6 +627,10 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
         rc = run_conv(e, L, crop0, ncrops, slab_off, s, pn, false, use_pending);
         if (use_pending) ds_pending = false;
         if (rc) return rc;
+        if (stop <= (int)i + 1) {
+            if (ds_pending) HIPCHK(e, hipStreamWaitEvent(s, e->ev_ds_join, 0));  // no side-stream work outlives the call
+            return PA_OK;
+        }
     }
     {
         ProfScope ps(e, s, "avgpool", 0.0, ncrops * ((e->bf16 ? 2.0 : 4.0) * 16.0 * 512 + 4.0 * 512));
@@ -632,6 +640,7 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
         else
             HIPCHK(e, launch_avgpool(e->layer4_out + (size_t)crop0 * 36 * 512, e->pooled + (size_t)crop0 * 512, ncrops, s));
     }
+    if (stop <= 18) return PA_OK;
     ConvLayer fc = e->fc;
     fc.out = feats_out;
     rc = run_conv(e, fc, crop0, ncrops, slab_off, s, "igemm_fc");
@@ -642,14 +651,14 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
 // (fork/join with events): every layer is then two kernels of half the grid that drift out of
 // phase, so the launch gaps, prologues, epilogues and split-K reduces of one half are covered
 // by the steady-state MFMA loop of the other (the layers' outside-the-loop time was ~14 %).
-int run_backbone(pa_engine* e, int ncrops, const float* x_in, float* feats_out, hipStream_t s) {
-    if (!e->interleave || ncrops < 64 || !e->side) return run_backbone_part(e, 0, ncrops, x_in, feats_out, 0, s);
+int run_backbone(pa_engine* e, int ncrops, const float* x_in, float* feats_out, hipStream_t s, int stop = PA_TRACE_STAGES) {
+    if (!e->interleave || ncrops < 64 || !e->side) return run_backbone_part(e, 0, ncrops, x_in, feats_out, 0, s, stop);
     const int half = (ncrops / 2 + 7) & ~7;
     HIPCHK(e, hipEventRecord(e->ev_fork, s));
     HIPCHK(e, hipStreamWaitEvent(e->side, e->ev_fork, 0));
-    int rc = run_backbone_part(e, 0, half, x_in, feats_out, 0, s);
+    int rc = run_backbone_part(e, 0, half, x_in, feats_out, 0, s, stop);
     if (rc) return rc;
-    rc = run_backbone_part(e, half, ncrops - half, x_in, feats_out, e->slab_floats / 2, e->side);
+    rc = run_backbone_part(e, half, ncrops - half, x_in, feats_out, e->slab_floats / 2, e->side, stop);
     if (rc) return rc;
     HIPCHK(e, hipEventRecord(e->ev_join, e->side));
     HIPCHK(e, hipStreamWaitEvent(s, e->ev_join, 0));
@@ -1239,6 +1248,54 @@ int pa_backbone_windows(pa_engine* e, const float* x, int32_t n_crops, float* fe
         const int rc = run_backbone(e, n, e->x0, feats + (size_t)c0 * PA_FEATURE_STRIDE, s);
         if (rc) return rc;
     }
+    return PA_OK;
+}
+
+int pa_backbone_trace(pa_engine* e, const float* x, int32_t n_crops, int32_t stage, void* out, size_t out_bytes, void* aux,
+                      size_t aux_bytes, void* stream) {
+    if (!e || !x || !out) return fail(e, PA_ERR_INVALID_ARG, "pa_backbone_trace: bad argument");
+    if (stage < 0 || stage >= PA_TRACE_STAGES) return fail(e, PA_ERR_INVALID_ARG, "pa_backbone_trace: stage out of range");
+    if (n_crops < 1 || n_crops > e->max_crops) return fail(e, PA_ERR_INVALID_ARG, "pa_backbone_trace: n_crops outside 1..max_crops");
+    if (e->convs.size() != 17) return fail(e, PA_ERR_INVALID_ARG, "pa_backbone_trace: unexpected layer table");
+    const size_t n = (size_t)n_crops, es = e->bf16 ? 2 : 4;  // storage element of the stem and the 3x3 stack
+    const void* src;
+    const void* aux_src = nullptr;
+    size_t bytes;
+    bool has_branch = false;
+    if (stage == 0) {
+        src = e->x0;
+        bytes = n * 134 * 134 * 4 * es;
+    } else if (stage == 1) {
+        src = e->p1;
+        bytes = n * 34 * 34 * 64 * es;
+    } else if (stage <= 17) {
+        const ConvLayer& L = e->convs[stage - 1];
+        const size_t w = (size_t)L.out_hw + 2 * L.out_pad;
+        src = L.out;
+        bytes = n * w * w * L.cout * es;
+        has_branch = L.in2 != nullptr;
+        aux_src = L.ds_out;
+    } else if (stage == 18) {
+        src = e->pooled;
+        bytes = n * 512 * sizeof(float);
+    } else {
+        src = e->feats_tmp;
+        bytes = n * PA_FEATURE_STRIDE * sizeof(float);
+    }
+    if (out_bytes < bytes) return fail(e, PA_ERR_INVALID_ARG, "pa_backbone_trace: out is smaller than the stage");
+    if (has_branch && aux) {
+        if (!aux_src) return fail(e, PA_ERR_INVALID_ARG, "pa_backbone_trace: this stage stores no downsample branch");
+        if (aux_bytes < bytes) return fail(e, PA_ERR_INVALID_ARG, "pa_backbone_trace: aux is smaller than the stage");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // what pa_backbone_windows enqueues for one chunk of n_crops, cut short after `stage`
+    HIPCHK(e, launch_nchw_to_padded(x, e->x0, n_crops, e->bf16 ? 1 : 0, s));
+    if (stage > 0) {
+        const int rc = run_backbone(e, n_crops, e->x0, e->feats_tmp, s, stage);
+        if (rc) return rc;
+    }
+    HIPCHK(e, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, s));
+    if (has_branch && aux) HIPCHK(e, hipMemcpyAsync(aux, aux_src, bytes, hipMemcpyDeviceToDevice, s));
     return PA_OK;
 }
 

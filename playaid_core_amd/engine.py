@@ -196,6 +196,44 @@ class Engine:
         self._check(self._lib.pa_infer_windows(self._h, _ptr(xd), xd.shape[0], _ptr(out), self._stream()))
         return out
 
+    # stages of backbone_trace that store the 1x1/2 downsample branch: layer2/3/4.0.conv2
+    TRACE_BRANCH_STAGES = (7, 11, 15)
+
+    def trace_shape(self, n: int, stage: int) -> Tuple[int, ...]:
+        """Shape of ``backbone_trace``'s output for n crops (zero border included)."""
+        if stage == 0:
+            return (n, 134, 134, 4)
+        if stage == 1:
+            return (n, 34, 34, 64)
+        if 2 <= stage <= 17:
+            li = (stage - 2) // 4
+            hw = (32, 16, 8, 4)[li] + 2
+            return (n, hw, hw, (64, 128, 256, 512)[li])
+        if stage == 18:
+            return (n, 512)
+        if stage == 19:
+            return (n, _lib.PA_FEATURE_STRIDE)
+        raise ValueError(f"stage must be 0..{_lib.PA_TRACE_STAGES - 1}")
+
+    def backbone_trace(self, x: torch.Tensor, stage: int, aux: bool = False):
+        """Test aid (``pa_backbone_trace``): run the backbone of ``pa_backbone_windows`` on x float32[n,3,128,128]
+        up to ``stage`` and return that stage's buffer as stored -- bfloat16 for stages 0-17 of a bf16 engine,
+        float32 otherwise. ``aux=True`` (stages 7, 11, 15 only) returns ``(out, branch)`` with the stored 1x1/2
+        downsample branch the stage's convolution added as its residual."""
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, 128, 128):
+            raise ValueError(f"expected [n,3,128,128], got {tuple(x.shape)}")
+        if aux and stage not in self.TRACE_BRANCH_STAGES:
+            raise ValueError(f"aux exists at stages {self.TRACE_BRANCH_STAGES} only")
+        xd = self._dev(x, torch.float32)
+        n = xd.shape[0]
+        dt = torch.bfloat16 if self.compute_dtype == "bf16" and stage <= 17 else torch.float32
+        out = torch.empty(self.trace_shape(n, stage), dtype=dt, device=self.device)
+        br = torch.empty_like(out) if aux else None
+        nbytes = out.numel() * out.element_size()
+        self._check(self._lib.pa_backbone_trace(self._h, _ptr(xd), n, stage, _ptr(out), nbytes, _ptr(br),
+                                                nbytes if aux else 0, self._stream()))
+        return (out, br) if aux else out
+
     # -- f4: damage HUD crops -------------------------------------------------
     def crop_resize_width(self, frames, rects, out_w: int = 256):
         """``YoloCrop.crop_img`` + ``imutils.resize(width=out_w)`` (``ai_runner.py:114,556-571``) for up to four pixel
