@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 12
+#define PA_ABI_VERSION 13
 #define PA_WEIGHT_MAGIC 0x31574150 /* "PAW1" */
 #define PA_LSTM_MAGIC 0x314c4150   /* "PAL1" */
 #define PA_ENCODER_MAGIC 0x31454150 /* "PAE1" */
@@ -260,6 +260,37 @@ int pa_detector_forward(pa_detector* h, const uint8_t* frames, int32_t n, int32_
  * layer i took on `stream`. Synchronises the stream. */
 int pa_detector_forward_timed(pa_detector* h, const uint8_t* frames, int32_t n, int32_t height, int32_t width, float* pred, void* stream,
                               float* layer_us, int32_t cap);
+/* Test aids (ABI 13). pa_detector_trace enqueues exactly what pa_detector_forward enqueues for n (1..max_images) frames in one
+ * range of images -- letterbox, kernels, tiles, fusions, knobs -- for layers 0..last_layer (-1: the letterbox alone), then copies
+ * images [img0, img0 + n_img) of the handle's capacity of buffer `buf`, as stored (zero border included), to `out` (device).
+ * buf = -1 is the letter-boxed input x0 [image][net_h + 4][net_w + 4][4]: fp32 / 255, or (PA_DTYPE_EMULATED_F32 with the bf16
+ * stem) the pixel integers as bf16, 2 bytes each. A layer buffer holds (h + 2 pad) x (w + 2 pad) x cstride fp32 per image, the
+ * geometry of the rows that touch it. A layer that one launch runs together with others (SPPF's pools, an up-sampling fused
+ * into its producer) runs with its group: *last_done (host, may be NULL) = the last layer run. Decode layers write `pred`
+ * (device, [n][rows][5 + nc]). PA_ERR_INVALID_ARG for a layer, buffer or image range out of range, n outside 1..max_images
+ * or out_bytes short of the range. */
+int pa_detector_trace(pa_detector* h, const uint8_t* frames, int32_t n, int32_t height, int32_t width, int32_t last_layer, int32_t buf,
+                      int32_t img0, int32_t n_img, void* out, size_t out_bytes, float* pred, int32_t* last_done, void* stream);
+/* The kernel form each layer ran as in the last forward or trace (decided at run time: a launcher that refuses a shape passes
+ * the layer on to the next form). forms: host int32[cap], cap >= the number of layers. */
+typedef enum pa_det_form {
+    PA_DET_FORM_NOT_RUN = 0,
+    PA_DET_FORM_STEM_DIRECT = 1,  /* stem6x6_direct_kernel (exact fp32) */
+    PA_DET_FORM_STEM_BF16 = 2,    /* stem6x6_bf16_kernel (integer pixels, three bf16 slices of W / 255) */
+    PA_DET_FORM_WINO = 3,         /* Winograd F(2x2, 3x3), wino.hip */
+    PA_DET_FORM_PATCH = 4,        /* patch-resident blocked 3x3, patchconv.hip */
+    PA_DET_FORM_PGEMM = 5,        /* persistent GEMM, pigemm.hip */
+    PA_DET_FORM_PGEMM_UP = 6,     /* ... writing the next layer's 2x up-sampling too */
+    PA_DET_FORM_PSGEMM = 7,       /* emulated-fp32 persistent GEMM, psgemm.hip */
+    PA_DET_FORM_PSGEMM_UP = 8,    /* ... writing the next layer's 2x up-sampling too */
+    PA_DET_FORM_IGEMM = 9,        /* one-tile-per-workgroup implicit GEMM, igemm.hip */
+    PA_DET_FORM_SPPF = 10,        /* SPPF's three max-pools in one launch (this layer and the two absorbed after it) */
+    PA_DET_FORM_MAXPOOL = 11,     /* one 5x5 max-pool */
+    PA_DET_FORM_UPSAMPLE = 12,    /* one 2x up-sampling */
+    PA_DET_FORM_ABSORBED = 13,    /* run by the launch of an earlier layer */
+    PA_DET_FORM_DECODE = 14       /* Detect decode */
+} pa_det_form;
+int pa_detector_layer_forms(const pa_detector* h, int32_t* forms, int32_t cap);
 
 /* Replaces AIRunner.clean_yolo_crops / clean_yolo_crops_for_fighter (ai_runner.py:226-289, 306-424) on the table
  * pa_detect_postprocess wrote (dets float32[n_labels][max_det][6], counts int32[n_labels]; label n = index n - 1), with no

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PA_LIB_PATH: load a differently built library (e.g. the ablation build used by scripts/)
 LIB_PATH = os.environ.get("PA_LIB_PATH") or os.path.join(HERE, "libplayaid_hip.so")
 
-PA_ABI_VERSION = 12
+PA_ABI_VERSION = 13
 PA_DTYPE_F32 = 0
 PA_DTYPE_BF16 = 1
 PA_DTYPE_EMULATED_F32 = 2
@@ -22,6 +22,9 @@ PA_LSTM_MAGIC = 0x314C4150
 PA_ENCODER_MAGIC = 0x31454150
 PA_FEATURE_STRIDE = 1024
 PA_TRACE_STAGES = 20
+# pa_det_form (include/playaid_hip.h): the kernel form a detector layer ran as, by value
+DET_FORMS = ("not_run", "stem_direct", "stem_bf16", "wino", "patch", "pgemm", "pgemm_up", "psgemm", "psgemm_up", "igemm", "sppf",
+             "maxpool", "upsample", "absorbed", "decode")
 
 PA_OK = 0
 PA_ERR_INVALID_ARG = -1
@@ -128,6 +131,9 @@ SYMBOLS = [
     ("pa_detector_rows", C.c_int, [_P]),
     ("pa_detector_forward", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("pa_detector_forward_timed", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32]),
+    ("pa_detector_trace", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P,
+                                    _P, _P]),
+    ("pa_detector_layer_forms", C.c_int, [_P, _P, C.c_int32]),
     ("pa_clean_detections", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("pa_save_one_box_crops", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
                                         C.c_size_t, _P, _P]),

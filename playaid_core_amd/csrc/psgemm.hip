@@ -174,6 +174,9 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
     // bias of the column -> LDS (the accumulators of every tile start from it)
     float* const bias_s = (float*)(lds + NSTAGE * STAGE);
     if (tid < BN) bias_s[tid] = p.bias ? p.bias[tile_n * BN + tid] : 0.f;
+    // the store complete before the workgroup's first barrier, behind which every consumer wave reads bias_s: gfx950's barrier
+    // waits for nothing by itself, and hipcc inserts no wait in front of it
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
     if (wave_id >= 4) {
         // =============================== loader waves ===============================

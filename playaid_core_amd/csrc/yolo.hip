@@ -500,6 +500,8 @@ struct pa_detector {
     std::vector<pa_net_layer> layers;
     std::vector<float*> bufs;
     std::vector<size_t> buf_floats;
+    std::vector<size_t> img_stride;     // per buffer: floats from one image to the next, as every row touching it steps them
+    std::vector<int32_t> forms;         // per layer: the pa_det_form the last forward or trace launched it as
     float* weights = nullptr;
     size_t n_weights = 0;
     float* wino_weights = nullptr;      // the stride-1 3x3 layers' filters in the Winograd kernel's layout (wino.hip)
@@ -566,6 +568,16 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         if (buf < 0 || buf >= n_bufs || pad < 0 || cstride < c || coff < 0 || coff + c > cstride || (coff & 3) || (cstride & 3)) return false;
         return (long long)(hh + 2 * pad) * (ww + 2 * pad) * cstride <= buf_floats_per_image[buf];
     };
+    // Every kernel steps from image to image by its slice's geometry, (h + 2 pad) x (w + 2 pad) x cstride floats, and a range of
+    // images that starts at image i0 starts i0 such steps into each buffer: all rows touching a buffer must agree on that step.
+    // buf_floats_per_image may be larger (the rest of each image's share stays unused) but never decides where an image starts.
+    std::vector<size_t> img_stride(n_bufs, 0);
+    auto stride_ok = [&](int buf, int hh, int ww, int pad, int cstride) {
+        const size_t st = (size_t)(hh + 2 * pad) * (ww + 2 * pad) * cstride;
+        if (img_stride[buf] == 0) img_stride[buf] = st;
+        return img_stride[buf] == st;
+    };
+    const char* disagree = "rows touching one buffer disagree on its image stride";
     int rows = 0, n_decode = 0;
     const int no = 5 + num_classes;
     for (int i = 0; i < n_layers; ++i) {
@@ -585,17 +597,24 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
             if (L.w_off < 0 || L.b_off < 0 || (size_t)L.w_off + (size_t)L.cout * L.ksize * L.ksize * L.cin > n_weights ||
                 (size_t)L.b_off + L.cout > n_weights)
                 return bad(i, "weights outside the blob");
+            if (!stride_ok(L.in_buf, L.in_h, L.in_w, L.in_pad, L.in_cstride) || !stride_ok(L.out_buf, oh, ow, L.out_pad, L.out_cstride) ||
+                (L.res_buf >= 0 && !stride_ok(L.res_buf, oh, ow, L.out_pad, L.out_cstride)))
+                return bad(i, disagree);
         } else if (L.kind == 3) {
             if (L.in_h != net_h || L.in_w != net_w || L.cout != 32 || L.w_off < 0 || (size_t)L.w_off + (size_t)64 * 56 > n_weights || (L.w_off & 3) ||
                 L.b_off < 0 || (size_t)L.b_off + L.cout > n_weights || (L.b_off & 3) ||
                 !slice_ok(L.out_buf, net_h / 2, net_w / 2, L.out_pad, L.out_cstride, L.out_coff, L.cout))
                 return bad(i, "bad stem");
+            if (!stride_ok(L.out_buf, net_h / 2, net_w / 2, L.out_pad, L.out_cstride)) return bad(i, disagree);
         } else if (L.kind == 4 || L.kind == 5) {
             if (L.cin % 4 || !slice_ok(L.in_buf, L.in_h, L.in_w, L.in_pad, L.in_cstride, L.in_coff, L.cin) ||
                 !slice_ok(L.out_buf, oh, ow, L.out_pad, L.out_cstride, L.out_coff, L.cin))
                 return bad(i, "bad pool / up-sampling slice");
+            if (!stride_ok(L.in_buf, L.in_h, L.in_w, L.in_pad, L.in_cstride) || !stride_ok(L.out_buf, oh, ow, L.out_pad, L.out_cstride))
+                return bad(i, disagree);
         } else if (L.kind == 6) {
             if (!slice_ok(L.in_buf, L.in_h, L.in_w, L.in_pad, L.in_cstride, L.in_coff, 3 * no)) return bad(i, "bad decode slice");
+            if (!stride_ok(L.in_buf, L.in_h, L.in_w, L.in_pad, L.in_cstride)) return bad(i, disagree);
             rows += 3 * L.in_h * L.in_w;
             ++n_decode;
         } else {
@@ -703,6 +722,8 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
     }
     h->bufs.assign(n_bufs, nullptr);
     h->buf_floats.assign(buf_floats_per_image, buf_floats_per_image + n_bufs);
+    for (int b = 0; b < n_bufs; ++b) h->img_stride.push_back(img_stride[b] ? img_stride[b] : h->buf_floats[b]);
+    h->forms.assign(n_layers, PA_DET_FORM_NOT_RUN);
     for (int b = 0; b < n_bufs; ++b) {
         // the convolution kernels address a buffer with 32-bit BYTE offsets (buffer_load ... lds): 2 GB per buffer
         if ((unsigned long long)max_images * (unsigned long long)h->buf_floats[b] + 128ull * 2048 >= (1ull << 29)) {
@@ -737,8 +758,10 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
 // i0: the first image's slot in the handle's buffers (frames / pred point at that image's data): two half batches can run on two
 // streams side by side, each in its own image range of the same buffers (pa_detector_forward)
 // [lbeg, lend): the layers to run (lend < 0: to the end; the letterbox belongs to layer 0) -- pa_detector_forward's blocked order.
+// A group one launch runs (SPPF's pools, a fused up-sampling) is run whole even where lend falls inside it; *done (may be NULL):
+// the last layer run. Every layer run records its kernel form in h->forms.
 static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_t height, int32_t width, float* pred, void* stream,
-                        std::vector<hipEvent_t>* ev, int i0 = 0, int lbeg = 0, int lend = -1) {
+                        std::vector<hipEvent_t>* ev, int i0 = 0, int lbeg = 0, int lend = -1, int* done = nullptr) {
     if (!h) return PA_ERR_INVALID_ARG;
     auto fail = [&](int code, const std::string& msg) { h->last_error = msg; return code; };
     if (!frames || !pred || n < 1 || height < 1 || width < 1) return fail(PA_ERR_INVALID_ARG, "pa_detector_forward: bad argument");
@@ -746,7 +769,8 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
     hipStream_t s = (hipStream_t)stream;
     float* const X0 = h->x0 + (size_t)i0 * (h->net_h + 4) * (h->net_w + 4) * 4;
     unsigned short* const X0B = reinterpret_cast<unsigned short*>(h->x0) + (size_t)i0 * (h->net_h + 4) * (h->net_w + 4) * 4;   // the same buffer as bf16 (stem_frag)
-    auto BUF = [&](int b) -> float* { return h->bufs[b] + (size_t)i0 * h->buf_floats[b]; };
+    // (image i0 of a buffer sits i0 image strides in: the step its rows take, not buf_floats, which may be larger)
+    auto BUF = [&](int b) -> float* { return h->bufs[b] + (size_t)i0 * h->img_stride[b]; };
 #define DT_HIP(call)                                                                                         \
     do {                                                                                                     \
         hipError_t e__ = (call);                                                                             \
@@ -777,7 +801,8 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             ++di;
         }
     const size_t l_end = lend < 0 ? h->layers.size() : (size_t)lend;
-    for (size_t li = (size_t)lbeg; li < l_end; ++li) {
+    size_t li = (size_t)lbeg;
+    for (; li < l_end; ++li) {
         const pa_net_layer& L = h->layers[li];
         if (ev) DT_HIP(hipEventRecord((*ev)[li], s));  // (profiling call only: layer li runs between events li and li + 1)
         if (L.kind == 3 && h->stem_frag) {   // PA_DTYPE_EMULATED_F32: integer pixels, three bf16 slices of W / 255
@@ -801,6 +826,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             const long long wgs = (strips + 3) / 4;
             hipLaunchKernelGGL(pa::stem6x6_bf16_kernel<12>, dim3((unsigned)(wgs < 2ll * cus ? wgs : 2ll * cus)), dim3(256), 0, s, q);
             DT_HIP(hipGetLastError());
+            h->forms[li] = PA_DET_FORM_STEM_BF16;
             continue;
         }
         if (L.kind == 3) {
@@ -822,6 +848,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             const long long strips = (long long)n * q.row_blocks * q.col_blocks;
             hipLaunchKernelGGL(pa::stem6x6_direct_kernel<12>, dim3((unsigned)((strips + 3) / 4)), dim3(256), 0, s, q);
             DT_HIP(hipGetLastError());
+            h->forms[li] = PA_DET_FORM_STEM_DIRECT;
             continue;
         }
         if (L.kind == 4 && li + 2 < h->layers.size()) {
@@ -851,6 +878,8 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
                     DT_HIP(hipEventRecord((*ev)[li + 1], s));
                     DT_HIP(hipEventRecord((*ev)[li + 2], s));
                 }
+                h->forms[li] = PA_DET_FORM_SPPF;
+                h->forms[li + 1] = h->forms[li + 2] = PA_DET_FORM_ABSORBED;
                 li += 2;
                 continue;
             }
@@ -865,6 +894,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             else
                 hipLaunchKernelGGL(pa::upsample2_kernel, dim3(pa::grid_for(total)), dim3(256), 0, s, BUF(L.in_buf), gi, BUF(L.out_buf), go, n, L.cin);
             DT_HIP(hipGetLastError());
+            h->forms[li] = L.kind == 4 ? PA_DET_FORM_MAXPOOL : PA_DET_FORM_UPSAMPLE;
             continue;
         }
         if (L.kind == 6) {
@@ -872,6 +902,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             hipLaunchKernelGGL(pa::detect_decode_kernel, dim3((L.in_h * L.in_w * no + 255) / 256, n * 3), dim3(256), 0, s, BUF(L.in_buf), gi, 3, no,
                                L.aux[0], h->anchors + (size_t)di * 8, pred, h->rows, row0);
             DT_HIP(hipGetLastError());
+            h->forms[li] = PA_DET_FORM_DECODE;
             row0 += 3 * L.in_h * L.in_w;
             ++di;
             continue;
@@ -932,8 +963,10 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
                 fused_up = true;
             }
         };
+        int form = PA_DET_FORM_NOT_RUN;
         auto up_done = [&]() {
             if (fused_up && pe == hipSuccess) {
+                h->forms[li + 1] = PA_DET_FORM_ABSORBED;
                 ++li;   // the up-sampling layer is done
                 if (ev) (void)hipEventRecord((*ev)[li], s);   // (profiling call: the absorbed layer shows as empty)
             }
@@ -947,6 +980,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
                 fused_up = false;
                 pe = pa::launch_psgemm(p, h->split_weights + h->split_off[li], (size_t)n * p.out_img_stride - (size_t)L.out_coff, 0, s);
             }
+            form = fused_up ? PA_DET_FORM_PSGEMM_UP : PA_DET_FORM_PSGEMM;
             up_done();
         }
         if (pe == hipErrorInvalidValue && h->wino_off[li] >= 0) {
@@ -958,9 +992,12 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             q.out_px_stride = p.out_px_stride; q.out_row_stride = p.out_row_stride; q.out_img_stride = p.out_img_stride; q.out_pad = p.out_pad;
             q.relu = p.relu; q.res_after = p.res_after;
             pe = pa::launch_wino3x3(q, s);
+            form = PA_DET_FORM_WINO;
         }
-        if (pe == hipErrorInvalidValue && use_patch && L.ksize == 3 && L.stride == 1 && L.in_pad == 1)
+        if (pe == hipErrorInvalidValue && use_patch && L.ksize == 3 && L.stride == 1 && L.in_pad == 1) {
             pe = pa::launch_conv3x3_patch_blocked(p, s);  // input patch resident in LDS across the nine taps (patchconv.hip)
+            form = PA_DET_FORM_PATCH;
+        }
         if (pe != hipErrorInvalidValue) {
         } else if ((use_pgemm || p.N % 64) && !p.residual) {
             // 1x1 and stride-2 convolutions: persistent workgroups over runs of tiles (pigemm.hip)
@@ -971,13 +1008,17 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
                 fused_up = false;
                 pe = pa::launch_pgemm(p, 0, s);
             }
+            form = fused_up ? PA_DET_FORM_PGEMM_UP : PA_DET_FORM_PGEMM;
             up_done();
         } else if (p.N % 64 == 0) {
             const pa::GemmTile tile = (p.N % 128 == 0 && t128 / 2 >= 512) ? pa::TILE_128x128 : (t128 >= 512 ? pa::TILE_128x64 : pa::TILE_64x64);
             pe = pa::launch_igemm(p, tile, s);
+            form = PA_DET_FORM_IGEMM;
         }   // (32 output channels: the persistent and the patch kernel only -- the table builder keeps such layers on them)
         if (pe != hipSuccess) return fail(PA_ERR_HIP, "layer " + std::to_string(li) + ": " + hipGetErrorString(pe));
+        h->forms[fused_up ? li - 1 : li] = form;
     }
+    if (done) *done = (int)li - 1;   // (the loop ends one past the last layer it ran)
     if (ev) DT_HIP(hipEventRecord(ev->back(), s));
 #undef DT_HIP
     return PA_OK;
@@ -1042,6 +1083,40 @@ int pa_detector_forward_timed(pa_detector* h, const uint8_t* frames, int32_t n, 
     }
     for (hipEvent_t& e : ev) (void)hipEventDestroy(e);
     return rc;
+}
+
+int pa_detector_trace(pa_detector* h, const uint8_t* frames, int32_t n, int32_t height, int32_t width, int32_t last_layer, int32_t buf,
+                      int32_t img0, int32_t n_img, void* out, size_t out_bytes, float* pred, int32_t* last_done, void* stream) {
+    if (!h) return PA_ERR_INVALID_ARG;
+    auto fail = [&](const char* msg) { h->last_error = std::string("pa_detector_trace: ") + msg; return PA_ERR_INVALID_ARG; };
+    if (!frames || !pred || !out) return fail("bad argument");
+    if (n < 1 || n > h->max_images) return fail("n outside 1..max_images");
+    if (last_layer < -1 || last_layer >= (int32_t)h->layers.size()) return fail("layer out of range");
+    if (buf < -1 || buf >= (int32_t)h->bufs.size()) return fail("buffer out of range");
+    if (img0 < 0 || n_img < 1 || (long long)img0 + n_img > h->max_images) return fail("image range outside max_images");
+    // x0: [image][net_h + 4][net_w + 4][4], fp32 or (stem_frag) bf16; a layer buffer: its rows' image stride, fp32
+    const size_t stride = buf < 0 ? (size_t)(h->net_h + 4) * (h->net_w + 4) * 4 : h->img_stride[buf];
+    const size_t elem = buf < 0 && h->stem_frag ? 2 : 4;
+    const size_t bytes = (size_t)n_img * stride * elem;
+    if (out_bytes < bytes) return fail("out is smaller than the image range");
+    // what pa_detector_forward enqueues for n frames in one range, up to layer last_layer (and the rest of its group)
+    int done = -1;
+    const int rc = detector_run(h, frames, n, height, width, pred, stream, nullptr, 0, 0, last_layer + 1, &done);
+    if (rc) return rc;
+    const char* base = buf < 0 ? reinterpret_cast<const char*>(h->x0) : reinterpret_cast<const char*>(h->bufs[buf]);
+    const hipError_t e = hipMemcpyAsync(out, base + (size_t)img0 * stride * elem, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        h->last_error = std::string("pa_detector_trace: hipMemcpyAsync: ") + hipGetErrorString(e);
+        return PA_ERR_HIP;
+    }
+    if (last_done) *last_done = done;
+    return PA_OK;
+}
+
+int pa_detector_layer_forms(const pa_detector* h, int32_t* forms, int32_t cap) {
+    if (!h || !forms || cap < (int32_t)h->forms.size()) return PA_ERR_INVALID_ARG;
+    std::copy(h->forms.begin(), h->forms.end(), forms);
+    return PA_OK;
 }
 
 }  // extern "C"

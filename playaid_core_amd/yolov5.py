@@ -226,12 +226,27 @@ def build_yolov5s_table(sd: Mapping, net_hw: Tuple[int, int], nc: int):
     return T.layers, buf_floats, np.concatenate(T.weights), rows
 
 
+def buffer_geometry(layers) -> Dict[int, Tuple[int, int, int, int]]:
+    """buffer -> (h, w, pad, channels per pixel) as the table's rows address it (every row touching a buffer agrees)."""
+    geo = {}
+    for L in layers:
+        if L.kind in (0, 4, 5, 6):
+            geo[L.in_buf] = (L.in_h, L.in_w, L.in_pad, L.in_cstride)
+        if L.kind in (0, 3, 4, 5):
+            s = 2 if L.kind == 3 else max(L.stride, 1)
+            oh, ow = (L.in_h * 2, L.in_w * 2) if L.kind == 5 else (L.in_h // s, L.in_w // s)
+            geo[L.out_buf] = (oh, ow, L.out_pad, L.out_cstride)
+    return geo
+
+
 class YoloV5Detector:
     """``pa_detector_*`` handle for a YOLOv5s state dict. ``net_hw``: the network input (what ``letterbox(auto=True)`` picks
     for the clip: 384 x 640 for 16:9 frames at ``--imgsz 640``)."""
 
     def __init__(self, state_dict: Mapping, nc: int, net_hw: Tuple[int, int] = (384, 640), max_images: int = 64, device: str = "cuda:0",
-                 compute_dtype: str = "f32"):
+                 compute_dtype: str = "f32", buf_slack: int = 0):
+        """buf_slack: floats added to every buffer's share per image (tests: a table whose buffers are larger than the geometry
+        their rows address, which the public table API allows)."""
         self._lib = _lib.load()
         if compute_dtype not in ("f32", "emulated_f32"):
             raise ValueError("compute_dtype must be 'f32' or 'emulated_f32'")
@@ -241,7 +256,10 @@ class YoloV5Detector:
         self.device = torch.device(device)
         self.nc, self.net_hw, self.max_images = nc, tuple(net_hw), max_images
         layers, buf_floats, weights, rows = build_yolov5s_table(state_dict, self.net_hw, nc)
+        buf_floats = [b + buf_slack for b in buf_floats]
         self.rows = rows
+        self.layers, self.weights = layers, weights
+        self.buf_geometry = buffer_geometry(layers)
         arr = (_lib.pa_net_layer * len(layers))(*layers)
         bf = (C.c_int64 * len(buf_floats))(*buf_floats)
         h = C.c_void_p()
@@ -290,6 +308,42 @@ class YoloV5Detector:
         return out
 
     __call__ = forward
+
+    def trace(self, frames, last_layer: int, buf: int, img0: int = 0, n_img: int = None, pred: torch.Tensor = None):
+        """Test aid (``pa_detector_trace``): run what ``forward`` runs for frames uint8[n,H,W,3] (n <= max_images, one range)
+        through table row ``last_layer`` (-1: the letterbox alone) and return ``(images [img0, img0 + n_img) of buffer buf as
+        stored, the last row run)``: float32 [n_img][h + 2 pad][w + 2 pad][channels], or for buf = -1 the letter-boxed input
+        [n_img][net_h + 4][net_w + 4][4] (bfloat16 pixel integers under the emulated dtype's bf16 stem). ``pred``: where
+        decode rows write (a new [n, rows, 5 + nc] tensor if None; its rows past the decoded ones are left as they are)."""
+        fd = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
+        fd = fd.to(self.device).contiguous()
+        n, h, w, _ = fd.shape
+        n_img = self.max_images - img0 if n_img is None else n_img
+        if buf < 0:
+            shape, dt = (max(n_img, 0), self.net_hw[0] + 4, self.net_hw[1] + 4, 4), torch.float32
+            if self.compute_dtype == "emulated_f32":
+                dt = torch.bfloat16
+        else:
+            gh, gw, gp, gc = self.buf_geometry[buf]
+            shape, dt = (max(n_img, 0), gh + 2 * gp, gw + 2 * gp, gc), torch.float32
+        out = torch.empty(shape, dtype=dt, device=self.device)
+        if pred is None:
+            pred = torch.zeros((n, self.rows, 5 + self.nc), dtype=torch.float32, device=self.device)
+        done = C.c_int32(-2)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.pa_detector_trace(self._h, C.c_void_p(fd.data_ptr()), n, h, w, last_layer, buf, img0, n_img, C.c_void_p(out.data_ptr()),
+                                         out.numel() * out.element_size(), C.c_void_p(pred.data_ptr()), C.byref(done), stream)
+        if rc != 0:
+            raise EngineError(rc, self._lib.pa_detector_last_error(self._h).decode())
+        return out, done.value
+
+    def layer_forms(self) -> List[str]:
+        """The kernel form (``_lib.DET_FORMS``) each table row ran as in the last forward or trace."""
+        forms = (C.c_int32 * self.n_layers)()
+        rc = self._lib.pa_detector_layer_forms(self._h, forms, self.n_layers)
+        if rc != 0:
+            raise EngineError(rc, "pa_detector_layer_forms")
+        return [_lib.DET_FORMS[f] for f in forms]
 
     def detections(self, engine, frames, conf_thres: float = 0.25, iou_thres: float = 0.45, classes=(2, 3), max_det: int = 2):
         """-> (dets float32[n, max_det, 6], counts int32[n]) on the device: ``detect.py``'s label rows (``ai_runner.py:209-217``)."""

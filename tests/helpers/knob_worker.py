@@ -1,5 +1,6 @@
 """Child of tests/test_knobs.py: the A/B knobs of the library are environment variables read once per process (or per handle), so
-each setting runs in a process of its own. Computes the detection network's rows (emulated-fp32 handle) on four 720p frames and the
+each setting runs in a process of its own. Computes the detection network's rows (both dtypes, on the table and on the same table
+with enlarged buffers) on sixteen 720p frames and the
 action CNN's log-probabilities (exact and emulated engines) on an eight-frame clip and saves them."""
 import os
 import sys
@@ -20,13 +21,15 @@ def main():
     res = {}
     frames = synth.make_frames(16, 720, 1280, seed=5)
     for dt in ("f32", "emulated_f32"):
-        det = YoloV5Detector(synth.make_yolov5s_state_dict(), 6, (384, 640), max_images=16, compute_dtype=dt)
-        try:
-            rows = det(frames)
-            torch.cuda.synchronize()
-            res[f"rows_{dt}"] = rows.cpu().numpy()
-        finally:
-            det.close()
+        # (padded: every buffer 4096 floats larger per image than its rows' geometry, which the table API allows)
+        for key, slack in (("rows", 0), ("rows_padded", 4096)):
+            det = YoloV5Detector(synth.make_yolov5s_state_dict(), 6, (384, 640), max_images=16, compute_dtype=dt, buf_slack=slack)
+            try:
+                rows = det(frames)
+                torch.cuda.synchronize()
+                res[f"{key}_{dt}"] = rows.cpu().numpy()
+            finally:
+                det.close()
     sd = synth.make_state_dict(seed=1234)
     f8, b8 = synth.make_frames(8, 720, 1280), synth.make_boxes(8, 720, 1280)
     for dt in ("f32", "emulated_f32"):

@@ -363,3 +363,57 @@ def test_psgemm_copy_count_matches_the_loaders_waits(lib):
         assert count == nld * (nstage + 1), f"{name}: {count} LDS-DMA instructions, expected {nld} x ({nstage} + 1)"
         seen += 1
     assert seen >= 12
+
+
+def test_psgemm_bias_store_is_waited_for_before_the_first_barrier(lib):
+    """ADVICE round 6 (csrc/psgemm.hip): waves 0-1 store the column's bias to LDS and every consumer wave reads it behind the
+    workgroup's first `s_barrier`. gfx950's barrier waits for nothing itself, so the store must be waited for in between: in
+    every psgemm kernel of the object an `s_waitcnt lgkmcnt(0)` sits between the bias `ds_write` and the first barrier."""
+    asm = _device_disassembly("psgemm.o")
+    if asm is None:
+        pytest.skip("no llvm-objdump / object in this environment")
+    kernels = re.split(r"\n[0-9a-f]+ <(_ZN2pa13psgemm_kernel[^>]*)>:\n", asm)
+    seen = 0
+    for name, body in zip(kernels[1::2], kernels[2::2]):
+        code = [ln.split("//")[0].strip() for ln in body.splitlines()]
+        bar = next(i for i, ln in enumerate(code) if re.match(r"s_barrier\b", ln))
+        writes = [i for i, ln in enumerate(code[:bar]) if re.match(r"ds_(write|store)", ln)]
+        assert len(writes) == 1, f"{name}: {len(writes)} LDS stores before the first barrier, expected the bias store alone"
+        assert any(re.match(r"s_waitcnt\b.*\blgkmcnt\(0\)", ln) for ln in code[writes[0] + 1:bar]), \
+            f"{name}: no lgkmcnt(0) wait between the bias store and the first barrier"
+        seen += 1
+    assert seen >= 12
+
+
+def test_detector_create_refuses_rows_that_disagree_on_a_buffers_image_stride(lib):
+    """ADVICE round 6 (csrc/yolo.hip): a range of images that starts at image i0 (PA_DET_BLOCK's blocks, PA_DET_LANES' second
+    half) starts i0 image strides into every buffer, the step each kernel takes from image to image. buf_floats_per_image may
+    exceed that step, but two rows that step one buffer differently have no common image offset: the table is refused, before
+    any device call."""
+    from playaid_core_amd import _lib, synth
+    from playaid_core_amd.yolov5 import build_yolov5s_table
+
+    layers, bufs, weights, _ = build_yolov5s_table(synth.make_yolov5s_state_dict(), (64, 96), 6)
+
+    def create(layers, bufs):
+        arr = (_lib.pa_net_layer * len(layers))(*layers)
+        h = ctypes.c_void_p(0)
+        rc = lib.pa_detector_create(0, arr, len(layers), (ctypes.c_int64 * len(bufs))(*bufs), len(bufs), weights.ctypes.data_as(ctypes.c_void_p),
+                                    weights.size, 2, 64, 96, 6, ctypes.byref(h))
+        msg = lib.pa_detector_last_error(h).decode() if h else ""
+        if h:
+            lib.pa_detector_destroy(h)
+        return rc, msg
+
+    slack = [b + 65536 for b in bufs]
+    # the first 1x1 convolution that reads a 3x3's output (model.2's cv1 | cv2 on model.1's) claims a 1-pixel border on that
+    # border-less buffer: its slice fits the enlarged allocation, its image stride is not the one the 3x3 writes with
+    i = next(k for k, L in enumerate(layers) if L.kind == 0 and L.ksize == 1 and layers[k - 1].kind == 0)
+    src = layers[i].in_buf
+    assert all(L.in_pad == 0 for L in layers if L.in_buf == src and L.kind == 0) and layers[i].in_pad == 0
+    layers[i].in_pad = 1
+    rc, msg = create(layers, slack)
+    assert rc == _lib.PA_ERR_INVALID_ARG and f"layer {i}:" in msg and "image stride" in msg, (rc, msg)
+    layers[i].in_pad = 0
+    rc, msg = create(layers, [b - 4 for b in bufs])   # (and a buffer smaller than its rows' slices is still refused for that)
+    assert rc == _lib.PA_ERR_INVALID_ARG and "layer 0: bad stem" in msg, (rc, msg)

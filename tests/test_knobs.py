@@ -43,7 +43,7 @@ def default_outputs(tmp_path_factory):
 @pytest.mark.parametrize("knob,bitwise", KNOBS, ids=[",".join(f"{k}={v}" for k, v in kn.items()) for kn, _ in KNOBS])
 def test_knob_reproduces_the_default_outputs(default_outputs, tmp_path, knob, bitwise):
     got = _run(knob, str(tmp_path / "knob.npz"))
-    for key in ("rows_f32", "rows_emulated_f32", "logp_f32", "logp_emulated_f32"):
+    for key in ("rows_f32", "rows_emulated_f32", "rows_padded_f32", "rows_padded_emulated_f32", "logp_f32", "logp_emulated_f32"):
         a, b = got[key], default_outputs[key]
         assert a.shape == b.shape
         if bitwise:
@@ -52,3 +52,12 @@ def test_knob_reproduces_the_default_outputs(default_outputs, tmp_path, knob, bi
             assert np.abs(a[..., :4] - b[..., :4]).max() <= 4e-2 and np.abs(a[..., 4:] - b[..., 4:]).max() <= 2e-4, (knob, key)
         else:
             assert np.abs(a - b).max() <= 1e-5, (knob, key)
+
+
+@pytest.mark.gpu
+def test_padded_table_reproduces_the_default_rows(default_outputs):
+    """The table whose buffers are larger per image than their rows' geometry gives the tight table's rows bit for bit in the
+    default process (one range of images: no image offset is taken). Under PA_DET_BLOCK / PA_DET_LANES the padded rows are
+    held to the knob's own bars above: an image range that starts at image i0 must start i0 image strides of the rows in."""
+    for dt in ("f32", "emulated_f32"):
+        assert np.array_equal(default_outputs[f"rows_padded_{dt}"], default_outputs[f"rows_{dt}"]), dt
