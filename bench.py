@@ -21,10 +21,16 @@ rate is measured separately and reported next to `value`, never as it):
   the interior frames, one all-gather collects the records. A step is one pass
   over the whole clip.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) with `roofline`
-(dominant kernel family, timed with HIP events on the launch stream in a second
-pass right after the timed region) and `cpu_baseline` (the CPU oracle,
-reference-literal shape, on a bounded sample, N=1 only).
+Prints ONE JSON line on rank 0 with the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...). A plain run does only what
+that line needs: set up, warm up, time the steps, write `--dump-outputs`, print.
+
+`--full` adds everything else the benchmark measures, after the timed region:
+`roofline` and `kernels` (dominant kernel family, timed with HIP events on the
+launch stream in a second pass), `cpu_baseline` (the CPU oracle,
+reference-literal shape, on a bounded sample, N=1 only) and the N=1 side
+measurements (`pcie_inclusive*`, `decode_inclusive*`, `chain_inclusive*`,
+`emulated_fp32`, `clip_batches`). The `--no-*` switches thin out a `--full` run.
 
 `--dump-outputs DIR` writes what the last timed step returned -- the records
 decoded as Engine.decode_records does (char_id, action_id, prob, status) and
@@ -71,6 +77,21 @@ def _pmc_traffic(kernel_name, dtype, frames, height, width):
         if t.get("kernel") == kernel_name and t.get("workload") == {"frames": frames, "height": height, "width": width}:
             return t["traffic_bytes_per_launch"], f"profiles/{name} (committed rocprofv3 PMC pass, replayed)"
     return None, None
+
+
+def host_frames(n, height, width, first_frame=0, workers=8):
+    """synth.make_frames, frame by frame on a few threads (numpy releases the GIL in the hash): the same bytes, a fraction
+    of the wall time -- 64 1080p frames take ~12 s on one core."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    out = np.empty((n, height, width, 3), dtype=np.uint8)
+
+    def one(i):
+        out[i] = synth.make_frame(first_frame + i, height, width)
+
+    with ThreadPoolExecutor(max(1, min(workers, n))) as ex:
+        list(ex.map(one, range(n)))
+    return out
 
 
 _ORACLE_SAMPLE = {}   # cpu_baseline's sample and the oracle's log-probabilities on it (see there)
@@ -940,22 +961,25 @@ def main():
                     "(pa_clip_begin_batch: windows stay inside their own clip, results equal the per-clip ones) -- more crops per launch")
     ap.add_argument("--mixed-batch", type=int, default=64, help="--workload mixed: frames per resolution bucket batch (divides 64)")
     ap.add_argument("--clip-batch-side", type=int, default=4,
-                    help="side measurement `clip_batches` of the default run: this many clips per backbone batch (0 / 1: skip; also skipped "
+                    help="side measurement `clip_batches` of a --full run: this many clips per backbone batch (0 / 1: skip; also skipped "
                     "with --no-pcie)")
     ap.add_argument("--long-clip-batch", type=int, default=256,
                     help="configs[3]: frames per backbone batch of the long clip (the 64-frame batch is configs[1]'s workload, "
                     "not a property of the 8192-frame clip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the kernel pass (roofline, kernels), the CPU baseline and the side measurements; "
+                    "a plain run does only what the headline needs")
     ap.add_argument("--cpu-sample-frames", type=int, default=40)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive side measurement")
-    ap.add_argument("--no-decode", action="store_true", help="skip the decode-inclusive (Motion-JPEG) side measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the PCIe-inclusive side measurement")
+    ap.add_argument("--no-decode", action="store_true", help="--full: skip the decode-inclusive (Motion-JPEG) side measurement")
     ap.add_argument("--jpeg-quality", type=int, default=95, help="decode_inclusive: quality of the synthetic Motion-JPEG clip (OpenCV's default)")
     ap.add_argument("--jpeg-restart-blocks", type=int, default=0, help="decode_inclusive: restart interval in MCUs (0 = none, like OpenCV / FFmpeg writers)")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the kernel pass (kernels bracketed with HIP events)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse ranks > GPUs)")
     ap.add_argument("--no-pipeline", action="store_true", help="crop stage and backbone on one stream (no overlap across steps)")
     ap.add_argument("--camera-like", action="store_true", help="--workload chain: the clip with three bits of noise per sample (0.3-0.6 MB per 1080p frame at quality 95)")
-    ap.add_argument("--no-emulated", action="store_true", help="skip the emulated-fp32 side block (compute_dtype emulated_f32)")
+    ap.add_argument("--no-emulated", action="store_true", help="--full: skip the emulated-fp32 side block (compute_dtype emulated_f32)")
     ap.add_argument("--calibrate", action="store_true",
                     help="time every pair of candidate streams before the timed region and keep the fastest (round 5's default; round 6 measured "
                     "no difference between the pairs once warm: profiles/r06_hw_queues.txt)")
@@ -1018,7 +1042,7 @@ def main():
     if long_clip or os.environ.get("PA_BENCH_DEVICE_SYNTH") == "1":
         frames = synth.make_frames_torch(hi - lo, args.height, args.width, first_frame=lo, device=device)
     else:  # short clips: the host generator (rocprofv3 counter passes crash in the torch integer kernels of the device one)
-        frames = torch.from_numpy(synth.make_frames(hi - lo, args.height, args.width, first_frame=lo)).to(device)
+        frames = torch.from_numpy(host_frames(hi - lo, args.height, args.width, first_frame=lo)).to(device)
     boxes = torch.from_numpy(synth.make_boxes(hi - lo, args.height, args.width, first_frame=lo)).to(device)
     runner = FrameParallelClip(eng, S, DELTA)
     lanes = None
@@ -1061,12 +1085,12 @@ def main():
     if args.dump_outputs and rank == 0:   # before the kernel pass below reuses the result buffers
         names = dump_outputs(args.dump_outputs, caller_outputs(rec, lp))
         print(f"--dump-outputs: {', '.join(names)} -> {args.dump_outputs}", file=sys.stderr, flush=True)
-    # ---- kernel pass: clips again with every launch bracketed by HIP events on the launch stream
+    # ---- kernel pass (--full): clips again with every launch bracketed by HIP events on the launch stream
     # (pa_profile_enable). Kept out of the timed region because the event pairs serialise
     # neighbouring kernels and cost ~10 % throughput; its own wall time is reported as
     # profiled_ms_per_step.
     stats, dt_prof, prof_clips = [], None, 0
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         prof_clips = args.steps if long_clip else min(n_calls, 40)   # (step() calls of the kernel pass)
         if long_clip:
             prof_clips = min(prof_clips, 2)
@@ -1225,7 +1249,7 @@ def main():
                             "committed rocprofv3 PMC pass at configs[1]) the fused crop kernel is bound by vector issue -- 0.64 of the VALU slots "
                             "over the whole launch -- and moves 0.86 TB/s",
                 }
-        if world == 1 and not long_clip and not args.no_pcie:
+        if args.full and world == 1 and not long_clip and not args.no_pcie:
             result["pcie_inclusive"] = pcie_inclusive(eng, frames[:n_clip], boxes[:n_clip])
             result["pcie_inclusive_windows"] = pcie_inclusive_windows(eng, frames[:n_clip], boxes[:n_clip])
             if not args.no_decode:
@@ -1254,15 +1278,15 @@ def main():
                 except Exception as exc:
                     result["chain_inclusive_camera_like"] = {"error": f"{type(exc).__name__}: {exc}"}
                 quiet = None
-        if world == 1 and not args.no_cpu_baseline:   # (before the emulated block: its sample is that block's oracle check)
+        if args.full and world == 1 and not args.no_cpu_baseline:   # (before the emulated block: its sample is that block's oracle check)
             result["cpu_baseline"] = cpu_baseline(sd, args.height, args.width, args.cpu_sample_frames)
-        if world == 1 and not long_clip and args.dtype == "f32" and not args.no_pcie and not args.no_decode and not args.no_emulated:
+        if args.full and world == 1 and not long_clip and args.dtype == "f32" and not args.no_pcie and not args.no_decode and not args.no_emulated:
             try:
                 result["emulated_fp32"] = emulated_fp32_side(sd, frames[:n_clip], boxes[:n_clip], n_clip, args.height, args.width, S, DELTA, device,
                                                              args.jpeg_quality)
             except Exception as exc:  # a side measurement must never cost the line its headline
                 result["emulated_fp32"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not long_clip and kb == 1 and not args.no_pcie and not args.no_pipeline and args.clip_batch_side > 1:
+        if args.full and world == 1 and not long_clip and kb == 1 and not args.no_pcie and not args.no_pipeline and args.clip_batch_side > 1:
             try:
                 result["clip_batches"] = clip_batch_side(eng, n_clip, args.clip_batch_side, args.height, args.width, S, DELTA, max(args.lanes, 1))
             except Exception as exc:  # a side measurement must never cost the line its headline

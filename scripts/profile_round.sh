@@ -1,5 +1,5 @@
 #!/bin/bash
-# One measurement set for profiles/: plain bench line, rocprofv3 --kernel-trace --stats of the same
+# One measurement set for profiles/: bench.py --full line, rocprofv3 --kernel-trace --stats of the same
 # workload on one stream, and three separate PMC passes (FETCH_SIZE, WRITE_SIZE, SQ), each with
 # --kernel-trace only, then the summaries (scripts/rocprof_families.py, pmc_traffic.py, pmc_sq.py).
 # Run on the GPU box through gpurun:
@@ -11,9 +11,9 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py "$@" > $O/bench_line.json 2> $O/bench.err
+python3 $R/bench.py --full "$@" > $O/bench_line.json 2> $O/bench.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --no-pcie --no-pipeline "$@" > $O/bench_line_under_rocprof.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-pcie --no-pipeline "$@" > $O/bench_line_under_rocprof.json 2> $O/stats.err
 echo "stats done"
 PMC="--steps 5 --warmup 1 --inner-repeat 1 --no-cpu-baseline --no-pcie --no-profile --no-pipeline"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py $PMC "$@" > $O/pmc_fetch.log 2>&1

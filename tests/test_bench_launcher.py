@@ -164,3 +164,42 @@ def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
     rows = np.load(tmp_path / "s1" / "rows.npy").astype(np.int64)
     assert 0 < len(rows) < 40 and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
     assert np.array_equal(np.load(tmp_path / "s1" / "logp.npy"), lp[rows])
+
+
+def test_host_frames_are_make_frames():
+    """bench.py synthesises the short clip on a few threads: the same bytes as synth.make_frames, offset included."""
+    import numpy as np
+
+    from playaid_core_amd import synth
+
+    bench = _bench()
+    for n, first in ((5, 0), (3, 61), (1, 7)):
+        assert np.array_equal(bench.host_frames(n, 90, 160, first_frame=first), synth.make_frames(n, 90, 160, first_frame=first))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only():
+    """A plain ``bench.py --gpus 1 --steps N --warmup W`` sets up, warms up, times and prints: no kernel pass, CPU baseline or
+    side measurement (those are --full's), and at most 30 s of the whole run spent outside the N + W steps."""
+    import json
+    import subprocess
+    import time
+
+    steps, warmup = 3, 1
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)]
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.rstrip().splitlines()[-1])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == 1
+    assert d["metric"].startswith("1080p frames/sec") and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] > 0 and d["ms_per_step"] > 0
+    moved = {"roofline", "cpu_baseline", "emulated_fp32", "chain_frames_per_s", "chain_camera_like_frames_per_s", "decode_inclusive_frames_per_s",
+             "decode_camera_like_frames_per_s", "pcie_inclusive_frames_per_s"}
+    assert not moved & set(d), sorted(moved & set(d))
+    outside = wall - (steps + warmup) * d["ms_per_step"] / 1e3
+    assert outside <= 30.0, f"{outside:.1f} s outside the steps"
