@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 13
+#define PA_ABI_VERSION 14
 #define PA_WEIGHT_MAGIC 0x31574150 /* "PAW1" */
 #define PA_LSTM_MAGIC 0x314c4150   /* "PAL1" */
 #define PA_ENCODER_MAGIC 0x31454150 /* "PAE1" */
@@ -247,7 +247,20 @@ int pa_detector_create(int32_t device, const pa_net_layer* layers, int32_t n_lay
 /* The same with the convolutions' arithmetic chosen (ABI 11): PA_DTYPE_F32 (= pa_detector_create) or PA_DTYPE_EMULATED_F32 -- the
  * 1x1 and stride-2 3x3 convolutions then run on the bf16 matrix cores with fp32-accurate sums (see PA_DTYPE_EMULATED_F32; the
  * stride-1 3x3 layers keep their exact Winograd kernel), and so does the 6x6 stem: the letter-boxed pixels are integers 0..255,
- * one exact bf16 value each, multiplied with the three bf16 slices of W / 255 (csrc/yolo.hip, stem6x6_bf16_kernel). Never the default. */
+ * one exact bf16 value each, multiplied with the three bf16 slices of W / 255 (csrc/yolo.hip, stem6x6_bf16_kernel). Never the default.
+ *
+ * PA_DTYPE_BF16 (ABI 14; never the default): bf16 storage and bf16 products. Rounding model:
+ *   - letter-boxed input: the pixel integers 0..255 as bf16 (exact);
+ *   - stem: stem6x6_bf16_kernel's product of the integers with the three bf16 slices of fp32 W / 255, + fp32 bias, SiLU in fp32,
+ *     ONE round-to-nearest-even (RNE) to bf16 on the store;
+ *   - every other convolution (csrc/bgemm.hip): the folded fp32 weights rounded RNE to bf16 once, at create; the activations as
+ *     stored (bf16); products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; + fp32 bias, SiLU in fp32; a residual (the
+ *     in-place Bottleneck's, res_after) added as its stored bf16 value in fp32 after the activation; ONE RNE rounding on the store;
+ *   - the Detect heads -- the convolutions whose output buffer a decode row (kind 6) reads -- store fp32, and the decode runs on
+ *     fp32 as under PA_DTYPE_F32;
+ *   - max-pools (SPPF, fused or not) and 2x up-samplings (fused into the producer or not): on bf16, exact.
+ * Buffers hold 2 bytes per element, 4 for those a decode row reads (buf_floats_per_image counts elements). Create fails, naming
+ * the row, where a row has no bf16 form. Detections are NOT within the fp32 path's 1e-4 parity bar (tests state their own). */
 int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t n_layers, const int64_t* buf_floats_per_image, int32_t n_bufs,
                              const float* weights_host, size_t n_weights, int32_t max_images, int32_t net_h, int32_t net_w, int32_t num_classes,
                              int32_t compute_dtype, pa_detector** out);
@@ -264,8 +277,9 @@ int pa_detector_forward_timed(pa_detector* h, const uint8_t* frames, int32_t n, 
  * range of images -- letterbox, kernels, tiles, fusions, knobs -- for layers 0..last_layer (-1: the letterbox alone), then copies
  * images [img0, img0 + n_img) of the handle's capacity of buffer `buf`, as stored (zero border included), to `out` (device).
  * buf = -1 is the letter-boxed input x0 [image][net_h + 4][net_w + 4][4]: fp32 / 255, or (PA_DTYPE_EMULATED_F32 with the bf16
- * stem) the pixel integers as bf16, 2 bytes each. A layer buffer holds (h + 2 pad) x (w + 2 pad) x cstride fp32 per image, the
- * geometry of the rows that touch it. A layer that one launch runs together with others (SPPF's pools, an up-sampling fused
+ * stem) the pixel integers as bf16, 2 bytes each. A layer buffer holds (h + 2 pad) x (w + 2 pad) x cstride elements per image, the
+ * geometry of the rows that touch it: fp32, or under PA_DTYPE_BF16 bf16 (2 bytes) except the buffers a decode row reads; out_bytes
+ * is checked against that element size. A layer that one launch runs together with others (SPPF's pools, an up-sampling fused
  * into its producer) runs with its group: *last_done (host, may be NULL) = the last layer run. Decode layers write `pred`
  * (device, [n][rows][5 + nc]). PA_ERR_INVALID_ARG for a layer, buffer or image range out of range, n outside 1..max_images
  * or out_bytes short of the range. */
@@ -288,7 +302,9 @@ typedef enum pa_det_form {
     PA_DET_FORM_MAXPOOL = 11,     /* one 5x5 max-pool */
     PA_DET_FORM_UPSAMPLE = 12,    /* one 2x up-sampling */
     PA_DET_FORM_ABSORBED = 13,    /* run by the launch of an earlier layer */
-    PA_DET_FORM_DECODE = 14       /* Detect decode */
+    PA_DET_FORM_DECODE = 14,      /* Detect decode */
+    PA_DET_FORM_BGEMM = 15,       /* one-slice bf16 persistent GEMM, bgemm.hip (PA_DTYPE_BF16; ABI 14) */
+    PA_DET_FORM_BGEMM_UP = 16     /* ... writing the next layer's 2x up-sampling too */
 } pa_det_form;
 int pa_detector_layer_forms(const pa_detector* h, int32_t* forms, int32_t cap);
 

@@ -21,6 +21,7 @@ SOURCES = [
     ("igemm.hip", []),
     ("pigemm.hip", []),
     ("psgemm.hip", []),
+    ("bgemm.hip", []),
     ("igemm_bf16.hip", []),
     ("patchconv.hip", []),
     ("patchconv_bf16.hip", []),

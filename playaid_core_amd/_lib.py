@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PA_LIB_PATH: load a differently built library (e.g. the ablation build used by scripts/)
 LIB_PATH = os.environ.get("PA_LIB_PATH") or os.path.join(HERE, "libplayaid_hip.so")
 
-PA_ABI_VERSION = 13
+PA_ABI_VERSION = 14
 PA_DTYPE_F32 = 0
 PA_DTYPE_BF16 = 1
 PA_DTYPE_EMULATED_F32 = 2
@@ -24,7 +24,7 @@ PA_FEATURE_STRIDE = 1024
 PA_TRACE_STAGES = 20
 # pa_det_form (include/playaid_hip.h): the kernel form a detector layer ran as, by value
 DET_FORMS = ("not_run", "stem_direct", "stem_bf16", "wino", "patch", "pgemm", "pgemm_up", "psgemm", "psgemm_up", "igemm", "sppf",
-             "maxpool", "upsample", "absorbed", "decode")
+             "maxpool", "upsample", "absorbed", "decode", "bgemm", "bgemm_up")
 
 PA_OK = 0
 PA_ERR_INVALID_ARG = -1

@@ -1,0 +1,445 @@
+// One-slice bf16 form of the persistent implicit-GEMM convolution (psgemm.hip's launcher conventions and loader / consumer split):
+// the detection network's PA_DTYPE_BF16 convolutions -- every 1x1, stride-2 3x3 and stride-1 3x3 row of its table.
+//
+// What changes against psgemm.hip's emulated-fp32 kernel:
+//   * activations are bf16 in HBM and in the LDS ring: a k-step (32 k) of a pixel is one 64-byte row, half the bytes of the fp32
+//     row. 16-byte chunk c of row r sits at chunk c ^ ((r >> 2) & 3): a ds_read_b128 of 16 rows x one logical chunk (the lane
+//     groups {0-3, 12-15, 20-27}, ...) hits 16 distinct 16-byte slots of the 256-byte bank span;
+//   * the weights are ONE plane, rounded to nearest even once at create (bgemm_pack_weights), in psgemm's plane layout
+//     [tile_n][k-step][BN rows][4 chunks][8], chunk c of row r at c ^ ((r >> 2) & 3); 32-channel tiles pad the 2 KiB image to 4;
+//   * the consumers feed the LDS fragments straight into ONE v_mfma_f32_32x32x16_bf16 per product (no split in registers): a
+//     k-step is 2 x BN / 32 matrix instructions, fed from registers read one k-step ahead;
+//   * the epilogue adds the fp32 bias (the accumulators start from it), applies SiLU / ReLU in fp32, adds a bf16 residual in fp32,
+//     and rounds once to nearest even on the store (8 bytes per lane and 4 channels); the fused 2x up-sampled copy is the same
+//     bf16 value. OUT_F32: the Detect heads' fp32 store instead (no residual, no up-sampling).
+// Loader waves 4-7: per k-step 2 activation pieces (128 rows x 64 bytes = 8 KiB) and BN / 64 weight pieces (at least one) of 1 KiB
+// each, counted waits as in psgemm.hip.
+#include "pa_kernels.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+namespace pa {
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) const u32x4 lds_cu4;
+typedef __attribute__((address_space(3))) float lds_f;
+
+__device__ __forceinline__ i32x4 bg_rsrc(const void* base, unsigned num_bytes) {
+    const unsigned long long a = (unsigned long long)base;
+    return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32) & 0xffff), (int)num_bytes, 0x00020000};
+}
+
+// 16 bytes per lane, L2 / HBM -> LDS at lds_addr + 16 * lane (psgemm.hip's ps_dma16: M0 written and read in one statement)
+__device__ __forceinline__ void bg_dma16(i32x4 rsrc, int voff_bytes, int soff_bytes, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
+                 :
+                 : "v"(voff_bytes), "s"(rsrc), "s"(soff_bytes), "s"(lds_addr)
+                 : "memory");
+}
+
+__device__ __forceinline__ int bg_sdiv(int n, int d, unsigned magic, int& rem) {   // (psgemm.hip's ps_sdiv)
+    int q = (int)__umulhi((unsigned)n, magic);
+    int r = n - q * d;
+    if (r < 0) { --q; r += d; }
+    if (r >= d) { ++q; r -= d; }
+    rem = r;
+    return q;
+}
+
+// four fp32 values -> four bf16, round to nearest even (v_cvt_pk_bf16_f32), element 0 in the low half of word 0
+__device__ __forceinline__ u32x2 bg_pack4(f32x4 v) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 lo = __builtin_convertvector((f32x2{v.x, v.y}), bf16x2), hi = __builtin_convertvector((f32x2{v.z, v.w}), bf16x2);
+    return u32x2{__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi)};
+}
+__device__ __forceinline__ f32x4 bg_unpack4(u32x2 q) {
+    return f32x4{__uint_as_float(q.x << 16), __uint_as_float(q.x & 0xffff0000u), __uint_as_float(q.y << 16), __uint_as_float(q.y & 0xffff0000u)};
+}
+
+constexpr int bg_b_pieces(int bn) { return bn == 32 ? 4 : bn / 16; }   // 1 KiB DMA pieces of a stage's weight image (32: 2 + 2 of padding)
+
+}  // namespace
+
+// ACT: 0 none, 1 ReLU, 2 SiLU. RES: a bf16 residual addressed like the output, added before (ResNet) or after (YOLOv5's Bottleneck,
+// p.res_after) the activation; it may alias the output (every value is read by the lane that writes it). OUT_F32: fp32 output.
+template <int BN, int NSTAGE, int ACT, bool RES, bool OUT_F32>
+__global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const unsigned short* __restrict__ wsp, unsigned out_bytes, unsigned up_bytes) {
+    static_assert(!(RES && OUT_F32), "the fp32-output form is the Detect heads': no residual");
+    constexpr int BM = 128, CB = BN / 32;
+    constexpr int A_BYTES = BM * 64;
+    constexpr int PB = bg_b_pieces(BN) / 4;       // weight pieces per loader wave and k-step
+    constexpr int B_BYTES = bg_b_pieces(BN) * 1024;
+    constexpr int STAGE = A_BYTES + B_BYTES;
+    constexpr int NLD = 2 + PB;                   // LDS-DMA instructions per loader wave and k-step
+    constexpr int OE = OUT_F32 ? 4 : 2;           // output element bytes
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[NSTAGE * STAGE + BN * 4];
+
+    // --- this workgroup's tiles (psgemm.hip): one channel column, every lm-th pixel tile of its XCD's contiguous share ----
+    const int b = blockIdx.x, xcd = b & 7, local = b >> 3, per = p.pg_per;
+    const int TN = p.tiles_n, TM = p.tiles_m;
+    const int LM = per / TN;
+    const int tile_n = local % TN, lm = local / TN;
+    const int t_lo = (int)(((long long)xcd * TM) >> 3), t_hi = (int)(((long long)(xcd + 1) * TM) >> 3);
+    const int nt = t_lo + lm < t_hi ? (t_hi - t_lo - lm + LM - 1) / LM : 0;
+    if (nt == 0) return;
+    const int nk = p.ktot >> 5;
+    const int total = nt * nk;
+
+    const int tid = threadIdx.x;
+    const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
+    const unsigned lds_base = (unsigned)(size_t)(lds_f*)(float*)lds;
+
+    float* const bias_s = (float*)(lds + NSTAGE * STAGE);
+    if (tid < BN) bias_s[tid] = p.bias ? p.bias[tile_n * BN + tid] : 0.f;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the bias store complete before the first barrier: psgemm.hip)
+
+    if (wave_id >= 4) {
+        // =============================== loader waves ===============================
+        const int lw = wave_id - 4, ltid = tid - 256;
+        const int row0 = ltid >> 2;                          // 0..63: four lanes per 64-byte row
+        const int colq = (ltid & 3) ^ ((row0 >> 2) & 3);     // LDS chunk c of activation row r holds logical chunk c ^ ((r >> 2) & 3)
+        const i32x4 act_rs = bg_rsrc(p.act, 0xffffffffu);
+        const i32x4 wgt_rs = bg_rsrc(wsp + (size_t)tile_n * nk * (B_BYTES / 2), 0xffffffffu);
+        // pixel addressing in bytes (psgemm.hip's, with a lane's distance from the run's first pixel up to 63)
+        const int in_ps = p.in_px_stride * p.stride * 2, in_rs = p.in_row_stride * p.stride * 2;
+        const int in_wrap_x = in_rs - p.wo * in_ps;
+        const int in_wrap_y = p.in_img_stride * 2 - p.pg_ho * in_rs;
+        const int in_org = (p.off_y * p.in_row_stride + p.off_x * p.in_px_stride) * 2;
+        const int nwx = 1 + 62 / p.wo, nwy = (p.pg_ho - 1 + nwx) / p.pg_ho;
+        int in_lane = row0 * in_ps + colq * 16;
+        asm volatile("" : "+v"(in_lane));
+        int in_last;   // pixel M - 1: what the rows past M of a partial last tile read (computed, dropped)
+        {
+            int rem, ox;
+            const int img = bg_sdiv(p.M - 1, p.howo, p.pg_magic_howo, rem);
+            const int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox);
+            in_last = img * (p.in_img_stride * 2) + oy * in_rs + ox * in_ps + in_org + colq * 16;
+        }
+        auto in_offset = [&](int m_base) {
+            int rem, ox_b;
+            const int img_b = bg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
+            int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
+            int off = img_b * (p.in_img_stride * 2) + oy * in_rs + ox_b * in_ps + in_org + in_lane;
+            int ox = ox_b + row0;
+            for (int w = 0; w < nwx; ++w) {
+                const bool c = ox >= p.wo;
+                ox -= c ? p.wo : 0;
+                off += c ? in_wrap_x : 0;
+                oy += c ? 1 : 0;
+            }
+            for (int w = 0; w < nwy; ++w) {
+                const bool c = oy >= p.pg_ho;
+                oy -= c ? p.pg_ho : 0;
+                off += c ? in_wrap_y : 0;
+            }
+            return m_base + row0 < p.M ? off : in_last;
+        };
+        int i_tile = t_lo + lm, i_ks = 0, i_ky = 0, i_kx = 0, i_kc = 0;
+        int a_off[2];
+        auto rows_of = [&](int tile_m) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a_off[i] = in_offset(tile_m * BM + 64 * i);
+        };
+        rows_of(i_tile);
+        int b_lane = lw * PB * 1024 + lane * 16;
+        asm volatile("" : "+v"(b_lane));
+        auto issue = [&](int slot) {
+            const unsigned sb = lds_base + slot * STAGE;
+            const int tapoff = (i_ky * p.in_row_stride + i_kx * p.in_px_stride + i_kc) * 2;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) bg_dma16(act_rs, a_off[i], tapoff, sb + lw * 1024 + i * 4096);
+            const int koff = i_ks * B_BYTES;
+#pragma unroll
+            for (int j = 0; j < PB; ++j) bg_dma16(wgt_rs, b_lane, koff + j * 1024, sb + A_BYTES + (lw * PB + j) * 1024);
+            i_kc += 32;
+            if (i_kc == p.chunk) {
+                i_kc = 0;
+                if (++i_kx == p.kw_taps) { i_kx = 0; ++i_ky; }
+            }
+            if (++i_ks == nk) {
+                i_ks = 0; i_ky = 0; i_kx = 0; i_kc = 0;
+                i_tile += LM;
+                rows_of(i_tile < t_hi ? i_tile : t_hi - 1);
+            }
+        };
+        // in front of barrier g + 1 exactly the copies of the (at most NSTAGE - 2) stages issued after stage g + 1 may be outstanding
+        auto wait_stage = [&](int younger) {
+            if (NSTAGE >= 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NLD) : "memory");
+            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        };
+        static_assert(NSTAGE >= 2 && NSTAGE <= 4, "wait_stage covers rings of two to four stages");
+        int slot = 0;
+#pragma unroll
+        for (int s = 0; s < NSTAGE; ++s)
+            if (s < total) issue(s);
+        {
+            const int younger = (total < NSTAGE ? total : NSTAGE) - 1;
+            if (younger >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NLD) : "memory");
+            else wait_stage(younger);
+        }
+        __builtin_amdgcn_s_barrier();   // stage 0 (and bias_s) in LDS
+        for (int g = 0; g + 1 < total; ++g) {
+            const int inflight = (g + NSTAGE < total ? g + NSTAGE : total) - (g + 2);
+            wait_stage(inflight);
+            __builtin_amdgcn_s_barrier();   // stage g + 1 landed; every consumer's reads of stage g have returned
+            if (g + NSTAGE < total) issue(slot);
+            slot = slot + 1 == NSTAGE ? 0 : slot + 1;
+        }
+        __builtin_amdgcn_s_barrier();   // (the consumers' barrier of the last k-step)
+        return;
+    }
+
+    // =============================== consumer waves ===============================
+    const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t res_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.residual : p.out), 0, (int)out_bytes, 0x00020000);
+    const int ch0 = tile_n * BN + 4 * lh;
+    const int nwx = p.pg_nwx, nwy = p.pg_nwy;
+    // output, in BYTES: O(m) = (img * OIS + (oy + pad) * ORS + (ox + pad) * OPS + ch0) * OE
+    const int out_wrap_x = (p.out_row_stride - p.wo * p.out_px_stride) * OE;
+    const int out_wrap_y = (p.out_img_stride - p.pg_ho * p.out_row_stride) * OE;
+    int out_lane = (lr * p.out_px_stride + p.out_pad * (p.out_row_stride + p.out_px_stride) + ch0) * OE;
+    asm volatile("" : "+v"(out_lane));
+    auto out_offset = [&](int m_base) -> unsigned {
+        int rem, ox_b;
+        const int img_b = bg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
+        int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
+        int off = (img_b * p.out_img_stride + oy * p.out_row_stride + ox_b * p.out_px_stride) * OE + out_lane;
+        int ox = ox_b + lr;
+        for (int w = 0; w < nwx; ++w) {
+            const bool c = ox >= p.wo;
+            ox -= c ? p.wo : 0;
+            off += c ? out_wrap_x : 0;
+            oy += c ? 1 : 0;
+        }
+        for (int w = 0; w < nwy; ++w) {
+            const bool c = oy >= p.pg_ho;
+            oy -= c ? p.pg_ho : 0;
+            off += c ? out_wrap_y : 0;
+        }
+        return m_base + lr < p.M ? (unsigned)off : 0x80000000u;   // past M: beyond num_records, dropped
+    };
+    // the nearest-neighbour x2 up-sampled copy (psgemm.hip): the same walk with doubled row and pixel strides, bf16
+    const __amdgpu_buffer_rsrc_t up_rs = __builtin_amdgcn_make_buffer_rsrc(p.up_out ? p.up_out : p.out, 0, (int)(p.up_out ? up_bytes : out_bytes), 0x00020000);
+    const int up_rs_b = 2 * p.up_row_stride * 2, up_ps_b = 2 * p.up_px_stride * 2;
+    const int up_wrap_x = up_rs_b - p.wo * up_ps_b, up_wrap_y = p.up_img_stride * 2 - p.pg_ho * up_rs_b;
+    int up_lane = lr * up_ps_b + (p.up_pad * (p.up_row_stride + p.up_px_stride) + ch0) * 2;
+    asm volatile("" : "+v"(up_lane));
+    auto up_offset = [&](int m_base) -> unsigned {
+        int rem, ox_b;
+        const int img_b = bg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
+        int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
+        int off = img_b * p.up_img_stride * 2 + oy * up_rs_b + ox_b * up_ps_b + up_lane;
+        int ox = ox_b + lr;
+        for (int w = 0; w < nwx; ++w) {
+            const bool c = ox >= p.wo;
+            ox -= c ? p.wo : 0;
+            off += c ? up_wrap_x : 0;
+            oy += c ? 1 : 0;
+        }
+        for (int w = 0; w < nwy; ++w) {
+            const bool c = oy >= p.pg_ho;
+            oy -= c ? p.pg_ho : 0;
+            off += c ? up_wrap_y : 0;
+        }
+        return m_base + lr < p.M ? (unsigned)off : 0x80000000u;
+    };
+
+    // LDS read addresses (bytes) of the two k halves: this wave's pixel row lr; the weight rows lr of each 32-channel block
+    unsigned a_rd[2], b_rd[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        a_rd[h] = lds_base + (wave_id * 32 + lr) * 64 + (((2 * h + lh) ^ ((lr >> 2) & 3)) * 16);
+        b_rd[h] = lds_base + A_BYTES + (lr * 4 + ((2 * h + lh) ^ ((lr >> 2) & 3))) * 16;
+        asm volatile("" : "+v"(a_rd[h]), "+v"(b_rd[h]));
+    }
+
+    u32x4 a0[2], a1[2], w0[CB][2], w1[CB][2];
+    f32x16 acc[CB];
+    u32x2 res2[CB][4];
+    auto read = [&](u32x4 (&a)[2], u32x4 (&w)[CB][2], unsigned sb) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            a[h] = *(lds_cu4*)(size_t)(a_rd[h] + sb);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) w[cb][h] = *(lds_cu4*)(size_t)(b_rd[h] + sb + cb * 32 * 64);
+        }
+    };
+
+    int slot = 0, ks = 0, t = 0;
+    unsigned o_off = 0, u_off = 0;
+    // one k-step: its operands (cur) are in flight or in registers; the next k-step's are read behind the barrier while the
+    // matrix instructions of this one run. Every k-step of every tile, one barrier each (the loaders' count).
+    auto step = [&](const u32x4 (&ca)[2], const u32x4 (&cw)[CB][2], u32x4 (&na)[2], u32x4 (&nw)[CB][2]) {
+        if (ks == 0) {
+            const int tile_m = t_lo + lm + t * LM;
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 b4 = *(const f32x4*)(bias_s + cb * 32 + 8 * g + 4 * lh);
+                    acc[cb][4 * g] = b4.x; acc[cb][4 * g + 1] = b4.y; acc[cb][4 * g + 2] = b4.z; acc[cb][4 * g + 3] = b4.w;
+                }
+            o_off = out_offset(tile_m * BM + wave_id * 32);
+            u_off = p.up_out ? up_offset(tile_m * BM + wave_id * 32) : 0u;
+        }
+        if (RES && ks == nk - 1) {   // the tile's residual values, requested ahead of the last k-step's matrix instructions
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const unsigned off = o_off == 0x80000000u ? o_off : o_off + (unsigned)(cb * 32 + 8 * gq) * 2u;
+                    res2[cb][gq] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(res_rs, off, 0, 0));
+                }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this k-step's operands are in registers: its slot may be refilled
+        __builtin_amdgcn_s_barrier();                          // stage g + 1 landed (the loaders waited for it)
+        __builtin_amdgcn_sched_barrier(0);
+        const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
+        read(na, nw, (unsigned)(nslot * STAGE));   // (the last k-step reads a slot nobody refills: stale, unused)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, cw[cb][h]), __builtin_bit_cast(bf16x8, ca[h]), acc[cb], 0, 0, 0);
+        slot = nslot;
+        if (++ks < nk) return;
+        ks = 0;
+        ++t;
+        // ---- epilogue of the tile, from the accumulators: lane = pixel lr of the wave's 32, channels ch0 + 32 cb + 8 g + 0..3 ----
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                f32x4 v = f32x4{acc[cb][4 * gq], acc[cb][4 * gq + 1], acc[cb][4 * gq + 2], acc[cb][4 * gq + 3]};   // (bias inside)
+                if (RES && !p.res_after) v += bg_unpack4(res2[cb][gq]);
+                if (ACT == 2) {
+                    v.x = silu_fast(v.x); v.y = silu_fast(v.y); v.z = silu_fast(v.z); v.w = silu_fast(v.w);
+                } else if (ACT == 1) {
+                    v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
+                }
+                if (RES && p.res_after) v += bg_unpack4(res2[cb][gq]);
+                const unsigned off = o_off == 0x80000000u ? o_off : o_off + (unsigned)(cb * 32 + 8 * gq) * OE;
+                if (OUT_F32) {
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rs, off, 0, 0);
+                } else {
+                    const u32x2 q = bg_pack4(v);
+                    __builtin_amdgcn_raw_buffer_store_b64(q, out_rs, off, 0, 0);
+                    if (p.up_out) {
+#pragma unroll
+                        for (int q4 = 0; q4 < 4; ++q4) {
+                            const unsigned uo = u_off == 0x80000000u ? u_off : u_off + (unsigned)((q4 >> 1) * p.up_row_stride + (q4 & 1) * p.up_px_stride + cb * 32 + 8 * gq) * 2u;
+                            __builtin_amdgcn_raw_buffer_store_b64(q, up_rs, uo, 0, 0);
+                        }
+                    }
+                }
+            }
+    };
+
+    __builtin_amdgcn_s_barrier();   // stage 0 (and bias_s) in LDS
+    read(a0, w0, 0u);
+    int g = 0;
+    for (; g + 1 < total; g += 2) {   // (two k-steps per trip: the operand sets trade places without register copies)
+        step(a0, w0, a1, w1);
+        step(a1, w1, a0, w0);
+    }
+    if (g < total) step(a0, w0, a1, w1);
+}
+
+int bgemm_pick_bn(int N, int residual) { return psgemm_pick_bn(N, residual); }
+
+size_t bgemm_weight_elems(int N, int ktot, int residual) {
+    const int bn = bgemm_pick_bn(N, residual);
+    if (bn == 0 || ktot % 32 != 0 || N <= 0 || ktot <= 0) return 0;
+    return (size_t)(N / bn) * (ktot / 32) * (bg_b_pieces(bn) * 512);
+}
+
+static inline unsigned short bg_bf16_rne(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)(u >> 16);   // inf / nan: truncate
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (unsigned short)(u >> 16);
+}
+
+// w [N][ktot] fp32 (K contiguous, BatchNorm folded) -> one RNE bf16 plane in the kernel's stage images:
+// [tile_n][k-step][row r][chunk c'][8], chunk c' of row r holding k 8 (c' ^ ((r >> 2) & 3)) .. + 7 (32-channel tiles: + 2 KiB of zeros)
+void bgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned short* out) {
+    const int bn = bgemm_pick_bn(N, residual), nk = ktot / 32, tn_n = N / bn;
+    const size_t stage = (size_t)bg_b_pieces(bn) * 512;   // elements
+    memset(out, 0, bgemm_weight_elems(N, ktot, residual) * sizeof(unsigned short));
+    for (int tn = 0; tn < tn_n; ++tn)
+        for (int ks = 0; ks < nk; ++ks) {
+            unsigned short* img = out + ((size_t)tn * nk + ks) * stage;
+            for (int r = 0; r < bn; ++r)
+                for (int c = 0; c < 4; ++c) {
+                    const int cp = c ^ ((r >> 2) & 3);
+                    for (int j = 0; j < 8; ++j) img[((size_t)r * 4 + cp) * 8 + j] = bg_bf16_rne(w[(size_t)(tn * bn + r) * ktot + ks * 32 + c * 8 + j]);
+                }
+        }
+}
+
+// Conv mode of GemmParams with bf16 storage behind the float* fields (every stride and count in ELEMENTS): act, residual and
+// up_out bf16, out bf16 or (out_f32) fp32. out_elems / up_elems: elements from p.out / p.up_out to the end of the buffer.
+// Refuses (hipErrorInvalidValue) what the 32-bit byte offsets of the loaders and the store descriptors cannot span: the input
+// images the layer reads, the output, the up-sampled copy -- 2 GB each.
+hipError_t launch_bgemm(const GemmParams& p_in, const unsigned short* wsp, size_t out_elems, size_t up_elems, bool out_f32, hipStream_t s) {
+    GemmParams p = p_in;
+    const int bn = bgemm_pick_bn(p.N, p.residual != nullptr);
+    if (p.gather || p.k2_steps || bn == 0 || p.chunk % 32 != 0 || p.M <= 0 || p.M >= (1 << 24) || p.howo <= 0 || p.howo >= (1 << 16) ||
+        p.ktot != p.taps * p.chunk || !wsp || out_elems == 0 || p.howo % p.wo != 0 || (out_f32 && (p.residual || p.up_out)))
+        return hipErrorInvalidValue;
+    const unsigned long long oe = out_f32 ? 4 : 2;
+    const unsigned long long images = (unsigned long long)((p.M + p.howo - 1) / p.howo);
+    // the input span the loaders address with int byte offsets: every image of the range, its border and channel slice included
+    const unsigned long long in_bytes = (images * (unsigned long long)p.in_img_stride) * 2ull;
+    if (p.in_img_stride <= 0 || in_bytes >= (1ull << 31) || out_elems * oe >= (1ull << 31)) return hipErrorInvalidValue;
+    if (p.up_out && (up_elems == 0 || up_elems * 2ull >= (1ull << 31) || p.up_px_stride % 4 || p.up_row_stride % 4 || p.up_img_stride % 4 ||
+                     (reinterpret_cast<unsigned long long>(p.up_out) & 7ull)))
+        return hipErrorInvalidValue;
+    p.tiles_n = p.N / bn;
+    p.tiles_m = (p.M + 127) / 128;
+    const int share = (p.tiles_m + 7) / 8;
+    int lm = 32 / p.tiles_n;
+    lm = lm < 1 ? 1 : (lm > share ? share : lm);
+    const int per = lm * p.tiles_n;
+    const int grid = per * 8;
+    auto magic = [](int d) { return (unsigned)std::min<unsigned long long>(((1ull << 32) + d - 1) / d, 0xffffffffull); };
+    p.pg_per = per;
+    p.pg_ho = p.howo / p.wo;
+    p.pg_magic_howo = magic(p.howo);
+    p.pg_magic_wo = magic(p.wo);
+    p.pg_nwx = 1 + 30 / p.wo;
+    p.pg_nwy = (p.pg_ho - 1 + p.pg_nwx) / p.pg_ho;
+    const unsigned out_bytes = (unsigned)(out_elems * oe), up_bytes = (unsigned)(up_elems * 2);
+#define PA_BG_LAUNCH2(BN_, RES_, F32_)                                                                                                \
+    do {                                                                                                                             \
+        if (p.relu == 2) hipLaunchKernelGGL((bgemm_kernel<BN_, 4, 2, RES_, F32_>), dim3(grid), dim3(512), 0, s, p, wsp, out_bytes, up_bytes);     \
+        else if (p.relu == 1) hipLaunchKernelGGL((bgemm_kernel<BN_, 4, 1, RES_, F32_>), dim3(grid), dim3(512), 0, s, p, wsp, out_bytes, up_bytes); \
+        else hipLaunchKernelGGL((bgemm_kernel<BN_, 4, 0, RES_, F32_>), dim3(grid), dim3(512), 0, s, p, wsp, out_bytes, up_bytes);                 \
+    } while (0)
+#define PA_BG_LAUNCH(BN_)                                                                                                            \
+    do {                                                                                                                             \
+        if (out_f32) PA_BG_LAUNCH2(BN_, false, true);                                                                                \
+        else if (p.residual) PA_BG_LAUNCH2(BN_, true, false);                                                                        \
+        else PA_BG_LAUNCH2(BN_, false, false);                                                                                       \
+    } while (0)
+    if (bn == 128) PA_BG_LAUNCH(128);
+    else if (bn == 64) PA_BG_LAUNCH(64);
+    else PA_BG_LAUNCH(32);
+#undef PA_BG_LAUNCH
+#undef PA_BG_LAUNCH2
+    return hipGetLastError();
+}
+
+}  // namespace pa

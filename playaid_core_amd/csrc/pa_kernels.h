@@ -92,6 +92,13 @@ int psgemm_pick_bn(int N, int residual);          // channels per workgroup (128
 size_t psgemm_weight_elems(int N, int ktot, int residual);
 void psgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned short* out);
 hipError_t launch_psgemm(const GemmParams& p, const unsigned short* wsp, size_t out_floats, size_t up_floats, hipStream_t s);   // (up_floats: the same for p.up_out, 0 without one)
+// one-slice bf16 form of it (bgemm.hip, the detection network's PA_DTYPE_BF16 convolutions): bf16 activations, residual and up-sampled
+// copy behind the float* fields (strides and counts in elements), the weights as ONE round-to-nearest-even bf16 plane in psgemm's plane
+// layout (bgemm_pack_weights), one matrix instruction per product, fp32 accumulate, one rounding on the store; out_f32: fp32 output
+// (the Detect heads; no residual, no up-sampling). out_elems / up_elems: elements from p.out / p.up_out to the end of the buffer.
+size_t bgemm_weight_elems(int N, int ktot, int residual);
+void bgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned short* out);
+hipError_t launch_bgemm(const GemmParams& p, const unsigned short* wsp, size_t out_elems, size_t up_elems, bool out_f32, hipStream_t s);
 // bf16 activations / weights (uint16_t storage behind the float* fields, every count in elements),
 // f32 accumulate on v_mfma_f32_32x32x16_bf16; conv mode only (igemm_bf16.hip)
 hipError_t launch_igemm_bf16(const GemmParams& p, GemmTile tile, hipStream_t s);

@@ -16,6 +16,8 @@
 //   6  Detect decode of one scale: sigmoid, grid / anchor arithmetic -> rows (cx, cy, w, h, obj, classes) in net pixels
 // Before the table runs, letterbox_kernel does what detect.py's LoadImages does to a frame: cv2.resize(INTER_LINEAR) to
 // the un-padded size, a 114-grey border up to the network input (a multiple of 32), BGR -> RGB, / 255.
+// PA_DTYPE_BF16 (include/playaid_hip.h states its rounding model): bf16 buffers (fp32 for the ones a decode row reads), the bf16
+// stem with a bf16 store, every convolution on the one-slice bf16 GEMM (bgemm.hip), the pools and the up-sampling on bf16.
 #include "pa_kernels.h"
 #include "../../include/playaid_hip.h"
 #include <cstdlib>
@@ -98,8 +100,22 @@ __device__ __forceinline__ size_t px_off(const SliceGeom& g, int img, int y, int
     return (((size_t)img * (g.h + 2 * g.pad) + y + g.pad) * (g.w + 2 * g.pad) + x + g.pad) * g.cstride + g.coff;
 }
 
+// four consecutive channels of a slice as fp32, element type fp32 or bf16 (PA_DTYPE_BF16's buffers; widening and narrowing an
+// exact bf16 value round nothing, so the max-pools and the up-sampling stay exact)
+__device__ __forceinline__ float4 ld4(const float* q) { return *reinterpret_cast<const float4*>(q); }
+__device__ __forceinline__ float4 ld4(const unsigned short* q) {
+    const uint2 u = *reinterpret_cast<const uint2*>(q);
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+}
+__device__ __forceinline__ void st4(float* q, float4 v) { *reinterpret_cast<float4*>(q) = v; }
+__device__ __forceinline__ void st4(unsigned short* q, float4 v) {   // (v holds bf16 values: the high halves are exact)
+    *reinterpret_cast<uint2*>(q) = make_uint2((__float_as_uint(v.x) >> 16) | (__float_as_uint(v.y) & 0xffff0000u),
+                                              (__float_as_uint(v.z) >> 16) | (__float_as_uint(v.w) & 0xffff0000u));
+}
+
 // max-pool 5x5, stride 1, padding 2 (nn.MaxPool2d: the padding does not take part), 4 channels per thread
-__global__ __launch_bounds__(256) void maxpool5_kernel(const float* __restrict__ in, SliceGeom gi, float* __restrict__ out, SliceGeom go, int n,
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool5_kernel(const T* __restrict__ in, SliceGeom gi, T* __restrict__ out, SliceGeom go, int n,
                                                        int c) {
     const int c4 = c / 4;
     const long long total = (long long)n * gi.h * gi.w * c4;
@@ -116,11 +132,11 @@ __global__ __launch_bounds__(256) void maxpool5_kernel(const float* __restrict__
             for (int dx = -2; dx <= 2; ++dx) {
                 const int xx = x + dx;
                 if (xx < 0 || xx >= gi.w) continue;
-                const float4 v = *reinterpret_cast<const float4*>(in + px_off(gi, img, yy, xx) + q * 4);
+                const float4 v = ld4(in + px_off(gi, img, yy, xx) + q * 4);
                 m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
             }
         }
-        *reinterpret_cast<float4*>(out + px_off(go, img, y, x) + q * 4) = m;
+        st4(out + px_off(go, img, y, x) + q * 4, m);
     }
 }
 
@@ -129,8 +145,8 @@ __global__ __launch_bounds__(256) void maxpool5_kernel(const float* __restrict__
 // x, clipped at the border. One workgroup = one image x CG channels with the whole map in LDS: separable, the three
 // horizontal maxima of every pixel, then the three vertical ones -> the three output slices. (Three launches of
 // maxpool5_kernel: 28 us each on a 12 x 20 map -- launch latency, not work.)
-template <int CG>
-__global__ __launch_bounds__(256) void sppf_pools_kernel(const float* __restrict__ in, SliceGeom gi, float* __restrict__ out, SliceGeom g1,
+template <int CG, typename T>
+__global__ __launch_bounds__(256) void sppf_pools_kernel(const T* __restrict__ in, SliceGeom gi, T* __restrict__ out, SliceGeom g1,
                                                          SliceGeom g2, SliceGeom g3) {
     extern __shared__ float sm[];
     constexpr int Q = CG / 4;
@@ -142,7 +158,7 @@ __global__ __launch_bounds__(256) void sppf_pools_kernel(const float* __restrict
     auto mx = [](float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); };
     for (int i = threadIdx.x; i < hw * Q; i += 256) {
         const int q = i % Q, pix = i / Q;
-        xs[i] = *reinterpret_cast<const float4*>(in + px_off(gi, img, pix / gi.w, pix % gi.w) + c0 + q * 4);
+        xs[i] = ld4(in + px_off(gi, img, pix / gi.w, pix % gi.w) + c0 + q * 4);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < hw * Q; i += 256) {
@@ -173,14 +189,15 @@ __global__ __launch_bounds__(256) void sppf_pools_kernel(const float* __restrict
             if (up) c = mx(c, h13[i - d * row]);
             if (dn) c = mx(c, h13[i + d * row]);
         }
-        *reinterpret_cast<float4*>(out + px_off(g1, img, y, x) + c0 + q * 4) = a;
-        *reinterpret_cast<float4*>(out + px_off(g2, img, y, x) + c0 + q * 4) = b;
-        *reinterpret_cast<float4*>(out + px_off(g3, img, y, x) + c0 + q * 4) = c;
+        st4(out + px_off(g1, img, y, x) + c0 + q * 4, a);
+        st4(out + px_off(g2, img, y, x) + c0 + q * 4, b);
+        st4(out + px_off(g3, img, y, x) + c0 + q * 4, c);
     }
 }
 
 // nn.Upsample(scale_factor=2, mode="nearest"): out[y][x] = in[y / 2][x / 2]
-__global__ __launch_bounds__(256) void upsample2_kernel(const float* __restrict__ in, SliceGeom gi, float* __restrict__ out, SliceGeom go, int n,
+template <typename T>
+__global__ __launch_bounds__(256) void upsample2_kernel(const T* __restrict__ in, SliceGeom gi, T* __restrict__ out, SliceGeom go, int n,
                                                         int c) {
     const int c4 = c / 4;
     const long long total = (long long)n * go.h * go.w * c4;
@@ -190,8 +207,7 @@ __global__ __launch_bounds__(256) void upsample2_kernel(const float* __restrict_
         const int x = (int)(pix % go.w);
         pix /= go.w;
         const int y = (int)(pix % go.h), img = (int)(pix / go.h);
-        *reinterpret_cast<float4*>(out + px_off(go, img, y, x) + q * 4) =
-            *reinterpret_cast<const float4*>(in + px_off(gi, img, y >> 1, x >> 1) + q * 4);
+        st4(out + px_off(go, img, y, x) + q * 4, ld4(in + px_off(gi, img, y >> 1, x >> 1) + q * 4));
     }
 }
 
@@ -367,7 +383,7 @@ struct StemBf16Params {
     const unsigned short* x;      // [n][net_h + 4][net_w + 4][4] bf16 integers, 2-pixel zero border, channel 3 = 0
     const unsigned short* wfrag;  // [9 steps][3 slices][64 lanes][8]: slice of W[lane & 31][k] / 255, k = 16 s + 8 (lane >> 5) + i = 24 ky + 4 kx + c
     const float* bias;            // [32]
-    float* out;
+    float* out;                   // (OUT_BF16: bf16 elements behind the pointer; strides below in elements)
     int32_t n, net_h, net_w, oh, ow;
     int32_t out_px_stride, out_row_stride, out_img_stride, out_pad;
     int32_t row_blocks, col_blocks;
@@ -377,7 +393,8 @@ struct StemBf16Params {
 #ifndef PA_STEM_ABL
 #define PA_STEM_ABL 0
 #endif
-template <int ROWS>
+// OUT_BF16 (PA_DTYPE_BF16): the same fp32 value -- bias, SiLU -- rounded once to nearest even bf16 on the store.
+template <int ROWS, bool OUT_BF16>
 __global__ __launch_bounds__(256, 2) void stem6x6_bf16_kernel(const StemBf16Params p) {
     typedef float f32x16 __attribute__((ext_vector_type(16)));
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -419,11 +436,12 @@ __global__ __launch_bounds__(256, 2) void stem6x6_bf16_kernel(const StemBf16Para
         const int oxc = ox < p.ow ? ox : p.ow - 1;
         const unsigned short* xin = p.x + ((size_t)img * in_h * in_w + 2 * oxc) * 4;
         // this image's slice of the output as a buffer: a store at offset >= num_records goes nowhere
+        constexpr int OE = OUT_BF16 ? 2 : 4;   // output element bytes
         const __amdgpu_buffer_rsrc_t out_rs =
-            __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)img * p.out_img_stride, 0, p.out_img_stride * 4, 0x00020000);
+            __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (size_t)img * p.out_img_stride * OE, 0, p.out_img_stride * OE, 0x00020000);
         // accumulator register 4 g + e of this lane: pixel column cb * 32 + 8 g + 4 lh + e, channel lr
         const int px0 = cb * 32 + 4 * lh;
-        const unsigned col0 = (unsigned)(((px0 + p.out_pad) * p.out_px_stride + lr) * 4);
+        const unsigned col0 = (unsigned)(((px0 + p.out_pad) * p.out_px_stride + lr) * OE);
         u32x4 win[NSLOT];
         auto load_run = [&](int slot, int st, int oy) {  // (rows past the image: clamped, they feed output rows nobody stores)
             const int row = 2 * oy + ky_of[st];
@@ -460,6 +478,7 @@ __global__ __launch_bounds__(256, 2) void stem6x6_bf16_kernel(const StemBf16Para
                 }
             __builtin_amdgcn_sched_barrier(0);
             if (PA_STEM_LANE_IS_PIXEL) {   // (bias added here: the accumulators started from one channel's value)
+                static_assert(!PA_STEM_LANE_IS_PIXEL || !OUT_BF16, "the A/B lane-is-pixel build has no bf16 store");
                 const unsigned coff = ox < p.ow && oy < p.oh ? (unsigned)(((ox + p.out_pad) * p.out_px_stride + 4 * lh) * 4 + (oy + p.out_pad) * p.out_row_stride * 4) : 0xFFFFFFFFu;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -471,7 +490,7 @@ __global__ __launch_bounds__(256, 2) void stem6x6_bf16_kernel(const StemBf16Para
                 }
                 continue;
             }
-            const unsigned row_off = col0 + (unsigned)((oy + p.out_pad) * p.out_row_stride * 4);
+            const unsigned row_off = col0 + (unsigned)((oy + p.out_pad) * p.out_row_stride * OE);
 #pragma unroll
             for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -480,8 +499,9 @@ __global__ __launch_bounds__(256, 2) void stem6x6_bf16_kernel(const StemBf16Para
                     if (!(PA_STEM_ABL & 2)) v = silu_fast(v);
                     if ((PA_STEM_ABL & 4) && v != 12345.678f) continue;
                     const bool live = oy < p.oh && px0 + 8 * g + e < p.ow;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rs,
-                                                          live ? row_off + (unsigned)((8 * g + e) * p.out_px_stride * 4) : 0xFFFFFFFFu, 0, 0);
+                    const unsigned off = live ? row_off + (unsigned)((8 * g + e) * p.out_px_stride * OE) : 0xFFFFFFFFu;
+                    if (OUT_BF16) __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), out_rs, off, 0, 0);
+                    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), out_rs, off, 0, 0);
                 }
         }
     }
@@ -500,7 +520,8 @@ struct pa_detector {
     std::vector<pa_net_layer> layers;
     std::vector<float*> bufs;
     std::vector<size_t> buf_floats;
-    std::vector<size_t> img_stride;     // per buffer: floats from one image to the next, as every row touching it steps them
+    std::vector<size_t> img_stride;     // per buffer: elements from one image to the next, as every row touching it steps them
+    std::vector<int> buf_elem;          // per buffer: bytes per element -- 4, or under PA_DTYPE_BF16 2 except where a decode row reads
     std::vector<int32_t> forms;         // per layer: the pa_det_form the last forward or trace launched it as
     float* weights = nullptr;
     size_t n_weights = 0;
@@ -511,6 +532,8 @@ struct pa_detector {
     unsigned short* stem_frag = nullptr;       // PA_DTYPE_EMULATED_F32: the stem's W / 255 as stem6x6_bf16_kernel's 27 register fragments (x0 then holds bf16 integers)
     unsigned short* split_weights = nullptr;   // those layers' weights as three bf16 slices in the kernel's stage-image order
     std::vector<long long> split_off;   // per layer: element offset into split_weights, -1 = the layer keeps its exact fp32 kernel
+    unsigned short* bf_weights = nullptr;      // PA_DTYPE_BF16: every convolution's weights as one RNE bf16 plane (bgemm.hip's stage images)
+    std::vector<long long> bf_off;      // per layer: element offset into bf_weights, -1 = not a convolution
     hipStream_t side = nullptr;         // PA_DET_LANES=2: the second half batch's stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     float* x0 = nullptr;       // letter-boxed input [max_images][net_h + 4][net_w + 4][4]
@@ -527,6 +550,7 @@ void pa_detector_destroy(pa_detector* h) {
     (void)hipFree(h->weights);
     (void)hipFree(h->wino_weights);
     (void)hipFree(h->split_weights);
+    (void)hipFree(h->bf_weights);
     (void)hipFree(h->stem_frag);
     (void)hipFree(h->x0);
     (void)hipFree(h->anchors);
@@ -553,7 +577,7 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
     *out = nullptr;
     if (!layers || n_layers < 1 || !buf_floats_per_image || n_bufs < 1 || !weights_host || n_weights < 1 || max_images < 1 || net_h < 32 ||
         net_w < 32 || net_h % 32 || net_w % 32 || num_classes < 1 || num_classes > 80 ||
-        (compute_dtype != PA_DTYPE_F32 && compute_dtype != PA_DTYPE_EMULATED_F32))
+        (compute_dtype != PA_DTYPE_F32 && compute_dtype != PA_DTYPE_EMULATED_F32 && compute_dtype != PA_DTYPE_BF16))
         return PA_ERR_INVALID_ARG;
     pa_detector* h = new pa_detector();
     *out = h;
@@ -646,7 +670,7 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         int eligible = 0;
         for (int i = 0; i < n_layers; ++i) {
             const pa_net_layer& L = h->layers[i];
-            if (use_wino && L.kind == 0 && L.ksize == 3 && L.stride == 1 && L.in_pad == 1 && L.in_h % 4 == 0 && L.in_w % 4 == 0 && L.cin % 8 == 0 &&
+            if (use_wino && compute_dtype != PA_DTYPE_BF16 && L.kind == 0 && L.ksize == 3 && L.stride == 1 && L.in_pad == 1 && L.in_h % 4 == 0 && L.in_w % 4 == 0 && L.cin % 8 == 0 &&
                 ((wino_mask >> (eligible++ & 63)) & 1ul)) {
                 h->wino_off[i] = (long long)total;
                 h->wino_bn[i] = pa::wino_pick_bn(L.cout, (long long)max_images * (L.in_h / 4) * (L.in_w / 4));
@@ -661,7 +685,76 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
             if (!chk(hipMemcpy(h->wino_weights, ug.data(), total * sizeof(float), hipMemcpyHostToDevice), "upload Winograd filters")) return PA_ERR_HIP;
         }
     }
+    // the 6x6 / 2 stem's W / 255 as stem6x6_bf16_kernel's 27 register fragments, three bf16 slices each (PA_DTYPE_EMULATED_F32, PA_DTYPE_BF16)
+    auto make_stem_frag = [&](const pa_net_layer& L) -> bool {
+        // lane layout of the direct kernel: W[ch][c][ky][3 half + j] sits at half * cout * 56 + ch * 56 + ky * 9 + j * 3 + c.
+        // -> [step][slice][lane][8]: lane = 32 khalf + ch supplies k = 16 step + 8 khalf + i, k = 24 ky + 4 kx + c
+        std::vector<unsigned short> frag((size_t)9 * 3 * 64 * 8, 0);
+        auto rne = [](double v) {   // bf16 nearest-even of a double, and its value
+            float f = (float)v;
+            uint32_t u;
+            memcpy(&u, &f, 4);
+            u += 0x7fffu + ((u >> 16) & 1u);
+            return (unsigned short)(u >> 16);
+        };
+        auto val = [](unsigned short hq) { const uint32_t u = (uint32_t)hq << 16; float f; memcpy(&f, &u, 4); return (double)f; };
+        for (int st = 0; st < 9; ++st)
+            for (int ln = 0; ln < 64; ++ln)
+                for (int e = 0; e < 8; ++e) {
+                    const int ch = ln & 31, k = 16 * st + 8 * (ln >> 5) + e, ky = k / 24, kx = (k % 24) / 4, c = k % 4;
+                    if (c == 3) continue;
+                    double r = (double)weights_host[L.w_off + (size_t)(kx / 3) * L.cout * 56 + (size_t)ch * 56 + ky * 9 + (kx % 3) * 3 + c] / 255.0;
+                    for (int sl = 0; sl < 3; ++sl) {
+                        const unsigned short hq = rne(r);
+                        frag[((size_t)(st * 3 + sl) * 64 + ln) * 8 + e] = hq;
+                        r -= val(hq);
+                    }
+                }
+        if (!chk(hipMalloc(&h->stem_frag, frag.size() * sizeof(unsigned short)), "hipMalloc stem fragments")) return false;
+        if (!chk(hipMemcpy(h->stem_frag, frag.data(), frag.size() * sizeof(unsigned short), hipMemcpyHostToDevice), "upload stem fragments")) return false;
+        return true;
+    };
     h->split_off.assign(n_layers, -1);
+    h->bf_off.assign(n_layers, -1);
+    h->buf_elem.assign(n_bufs, 4);
+    if (compute_dtype == PA_DTYPE_BF16) {
+        // bf16 storage: 2 bytes per element in every buffer but those a decode row reads (the Detect heads store fp32 there);
+        // every row needs its bf16 form -- no fp32 kernel runs inside a bf16 network
+        h->buf_elem.assign(n_bufs, 2);
+        for (const pa_net_layer& L : h->layers)
+            if (L.kind == 6) h->buf_elem[L.in_buf] = 4;
+        auto nobf = [&](int i, const char* why) { return bad(i, (std::string("no bf16 form: ") + why).c_str()); };
+        size_t total = 0;
+        for (int i = 0; i < n_layers; ++i) {
+            const pa_net_layer& L = h->layers[i];
+            if (L.kind == 3) {
+                if (L.cout != 32 || L.ksize != 6 || L.stride != 2) return nobf(i, "the stem kernel takes the 6x6 / 2, 32-channel stem only");
+                if (h->buf_elem[L.out_buf] != 2) return nobf(i, "the stem writes a buffer a decode row reads");
+                if (h->stem_frag) return nobf(i, "a second stem");
+                if (!make_stem_frag(L)) return PA_ERR_HIP;
+            } else if (L.kind == 0) {
+                if (h->buf_elem[L.in_buf] != 2 || (L.res_buf >= 0 && h->buf_elem[L.res_buf] != 2))
+                    return nobf(i, "the convolution reads a buffer a decode row reads (fp32)");
+                if (h->buf_elem[L.out_buf] == 4 && L.res_buf >= 0) return nobf(i, "an fp32 head output with a residual");
+                const size_t n_el = pa::bgemm_weight_elems(L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0);
+                if (n_el == 0) return nobf(i, "channel counts the one-slice GEMM does not tile");
+                h->bf_off[i] = (long long)total;
+                total += n_el;
+            } else if (L.kind == 4 || L.kind == 5) {
+                if (h->buf_elem[L.in_buf] != 2 || h->buf_elem[L.out_buf] != 2) return nobf(i, "a pool / up-sampling on a buffer a decode row reads (fp32)");
+            }
+        }
+        if (total) {
+            std::vector<unsigned short> bw(total);
+            for (int i = 0; i < n_layers; ++i)
+                if (h->bf_off[i] >= 0) {
+                    const pa_net_layer& L = h->layers[i];
+                    pa::bgemm_pack_weights(weights_host + L.w_off, L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0, bw.data() + h->bf_off[i]);
+                }
+            if (!chk(hipMalloc(&h->bf_weights, total * sizeof(unsigned short)), "hipMalloc bf16 weights")) return PA_ERR_HIP;
+            if (!chk(hipMemcpy(h->bf_weights, bw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload bf16 weights")) return PA_ERR_HIP;
+        }
+    }
     if (compute_dtype == PA_DTYPE_EMULATED_F32) {
         // the 1x1 and the stride-2 3x3 convolutions (and, with PA_DET_EMU_S1=1, the stride-1 3x3 ones in place of their Winograd
         // form) on the emulated-fp32 kernel (psgemm.hip): weights split into three bf16 slices here, once
@@ -675,31 +768,7 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         for (int i = 0; i < n_layers; ++i) {
             const pa_net_layer& L = h->layers[i];
             if (L.kind == 3 && emu_stem && L.cout == 32 && L.ksize == 6 && L.stride == 2 && !h->stem_frag) {
-                // lane layout of the direct kernel: W[ch][c][ky][3 half + j] sits at half * cout * 56 + ch * 56 + ky * 9 + j * 3 + c.
-                // -> [step][slice][lane][8]: lane = 32 khalf + ch supplies k = 16 step + 8 khalf + i, k = 24 ky + 4 kx + c
-                std::vector<unsigned short> frag((size_t)9 * 3 * 64 * 8, 0);
-                auto rne = [](double v) {   // bf16 nearest-even of a double, and its value
-                    float f = (float)v;
-                    uint32_t u;
-                    memcpy(&u, &f, 4);
-                    u += 0x7fffu + ((u >> 16) & 1u);
-                    return (unsigned short)(u >> 16);
-                };
-                auto val = [](unsigned short hq) { const uint32_t u = (uint32_t)hq << 16; float f; memcpy(&f, &u, 4); return (double)f; };
-                for (int st = 0; st < 9; ++st)
-                    for (int ln = 0; ln < 64; ++ln)
-                        for (int e = 0; e < 8; ++e) {
-                            const int ch = ln & 31, k = 16 * st + 8 * (ln >> 5) + e, ky = k / 24, kx = (k % 24) / 4, c = k % 4;
-                            if (c == 3) continue;
-                            double r = (double)weights_host[L.w_off + (size_t)(kx / 3) * L.cout * 56 + (size_t)ch * 56 + ky * 9 + (kx % 3) * 3 + c] / 255.0;
-                            for (int sl = 0; sl < 3; ++sl) {
-                                const unsigned short hq = rne(r);
-                                frag[((size_t)(st * 3 + sl) * 64 + ln) * 8 + e] = hq;
-                                r -= val(hq);
-                            }
-                        }
-                if (!chk(hipMalloc(&h->stem_frag, frag.size() * sizeof(unsigned short)), "hipMalloc stem fragments")) return PA_ERR_HIP;
-                if (!chk(hipMemcpy(h->stem_frag, frag.data(), frag.size() * sizeof(unsigned short), hipMemcpyHostToDevice), "upload stem fragments")) return PA_ERR_HIP;
+                if (!make_stem_frag(L)) return PA_ERR_HIP;
                 continue;
             }
             if (L.kind != 0 || L.cin % 32 || L.cout % 32) continue;
@@ -731,7 +800,7 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
             return PA_ERR_CAPACITY;
         }
         // (+ slack: a partial last tile of the GEMM reads rows past the last image)
-        const size_t bytes = ((size_t)max_images * h->buf_floats[b] + 128 * 2048) * sizeof(float);
+        const size_t bytes = ((size_t)max_images * h->buf_floats[b] + 128 * 2048) * h->buf_elem[b];
         if (!chk(hipMalloc(&h->bufs[b], bytes), "hipMalloc activations")) return PA_ERR_HIP;
         if (!chk(hipMemset(h->bufs[b], 0, bytes), "hipMemset activations")) return PA_ERR_HIP;  // the zero borders stay zero
     }
@@ -771,6 +840,12 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
     unsigned short* const X0B = reinterpret_cast<unsigned short*>(h->x0) + (size_t)i0 * (h->net_h + 4) * (h->net_w + 4) * 4;   // the same buffer as bf16 (stem_frag)
     // (image i0 of a buffer sits i0 image strides in: the step its rows take, not buf_floats, which may be larger)
     auto BUF = [&](int b) -> float* { return h->bufs[b] + (size_t)i0 * h->img_stride[b]; };
+    // PA_DTYPE_BF16: a slice of a buffer of either element size (first channel coff of image i0's padded pixel (0, 0))
+    const bool bf = h->compute_dtype == PA_DTYPE_BF16;
+    auto SLICE = [&](int b, int coff) -> char* {
+        return reinterpret_cast<char*>(h->bufs[b]) + ((size_t)i0 * h->img_stride[b] + (size_t)coff) * h->buf_elem[b];
+    };
+    typedef unsigned short bf16_t;
 #define DT_HIP(call)                                                                                         \
     do {                                                                                                     \
         hipError_t e__ = (call);                                                                             \
@@ -811,7 +886,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             q.x = X0B;
             q.wfrag = h->stem_frag;
             q.bias = h->weights + L.b_off;
-            q.out = BUF(L.out_buf) + L.out_coff;
+            q.out = reinterpret_cast<float*>(SLICE(L.out_buf, L.out_coff));
             q.n = n; q.net_h = h->net_h; q.net_w = h->net_w; q.oh = oh; q.ow = ow;
             q.out_px_stride = L.out_cstride;
             q.out_row_stride = (ow + 2 * L.out_pad) * L.out_cstride;
@@ -824,7 +899,9 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             // two workgroups per CU (225 registers), each wave walking strips
             static const int cus = [] { hipDeviceProp_t pr; int d = 0; return hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&pr, d) == hipSuccess ? pr.multiProcessorCount : 256; }();
             const long long wgs = (strips + 3) / 4;
-            hipLaunchKernelGGL(pa::stem6x6_bf16_kernel<12>, dim3((unsigned)(wgs < 2ll * cus ? wgs : 2ll * cus)), dim3(256), 0, s, q);
+            const dim3 grid((unsigned)(wgs < 2ll * cus ? wgs : 2ll * cus));
+            if (bf) hipLaunchKernelGGL((pa::stem6x6_bf16_kernel<12, true>), grid, dim3(256), 0, s, q);
+            else hipLaunchKernelGGL((pa::stem6x6_bf16_kernel<12, false>), grid, dim3(256), 0, s, q);
             DT_HIP(hipGetLastError());
             h->forms[li] = PA_DET_FORM_STEM_BF16;
             continue;
@@ -868,11 +945,17 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
                 pa::SliceGeom g1 = {L.in_h, L.in_w, L.out_pad, L.out_cstride, L.out_coff};
                 pa::SliceGeom g2 = {L.in_h, L.in_w, L2.out_pad, L2.out_cstride, L2.out_coff};
                 pa::SliceGeom g3 = {L.in_h, L.in_w, L3.out_pad, L3.out_cstride, L3.out_coff};
-                const size_t lds = (size_t)4 * hw * cg * sizeof(float);
-                if (cg == 16)
-                    hipLaunchKernelGGL(pa::sppf_pools_kernel<16>, dim3(L.cin / 16, n), dim3(256), lds, s, BUF(L.in_buf), gi, BUF(L.out_buf), g1, g2, g3);
-                else
-                    hipLaunchKernelGGL(pa::sppf_pools_kernel<8>, dim3(L.cin / 8, n), dim3(256), lds, s, BUF(L.in_buf), gi, BUF(L.out_buf), g1, g2, g3);
+                const size_t lds = (size_t)4 * hw * cg * sizeof(float);   // (fp32 in LDS for either element type)
+                if (bf) {
+                    const bf16_t* in = reinterpret_cast<const bf16_t*>(SLICE(L.in_buf, 0));
+                    bf16_t* out = reinterpret_cast<bf16_t*>(SLICE(L.out_buf, 0));
+                    if (cg == 16) hipLaunchKernelGGL((pa::sppf_pools_kernel<16, bf16_t>), dim3(L.cin / 16, n), dim3(256), lds, s, in, gi, out, g1, g2, g3);
+                    else hipLaunchKernelGGL((pa::sppf_pools_kernel<8, bf16_t>), dim3(L.cin / 8, n), dim3(256), lds, s, in, gi, out, g1, g2, g3);
+                } else if (cg == 16) {
+                    hipLaunchKernelGGL((pa::sppf_pools_kernel<16, float>), dim3(L.cin / 16, n), dim3(256), lds, s, BUF(L.in_buf), gi, BUF(L.out_buf), g1, g2, g3);
+                } else {
+                    hipLaunchKernelGGL((pa::sppf_pools_kernel<8, float>), dim3(L.cin / 8, n), dim3(256), lds, s, BUF(L.in_buf), gi, BUF(L.out_buf), g1, g2, g3);
+                }
                 DT_HIP(hipGetLastError());
                 if (ev) {  // (profiling call: the two absorbed layers show as empty)
                     DT_HIP(hipEventRecord((*ev)[li + 1], s));
@@ -889,10 +972,16 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             const int oh = L.kind == 5 ? L.in_h * 2 : L.in_h, ow = L.kind == 5 ? L.in_w * 2 : L.in_w;
             pa::SliceGeom go = {oh, ow, L.out_pad, L.out_cstride, L.out_coff};
             const long long total = (long long)n * oh * ow * (L.cin / 4);
-            if (L.kind == 4)
-                hipLaunchKernelGGL(pa::maxpool5_kernel, dim3(pa::grid_for(total)), dim3(256), 0, s, BUF(L.in_buf), gi, BUF(L.out_buf), go, n, L.cin);
+            const bf16_t* bin = reinterpret_cast<const bf16_t*>(SLICE(L.in_buf, 0));
+            bf16_t* bout = reinterpret_cast<bf16_t*>(SLICE(L.out_buf, 0));
+            if (L.kind == 4 && bf)
+                hipLaunchKernelGGL(pa::maxpool5_kernel<bf16_t>, dim3(pa::grid_for(total)), dim3(256), 0, s, bin, gi, bout, go, n, L.cin);
+            else if (L.kind == 4)
+                hipLaunchKernelGGL(pa::maxpool5_kernel<float>, dim3(pa::grid_for(total)), dim3(256), 0, s, BUF(L.in_buf), gi, BUF(L.out_buf), go, n, L.cin);
+            else if (bf)
+                hipLaunchKernelGGL(pa::upsample2_kernel<bf16_t>, dim3(pa::grid_for(total)), dim3(256), 0, s, bin, gi, bout, go, n, L.cin);
             else
-                hipLaunchKernelGGL(pa::upsample2_kernel, dim3(pa::grid_for(total)), dim3(256), 0, s, BUF(L.in_buf), gi, BUF(L.out_buf), go, n, L.cin);
+                hipLaunchKernelGGL(pa::upsample2_kernel<float>, dim3(pa::grid_for(total)), dim3(256), 0, s, BUF(L.in_buf), gi, BUF(L.out_buf), go, n, L.cin);
             DT_HIP(hipGetLastError());
             h->forms[li] = L.kind == 4 ? PA_DET_FORM_MAXPOOL : PA_DET_FORM_UPSAMPLE;
             continue;
@@ -954,7 +1043,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             if (U.kind == 5 && U.in_buf == L.out_buf && U.in_coff == L.out_coff && U.in_cstride == L.out_cstride && U.in_pad == L.out_pad &&
                 U.cin == L.cout && U.in_h == oh && U.in_w == ow && U.out_buf != L.out_buf) {
                 const int up_wb = 2 * ow + 2 * U.out_pad, up_hb = 2 * oh + 2 * U.out_pad;
-                p.up_out = BUF(U.out_buf) + U.out_coff;
+                p.up_out = bf ? reinterpret_cast<float*>(SLICE(U.out_buf, U.out_coff)) : BUF(U.out_buf) + U.out_coff;
                 p.up_px_stride = U.out_cstride;
                 p.up_row_stride = up_wb * U.out_cstride;
                 p.up_img_stride = up_hb * up_wb * U.out_cstride;
@@ -971,6 +1060,29 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
                 if (ev) (void)hipEventRecord((*ev)[li], s);   // (profiling call: the absorbed layer shows as empty)
             }
         };
+        if (bf) {
+            // PA_DTYPE_BF16 (bgemm.hip): every convolution, bf16 slices; the Detect heads (a decode row reads their buffer) store fp32.
+            // No other form: a shape the one-slice kernel refuses fails the call
+            p.act = reinterpret_cast<const float*>(SLICE(L.in_buf, L.in_coff));
+            p.residual = L.res_buf >= 0 ? reinterpret_cast<const float*>(SLICE(L.res_buf, L.res_coff)) : nullptr;
+            p.out = reinterpret_cast<float*>(SLICE(L.out_buf, L.out_coff));
+            const bool out_f32 = h->buf_elem[L.out_buf] == 4;
+            const unsigned short* w = h->bf_weights + h->bf_off[li];
+            const size_t out_elems = (size_t)n * p.out_img_stride - (size_t)L.out_coff;
+            if (!out_f32) try_up();
+            pe = pa::launch_bgemm(p, w, out_elems, up_floats, out_f32, s);
+            if (fused_up && pe == hipErrorInvalidValue) {
+                p.up_out = nullptr;
+                fused_up = false;
+                pe = pa::launch_bgemm(p, w, out_elems, 0, out_f32, s);
+            }
+            if (pe != hipSuccess)
+                return fail(PA_ERR_HIP, "layer " + std::to_string(li) + " (bf16): " + (pe == hipErrorInvalidValue ? std::string("the one-slice GEMM refuses its shape") : hipGetErrorString(pe)));
+            form = fused_up ? PA_DET_FORM_BGEMM_UP : PA_DET_FORM_BGEMM;
+            up_done();
+            h->forms[fused_up ? li - 1 : li] = form;
+            continue;
+        }
         if (h->split_off[li] >= 0) {
             // emulated fp32 (psgemm.hip); out_floats: from the layer's first output channel to the end of the images in flight
             try_up();
@@ -1094,9 +1206,10 @@ int pa_detector_trace(pa_detector* h, const uint8_t* frames, int32_t n, int32_t 
     if (last_layer < -1 || last_layer >= (int32_t)h->layers.size()) return fail("layer out of range");
     if (buf < -1 || buf >= (int32_t)h->bufs.size()) return fail("buffer out of range");
     if (img0 < 0 || n_img < 1 || (long long)img0 + n_img > h->max_images) return fail("image range outside max_images");
-    // x0: [image][net_h + 4][net_w + 4][4], fp32 or (stem_frag) bf16; a layer buffer: its rows' image stride, fp32
+    // x0: [image][net_h + 4][net_w + 4][4], fp32 or (stem_frag) bf16; a layer buffer: its rows' image stride, of its element size
+    // (PA_DTYPE_BF16: 2 bytes, 4 for the buffers a decode row reads)
     const size_t stride = buf < 0 ? (size_t)(h->net_h + 4) * (h->net_w + 4) * 4 : h->img_stride[buf];
-    const size_t elem = buf < 0 && h->stem_frag ? 2 : 4;
+    const size_t elem = buf < 0 ? (h->stem_frag ? 2 : 4) : (size_t)h->buf_elem[buf];
     const size_t bytes = (size_t)n_img * stride * elem;
     if (out_bytes < bytes) return fail("out is smaller than the image range");
     // what pa_detector_forward enqueues for n frames in one range, up to layer last_layer (and the rest of its group)

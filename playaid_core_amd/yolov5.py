@@ -14,7 +14,9 @@ the producers write their channel slice of:
 ``YoloV5Detector.labels(engine, frames)`` returns the label text the runner reads, ``detections`` the device table that
 ``detector_path.run_detections_to_labels`` takes: decode -> detect -> repair -> crops -> CNN -> labels without leaving the GPU.
 The arithmetic contract is ``oracle/yolov5.py`` (live torch CPU kernels on the same state dict; parity unpinned: no
-checkpoint, no YOLOv5 checkout). fp32 throughout.
+checkpoint, no YOLOv5 checkout). fp32 by default; ``compute_dtype="emulated_f32"`` keeps fp32 accuracy on the bf16 matrix
+cores, ``compute_dtype="bf16"`` stores bf16 and multiplies bf16 (include/playaid_hip.h states its rounding model; its detections
+are not within the fp32 path's 1e-4 bar).
 """
 from __future__ import annotations
 
@@ -248,8 +250,8 @@ class YoloV5Detector:
         """buf_slack: floats added to every buffer's share per image (tests: a table whose buffers are larger than the geometry
         their rows address, which the public table API allows)."""
         self._lib = _lib.load()
-        if compute_dtype not in ("f32", "emulated_f32"):
-            raise ValueError("compute_dtype must be 'f32' or 'emulated_f32'")
+        if compute_dtype not in ("f32", "emulated_f32", "bf16"):
+            raise ValueError("compute_dtype must be 'f32', 'emulated_f32' or 'bf16'")
         self.compute_dtype = compute_dtype
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("no HIP device visible to PyTorch-ROCm; the detection network has no CPU fallback")
@@ -260,6 +262,9 @@ class YoloV5Detector:
         self.rows = rows
         self.layers, self.weights = layers, weights
         self.buf_geometry = buffer_geometry(layers)
+        # element type of each buffer as stored: bf16 under compute_dtype="bf16" except the Detect heads' (what a decode row reads)
+        head_bufs = {L.in_buf for L in layers if L.kind == 6}
+        self.buf_dtype = {b: torch.float32 if compute_dtype != "bf16" or b in head_bufs else torch.bfloat16 for b in self.buf_geometry}
         arr = (_lib.pa_net_layer * len(layers))(*layers)
         bf = (C.c_int64 * len(buf_floats))(*buf_floats)
         h = C.c_void_p()
@@ -312,8 +317,9 @@ class YoloV5Detector:
     def trace(self, frames, last_layer: int, buf: int, img0: int = 0, n_img: int = None, pred: torch.Tensor = None):
         """Test aid (``pa_detector_trace``): run what ``forward`` runs for frames uint8[n,H,W,3] (n <= max_images, one range)
         through table row ``last_layer`` (-1: the letterbox alone) and return ``(images [img0, img0 + n_img) of buffer buf as
-        stored, the last row run)``: float32 [n_img][h + 2 pad][w + 2 pad][channels], or for buf = -1 the letter-boxed input
-        [n_img][net_h + 4][net_w + 4][4] (bfloat16 pixel integers under the emulated dtype's bf16 stem). ``pred``: where
+        stored, the last row run)``: [n_img][h + 2 pad][w + 2 pad][channels] of ``buf_dtype[buf]`` (float32; bfloat16 under
+        compute_dtype="bf16" except the Detect heads' buffers), or for buf = -1 the letter-boxed input [n_img][net_h + 4][net_w + 4][4]
+        (bfloat16 pixel integers under the bf16 stem of "emulated_f32" and "bf16"). ``pred``: where
         decode rows write (a new [n, rows, 5 + nc] tensor if None; its rows past the decoded ones are left as they are)."""
         fd = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
         fd = fd.to(self.device).contiguous()
@@ -321,11 +327,11 @@ class YoloV5Detector:
         n_img = self.max_images - img0 if n_img is None else n_img
         if buf < 0:
             shape, dt = (max(n_img, 0), self.net_hw[0] + 4, self.net_hw[1] + 4, 4), torch.float32
-            if self.compute_dtype == "emulated_f32":
+            if self.compute_dtype in ("emulated_f32", "bf16"):
                 dt = torch.bfloat16
         else:
             gh, gw, gp, gc = self.buf_geometry[buf]
-            shape, dt = (max(n_img, 0), gh + 2 * gp, gw + 2 * gp, gc), torch.float32
+            shape, dt = (max(n_img, 0), gh + 2 * gp, gw + 2 * gp, gc), self.buf_dtype[buf]
         out = torch.empty(shape, dtype=dt, device=self.device)
         if pred is None:
             pred = torch.zeros((n, self.rows, 5 + self.nc), dtype=torch.float32, device=self.device)

@@ -14,7 +14,7 @@ from playaid_core_amd.yolov5 import YoloV5Detector, build_yolov5s_table  # noqa:
 n, H, W = int(os.environ.get("N", 64)), 1080, 1920
 dev = torch.device("cuda:0")
 sd = synth.make_yolov5s_state_dict()
-DTYPE = os.environ.get("DTYPE", "f32")   # f32 | emulated_f32
+DTYPE = os.environ.get("DTYPE", "f32")   # f32 | emulated_f32 | bf16
 det = YoloV5Detector(sd, 6, (384, 640), max_images=n, device="cuda:0", compute_dtype=DTYPE)
 layers = build_yolov5s_table(sd, (384, 640), 6)[0]
 frames = torch.from_numpy(synth.make_frames(4, H, W)).to(dev).repeat((n + 3) // 4, 1, 1, 1)[:n].contiguous()
