@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 14
+#define PA_ABI_VERSION 15
 #define PA_WEIGHT_MAGIC 0x31574150 /* "PAW1" */
 #define PA_LSTM_MAGIC 0x314c4150   /* "PAL1" */
 #define PA_ENCODER_MAGIC 0x31454150 /* "PAE1" */
@@ -605,6 +605,19 @@ int pa_lstm_forward(pa_lstm* h, const float* x, int32_t ld, int32_t seq_len, int
  * Call this after synchronising the stream of a pa_lstm_forward: PA_ERR_HIP ONCE if that happened (the handle launches one
  * kernel per time step from then on and later calls are valid), PA_OK otherwise. */
 int pa_lstm_last_status(pa_lstm* h);
+/* Test aid (ABI 15): per layer, the form the last pa_lstm_forward launched it as -- the fallback it really took (a grid the
+ * device cannot hold, PA_LSTM_STEPS, a handle past a timeout), not the path it would have preferred. forms: host
+ * int32[cap], cap >= num_layers. Enqueues nothing. */
+typedef enum pa_lstm_form {
+    PA_LSTM_FORM_NOT_RUN = 0,
+    PA_LSTM_FORM_STEPS = 1,  /* one lstm_step_kernel launch per time step */
+    PA_LSTM_FORM_U1 = 2,     /* persistent lstm_layer_kernel, vector recurrent product, 1 hidden unit per workgroup */
+    PA_LSTM_FORM_U2 = 3,     /* ... 2 units */
+    PA_LSTM_FORM_U4 = 4,     /* ... 4 units */
+    PA_LSTM_FORM_U8 = 5,     /* ... 8 units */
+    PA_LSTM_FORM_MFMA = 6    /* persistent, 4 units, recurrent product on the fp32 matrix cores */
+} pa_lstm_form;
+int pa_lstm_layer_forms(const pa_lstm* h, int32_t* forms, int32_t cap);
 
 /* A conv-net given as a table (the ResNet-50 backbone of ResnetTransformerDetector,
  * playaid/models/resnet_transformer_detector.py:37), run on the engine's fp32 convolution kernels. Weights arrive
@@ -636,6 +649,26 @@ void pa_convnet_destroy(pa_convnet* h);
 const char* pa_convnet_last_error(const pa_convnet* h);
 /* x float32[n,3,128,128] (NCHW, device) -> out: the last layer's output buffer, float32[n, out_floats_per_crop]. */
 int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int32_t out_floats_per_crop, void* stream);
+/* Test aids (ABI 15). pa_convnet_trace enqueues exactly what pa_convnet_forward enqueues for n (1..max_crops) crops -- kernels,
+ * tiles, knobs -- for layers 0..last_row (-1: the input conversion alone), then copies the WHOLE buffer `buf` as stored to `out`
+ * (device): max_crops x buf_floats_per_crop[buf] floats, zero borders and the crops at n and above included; each layer writes
+ * crop i of its output at i x its own per-crop geometry ((hw + 2 pad)^2 x channels). buf = -1 is the stem's input
+ * [max_crops][134][134][4]. PA_ERR_INVALID_ARG for a row or buffer out of range, n outside 1..max_crops or out_bytes short of
+ * the buffer; nothing is enqueued then. pa_convnet_layer_forms: the form each layer ran as in the last forward or trace (a
+ * launcher that refuses a shape passes the layer on to the next form); forms: host int32[cap], cap >= n_descs. */
+int pa_convnet_trace(pa_convnet* h, const float* x, int32_t n, int32_t last_row, int32_t buf, void* out, size_t out_bytes, void* stream);
+typedef enum pa_cn_form {
+    PA_CN_FORM_NOT_RUN = 0,
+    PA_CN_FORM_STEM_POOL = 1,       /* stem + max-pool, stem_pool.hip */
+    PA_CN_FORM_AVGPOOL = 2,         /* global average pool */
+    PA_CN_FORM_WINO = 3,            /* Winograd F(2x2, 3x3), wino.hip */
+    PA_CN_FORM_PATCH = 4,           /* patch-resident 3x3, patchconv.hip */
+    PA_CN_FORM_IGEMM_128x128 = 5,   /* implicit GEMM, igemm.hip, 128 x 128 tiles */
+    PA_CN_FORM_IGEMM_128x64 = 6,    /* ... 128 x 64 tiles */
+    PA_CN_FORM_IGEMM_64x64 = 7,     /* ... 64 x 64 tiles */
+    PA_CN_FORM_PSGEMM = 8           /* emulated-fp32 persistent GEMM, psgemm.hip (PA_DTYPE_EMULATED_F32) */
+} pa_cn_form;
+int pa_convnet_layer_forms(const pa_convnet* h, int32_t* forms, int32_t cap);
 
 /* One stride-1 3x3 convolution (padding 1) on the Winograd F(2x2, 3x3) kernel of the fp32 convolution stack
  * (csrc/wino.hip) -- the operator the engine's ResNet-18 / the detector's Bottlenecks run their stride-1 3x3 layers on,

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # PA_LIB_PATH: load a differently built library (e.g. the ablation build used by scripts/)
 LIB_PATH = os.environ.get("PA_LIB_PATH") or os.path.join(HERE, "libplayaid_hip.so")
 
-PA_ABI_VERSION = 14
+PA_ABI_VERSION = 15
 PA_DTYPE_F32 = 0
 PA_DTYPE_BF16 = 1
 PA_DTYPE_EMULATED_F32 = 2
@@ -25,6 +25,9 @@ PA_TRACE_STAGES = 20
 # pa_det_form (include/playaid_hip.h): the kernel form a detector layer ran as, by value
 DET_FORMS = ("not_run", "stem_direct", "stem_bf16", "wino", "patch", "pgemm", "pgemm_up", "psgemm", "psgemm_up", "igemm", "sppf",
              "maxpool", "upsample", "absorbed", "decode", "bgemm", "bgemm_up")
+# pa_cn_form / pa_lstm_form (ABI 15): the form a conv-net table row / an LSTM layer ran as, by value
+CN_FORMS = ("not_run", "stem_pool", "avgpool", "wino", "patch", "igemm_128x128", "igemm_128x64", "igemm_64x64", "psgemm")
+LSTM_FORMS = ("not_run", "steps", "u1", "u2", "u4", "u8", "mfma")
 
 PA_OK = 0
 PA_ERR_INVALID_ARG = -1
@@ -169,6 +172,7 @@ SYMBOLS = [
     ("pa_lstm_last_error", C.c_char_p, [_P]),
     ("pa_lstm_last_status", C.c_int, [_P]),
     ("pa_lstm_forward", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    ("pa_lstm_layer_forms", C.c_int, [_P, _P, C.c_int32]),
     ("pa_convnet_create", C.c_int, [C.c_int32, C.POINTER(pa_conv_desc), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _P, C.c_size_t,
                                     C.c_int32, C.POINTER(_P)]),
     ("pa_convnet_create_dtype", C.c_int, [C.c_int32, C.POINTER(pa_conv_desc), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _P, C.c_size_t,
@@ -176,6 +180,8 @@ SYMBOLS = [
     ("pa_convnet_destroy", None, [_P]),
     ("pa_convnet_last_error", C.c_char_p, [_P]),
     ("pa_convnet_forward", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P]),
+    ("pa_convnet_trace", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
+    ("pa_convnet_layer_forms", C.c_int, [_P, _P, C.c_int32]),
     ("pa_detector_plan", C.c_int, [_P] * 5 + [C.c_int32] + [_P] * 7),
     ("pa_detector_plan_desc", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_longlong, _P, C.c_int32, C.c_longlong, _P]),
     ("pa_square_crops_src", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),

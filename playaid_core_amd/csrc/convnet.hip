@@ -12,6 +12,7 @@
 // Nothing here is specific to ResNet-50; the table in playaid_core_amd/resnet_transformer_detector.py is.
 #include "pa_kernels.h"
 #include "../../include/playaid_hip.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -53,6 +54,7 @@ struct pa_convnet {
     unsigned short* split_weights = nullptr;   // those layers' weights as three bf16 slices (psgemm_pack_weights)
     std::vector<long long> split_off;          // per layer: element offset into split_weights, -1 = the exact kernel
     float* x0 = nullptr;  // [max_crops][134][134][4] model input of the stem
+    std::vector<int32_t> forms;  // per layer: the pa_cn_form the last forward or trace launched it as (pa_convnet_layer_forms)
     std::string last_error;
 };
 
@@ -94,6 +96,8 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
     h->compute_dtype = compute_dtype;
     h->max_crops = max_crops;
     h->descs.assign(descs, descs + n_descs);
+    h->forms.assign(n_descs, PA_CN_FORM_NOT_RUN);
+    h->buf_floats.assign(buf_floats_per_crop, buf_floats_per_crop + n_bufs);
     // validate the table: buffer indices, weight ranges, buffer sizes, one geometry per bordered buffer
     struct Geom { int hw = -1, pad = -1, c = -1; };
     std::vector<Geom> geom(n_bufs);
@@ -193,7 +197,6 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
         }
     }
     h->bufs.assign(n_bufs, nullptr);
-    h->buf_floats.assign(buf_floats_per_crop, buf_floats_per_crop + n_bufs);
     for (int b = 0; b < n_bufs; ++b) {
         // (+ one 128-pixel tile of slack: a partial last tile of the patch kernel reads past the last crop)
         const size_t bytes = ((size_t)max_crops * h->buf_floats[b] + 128 * 2048) * sizeof(float);
@@ -216,18 +219,20 @@ void pa_convnet_destroy(pa_convnet* h) {
     delete h;
 }
 
-int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int32_t out_floats_per_crop, void* stream) {
-    if (!h) return PA_ERR_INVALID_ARG;
-    if (!x || !out || n < 1) return cn_fail(h, PA_ERR_INVALID_ARG, "pa_convnet_forward: bad argument");
-    if (n > h->max_crops) return cn_fail(h, PA_ERR_CAPACITY, "pa_convnet_forward: more crops than max_crops");
-    hipStream_t s = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// What pa_convnet_forward enqueues for n crops, up to and including layer `last` (-1: the input conversion alone); records
+// each layer's form. Arguments are checked by the callers.
+int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t s) {
 #define CN_HIP(call)                                                                                  \
     do {                                                                                              \
         hipError_t e__ = (call);                                                                      \
         if (e__ != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
     CN_HIP(pa::launch_nchw_to_padded(x, h->x0, n, 0, s));
-    for (size_t li = 0; li < h->descs.size(); ++li) {
+    for (int li = 0; li <= last; ++li) {
         const pa_conv_desc& d = h->descs[li];
         if (d.kind == 1) {
             pa::StemPoolParams sp;
@@ -238,6 +243,7 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
             sp.out = h->bufs[d.out_buf];
             sp.crops = n;
             CN_HIP(pa::launch_stem_pool(sp, s));
+            h->forms[li] = PA_CN_FORM_STEM_POOL;
             continue;
         }
         if (d.kind == 2) {
@@ -246,6 +252,7 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
             grid = grid > 2048 ? 2048 : grid;
             hipLaunchKernelGGL(pa::avgpool_any_kernel, dim3(grid), dim3(256), 0, s, h->bufs[d.in_buf], h->bufs[d.out_buf], n, d.in_hw, d.in_pad, d.cin);
             CN_HIP(hipGetLastError());
+            h->forms[li] = PA_CN_FORM_AVGPOOL;
             continue;
         }
         const int out_hw = d.in_hw / d.stride;
@@ -280,8 +287,10 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
         const long long t128 = (long long)((p.M + 127) / 128) * (p.N / 64);
         const pa::GemmTile tile = (p.N % 128 == 0 && t128 / 2 >= 512) ? pa::TILE_128x128 : (t128 >= 512 ? pa::TILE_128x64 : pa::TILE_64x64);
         hipError_t pe = hipErrorInvalidValue;
+        int32_t form = PA_CN_FORM_PSGEMM;
         if (h->split_off[li] >= 0) pe = pa::launch_psgemm(p, h->split_weights + h->split_off[li], (size_t)n * p.out_img_stride, 0, s);
         if (pe == hipErrorInvalidValue && h->wino_off[li] >= 0) {
+            form = PA_CN_FORM_WINO;
             pa::WinoParams q;
             memset(&q, 0, sizeof(q));
             q.act = p.act; q.wgt = h->wino_weights + h->wino_off[li]; q.bias = p.bias; q.residual = p.residual; q.out = p.out;
@@ -291,11 +300,38 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
             q.relu = p.relu;
             pe = pa::launch_wino3x3(q, s);
         }
-        if (pe == hipErrorInvalidValue && d.ksize == 3 && d.stride == 1 && d.in_pad == 1) pe = pa::launch_conv3x3_patch(p, tile == pa::TILE_64x64 ? 64 : 128, s);
-        if (pe == hipErrorInvalidValue) pe = pa::launch_igemm(p, tile, s);
+        if (pe == hipErrorInvalidValue && d.ksize == 3 && d.stride == 1 && d.in_pad == 1) {
+            form = PA_CN_FORM_PATCH;
+            pe = pa::launch_conv3x3_patch(p, tile == pa::TILE_64x64 ? 64 : 128, s);
+        }
+        if (pe == hipErrorInvalidValue) {
+            form = tile == pa::TILE_128x128 ? PA_CN_FORM_IGEMM_128x128 : (tile == pa::TILE_128x64 ? PA_CN_FORM_IGEMM_128x64 : PA_CN_FORM_IGEMM_64x64);
+            pe = pa::launch_igemm(p, tile, s);
+        }
         if (pe != hipSuccess) return cn_fail(h, PA_ERR_HIP, "layer " + std::to_string(li) + ": " + hipGetErrorString(pe));
+        h->forms[li] = form;
     }
-    // the last layer's output, interior only when it is bordered (a pooled vector has no border)
+#undef CN_HIP
+    return PA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int32_t out_floats_per_crop, void* stream) {
+    if (!h) return PA_ERR_INVALID_ARG;
+    if (!x || !out || n < 1) return cn_fail(h, PA_ERR_INVALID_ARG, "pa_convnet_forward: bad argument");
+    if (n > h->max_crops) return cn_fail(h, PA_ERR_CAPACITY, "pa_convnet_forward: more crops than max_crops");
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = convnet_run(h, x, n, (int)h->descs.size() - 1, s);
+    if (rc != PA_OK) return rc;
+#define CN_HIP(call)                                                                                  \
+    do {                                                                                              \
+        hipError_t e__ = (call);                                                                      \
+        if (e__ != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+    // the last layer's output buffer as stored, zero border included when it has one (a pooled vector has none)
     const pa_conv_desc& last = h->descs.back();
     int ohw, oc;
     out_geom(last, &ohw, &oc);
@@ -304,6 +340,30 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
     if (out_floats_per_crop != per_crop) return cn_fail(h, PA_ERR_INVALID_ARG, "pa_convnet_forward: out_floats_per_crop does not match the last layer");
     CN_HIP(hipMemcpyAsync(out, h->bufs[last.out_buf], (size_t)n * per_crop * sizeof(float), hipMemcpyDeviceToDevice, s));
 #undef CN_HIP
+    return PA_OK;
+}
+
+int pa_convnet_trace(pa_convnet* h, const float* x, int32_t n, int32_t last_row, int32_t buf, void* out, size_t out_bytes, void* stream) {
+    if (!h) return PA_ERR_INVALID_ARG;
+    auto fail = [&](const char* msg) { return cn_fail(h, PA_ERR_INVALID_ARG, std::string("pa_convnet_trace: ") + msg); };
+    if (!x || !out) return fail("bad argument");
+    if (n < 1 || n > h->max_crops) return fail("n outside 1..max_crops");
+    if (last_row < -1 || last_row >= (int32_t)h->descs.size()) return fail("row out of range");
+    if (buf < -1 || buf >= (int32_t)h->buf_floats.size()) return fail("buffer out of range");
+    const size_t floats = (size_t)h->max_crops * (buf < 0 ? (size_t)134 * 134 * 4 : (size_t)h->buf_floats[buf]);
+    if (out_bytes < floats * sizeof(float)) return fail("out is smaller than the buffer");
+    if (buf >= (int32_t)h->bufs.size() || !h->x0) return fail("the handle holds no buffers (its creation failed)");
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = convnet_run(h, x, n, last_row, s);
+    if (rc != PA_OK) return rc;
+    const hipError_t e = hipMemcpyAsync(out, buf < 0 ? h->x0 : h->bufs[buf], floats * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string("pa_convnet_trace: hipMemcpyAsync: ") + hipGetErrorString(e));
+    return PA_OK;
+}
+
+int pa_convnet_layer_forms(const pa_convnet* h, int32_t* forms, int32_t cap) {
+    if (!h || !forms || cap < (int32_t)h->forms.size()) return PA_ERR_INVALID_ARG;
+    std::copy(h->forms.begin(), h->forms.end(), forms);
     return PA_OK;
 }
 

@@ -391,6 +391,7 @@ struct pa_lstm {
     bool sync_pending = false;            // a forward has been enqueued since the words were last read
     int occ_blocks = -1, occ_key = -1;    // co-resident lstm_layer_kernel workgroups the device holds for batch * 16 + U == occ_key
     bool persistent = true;               // one launch per layer (lstm_layer_kernel); false after a barrier timeout
+    std::vector<int32_t> forms;           // per layer: the pa_lstm_form the last forward launched it as (pa_lstm_layer_forms)
     std::string last_error;
 };
 
@@ -426,6 +427,7 @@ int pa_lstm_create(int32_t device, int32_t input_dim, int32_t hidden_dim, int32_
     *out = h;  // handed back on failure too (pa_lstm_last_error, then pa_lstm_destroy)
     h->in_dim = input_dim; h->hid = hidden_dim; h->layers = num_layers; h->actions = num_actions; h->max_rows = max_rows;
     h->device = device;
+    h->forms.assign(num_layers, PA_LSTM_FORM_NOT_RUN);
     auto chk = [&](hipError_t e, const char* what) -> bool {
         if (e == hipSuccess) return true;
         h->last_error = std::string(what) + ": " + hipGetErrorString(e);
@@ -482,6 +484,12 @@ int pa_lstm_last_status(pa_lstm* h) {
     h->last_error = "pa_lstm_forward: the grid barrier of the per-layer kernel timed out (its workgroups were not all resident); "
                     "that call's log-probabilities are NaN, later calls launch one kernel per time step";
     return PA_ERR_HIP;
+}
+
+int pa_lstm_layer_forms(const pa_lstm* h, int32_t* forms, int32_t cap) {
+    if (!h || !forms || cap < (int32_t)h->forms.size()) return PA_ERR_INVALID_ARG;
+    for (size_t l = 0; l < h->forms.size(); ++l) forms[l] = h->forms[l];
+    return PA_OK;
 }
 
 void pa_lstm_destroy(pa_lstm* h) {
@@ -568,6 +576,7 @@ int pa_lstm_forward(pa_lstm* h, const float* x, int32_t ld, int32_t seq_len, int
             const hipError_t ce = 2 * (H / U) <= h->occ_blocks ? hipLaunchKernel(fn, dim3(H / U), dim3(256), args, lds, s) : hipErrorCooperativeLaunchTooLarge;
             if (ce == hipSuccess) {
                 (void)hipMemcpyAsync(h->sync_host + 2 * l, h->sync_words + 2 * l, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
+                h->forms[l] = mf ? PA_LSTM_FORM_MFMA : (U == 8 ? PA_LSTM_FORM_U8 : U == 4 ? PA_LSTM_FORM_U4 : U == 2 ? PA_LSTM_FORM_U2 : PA_LSTM_FORM_U1);
                 continue;
             }
             (void)hipGetLastError();   // the grid cannot be co-resident on this device (or no cooperative launches): per-step kernels
@@ -576,6 +585,7 @@ int pa_lstm_forward(pa_lstm* h, const float* x, int32_t ld, int32_t seq_len, int
         for (int t = 0; t < seq_len; ++t)
             hipLaunchKernelGGL(pa::lstm_step_kernel, dim3(H / 8), dim3(256), step_lds, s, h->pre + (size_t)t * batch * 4 * H, h->w_hh[l],
                                h->b_hh[l], t ? hs + (size_t)(t - 1) * batch * H : nullptr, h->c, hs + (size_t)t * batch * H, batch, H);
+        h->forms[l] = PA_LSTM_FORM_STEPS;
     }
     hipLaunchKernelGGL(pa::lstm_decode_kernel, dim3(M), dim3(128), 0, s, h->hseq[(h->layers - 1) & 1], h->w1, h->b1, h->w2, h->b2, logp, H,
                        h->actions, h->sync_words, h->layers);

@@ -170,6 +170,8 @@ class ConvNet:
         self.device = torch.device(device)
         self.max_crops = max_crops
         self.out_floats = out_floats
+        self.buf_floats = [int(b) for b in buf_floats]
+        self.n_rows = len(descs)
         arr = (_lib.pa_conv_desc * len(descs))()
         for i, d in enumerate(descs):
             for k, v in d.items():
@@ -189,6 +191,27 @@ class ConvNet:
         if getattr(self, "_h", None):
             self._lib.pa_convnet_destroy(self._h)
             self._h = None
+
+    def trace(self, x: torch.Tensor, last_row: int, buf: int) -> torch.Tensor:
+        """Test aid (``pa_convnet_trace``): run what ``forward`` runs for x float32[n,3,128,128] (n <= max_crops, one group)
+        through table row ``last_row`` (-1: the input conversion alone) and return the whole of buffer ``buf`` as stored:
+        float32[max_crops * buf_floats[buf]] on the device (buf = -1: the stem input, [max_crops][134][134][4])."""
+        xd = x.to(self.device, torch.float32).contiguous()
+        floats = self.max_crops * (134 * 134 * 4 if buf < 0 else self.buf_floats[buf])
+        out = torch.empty(floats, dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.pa_convnet_trace(self._h, _ptr(xd), int(xd.shape[0]), last_row, buf, _ptr(out), out.numel() * 4, stream)
+        if rc != 0:
+            raise EngineError(rc, self._lib.pa_convnet_last_error(self._h).decode())
+        return out
+
+    def layer_forms(self) -> List[str]:
+        """The kernel form (``_lib.CN_FORMS``) each table row ran as in the last forward or trace."""
+        forms = (C.c_int32 * self.n_rows)()
+        rc = self._lib.pa_convnet_layer_forms(self._h, forms, self.n_rows)
+        if rc != 0:
+            raise EngineError(rc, "pa_convnet_layer_forms")
+        return [_lib.CN_FORMS[f] for f in forms]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x float32[n,3,128,128] -> float32[n, out_floats] on the device (groups of max_crops)."""

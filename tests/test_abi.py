@@ -124,6 +124,64 @@ def test_side_model_handles_reject_bad_tables_without_gpu(lib):
     assert rc == _lib.PA_ERR_INVALID_ARG and "unknown kind" in msg
 
 
+def test_abi_15_test_aids_refuse_bad_arguments(lib):
+    """pa_convnet_trace, pa_convnet_layer_forms and pa_lstm_layer_forms (ABI 15) refuse a bad handle, row, buffer, crop
+    count or output size before anything is enqueued (with or without a GPU: a handle whose creation stopped at the device
+    still carries its table), and their form enums match the header."""
+    import numpy as np
+
+    from playaid_core_amd import _lib, synth
+    from playaid_core_amd.rnn_action_detector import pack_lstm_blob
+
+    assert lib.pa_abi_version() == _lib.PA_ABI_VERSION == 15
+    hdr = open(os.path.join(ROOT, "include", "playaid_hip.h")).read()
+    for enum, prefix, names in (("pa_cn_form", "PA_CN_FORM_", _lib.CN_FORMS), ("pa_lstm_form", "PA_LSTM_FORM_", _lib.LSTM_FORMS)):
+        body = re.search(r"typedef enum %s \{(.*?)\} %s;" % (enum, enum), hdr, re.S).group(1)
+        vals = {int(v): name.lower() for name, v in re.findall(prefix + r"(\w+)\s*=\s*(\d+)", body)}
+        assert sorted(vals) == list(range(len(vals))) and tuple(vals[i] for i in range(len(vals))) == names
+    forms = (ctypes.c_int32 * 8)()
+    assert lib.pa_convnet_trace(None, None, 1, 0, 0, None, 0, None) == _lib.PA_ERR_INVALID_ARG
+    assert lib.pa_convnet_layer_forms(None, forms, 8) == _lib.PA_ERR_INVALID_ARG
+    assert lib.pa_lstm_layer_forms(None, forms, 8) == _lib.PA_ERR_INVALID_ARG
+
+    # a two-row table: a 3x3 convolution 0 -> 1 and a 1x1 convolution 1 -> 0; max_crops 4
+    d = dict(kind=0, cin=64, cout=64, ksize=3, stride=1, in_hw=8, in_buf=0, in_pad=1, out_buf=1, out_pad=1, res_buf=-1, relu=1, w_off=0,
+             b_off=64 * 9 * 64)
+    arr = (_lib.pa_conv_desc * 2)()
+    for i, kw in enumerate((d, dict(d, ksize=1, in_buf=1, out_buf=0))):
+        for k, v in kw.items():
+            setattr(arr[i], k, v)
+    bufs = (ctypes.c_int64 * 2)(10 * 10 * 64, 10 * 10 * 64)
+    w = np.zeros(64 * 9 * 64 + 64, np.float32)
+    h = ctypes.c_void_p(0)
+    rc = lib.pa_convnet_create(0, arr, 2, bufs, 2, w.ctypes.data_as(ctypes.c_void_p), w.size, 4, ctypes.byref(h))
+    assert h, rc
+    try:
+        x = ctypes.c_void_p(16)   # never dereferenced: every call below is refused first
+        full = 4 * 10 * 10 * 64 * 4
+        for n, row, buf, nbytes in ((0, 0, 0, full), (5, 0, 0, full), (1, 2, 0, full), (1, -2, 0, full), (1, 0, 2, full),
+                                    (1, 0, -2, full), (1, 0, 0, full - 4), (1, -1, -1, 4 * 134 * 134 * 4 * 4 - 4)):
+            assert lib.pa_convnet_trace(h, x, n, row, buf, x, nbytes, None) == _lib.PA_ERR_INVALID_ARG, (n, row, buf, nbytes)
+            assert b"pa_convnet_trace" in lib.pa_convnet_last_error(h)
+        assert lib.pa_convnet_trace(h, None, 1, 0, 0, x, full, None) == _lib.PA_ERR_INVALID_ARG
+        assert lib.pa_convnet_layer_forms(h, forms, 1) == _lib.PA_ERR_INVALID_ARG   # cap < rows
+        if rc == _lib.PA_OK:
+            assert lib.pa_convnet_layer_forms(h, forms, 2) == _lib.PA_OK and list(forms[:2]) == [0, 0]   # nothing run yet
+    finally:
+        lib.pa_convnet_destroy(h)
+
+    blob = pack_lstm_blob(synth.make_rnn_state_dict(seed=3, num_actions=9), 9)
+    hl = ctypes.c_void_p(0)
+    rc = lib.pa_lstm_create(0, 300, 512, 3, 9, 64, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, ctypes.byref(hl))
+    assert hl, rc
+    try:
+        assert lib.pa_lstm_layer_forms(hl, forms, 2) == _lib.PA_ERR_INVALID_ARG   # cap < layers
+        assert lib.pa_lstm_layer_forms(hl, None, 3) == _lib.PA_ERR_INVALID_ARG
+        assert lib.pa_lstm_layer_forms(hl, forms, 3) == _lib.PA_OK and list(forms[:3]) == [0, 0, 0]   # no forward yet
+    finally:
+        lib.pa_lstm_destroy(hl)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from playaid_core_amd import _lib
 

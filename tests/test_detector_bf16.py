@@ -249,14 +249,14 @@ def test_bf16_dtype_is_accepted_and_named():
         YoloV5Detector(synth.make_yolov5s_state_dict(), NC, (64, 96), compute_dtype="fp16")
 
 
-def test_det_forms_match_the_header_enum():
+def test_det_forms_and_abi_15_match_the_header():
     hdr = open(os.path.join(ROOT, "include", "playaid_hip.h")).read()
     body = re.search(r"typedef enum pa_det_form \{(.*?)\} pa_det_form;", hdr, re.S).group(1)
     enum = {int(v): name.lower() for name, v in re.findall(r"PA_DET_FORM_(\w+)\s*=\s*(\d+)", body)}
     assert sorted(enum) == list(range(len(enum)))
     assert tuple(enum[i] for i in range(len(enum))) == _lib.DET_FORMS
     assert _lib.DET_FORMS[15:] == ("bgemm", "bgemm_up")
-    assert re.search(r"#define PA_ABI_VERSION (\d+)", hdr).group(1) == str(_lib.PA_ABI_VERSION) == "14"
+    assert re.search(r"#define PA_ABI_VERSION (\d+)", hdr).group(1) == str(_lib.PA_ABI_VERSION) == "15"
 
 
 def test_bf16_roundings():
