@@ -53,7 +53,12 @@ typedef enum pa_status {
 
 /* per-crop status words written by the preprocess stage */
 #define PA_CROP_OK 0
-#define PA_CROP_EMPTY 1        /* empty / off-screen slice: reference returns (False, None), fighter.py:356-362 */
+#define PA_CROP_EMPTY 1        /* empty / off-screen slice: reference returns (False, None), fighter.py:356-362.
+                                 A (d x 0) slice (box off the right / left edge with exactly d rows left) is NOT
+                                 empty: ImageOps.pad skips the resize (contain size == source size) and returns
+                                 a black d x d canvas, so that crop is PA_CROP_OK with all-zero pixels. A (0 x d)
+                                 slice stays PA_CROP_EMPTY: there Pillow raises ZeroDivisionError, which the
+                                 reference does not catch (it crashes) -- a stated departure. */
 #define PA_CROP_BAD_BOX 2      /* non-finite box or square side <= 0 (reference raises) */
 #define PA_CROP_UPSCALE 3      /* reserved (was: square side < 128 px rejected; the enlarging branch is implemented now) */
 #define PA_CROP_FILTER_TOO_WIDE 4 /* bicubic support beyond the kernel's table size (scale > 3.5) */

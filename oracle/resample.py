@@ -153,15 +153,24 @@ def pil_contain_size(w: int, h: int, size: Tuple[int, int]) -> Tuple[int, int]:
 
 
 def pil_pad_black(img: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
-    """``np.array(ImageOps.pad(Image.fromarray(img), size, color="black"))``.
-    Raises ValueError for an empty input (the reference maps that to
-    ``(False, None)`` at ``fighter.py:356-357``; Pillow 12 raises
-    ZeroDivisionError for a zero-height slice and ValueError for a zero-width
-    one -- both are treated as "no crop" here)."""
+    """``np.array(ImageOps.pad(Image.fromarray(img), size, color="black"))``,
+    empty inputs included, following Pillow's own order of events:
+
+    * a zero-height input: ``ImageOps.contain`` divides by the height, and
+      Pillow raises ZeroDivisionError. The reference does not catch it
+      (``fighter.py:349-357`` catches ValueError only), so it crashes; this
+      restatement raises ValueError instead, which ``yolo_crop.square_crop``
+      maps to "no crop" -- a stated departure (``PA_CROP_EMPTY``).
+    * a zero-width input: the contain size is (0, size[1]). When that equals
+      the source size, ``Image.resize`` is skipped (a copy) and the result is
+      the all-black canvas; otherwise ``Image.resize`` raises ValueError.
+    """
     h, w = img.shape[:2]
-    if h == 0 or w == 0 or size[0] <= 0 or size[1] <= 0:
-        raise ValueError("empty image")
+    if h == 0 or size[0] <= 0 or size[1] <= 0:
+        raise ValueError("empty image (Pillow: ZeroDivisionError in ImageOps.contain)")
     rw, rh = pil_contain_size(w, h, size)
+    if (rw, rh) == (w, h) and w == 0:
+        return np.zeros((size[1], size[0], img.shape[2]), dtype=np.uint8)
     if rw <= 0 or rh <= 0:
         raise ValueError("height and width must be > 0")
     resized = pil_resize_bicubic(img, rw, rh)

@@ -19,12 +19,16 @@ def yolo_pixels(cx, cy, w, h, image_width, image_height):
     return (int(cx * image_width), int(cy * image_height), int(w * image_width), int(h * image_height))
 
 
-def square_crop(image: np.ndarray, box, output_size: int = 128, padding: int = 0):
-    """``YoloCrop.square_crop`` (``fighter.py:323-381``) -> (ok, uint8[128,128,3]).
+def square_crop_pil_stage(image: np.ndarray, box, padding: int = 0):
+    """First half of ``YoloCrop.square_crop`` (``fighter.py:330-362``): the
+    clipped slice, letterboxed to d x d by ``ImageOps.pad`` when it is not
+    square. -> (ok, uint8[d, d, 3] or None).
 
     Follows the reference statement by statement, including numpy's slice
     semantics for a negative stop (an off-screen box above/left of the frame
-    wraps the stop index around, ``fighter.py:335-343``)."""
+    wraps the stop index around, ``fighter.py:335-343``). A (0 x d) slice,
+    where the reference crashes in Pillow, is (False, None) here (see
+    ``resample.pil_pad_black``)."""
     cx, cy, cw, ch = yolo_pixels(box[0], box[1], box[2], box[3], image.shape[1], image.shape[0])
     square_dim = max(cw, ch)
     square_half = int(square_dim / 2)
@@ -40,11 +44,26 @@ def square_crop(image: np.ndarray, box, output_size: int = 128, padding: int = 0
             return False, None
     if raw_crop.shape[0] == 0 or raw_crop.shape[1] == 0:
         return False, None
+    return True, raw_crop
+
+
+def square_crop_resize_stage(raw_crop: np.ndarray, output_size: int = 128) -> np.ndarray:
+    """Second half of ``YoloCrop.square_crop`` (``fighter.py:364-381``):
+    ``imutils.resize(width=128)`` (cv2 INTER_AREA), then a black pad when the
+    height came out short."""
     crop = R.imutils_resize_width(raw_crop, output_size)
     if crop.shape[0] != output_size or crop.shape[1] != output_size:
         crop = R.pil_pad_black(crop, (output_size, output_size))
     assert crop.shape == (output_size, output_size, 3)
-    return True, crop
+    return crop
+
+
+def square_crop(image: np.ndarray, box, output_size: int = 128, padding: int = 0):
+    """``YoloCrop.square_crop`` (``fighter.py:323-381``) -> (ok, uint8[128,128,3])."""
+    ok, raw_crop = square_crop_pil_stage(image, box, padding)
+    if not ok:
+        return False, None
+    return True, square_crop_resize_stage(raw_crop, output_size)
 
 
 def runner_input_from_crop(crop_bgr: np.ndarray, output_size: int = 128) -> np.ndarray:

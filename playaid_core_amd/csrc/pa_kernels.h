@@ -175,6 +175,9 @@ hipError_t launch_wino3x3(const WinoParams& p, hipStream_t s);
 // crop preprocessing (preprocess.hip)
 // ---------------------------------------------------------------------------
 #define PA_KSIZE_MAX 15
+// Plan-internal crop status (never reported): a (d x 0) slice that ImageOps.pad turns into a black d x d canvas
+// without resizing. The kernels treat it as a failed crop (all-zero pixels); the plan reports PA_CROP_OK.
+#define PA_CROP_BLANK 0x100
 // Stage buffers of crop_fused_kernel; + 2176 B of INTER_AREA tables = 80000 B: two 512-thread
 // workgroups per CU (16 waves). Measured ladder of this choice (64 x 1080p step, kernel alone):
 // 256 threads / 50944 B (3 per CU) 0.189 ms -> 512 threads / 46592 B 0.169 -> 512 threads / 77824 B

@@ -215,8 +215,15 @@ __device__ __forceinline__ BandLds band_lds(const CropPlan& pl, const BandRows& 
     const int s0 = align_up(n0 * l.p0, 16), s1 = align_up(n0 * l.p1, 16), s2 = align_up(n2 * l.p1, 16);
     l.off1 = s0;
     if (pl.need_h && pl.need_v) {
-        l.off2 = 0;
-        l.total = s0 + s1 > s2 ? s0 + s1 : s2;
+        // B2 reuses B0's space only when it fits there: the vertical pass reads B1 while it writes B2, so a B2
+        // larger than B0 (an enlarging slice: more / wider resized rows than source rows) must not reach B1
+        if (s2 <= s0) {
+            l.off2 = 0;
+            l.total = s0 + s1;
+        } else {
+            l.off2 = s0 + s1;
+            l.total = s0 + s1 + s2;
+        }
     } else if (pl.need_h) {
         l.off2 = 0;  // unused
         l.total = s0 + s1;
@@ -323,7 +330,10 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
         if (pl.sh != d || pl.sw != d) {
             // ImageOps.pad(raw_crop, (d, d), color="black")
             if (pl.sh == 0 || pl.sw == 0) {
-                pl.status = PA_CROP_EMPTY;
+                // Pillow's contain size of a (sh x 0) slice is (0, d): equal to the source size when sh == d, so
+                // ImageOps.pad skips the resize and returns the black d x d canvas (the reference's crop is all zero);
+                // any other empty slice raises (ValueError -> (False, None), or ZeroDivisionError for sh == 0)
+                pl.status = (pl.sw == 0 && pl.sh == d) ? PA_CROP_BLANK : PA_CROP_EMPTY;
             } else {
                 int rw = d, rh = d;
                 const double im_ratio = (double)pl.sw / (double)pl.sh;
@@ -422,7 +432,7 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
         }
         p.plans[crop] = pl;
         plan_sh = pl;
-        if (p.status) p.status[crop] = pl.status;
+        if (p.status) p.status[crop] = pl.status == PA_CROP_BLANK ? PA_CROP_OK : pl.status;
     }
     }
     __syncthreads();

@@ -12,8 +12,11 @@ seeds/geometry and expected outputs:
 * ai_output_128.yaml -- run_action_recognition output for the 128-frame 1080p
                         plumbing config (BASELINE.json configs[0])
 
-The reference itself cannot run in this container, so
-these are outputs of the restatement in oracle/, not of the reference.
+These are outputs of the restatement in oracle/, not of the reference. The
+known answers of the reference's own functions (square_crop, the log-projection
+box, the window sampler, the label text) are in reference_kats.json, written by
+make_reference_kats.py from a checkout of the reference; tests/test_reference_kats.py
+pins the oracle, the host mirrors and the HIP kernels to that file.
 """
 import json
 import os

@@ -40,6 +40,16 @@ def test_pad_black_empty_raises_like_reference_maps_to_false():
         R.pil_pad_black(np.zeros((10, 0, 3), np.uint8), (20, 20))
 
 
+def test_pad_black_zero_width_follows_pillows_contain_rule():
+    # (d x 0) -> (d, d): the contain size (0, d) equals the source size, so Pillow skips the resize and
+    # returns the black canvas; (10 x 0) -> (20, 20) still raises (above)
+    for h, s in [(20, 20), (128, 128)]:
+        a = np.zeros((h, 0, 3), np.uint8)
+        ref = np.array(ImageOps.pad(Image.fromarray(a), (s, s), color="black"))
+        out = R.pil_pad_black(a, (s, s))
+        assert out.shape == (s, s, 3) and np.array_equal(out, ref) and not out.any()
+
+
 def test_area_constant_image_stays_constant():
     for d, oh in [(315, 128), (200, 127), (256, 128), (384, 128), (129, 128), (577, 128)]:
         a = np.full((d, d, 3), 173, np.uint8)
