@@ -646,7 +646,24 @@ int pa_convnet_create(int32_t device, const pa_conv_desc* descs, int32_t n_descs
                       int32_t n_bufs, const float* weights_host, size_t n_weights, int32_t max_crops, pa_convnet** out);
 /* The same with the convolutions' arithmetic chosen (ABI 11): PA_DTYPE_F32 (= pa_convnet_create) or PA_DTYPE_EMULATED_F32 -- every
  * convolution that is not in Winograd form and has enough 128-pixel tiles at max_crops to fill half the chip runs on the emulated-fp32
- * persistent GEMM (csrc/psgemm.hip), the rest on the exact kernels. Never the default. */
+ * persistent GEMM (csrc/psgemm.hip), the rest on the exact kernels. Never the default.
+ *
+ * PA_DTYPE_BF16 (ABI 15, no new symbol; never the default): bf16 storage and bf16 products. Rounding model:
+ *   - input: the fp32 NCHW image rounded to nearest even (RNE) to bf16 (the engine's bf16 conversion into [134][134][4]);
+ *   - stem (kind 1): the folded 7x7 weights RNE to bf16 once at create ([64][224] as laid out); products on
+ *     v_mfma_f32_32x32x16_bf16, fp32 accumulation; then fp32 bias, ReLU and the 3x3/2 max-pool; ONE RNE to bf16 on the store;
+ *   - convolutions (kind 0), every row on csrc/bgemm.hip: the folded fp32 weights RNE to bf16 once at create; activations read
+ *     as stored (bf16); products on v_mfma_f32_32x32x16_bf16, fp32 accumulation; + fp32 bias, + the stored bf16 residual in
+ *     fp32 BEFORE the ReLU, ReLU, ONE RNE on the store. A split-K row sums the fp32 partials of contiguous k-ranges in split
+ *     order (the bias inside the first), then runs the same epilogue; results are bitwise repeatable. No Winograd form;
+ *   - global average pool (kind 2): the stored bf16 values summed in fp32 in a fixed order (row by row), times 1 / hw^2; fp32
+ *     output [n][C], so the last row of a bf16 table must be a pool.
+ * Buffers written by stem or convolution rows hold bf16 (2 bytes per element; buf_floats_per_crop still counts elements), those
+ * written by a pool fp32. Create refuses, naming the row, a buffer written in both types, a row reading an fp32 buffer, a
+ * convolution bgemm.hip cannot take (ReLU or none) and a table that does not end in a pool. Split-K: where the unsplit grid of a
+ * row at the call's n is below a quarter of the CUs (64 workgroups) and K >= 72 x 32, S in {2, 4, 8} with tiles x S <= 256 and at
+ * least 4 k-steps per slice, the largest; PA_CONVNET_BG_SPLIT=0 or 1 (read once) turns it off, =n forces S = n on every row whose grid
+ * is below half the CUs (A/B runs). */
 int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n_descs, const int64_t* buf_floats_per_crop,
                             int32_t n_bufs, const float* weights_host, size_t n_weights, int32_t max_crops, int32_t compute_dtype,
                             pa_convnet** out);
@@ -658,7 +675,8 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
  * tiles, knobs -- for layers 0..last_row (-1: the input conversion alone), then copies the WHOLE buffer `buf` as stored to `out`
  * (device): max_crops x buf_floats_per_crop[buf] floats, zero borders and the crops at n and above included; each layer writes
  * crop i of its output at i x its own per-crop geometry ((hw + 2 pad)^2 x channels). buf = -1 is the stem's input
- * [max_crops][134][134][4]. PA_ERR_INVALID_ARG for a row or buffer out of range, n outside 1..max_crops or out_bytes short of
+ * [max_crops][134][134][4]. Under PA_DTYPE_BF16 a bf16 buffer (and buf = -1) is copied as stored, 2 bytes per element, and
+ * out_bytes is checked against that size. PA_ERR_INVALID_ARG for a row or buffer out of range, n outside 1..max_crops or out_bytes short of
  * the buffer; nothing is enqueued then. pa_convnet_layer_forms: the form each layer ran as in the last forward or trace (a
  * launcher that refuses a shape passes the layer on to the next form); forms: host int32[cap], cap >= n_descs. */
 int pa_convnet_trace(pa_convnet* h, const float* x, int32_t n, int32_t last_row, int32_t buf, void* out, size_t out_bytes, void* stream);
@@ -671,7 +689,10 @@ typedef enum pa_cn_form {
     PA_CN_FORM_IGEMM_128x128 = 5,   /* implicit GEMM, igemm.hip, 128 x 128 tiles */
     PA_CN_FORM_IGEMM_128x64 = 6,    /* ... 128 x 64 tiles */
     PA_CN_FORM_IGEMM_64x64 = 7,     /* ... 64 x 64 tiles */
-    PA_CN_FORM_PSGEMM = 8           /* emulated-fp32 persistent GEMM, psgemm.hip (PA_DTYPE_EMULATED_F32) */
+    PA_CN_FORM_PSGEMM = 8,          /* emulated-fp32 persistent GEMM, psgemm.hip (PA_DTYPE_EMULATED_F32) */
+    PA_CN_FORM_BGEMM = 9,           /* one-slice bf16 persistent GEMM, bgemm.hip (PA_DTYPE_BF16) */
+    PA_CN_FORM_BGEMM_SPLITK = 10,   /* ... its split-K form */
+    PA_CN_FORM_AVGPOOL_BF16 = 11    /* global average pool of a bf16 map, fp32 out (PA_DTYPE_BF16) */
 } pa_cn_form;
 int pa_convnet_layer_forms(const pa_convnet* h, int32_t* forms, int32_t cap);
 

@@ -26,7 +26,8 @@ PA_TRACE_STAGES = 20
 DET_FORMS = ("not_run", "stem_direct", "stem_bf16", "wino", "patch", "pgemm", "pgemm_up", "psgemm", "psgemm_up", "igemm", "sppf",
              "maxpool", "upsample", "absorbed", "decode", "bgemm", "bgemm_up")
 # pa_cn_form / pa_lstm_form (ABI 15): the form a conv-net table row / an LSTM layer ran as, by value
-CN_FORMS = ("not_run", "stem_pool", "avgpool", "wino", "patch", "igemm_128x128", "igemm_128x64", "igemm_64x64", "psgemm")
+CN_FORMS = ("not_run", "stem_pool", "avgpool", "wino", "patch", "igemm_128x128", "igemm_128x64", "igemm_64x64", "psgemm",
+            "bgemm", "bgemm_splitk", "avgpool_bf16")
 LSTM_FORMS = ("not_run", "steps", "u1", "u2", "u4", "u8", "mfma")
 
 PA_OK = 0

@@ -14,6 +14,12 @@
 //     bf16 value. OUT_F32: the Detect heads' fp32 store instead (no residual, no up-sampling).
 // Loader waves 4-7: per k-step 2 activation pieces (128 rows x 64 bytes = 8 KiB) and BN / 64 weight pieces (at least one) of 1 KiB
 // each, counted waits as in psgemm.hip.
+//
+// Split-K form (SPLIT, the ResNet-50 table's small maps: launch_bgemm with p.splitk = S > 1): one workgroup per (output tile, k-slice),
+// slice s covering k-steps [s nk / S, (s + 1) nk / S); slice 0's accumulators start from the bias, the others' from zero. Each
+// consumer wave writes its 32 pixels x BN channels of fp32 partials to the slab and draws the ticket of (tile, wave); the last of
+// the S waves to arrive sums the S partials IN SPLIT ORDER (its own read back from the slab as well, so the sum does not depend on
+// who was last), resets the ticket and runs the unsplit epilogue (residual, activation, one rounding on the store).
 #include "pa_kernels.h"
 
 #include <algorithm>
@@ -72,9 +78,10 @@ constexpr int bg_b_pieces(int bn) { return bn == 32 ? 4 : bn / 16; }   // 1 KiB 
 
 // ACT: 0 none, 1 ReLU, 2 SiLU. RES: a bf16 residual addressed like the output, added before (ResNet) or after (YOLOv5's Bottleneck,
 // p.res_after) the activation; it may alias the output (every value is read by the lane that writes it). OUT_F32: fp32 output.
-template <int BN, int NSTAGE, int ACT, bool RES, bool OUT_F32>
+template <int BN, int NSTAGE, int ACT, bool RES, bool OUT_F32, bool SPLIT = false>
 __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const unsigned short* __restrict__ wsp, unsigned out_bytes, unsigned up_bytes) {
     static_assert(!(RES && OUT_F32), "the fp32-output form is the Detect heads': no residual");
+    static_assert(!(SPLIT && OUT_F32), "the split-K form stores bf16");
     constexpr int BM = 128, CB = BN / 32;
     constexpr int A_BYTES = BM * 64;
     constexpr int PB = bg_b_pieces(BN) / 4;       // weight pieces per loader wave and k-step
@@ -85,14 +92,19 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
     __shared__ __attribute__((aligned(1024))) unsigned char lds[NSTAGE * STAGE + BN * 4];
 
     // --- this workgroup's tiles (psgemm.hip): one channel column, every lm-th pixel tile of its XCD's contiguous share ----
+    // (SPLIT: the one tile w_tile = tile_m * TN + tile_n of workgroup w_tile * S + slice, k-steps ks_lo .. ks_lo + nk - 1)
     const int b = blockIdx.x, xcd = b & 7, local = b >> 3, per = p.pg_per;
     const int TN = p.tiles_n, TM = p.tiles_m;
-    const int LM = per / TN;
-    const int tile_n = local % TN, lm = local / TN;
-    const int t_lo = (int)(((long long)xcd * TM) >> 3), t_hi = (int)(((long long)(xcd + 1) * TM) >> 3);
+    const int S = SPLIT ? p.splitk : 1;
+    const int w_tile = SPLIT ? b / S : 0, slice = SPLIT ? b - w_tile * S : 0;
+    const int LM = SPLIT ? 1 : per / TN;
+    const int tile_n = SPLIT ? w_tile % TN : local % TN, lm = SPLIT ? 0 : local / TN;
+    const int t_lo = SPLIT ? w_tile / TN : (int)(((long long)xcd * TM) >> 3), t_hi = SPLIT ? t_lo + 1 : (int)(((long long)(xcd + 1) * TM) >> 3);
     const int nt = t_lo + lm < t_hi ? (t_hi - t_lo - lm + LM - 1) / LM : 0;
     if (nt == 0) return;
-    const int nk = p.ktot >> 5;
+    const int nk_all = p.ktot >> 5;
+    const int ks_lo = SPLIT ? slice * nk_all / S : 0;
+    const int nk = SPLIT ? (slice + 1) * nk_all / S - ks_lo : nk_all;
     const int total = nt * nk;
 
     const int tid = threadIdx.x;
@@ -101,7 +113,7 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
     const unsigned lds_base = (unsigned)(size_t)(lds_f*)(float*)lds;
 
     float* const bias_s = (float*)(lds + NSTAGE * STAGE);
-    if (tid < BN) bias_s[tid] = p.bias ? p.bias[tile_n * BN + tid] : 0.f;
+    if (tid < BN) bias_s[tid] = p.bias && slice == 0 ? p.bias[tile_n * BN + tid] : 0.f;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the bias store complete before the first barrier: psgemm.hip)
 
     if (wave_id >= 4) {
@@ -110,7 +122,7 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
         const int row0 = ltid >> 2;                          // 0..63: four lanes per 64-byte row
         const int colq = (ltid & 3) ^ ((row0 >> 2) & 3);     // LDS chunk c of activation row r holds logical chunk c ^ ((r >> 2) & 3)
         const i32x4 act_rs = bg_rsrc(p.act, 0xffffffffu);
-        const i32x4 wgt_rs = bg_rsrc(wsp + (size_t)tile_n * nk * (B_BYTES / 2), 0xffffffffu);
+        const i32x4 wgt_rs = bg_rsrc(wsp + (size_t)tile_n * nk_all * (B_BYTES / 2), 0xffffffffu);
         // pixel addressing in bytes (psgemm.hip's, with a lane's distance from the run's first pixel up to 63)
         const int in_ps = p.in_px_stride * p.stride * 2, in_rs = p.in_row_stride * p.stride * 2;
         const int in_wrap_x = in_rs - p.wo * in_ps;
@@ -145,7 +157,13 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
             }
             return m_base + row0 < p.M ? off : in_last;
         };
-        int i_tile = t_lo + lm, i_ks = 0, i_ky = 0, i_kx = 0, i_kc = 0;
+        int i_tile = t_lo + lm, i_ks = ks_lo, i_ky = 0, i_kx = 0, i_kc = 0;
+        if (SPLIT) {   // the slice's first k-step: tap (ky, kx), channel offset kc
+            const int k0 = ks_lo * 32, tap = k0 / p.chunk;
+            i_kc = k0 - tap * p.chunk;
+            i_ky = tap / p.kw_taps;
+            i_kx = tap - i_ky * p.kw_taps;
+        }
         int a_off[2];
         auto rows_of = [&](int tile_m) {
 #pragma unroll
@@ -167,7 +185,7 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
                 i_kc = 0;
                 if (++i_kx == p.kw_taps) { i_kx = 0; ++i_ky; }
             }
-            if (++i_ks == nk) {
+            if (++i_ks == ks_lo + nk) {   // (SPLIT: behind the slice's last issue; nothing is issued after it)
                 i_ks = 0; i_ky = 0; i_kx = 0; i_kc = 0;
                 i_tile += LM;
                 rows_of(i_tile < t_hi ? i_tile : t_hi - 1);
@@ -279,44 +297,8 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
 
     int slot = 0, ks = 0, t = 0;
     unsigned o_off = 0, u_off = 0;
-    // one k-step: its operands (cur) are in flight or in registers; the next k-step's are read behind the barrier while the
-    // matrix instructions of this one run. Every k-step of every tile, one barrier each (the loaders' count).
-    auto step = [&](const u32x4 (&ca)[2], const u32x4 (&cw)[CB][2], u32x4 (&na)[2], u32x4 (&nw)[CB][2]) {
-        if (ks == 0) {
-            const int tile_m = t_lo + lm + t * LM;
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 b4 = *(const f32x4*)(bias_s + cb * 32 + 8 * g + 4 * lh);
-                    acc[cb][4 * g] = b4.x; acc[cb][4 * g + 1] = b4.y; acc[cb][4 * g + 2] = b4.z; acc[cb][4 * g + 3] = b4.w;
-                }
-            o_off = out_offset(tile_m * BM + wave_id * 32);
-            u_off = p.up_out ? up_offset(tile_m * BM + wave_id * 32) : 0u;
-        }
-        if (RES && ks == nk - 1) {   // the tile's residual values, requested ahead of the last k-step's matrix instructions
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const unsigned off = o_off == 0x80000000u ? o_off : o_off + (unsigned)(cb * 32 + 8 * gq) * 2u;
-                    res2[cb][gq] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(res_rs, off, 0, 0));
-                }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this k-step's operands are in registers: its slot may be refilled
-        __builtin_amdgcn_s_barrier();                          // stage g + 1 landed (the loaders waited for it)
-        __builtin_amdgcn_sched_barrier(0);
-        const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
-        read(na, nw, (unsigned)(nslot * STAGE));   // (the last k-step reads a slot nobody refills: stale, unused)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int cb = 0; cb < CB; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, cw[cb][h]), __builtin_bit_cast(bf16x8, ca[h]), acc[cb], 0, 0, 0);
-        slot = nslot;
-        if (++ks < nk) return;
-        ks = 0;
-        ++t;
-        // ---- epilogue of the tile, from the accumulators: lane = pixel lr of the wave's 32, channels ch0 + 32 cb + 8 g + 0..3 ----
+    // ---- epilogue of a tile, from the accumulators: lane = pixel lr of the wave's 32, channels ch0 + 32 cb + 8 g + 0..3 ----
+    auto epilogue = [&]() {
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
@@ -345,6 +327,45 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
                 }
             }
     };
+    // one k-step: its operands (cur) are in flight or in registers; the next k-step's are read behind the barrier while the
+    // matrix instructions of this one run. Every k-step of every tile, one barrier each (the loaders' count).
+    auto step = [&](const u32x4 (&ca)[2], const u32x4 (&cw)[CB][2], u32x4 (&na)[2], u32x4 (&nw)[CB][2]) {
+        if (ks == 0) {
+            const int tile_m = t_lo + lm + t * LM;
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 b4 = *(const f32x4*)(bias_s + cb * 32 + 8 * g + 4 * lh);
+                    acc[cb][4 * g] = b4.x; acc[cb][4 * g + 1] = b4.y; acc[cb][4 * g + 2] = b4.z; acc[cb][4 * g + 3] = b4.w;
+                }
+            o_off = out_offset(tile_m * BM + wave_id * 32);
+            u_off = p.up_out ? up_offset(tile_m * BM + wave_id * 32) : 0u;
+        }
+        if (RES && !SPLIT && ks == nk - 1) {   // the tile's residual values, requested ahead of the last k-step's matrix instructions
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const unsigned off = o_off == 0x80000000u ? o_off : o_off + (unsigned)(cb * 32 + 8 * gq) * 2u;
+                    res2[cb][gq] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(res_rs, off, 0, 0));
+                }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this k-step's operands are in registers: its slot may be refilled
+        __builtin_amdgcn_s_barrier();                          // stage g + 1 landed (the loaders waited for it)
+        __builtin_amdgcn_sched_barrier(0);
+        const int nslot = slot + 1 == NSTAGE ? 0 : slot + 1;
+        read(na, nw, (unsigned)(nslot * STAGE));   // (the last k-step reads a slot nobody refills: stale, unused)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, cw[cb][h]), __builtin_bit_cast(bf16x8, ca[h]), acc[cb], 0, 0, 0);
+        slot = nslot;
+        if (++ks < nk) return;
+        ks = 0;
+        ++t;
+        if (!SPLIT) epilogue();
+    };
 
     __builtin_amdgcn_s_barrier();   // stage 0 (and bias_s) in LDS
     read(a0, w0, 0u);
@@ -354,6 +375,46 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
         step(a1, w1, a0, w0);
     }
     if (g < total) step(a0, w0, a1, w1);
+    if constexpr (SPLIT) {
+        // wino.hip's split-K hand-off (its comment gives the argument), per wave instead of per workgroup: every slab value is an
+        // agent-scope atomic store (written through the storing XCD's L2), the wave waits for them (vmcnt(0) as inline assembly)
+        // before lane 0's agent-scope ticket add, and the last arriver reads the slab with agent-scope atomic loads (served by L2 /
+        // memory, never a stale L1 line). Slab: [workgroup][wave][value e][lane], each store instruction one 256-byte run.
+        constexpr int NV = CB * 16;
+        float* const mine = p.slab + ((size_t)b * 4 + wave_id) * (NV * 64) + lane;
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) __hip_atomic_store(mine + (cb * 16 + e) * 64, acc[cb][e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        int32_t* const ticket = p.tickets + w_tile * 4 + wave_id;
+        int drawn = 0;
+        if (lane == 0) drawn = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        drawn = __builtin_amdgcn_readlane(drawn, 0);
+        asm volatile("" ::: "memory");
+        if (drawn != S - 1) return;
+        if (lane == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+        const float* const all = p.slab + ((size_t)w_tile * S * 4 + wave_id) * (NV * 64) + lane;   // slice sl: + sl * 4 * NV * 64
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[cb][e] = __hip_atomic_load(all + (cb * 16 + e) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int sl = 1; sl < S; ++sl)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    acc[cb][e] += __hip_atomic_load(all + ((size_t)sl * 4 * NV + cb * 16 + e) * 64, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (RES) {
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const unsigned off = o_off == 0x80000000u ? o_off : o_off + (unsigned)(cb * 32 + 8 * gq) * 2u;
+                    res2[cb][gq] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(res_rs, off, 0, 0));
+                }
+        }
+        epilogue();
+    }
 }
 
 int bgemm_pick_bn(int N, int residual) { return psgemm_pick_bn(N, residual); }
@@ -389,6 +450,36 @@ void bgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned 
         }
 }
 
+// workgroups per XCD of the unsplit persistent grid over tiles_m x tiles_n tiles (the grid is 8 x that): one channel column each,
+// lm pixel tiles of its XCD's share in turn, about 32 per XCD. launch_bgemm launches it; bgemm_pick_split judges it.
+static int bg_unsplit_per(int tiles_m, int tiles_n) {
+    const int share = (tiles_m + 7) / 8;
+    int lm = 32 / tiles_n;
+    lm = lm < 1 ? 1 : (lm > share ? share : lm);
+    return lm * tiles_n;
+}
+
+int bgemm_pick_split(const GemmParams& p, int force) {
+    const int bn = bgemm_pick_bn(p.N, p.residual != nullptr);
+    if (bn == 0 || p.M <= 0 || force == 0 || force == 1) return 1;
+    const int tn = p.N / bn, tm = (p.M + 127) / 128;
+    const int grid = 8 * bg_unsplit_per(tm, tn);   // the unsplit grid launch_bgemm would launch
+    if (grid >= 128) return 1;   // at least half the CUs (256 on an MI355X) busy
+    const int tiles = tm * tn, nk = p.ktot / 32;
+    auto fits = [&](int S) { return tiles * S <= BGEMM_SLAB_ITEMS && 4 * tiles <= BGEMM_TICKETS && nk / S >= 4; };
+    if (force > 1) return force <= 8 && fits(force) ? force : 1;
+    // what the per-row A/B of the ResNet-50 at 64 crops kept (profiles/r07_resformer_bf16_rows_ab.txt, three runs),
+    // split time over unsplit time: the 3x3 rows on 4 x 4 maps (grid 32, 144 k-steps) 0.48-0.90 at S = 4 or 8 (one outlier, 1.12,
+    // against 0.72 for the same row and S in the next column); the 3x3 rows on 8 x 8 maps (grid 64, 72 k-steps) 0.84-1.12 at S = 4,
+    // a wash; the 1x1 rows on 8 x 8 maps (32 k-steps) 0.86-1.47 at S = 4, slower in 9 of 10; the 1x1 rows on 4 x 4 maps (64
+    // k-steps) 0.90-1.26 at S = 8, 0.58-0.82 at S = 4 in one run only. The same row in the same form varies 0.68-1.20 between
+    // processes under this measurement, so only the classes that were faster in every run are split.
+    if (grid >= BGEMM_SPLIT_MAX_GRID || nk < BGEMM_SPLIT_MIN_KSTEPS) return 1;
+    for (int S = 8; S >= 2; S >>= 1)
+        if (fits(S)) return S;
+    return 1;
+}
+
 // Conv mode of GemmParams with bf16 storage behind the float* fields (every stride and count in ELEMENTS): act, residual and
 // up_out bf16, out bf16 or (out_f32) fp32. out_elems / up_elems: elements from p.out / p.up_out to the end of the buffer.
 // Refuses (hipErrorInvalidValue) what the 32-bit byte offsets of the loaders and the store descriptors cannot span: the input
@@ -409,10 +500,7 @@ hipError_t launch_bgemm(const GemmParams& p_in, const unsigned short* wsp, size_
         return hipErrorInvalidValue;
     p.tiles_n = p.N / bn;
     p.tiles_m = (p.M + 127) / 128;
-    const int share = (p.tiles_m + 7) / 8;
-    int lm = 32 / p.tiles_n;
-    lm = lm < 1 ? 1 : (lm > share ? share : lm);
-    const int per = lm * p.tiles_n;
+    const int per = bg_unsplit_per(p.tiles_m, p.tiles_n);
     const int grid = per * 8;
     auto magic = [](int d) { return (unsigned)std::min<unsigned long long>(((1ull << 32) + d - 1) / d, 0xffffffffull); };
     p.pg_per = per;
@@ -422,6 +510,30 @@ hipError_t launch_bgemm(const GemmParams& p_in, const unsigned short* wsp, size_
     p.pg_nwx = 1 + 30 / p.wo;
     p.pg_nwy = (p.pg_ho - 1 + p.pg_nwx) / p.pg_ho;
     const unsigned out_bytes = (unsigned)(out_elems * oe), up_bytes = (unsigned)(up_elems * 2);
+    if (p.splitk > 1) {
+        // split-K: workgroup w_tile * S + slice; the slab holds BGEMM_SLAB_ITEMS workgroups, the tickets 4 per tile
+        const int S = p.splitk, tiles = p.tiles_m * p.tiles_n;
+        if (out_f32 || p.up_out || !p.slab || !p.tickets || S > 8 || tiles * S > BGEMM_SLAB_ITEMS || 4 * tiles > BGEMM_TICKETS ||
+            p.ktot / 32 < S)
+            return hipErrorInvalidValue;
+#define PA_BG_SPLIT2(BN_, RES_)                                                                                                       \
+    do {                                                                                                                             \
+        if (p.relu == 1) hipLaunchKernelGGL((bgemm_kernel<BN_, 4, 1, RES_, false, true>), dim3(tiles * S), dim3(512), 0, s, p, wsp, out_bytes, 0u); \
+        else if (p.relu == 0) hipLaunchKernelGGL((bgemm_kernel<BN_, 4, 0, RES_, false, true>), dim3(tiles * S), dim3(512), 0, s, p, wsp, out_bytes, 0u); \
+        else return hipErrorInvalidValue;                                                                                            \
+    } while (0)
+#define PA_BG_SPLIT(BN_)                                                                                                             \
+    do {                                                                                                                             \
+        if (p.residual) PA_BG_SPLIT2(BN_, true);                                                                                     \
+        else PA_BG_SPLIT2(BN_, false);                                                                                               \
+    } while (0)
+        if (bn == 128) PA_BG_SPLIT(128);
+        else if (bn == 64) PA_BG_SPLIT(64);
+        else PA_BG_SPLIT(32);
+#undef PA_BG_SPLIT
+#undef PA_BG_SPLIT2
+        return hipGetLastError();
+    }
 #define PA_BG_LAUNCH2(BN_, RES_, F32_)                                                                                                \
     do {                                                                                                                             \
         if (p.relu == 2) hipLaunchKernelGGL((bgemm_kernel<BN_, 4, 2, RES_, F32_>), dim3(grid), dim3(512), 0, s, p, wsp, out_bytes, up_bytes);     \

@@ -9,6 +9,9 @@
 //           stride-1 3x3 layers it covers, the im2col engine (igemm.hip) for everything else (1x1 = a GEMM);
 //   kind 1  the 7x7/2 stem + BatchNorm + ReLU + 3x3/2 max-pool of a 128 x 128 x 3 input (stem_pool.hip);
 //   kind 2  global average pool of the interior.
+// Under PA_DTYPE_BF16 (never the default) the stem and convolution rows store bf16: the stem on stem_pool.hip's bf16 form, every
+// convolution on the one-slice bf16 GEMM (bgemm.hip), in its split-K form where the unsplit grid would leave most of the chip idle,
+// the pool on a bf16 twin of the fp32 one (fp32 out). Rounding model: include/playaid_hip.h next to pa_convnet_create_dtype.
 // Nothing here is specific to ResNet-50; the table in playaid_core_amd/resnet_transformer_detector.py is.
 #include "pa_kernels.h"
 #include "../../include/playaid_hip.h"
@@ -37,6 +40,22 @@ __global__ __launch_bounds__(256) void avgpool_any_kernel(const float* __restric
     }
 }
 
+// the same over a bf16 map (PA_DTYPE_BF16): the stored values summed in fp32 in the same fixed order (row by row), fp32 out
+__global__ __launch_bounds__(256) void avgpool_bf16_any_kernel(const unsigned short* __restrict__ in, float* __restrict__ out, int n, int hw, int pad, int C) {
+    const int w = hw + 2 * pad;
+    const size_t total = (size_t)n * C;
+    const float inv = 1.f / (float)(hw * hw);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        const size_t img = i / C;
+        const unsigned short* src = in + img * w * w * C + c;
+        float sum = 0.f;
+        for (int y = 0; y < hw; ++y)
+            for (int x = 0; x < hw; ++x) sum += __uint_as_float((unsigned)src[(size_t)((y + pad) * w + x + pad) * C] << 16);
+        out[i] = sum * inv;
+    }
+}
+
 }  // namespace
 }  // namespace pa
 
@@ -44,7 +63,7 @@ struct pa_convnet {
     int device = 0, max_crops = 0;
     std::vector<pa_conv_desc> descs;
     std::vector<float*> bufs;
-    std::vector<size_t> buf_floats;  // per crop
+    std::vector<size_t> buf_floats;  // per crop (elements)
     float* weights = nullptr;
     size_t n_weights = 0;
     float* wino_weights = nullptr;      // the stride-1 3x3 layers' filters in the Winograd kernel's layout (wino.hip)
@@ -53,7 +72,13 @@ struct pa_convnet {
     int compute_dtype = PA_DTYPE_F32;          // PA_DTYPE_EMULATED_F32: the layers listed in split_off run on psgemm.hip
     unsigned short* split_weights = nullptr;   // those layers' weights as three bf16 slices (psgemm_pack_weights)
     std::vector<long long> split_off;          // per layer: element offset into split_weights, -1 = the exact kernel
-    float* x0 = nullptr;  // [max_crops][134][134][4] model input of the stem
+    // PA_DTYPE_BF16: every stem and convolution row stores bf16 (the buffers it writes hold 2-byte elements), the pool fp32
+    std::vector<char> buf_bf16;                // per buffer: 1 = bf16 elements
+    unsigned short* bg_weights = nullptr;      // per row: the stem's [64][224] or bgemm_pack_weights' plane, RNE bf16
+    std::vector<long long> bg_off;             // per row: element offset into bg_weights, -1 = none
+    float* bg_slab = nullptr;                  // bgemm split-K partials: BGEMM_SLAB_ITEMS workgroups x 128 x 128 fp32
+    int32_t* bg_tickets = nullptr;             // BGEMM_TICKETS of them, zero between launches
+    float* x0 = nullptr;  // [max_crops][134][134][4] model input of the stem (bf16 elements under PA_DTYPE_BF16)
     std::vector<int32_t> forms;  // per layer: the pa_cn_form the last forward or trace launched it as (pa_convnet_layer_forms)
     std::string last_error;
 };
@@ -72,6 +97,51 @@ void out_geom(const pa_conv_desc& d, int* hw, int* c) {
     else { *hw = d.in_hw / d.stride; *c = d.cout; }
 }
 
+unsigned short cn_bf16_rne(float x) {
+    uint32_t u;
+    memcpy(&u, &x, 4);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (unsigned short)(u >> 16);
+}
+
+bool is_bf16(const pa_convnet* h, int buf) { return h->compute_dtype == PA_DTYPE_BF16 && (buf < 0 || h->buf_bf16[buf]); }
+
+// PA_CONVNET_BG_SPLIT (read once): unset = bgemm_pick_split's rule, 0 or 1 = no split-K, n = S forced to n on every row whose
+// unsplit grid is below half the CUs (A/B runs)
+int bg_split_knob() {
+    static const int v = getenv("PA_CONVNET_BG_SPLIT") ? atoi(getenv("PA_CONVNET_BG_SPLIT")) : -1;
+    return v;
+}
+
+// a convolution row's GemmParams for n crops: conv mode, strides and counts in elements, no pointers (create validates the
+// geometry before anything is allocated; convnet_run fills them in)
+pa::GemmParams conv_geometry(const pa_conv_desc& d, int n) {
+    const int out_hw = d.in_hw / d.stride;
+    const int in_w = d.in_hw + 2 * d.in_pad, out_w = out_hw + 2 * d.out_pad;
+    pa::GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = n * out_hw * out_hw;
+    p.N = d.cout;
+    p.taps = d.ksize * d.ksize;
+    p.kw_taps = d.ksize;
+    p.chunk = d.cin;
+    p.ktot = p.taps * p.chunk;
+    p.howo = out_hw * out_hw;
+    p.wo = out_hw;
+    p.in_px_stride = d.cin;
+    p.in_row_stride = in_w * d.cin;
+    p.in_img_stride = in_w * in_w * d.cin;
+    p.stride = d.stride;
+    p.off_y = p.off_x = d.in_pad - (d.ksize - 1) / 2;
+    p.out_px_stride = d.cout;
+    p.out_row_stride = out_w * d.cout;
+    p.out_img_stride = out_w * out_w * d.cout;
+    p.out_pad = d.out_pad;
+    p.relu = d.relu;
+    p.splitk = 1;
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -88,7 +158,7 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
     if (!out) return PA_ERR_INVALID_ARG;
     *out = nullptr;
     if (!descs || n_descs < 1 || !buf_floats_per_crop || n_bufs < 1 || !weights_host || n_weights < 1 || max_crops < 1 ||
-        (compute_dtype != PA_DTYPE_F32 && compute_dtype != PA_DTYPE_EMULATED_F32))
+        (compute_dtype != PA_DTYPE_F32 && compute_dtype != PA_DTYPE_EMULATED_F32 && compute_dtype != PA_DTYPE_BF16))
         return PA_ERR_INVALID_ARG;
     pa_convnet* h = new pa_convnet();
     *out = h;
@@ -98,6 +168,7 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
     h->descs.assign(descs, descs + n_descs);
     h->forms.assign(n_descs, PA_CN_FORM_NOT_RUN);
     h->buf_floats.assign(buf_floats_per_crop, buf_floats_per_crop + n_bufs);
+    h->buf_bf16.assign(n_bufs, compute_dtype == PA_DTYPE_BF16 ? 1 : 0);
     // validate the table: buffer indices, weight ranges, buffer sizes, one geometry per bordered buffer
     struct Geom { int hw = -1, pad = -1, c = -1; };
     std::vector<Geom> geom(n_bufs);
@@ -139,6 +210,33 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
             return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": unknown kind");
         }
     }
+    if (compute_dtype == PA_DTYPE_BF16) {
+        // element type of each buffer from its writers: stem and convolutions bf16, the pool fp32; one type per buffer, every row
+        // reads bf16, every convolution one bgemm takes, and the table ends in a pool (pa_convnet_forward's out is fp32)
+        std::vector<int> wrote(n_bufs, -1);   // -1 unwritten, 1 bf16, 0 fp32
+        for (int i = 0; i < n_descs; ++i) {
+            const pa_conv_desc& d = h->descs[i];
+            const int t = d.kind == 2 ? 0 : 1;
+            if (wrote[d.out_buf] >= 0 && wrote[d.out_buf] != t)
+                return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": buffer " + std::to_string(d.out_buf) + " written as both bf16 and fp32");
+            wrote[d.out_buf] = t;
+        }
+        for (int b = 0; b < n_bufs; ++b) h->buf_bf16[b] = wrote[b] == 0 ? 0 : 1;
+        for (int i = 0; i < n_descs; ++i) {
+            const pa_conv_desc& d = h->descs[i];
+            if (d.kind != 1 && (!h->buf_bf16[d.in_buf] || (d.kind == 0 && d.res_buf >= 0 && !h->buf_bf16[d.res_buf])))
+                return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": reads an fp32 buffer (bf16 rows read bf16)");
+            if (d.kind != 0) continue;
+            const pa::GemmParams p = conv_geometry(d, max_crops);
+            const unsigned long long in_bytes = (unsigned long long)max_crops * p.in_img_stride * 2ull;
+            const unsigned long long out_bytes = (unsigned long long)max_crops * p.out_img_stride * 2ull;
+            if (pa::psgemm_pick_bn(d.cout, d.res_buf >= 0) == 0 || p.M >= (1 << 24) || p.howo >= (1 << 16) || in_bytes >= (1ull << 31) ||
+                out_bytes >= (1ull << 31) || d.relu < 0 || d.relu > 1)
+                return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": a convolution the bf16 GEMM (bgemm.hip) cannot take");
+        }
+        if (h->descs.back().kind != 2)
+            return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(n_descs - 1) + ": a bf16 table must end in a pool (the output is fp32)");
+    }
     auto chk = [&](hipError_t e, const char* what) -> bool {
         if (e == hipSuccess) return true;
         h->last_error = std::string(what) + ": " + hipGetErrorString(e);
@@ -148,12 +246,12 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
     h->n_weights = n_weights;
     if (!chk(hipMalloc(&h->weights, n_weights * sizeof(float)), "hipMalloc weights")) return PA_ERR_HIP;
     if (!chk(hipMemcpy(h->weights, weights_host, n_weights * sizeof(float), hipMemcpyHostToDevice), "upload weights")) return PA_ERR_HIP;
-    {
+    h->wino_off.assign(n_descs, -1);
+    h->wino_bn.assign(n_descs, 0);
+    if (compute_dtype != PA_DTYPE_BF16) {
         // stride-1 3x3 convolutions on maps of 8 x 8 and larger run as Winograd F(2x2, 3x3) (wino.hip, as in the engine's
         // ResNet-18: the 4 x 4 maps stay on the direct kernel); PA_CONVNET_WINO=0 keeps the direct form (A/B)
         static const int use_wino = getenv("PA_CONVNET_WINO") ? atoi(getenv("PA_CONVNET_WINO")) : 1;
-        h->wino_off.assign(n_descs, -1);
-        h->wino_bn.assign(n_descs, 0);
         size_t total = 0;
         for (int i = 0; i < n_descs; ++i) {
             const pa_conv_desc& d = h->descs[i];
@@ -196,10 +294,36 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
             if (!chk(hipMemcpy(h->split_weights, sw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload split weights")) return PA_ERR_HIP;
         }
     }
+    h->bg_off.assign(n_descs, -1);
+    if (compute_dtype == PA_DTYPE_BF16) {
+        // the weights rounded to nearest even once: the stem's [64][224] as laid out, every convolution in bgemm's plane layout
+        size_t total = 0;
+        for (int i = 0; i < n_descs; ++i) {
+            const pa_conv_desc& d = h->descs[i];
+            if (d.kind == 2) continue;
+            h->bg_off[i] = (long long)total;
+            total += d.kind == 1 ? 64 * 224 : pa::bgemm_weight_elems(d.cout, d.ksize * d.ksize * d.cin, d.res_buf >= 0);
+            total = (total + 127) & ~(size_t)127;   // (every plane 256-byte aligned)
+        }
+        std::vector<unsigned short> bw(total, 0);
+        for (int i = 0; i < n_descs; ++i) {
+            const pa_conv_desc& d = h->descs[i];
+            if (d.kind == 1)
+                for (int k = 0; k < 64 * 224; ++k) bw[h->bg_off[i] + k] = cn_bf16_rne(weights_host[d.w_off + k]);
+            else if (d.kind == 0)
+                pa::bgemm_pack_weights(weights_host + d.w_off, d.cout, d.ksize * d.ksize * d.cin, d.res_buf >= 0, bw.data() + h->bg_off[i]);
+        }
+        if (!chk(hipMalloc(&h->bg_weights, total * sizeof(unsigned short)), "hipMalloc bf16 weights")) return PA_ERR_HIP;
+        if (!chk(hipMemcpy(h->bg_weights, bw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload bf16 weights")) return PA_ERR_HIP;
+        const size_t slab_bytes = (size_t)pa::BGEMM_SLAB_ITEMS * 128 * 128 * sizeof(float);
+        if (!chk(hipMalloc(&h->bg_slab, slab_bytes), "hipMalloc split-K slab")) return PA_ERR_HIP;
+        if (!chk(hipMalloc(&h->bg_tickets, pa::BGEMM_TICKETS * sizeof(int32_t)), "hipMalloc split-K tickets")) return PA_ERR_HIP;
+        if (!chk(hipMemset(h->bg_tickets, 0, pa::BGEMM_TICKETS * sizeof(int32_t)), "hipMemset split-K tickets")) return PA_ERR_HIP;
+    }
     h->bufs.assign(n_bufs, nullptr);
     for (int b = 0; b < n_bufs; ++b) {
         // (+ one 128-pixel tile of slack: a partial last tile of the patch kernel reads past the last crop)
-        const size_t bytes = ((size_t)max_crops * h->buf_floats[b] + 128 * 2048) * sizeof(float);
+        const size_t bytes = ((size_t)max_crops * h->buf_floats[b] + 128 * 2048) * (h->buf_bf16[b] ? 2 : sizeof(float));
         if (!chk(hipMalloc(&h->bufs[b], bytes), "hipMalloc activations")) return PA_ERR_HIP;
         if (!chk(hipMemset(h->bufs[b], 0, bytes), "hipMemset activations")) return PA_ERR_HIP;
     }
@@ -214,6 +338,9 @@ void pa_convnet_destroy(pa_convnet* h) {
     (void)hipFree(h->weights);
     (void)hipFree(h->wino_weights);
     (void)hipFree(h->split_weights);
+    (void)hipFree(h->bg_weights);
+    (void)hipFree(h->bg_slab);
+    (void)hipFree(h->bg_tickets);
     (void)hipFree(h->x0);
     for (float* b : h->bufs) (void)hipFree(b);
     delete h;
@@ -231,17 +358,19 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
         hipError_t e__ = (call);                                                                      \
         if (e__ != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
-    CN_HIP(pa::launch_nchw_to_padded(x, h->x0, n, 0, s));
+    const bool bf = h->compute_dtype == PA_DTYPE_BF16;
+    CN_HIP(pa::launch_nchw_to_padded(x, h->x0, n, bf ? 1 : 0, s));
     for (int li = 0; li <= last; ++li) {
         const pa_conv_desc& d = h->descs[li];
         if (d.kind == 1) {
             pa::StemPoolParams sp;
             memset(&sp, 0, sizeof(sp));
             sp.x = h->x0;
-            sp.wgt = h->weights + d.w_off;
+            sp.wgt = bf ? (const void*)(h->bg_weights + h->bg_off[li]) : (const void*)(h->weights + d.w_off);
             sp.bias = h->weights + d.b_off;
             sp.out = h->bufs[d.out_buf];
             sp.crops = n;
+            sp.in_bf16 = sp.out_bf16 = bf ? 1 : 0;
             CN_HIP(pa::launch_stem_pool(sp, s));
             h->forms[li] = PA_CN_FORM_STEM_POOL;
             continue;
@@ -250,39 +379,38 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
             const size_t total = (size_t)n * d.cin;
             int grid = (int)((total + 255) / 256);
             grid = grid > 2048 ? 2048 : grid;
-            hipLaunchKernelGGL(pa::avgpool_any_kernel, dim3(grid), dim3(256), 0, s, h->bufs[d.in_buf], h->bufs[d.out_buf], n, d.in_hw, d.in_pad, d.cin);
+            if (bf) {
+                hipLaunchKernelGGL(pa::avgpool_bf16_any_kernel, dim3(grid), dim3(256), 0, s, (const unsigned short*)h->bufs[d.in_buf], h->bufs[d.out_buf], n,
+                                   d.in_hw, d.in_pad, d.cin);
+                h->forms[li] = PA_CN_FORM_AVGPOOL_BF16;
+            } else {
+                hipLaunchKernelGGL(pa::avgpool_any_kernel, dim3(grid), dim3(256), 0, s, h->bufs[d.in_buf], h->bufs[d.out_buf], n, d.in_hw, d.in_pad, d.cin);
+                h->forms[li] = PA_CN_FORM_AVGPOOL;
+            }
             CN_HIP(hipGetLastError());
-            h->forms[li] = PA_CN_FORM_AVGPOOL;
             continue;
         }
-        const int out_hw = d.in_hw / d.stride;
-        const int in_w = d.in_hw + 2 * d.in_pad, out_w = out_hw + 2 * d.out_pad;
-        pa::GemmParams p;
-        memset(&p, 0, sizeof(p));
+        pa::GemmParams p = conv_geometry(d, n);
         p.act = h->bufs[d.in_buf];
         p.wgt = h->weights + d.w_off;
         p.bias = h->weights + d.b_off;
         p.residual = d.res_buf >= 0 ? h->bufs[d.res_buf] : nullptr;
         p.out = h->bufs[d.out_buf];
-        p.M = n * out_hw * out_hw;
-        p.N = d.cout;
-        p.taps = d.ksize * d.ksize;
-        p.kw_taps = d.ksize;
-        p.chunk = d.cin;
-        p.ktot = p.taps * p.chunk;
-        p.howo = out_hw * out_hw;
-        p.wo = out_hw;
-        p.in_px_stride = d.cin;
-        p.in_row_stride = in_w * d.cin;
-        p.in_img_stride = in_w * in_w * d.cin;
-        p.stride = d.stride;
-        p.off_y = p.off_x = d.in_pad - (d.ksize - 1) / 2;
-        p.out_px_stride = d.cout;
-        p.out_row_stride = out_w * d.cout;
-        p.out_img_stride = out_w * out_w * d.cout;
-        p.out_pad = d.out_pad;
-        p.relu = d.relu;
-        p.splitk = 1;
+        if (bf) {
+            // every convolution on the one-slice bf16 GEMM; split-K where bgemm_pick_split says (PA_CONVNET_BG_SPLIT: A/B)
+            const int S = pa::bgemm_pick_split(p, bg_split_knob());
+            if (S > 1) {
+                p.splitk = S;
+                p.slab = h->bg_slab;
+                p.tickets = h->bg_tickets;
+            }
+            const hipError_t pe = pa::launch_bgemm(p, h->bg_weights + h->bg_off[li], (size_t)n * p.out_img_stride, 0, false, s);
+            if (pe != hipSuccess)
+                return cn_fail(h, PA_ERR_HIP, "layer " + std::to_string(li) + " (bf16): " +
+                                                  (pe == hipErrorInvalidValue ? std::string("the bf16 GEMM refuses its shape") : hipGetErrorString(pe)));
+            h->forms[li] = S > 1 ? PA_CN_FORM_BGEMM_SPLITK : PA_CN_FORM_BGEMM;
+            continue;
+        }
         // tile: the largest shape that still gives the chip ~two workgroups per CU
         const long long t128 = (long long)((p.M + 127) / 128) * (p.N / 64);
         const pa::GemmTile tile = (p.N % 128 == 0 && t128 / 2 >= 512) ? pa::TILE_128x128 : (t128 >= 512 ? pa::TILE_128x64 : pa::TILE_64x64);
@@ -331,7 +459,8 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
         hipError_t e__ = (call);                                                                      \
         if (e__ != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
-    // the last layer's output buffer as stored, zero border included when it has one (a pooled vector has none)
+    // the last layer's output buffer as stored, zero border included when it has one (a pooled vector has none; under
+    // PA_DTYPE_BF16 the last row is a pool, fp32)
     const pa_conv_desc& last = h->descs.back();
     int ohw, oc;
     out_geom(last, &ohw, &oc);
@@ -350,13 +479,14 @@ int pa_convnet_trace(pa_convnet* h, const float* x, int32_t n, int32_t last_row,
     if (n < 1 || n > h->max_crops) return fail("n outside 1..max_crops");
     if (last_row < -1 || last_row >= (int32_t)h->descs.size()) return fail("row out of range");
     if (buf < -1 || buf >= (int32_t)h->buf_floats.size()) return fail("buffer out of range");
-    const size_t floats = (size_t)h->max_crops * (buf < 0 ? (size_t)134 * 134 * 4 : (size_t)h->buf_floats[buf]);
-    if (out_bytes < floats * sizeof(float)) return fail("out is smaller than the buffer");
+    const size_t elems = (size_t)h->max_crops * (buf < 0 ? (size_t)134 * 134 * 4 : (size_t)h->buf_floats[buf]);
+    const size_t bytes = elems * (is_bf16(h, buf) ? 2 : sizeof(float));
+    if (out_bytes < bytes) return fail("out is smaller than the buffer");
     if (buf >= (int32_t)h->bufs.size() || !h->x0) return fail("the handle holds no buffers (its creation failed)");
     hipStream_t s = (hipStream_t)stream;
     const int rc = convnet_run(h, x, n, last_row, s);
     if (rc != PA_OK) return rc;
-    const hipError_t e = hipMemcpyAsync(out, buf < 0 ? h->x0 : h->bufs[buf], floats * sizeof(float), hipMemcpyDeviceToDevice, s);
+    const hipError_t e = hipMemcpyAsync(out, buf < 0 ? h->x0 : h->bufs[buf], bytes, hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string("pa_convnet_trace: hipMemcpyAsync: ") + hipGetErrorString(e));
     return PA_OK;
 }

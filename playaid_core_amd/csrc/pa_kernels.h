@@ -75,6 +75,8 @@ struct GemmParams {
     const float* wgt2;
     float* out2;
     unsigned long long* clk;  // ablation builds only: in-kernel clock stamps
+    // split-K form of the one-slice bf16 GEMM (bgemm.hip, splitk > 1): 4 zeroed tickets per output tile, left zeroed behind a launch
+    int32_t* tickets;
 };
 
 // BM x BN (x BK; 32 unless named)
@@ -99,6 +101,15 @@ hipError_t launch_psgemm(const GemmParams& p, const unsigned short* wsp, size_t 
 size_t bgemm_weight_elems(int N, int ktot, int residual);
 void bgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned short* out);
 hipError_t launch_bgemm(const GemmParams& p, const unsigned short* wsp, size_t out_elems, size_t up_elems, bool out_f32, hipStream_t s);
+// Its split-K form: p.splitk = S > 1 runs one workgroup per (output tile, k-slice) -- bf16 output, no up-sampled copy; p.slab holds
+// BGEMM_SLAB_ITEMS workgroups' fp32 partial tiles (128 x BN each), p.tickets BGEMM_TICKETS zeroed ints. bgemm_pick_split: the S the
+// split rule gives the shape of p (conv mode, as launch_bgemm takes it): 1 unless its unsplit grid is below BGEMM_SPLIT_MAX_GRID
+// workgroups (a quarter of the CUs) and it has at least BGEMM_SPLIT_MIN_KSTEPS k-steps (of 32), else the largest S in {8, 4, 2} with
+// tiles * S <= BGEMM_SLAB_ITEMS and at least 4 k-steps per slice; force > 1 takes S = force instead (on every row whose unsplit grid
+// is below half the CUs, short K included, within the same two limits, else 1), force 0 or 1 gives 1 (no split), force < 0 is the
+// rule.
+constexpr int BGEMM_SLAB_ITEMS = 256, BGEMM_TICKETS = 4 * 128, BGEMM_SPLIT_MAX_GRID = 64, BGEMM_SPLIT_MIN_KSTEPS = 72;
+int bgemm_pick_split(const GemmParams& p, int force);
 // bf16 activations / weights (uint16_t storage behind the float* fields, every count in elements),
 // f32 accumulate on v_mfma_f32_32x32x16_bf16; conv mode only (igemm_bf16.hip)
 hipError_t launch_igemm_bf16(const GemmParams& p, GemmTile tile, hipStream_t s);

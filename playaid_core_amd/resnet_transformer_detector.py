@@ -12,6 +12,11 @@ The ResNet-50 runs on the engine's fp32 convolution kernels through a layer tabl
 ``csrc/convnet.hip``): BatchNorm folded in fp64 here, 1x1 convolutions as GEMMs on the im2col engine, the stride-1
 3x3 ones on the patch-resident kernel, the stem on ``stem_pool_kernel``. The encoder and the classifier run in
 ``csrc/transformer.hip`` (``pa_encoder_*``). No PyTorch fallback; training hooks (``:143-260``) are out of scope.
+
+``compute_dtype="bf16"`` (never the default) runs the ResNet-50 with bf16 storage and bf16 products: the stem on
+``stem_pool_kernel``'s bf16 form, every convolution on the one-slice bf16 GEMM (``csrc/bgemm.hip``, split-K on the small maps),
+the average pool summing bf16 in fp32; the pooled features and the encoder stay fp32. Rounding model: ``include/playaid_hip.h``
+next to ``pa_convnet_create_dtype``.
 """
 from __future__ import annotations
 
@@ -162,8 +167,8 @@ class ConvNet:
     def __init__(self, descs, buf_floats, weights: np.ndarray, out_floats: int, device: str = "cuda:0", max_crops: int = 64,
                  compute_dtype: str = "f32"):
         self._lib = _lib.load()
-        if compute_dtype not in ("f32", "emulated_f32"):
-            raise ValueError("compute_dtype must be 'f32' or 'emulated_f32'")
+        if compute_dtype not in ("f32", "emulated_f32", "bf16"):
+            raise ValueError("compute_dtype must be 'f32', 'emulated_f32' or 'bf16'")
         self.compute_dtype = compute_dtype
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("no HIP device visible to PyTorch-ROCm; this path has no CPU fallback")
@@ -172,6 +177,12 @@ class ConvNet:
         self.out_floats = out_floats
         self.buf_floats = [int(b) for b in buf_floats]
         self.n_rows = len(descs)
+        # element type of each buffer as stored (-1: the stem's input): under bf16 what a stem or convolution row writes is bf16,
+        # what a pool writes fp32 (include/playaid_hip.h, PA_DTYPE_BF16)
+        self.buf_dtype = {b: torch.float32 for b in range(-1, len(self.buf_floats))}
+        if compute_dtype == "bf16":
+            pooled = {int(d["out_buf"]) for d in descs if int(d["kind"]) == 2}
+            self.buf_dtype = {b: torch.float32 if b in pooled else torch.bfloat16 for b in self.buf_dtype}
         arr = (_lib.pa_conv_desc * len(descs))()
         for i, d in enumerate(descs):
             for k, v in d.items():
@@ -195,12 +206,13 @@ class ConvNet:
     def trace(self, x: torch.Tensor, last_row: int, buf: int) -> torch.Tensor:
         """Test aid (``pa_convnet_trace``): run what ``forward`` runs for x float32[n,3,128,128] (n <= max_crops, one group)
         through table row ``last_row`` (-1: the input conversion alone) and return the whole of buffer ``buf`` as stored:
-        float32[max_crops * buf_floats[buf]] on the device (buf = -1: the stem input, [max_crops][134][134][4])."""
+        [max_crops * buf_floats[buf]] elements of ``buf_dtype[buf]`` (float32, or bfloat16 for what a bf16 table's stem and
+        convolutions write) on the device (buf = -1: the stem input, [max_crops][134][134][4])."""
         xd = x.to(self.device, torch.float32).contiguous()
         floats = self.max_crops * (134 * 134 * 4 if buf < 0 else self.buf_floats[buf])
-        out = torch.empty(floats, dtype=torch.float32, device=self.device)
+        out = torch.empty(floats, dtype=self.buf_dtype.get(buf, torch.float32), device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.pa_convnet_trace(self._h, _ptr(xd), int(xd.shape[0]), last_row, buf, _ptr(out), out.numel() * 4, stream)
+        rc = self._lib.pa_convnet_trace(self._h, _ptr(xd), int(xd.shape[0]), last_row, buf, _ptr(out), out.numel() * out.element_size(), stream)
         if rc != 0:
             raise EngineError(rc, self._lib.pa_convnet_last_error(self._h).decode())
         return out
@@ -297,7 +309,9 @@ class ResnetTransformerDetector:
         self.max_rows = max_rows
         self._lib = _lib.load()
         descs, bufs, weights, feat_dim = build_resnet50_table(state_dict)
-        # (compute_dtype: beyond the reference's arguments -- "emulated_f32" = pa_convnet_create_dtype(PA_DTYPE_EMULATED_F32); never the default)
+        # (compute_dtype: beyond the reference's arguments -- "emulated_f32" = pa_convnet_create_dtype(PA_DTYPE_EMULATED_F32), "bf16" =
+        # PA_DTYPE_BF16: the ResNet-50 in bf16 on bgemm.hip, the encoder head fp32 as always; neither is the default, and bf16 is not
+        # within the fp32 path's 1e-4 bar)
         self._net = ConvNet(descs, bufs, weights, feat_dim, device=device, max_crops=min(max_rows, 64),
                             compute_dtype=kwargs.get("compute_dtype", "f32"))
         self.device = self._net.device
