@@ -218,17 +218,31 @@ int pa_backbone_crop_images(pa_engine* e, const uint8_t* images, size_t images_b
 int pa_detect_postprocess(pa_engine* e, const float* pred, int32_t n_frames, int32_t rows, int32_t num_classes,
                           float conf_thres, float iou_thres, uint32_t class_mask, int32_t max_det, int32_t net_height,
                           int32_t net_width, int32_t img_height, int32_t img_width, float* dets, int32_t* counts, void* stream);
+/* pa_detect_postprocess for up to 80 classes (a stock COCO checkpoint): num_classes 1..80, and the class filter as
+ * class_words, ceil(num_classes / 32) host words -- bit c % 32 of word c / 32 = class c allowed -- or NULL for every class
+ * (detect.py without --classes). Same arithmetic, same outputs and the same order of the dets rows as pa_detect_postprocess:
+ * for num_classes <= 32 and class_mask = class_words[0] both give the same dets and counts. One gating pass per frame reads
+ * every row once and compacts the rows over the gates; the max_det arg-max passes walk that list (a frame with more than
+ * 4096 such rows walks every row instead, with the same result). */
+int pa_detect_postprocess_classes(pa_engine* e, const float* pred, int32_t n_frames, int32_t rows, int32_t num_classes,
+                                  float conf_thres, float iou_thres, const uint32_t* class_words, int32_t max_det, int32_t net_height,
+                                  int32_t net_width, int32_t img_height, int32_t img_width, float* dets, int32_t* counts, void* stream);
 
 /* ---- f1: the detection network ---------------------------------------------
  *
  * Replaces the network half of the YOLOv5 subprocess (ai_runner.py:191-224: `detect.py --weights <yolov5s checkpoint>
  * --source <video>`): frames -> letterbox (cv2.resize INTER_LINEAR to the un-padded size, 114-grey border, BGR -> RGB,
  * / 255) -> a fully convolutional network given as a LAYER TABLE -> Detect decode -> pred float32[n][rows][5 + nc] in
- * network-input pixels, i.e. the input of pa_detect_postprocess. The table (playaid_core_amd/yolov5.py builds YOLOv5s
- * v7.0 from an ultralytics state dict) arrives BatchNorm-folded: per convolution [cout][ky][kx][cin] at w_off and the bias
- * [cout] at b_off (float offsets into one blob); the 6x6 stem as [cout][6 ky][8 px][4 ch] (kx >= 6 and channel 3 zero, cout % 64 == 0). Activations are
- * zero-bordered NHWC device buffers of buf_floats_per_image[b] floats per image; a layer addresses a CHANNEL SLICE of a
- * buffer (coff = first channel, cstride = channels per pixel of the buffer), so concatenations are free. */
+ * network-input pixels, i.e. the input of pa_detect_postprocess. The table (playaid_core_amd/yolov5.py builds any YOLOv5
+ * v6.0 / v7.0 P5 model -- n, s, m, l, x -- from an ultralytics state dict) arrives BatchNorm-folded: per convolution
+ * [cout][ky][kx][cin] at w_off and the bias [cout] at b_off (float offsets into one blob); the 6x6 stem in the lane layout of
+ * kind 3 below. Activations are zero-bordered NHWC device buffers of buf_floats_per_image[b] floats per image; a layer addresses
+ * a CHANNEL SLICE of a buffer (coff = first channel, cstride = channels per pixel of the buffer), so concatenations are free.
+ * Channel counts that are not multiples of 32 are the table's business: it pads them with zero weight rows, zero weight
+ * columns and zero biases (SiLU(0) = 0: the padding stays exactly 0 and moves no result).
+ * A stem wider than 32 channels is one kind-3 row per 32 of them, each with cout = 32, its own weights and bias, and
+ * out_coff = 32 g into the same buffer; under PA_DTYPE_EMULATED_F32 and PA_DTYPE_BF16 every such row gets its own bf16
+ * fragments and runs on stem6x6_bf16_kernel (form PA_DET_FORM_STEM_BF16), under PA_DTYPE_F32 on the direct kernel. */
 typedef struct pa_net_layer {
     int32_t kind;      /* 0 convolution, 3 stem 6x6/2 + SiLU on the letter-boxed image (cout == 32; weights float32[64][56]: lane l =
                           (kx / 3) * 32 + channel holds W[channel][c][ky][3 * (l / 32) + j] at ky * 9 + j * 3 + c), 4 max-pool 5x5/1,

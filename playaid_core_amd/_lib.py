@@ -126,6 +126,8 @@ SYMBOLS = [
     ("pa_backbone_crop_images", C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("pa_detect_postprocess", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("pa_detect_postprocess_classes", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, C.c_int32,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("pa_detector_create", C.c_int, [C.c_int32, C.POINTER(pa_net_layer), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _P, C.c_size_t,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
     ("pa_detector_create_dtype", C.c_int, [C.c_int32, C.POINTER(pa_net_layer), C.c_int32, C.POINTER(C.c_int64), C.c_int32, _P, C.c_size_t,

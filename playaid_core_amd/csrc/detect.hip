@@ -146,6 +146,172 @@ hipError_t launch_detect_nms(const DetectParams& q, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- up to 80 classes (pa_detect_postprocess_classes) ---------------------------------------------------------------------------
+//
+// The same selection as detect_nms_kernel -- the same gates, the same first maximum over the classes, the same (score, -row) key,
+// the same IoU arithmetic -- for nc up to 80 with the class filter as words of bits. A row is 5 + nc floats (340 bytes at
+// nc = 80), and re-reading every row in each of the max_det arg-max passes is what the nc <= 32 kernel does; here ONE gating pass
+// reads each row (objectness first, the class scores only behind an objectness over the threshold) and compacts the rows that
+// pass every gate into LDS as (row, score, class); the arg-max passes then walk that list, reading only the four box floats of
+// a candidate. The greedy choice depends on the key alone, so the order the list is filled in does not matter. A frame with more
+// candidates than the list holds runs its passes over every row instead (the same result, at the old cost).
+namespace {
+
+constexpr int NMS_CAP = 4096;   // candidates per frame in LDS (12 bytes each)
+
+// the gates of make_cand: -> class (>= 0) and score of a row that passes them, -1 otherwise
+__device__ __forceinline__ int gate_row(const float* __restrict__ p, int nc, float conf_thres, const uint32_t* words, float& score) {
+    const float obj = p[4];
+    if (!(obj > conf_thres)) return -1;
+    float best = p[5] * obj;
+    int j = 0;
+    for (int k = 1; k < nc; ++k) {
+        const float v = p[5 + k] * obj;
+        if (v > best) {  // first maximum
+            best = v;
+            j = k;
+        }
+    }
+    if (!(best > conf_thres) || !((words[j >> 5] >> (j & 31)) & 1u)) return -1;
+    score = best;
+    return j;
+}
+
+// make_cand's box of a row that passed the gates
+__device__ __forceinline__ void cand_box(const float* __restrict__ p, int j, float score, Cand& c) {
+    const float hw = p[2] / 2.f, hh = p[3] / 2.f;
+    c.score = score;
+    c.cls = j;
+    c.x1 = p[0] - hw; c.y1 = p[1] - hh; c.x2 = p[0] + hw; c.y2 = p[1] + hh;
+    const float off = (float)j * MAX_WH;
+    c.b0 = c.x1 + off; c.b1 = c.y1 + off; c.b2 = c.x2 + off; c.b3 = c.y2 + off;
+    c.area = (c.b2 - c.b0) * (c.b3 - c.b1);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(NMS_THREADS) void detect_nms_classes_kernel(const DetectParams q) {
+    __shared__ int cand_row[NMS_CAP];
+    __shared__ float cand_score[NMS_CAP];
+    __shared__ int cand_cls[NMS_CAP];
+    __shared__ unsigned long long wave_best[NMS_THREADS / 64];
+    __shared__ Cand kept[DET_MAX];
+    __shared__ int kept_row[DET_MAX];
+    __shared__ int n_kept, n_cand;
+    const int frame = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int stride = 5 + q.nc;
+    const float* pred = q.pred + (size_t)frame * q.rows * stride;
+    if (tid == 0) {
+        n_kept = 0;
+        n_cand = 0;
+    }
+    __syncthreads();
+    for (int r = tid; r < q.rows; r += NMS_THREADS) {
+        float sc;
+        const int j = gate_row(pred + (size_t)r * stride, q.nc, q.conf_thres, q.class_words, sc);
+        if (j < 0) continue;
+        const int slot = atomicAdd(&n_cand, 1);
+        if (slot < NMS_CAP) {
+            cand_row[slot] = r;
+            cand_score[slot] = sc;
+            cand_cls[slot] = j;
+        }
+    }
+    __syncthreads();
+    const bool compact = n_cand <= NMS_CAP;
+    const int n_scan = compact ? n_cand : q.rows;
+    for (int k = 0; k < q.max_det; ++k) {
+        const int nk = n_kept;
+        unsigned long long best = 0ull;  // (score bits << 32) | ~row: larger score first, then the lower row
+        for (int i = tid; i < n_scan; i += NMS_THREADS) {
+            int r = i, j;
+            float sc;
+            if (compact) {
+                r = cand_row[i];
+                sc = cand_score[i];
+                j = cand_cls[i];
+            } else if ((j = gate_row(pred + (size_t)r * stride, q.nc, q.conf_thres, q.class_words, sc)) < 0) {
+                continue;
+            }
+            Cand c;
+            cand_box(pred + (size_t)r * stride, j, sc, c);
+            bool out = false;
+            for (int t = 0; t < nk; ++t) {
+                if (kept_row[t] == r) {
+                    out = true;
+                    break;
+                }
+                const Cand& a = kept[t];
+                const float xx1 = fmaxf(a.b0, c.b0), yy1 = fmaxf(a.b1, c.b1);
+                const float xx2 = fminf(a.b2, c.b2), yy2 = fminf(a.b3, c.b3);
+                const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
+                const float inter = w * h;
+                const float ovr = inter / ((a.area + c.area) - inter);
+                if (ovr > q.iou_thres) {
+                    out = true;
+                    break;
+                }
+            }
+            if (out) continue;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(c.score) << 32) | (unsigned long long)(0xffffffffu - (unsigned)r);
+            best = key > best ? key : best;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const unsigned lo = __shfl_xor((unsigned)(best & 0xffffffffu), d, 64), hi = __shfl_xor((unsigned)(best >> 32), d, 64);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            best = o > best ? o : best;
+        }
+        if ((tid & 63) == 0) wave_best[tid >> 6] = best;
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long b = wave_best[0];
+            for (int w = 1; w < NMS_THREADS / 64; ++w) b = wave_best[w] > b ? wave_best[w] : b;
+            if (b != 0ull) {
+                const int r = (int)(0xffffffffu - (unsigned)(b & 0xffffffffu));
+                float sc;
+                const int j = gate_row(pred + (size_t)r * stride, q.nc, q.conf_thres, q.class_words, sc);
+                Cand c;
+                cand_box(pred + (size_t)r * stride, j, sc, c);
+                kept[nk] = c;
+                kept_row[nk] = r;
+                n_kept = nk + 1;
+            }
+        }
+        __syncthreads();
+        if (n_kept == nk) break;  // nothing left
+    }
+    // scale_boxes + clip + round, xyxy2xywh / gn, label-file order: as detect_nms_kernel
+    const int n = n_kept;
+    if (tid < n) {
+        const Cand& c = kept[tid];
+        float x1 = (c.x1 - q.pad_x) / q.gain, x2 = (c.x2 - q.pad_x) / q.gain;
+        float y1 = (c.y1 - q.pad_y) / q.gain, y2 = (c.y2 - q.pad_y) / q.gain;
+        x1 = rintf(fminf(fmaxf(x1, 0.f), q.img_w)); x2 = rintf(fminf(fmaxf(x2, 0.f), q.img_w));
+        y1 = rintf(fminf(fmaxf(y1, 0.f), q.img_h)); y2 = rintf(fminf(fmaxf(y2, 0.f), q.img_h));
+        float* o = q.dets + ((size_t)frame * q.max_det + (n - 1 - tid)) * 6;
+        o[0] = (float)c.cls;
+        o[1] = ((x1 + x2) / 2.f) / q.img_w;
+        o[2] = ((y1 + y2) / 2.f) / q.img_h;
+        o[3] = (x2 - x1) / q.img_w;
+        o[4] = (y2 - y1) / q.img_h;
+        o[5] = c.score;
+    }
+    if (tid >= n && tid < q.max_det) {
+        float* o = q.dets + ((size_t)frame * q.max_det + tid) * 6;
+        for (int i = 0; i < 6; ++i) o[i] = 0.f;
+    }
+    if (tid == 0) q.counts[frame] = n;
+}
+
+hipError_t launch_detect_nms_classes(const DetectParams& q, hipStream_t s) {
+    if (q.n_frames <= 0) return hipSuccess;
+    if (q.max_det < 1 || q.max_det > DET_MAX || q.nc < 1 || q.nc > DETECT_MAX_CLASSES || q.rows < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(detect_nms_classes_kernel, dim3(q.n_frames), dim3(NMS_THREADS), 0, s, q);
+    return hipGetLastError();
+}
+
 }  // namespace pa
 
 // ---- label repair on the device (rows a3 / f1) ---------------------------------------------------------------------------

@@ -1499,6 +1499,30 @@ int pa_detect_postprocess(pa_engine* e, const float* pred, int32_t n_frames, int
     return PA_OK;
 }
 
+int pa_detect_postprocess_classes(pa_engine* e, const float* pred, int32_t n_frames, int32_t rows, int32_t num_classes, float conf_thres,
+                                  float iou_thres, const uint32_t* class_words, int32_t max_det, int32_t net_height, int32_t net_width,
+                                  int32_t img_height, int32_t img_width, float* dets, int32_t* counts, void* stream) {
+    if (!e || !pred || !dets || !counts || n_frames < 1 || rows < 1 || num_classes < 1 || num_classes > DETECT_MAX_CLASSES || max_det < 1 ||
+        max_det > 8 || net_height < 1 || net_width < 1 || img_height < 1 || img_width < 1)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_detect_postprocess_classes: bad argument");
+    DetectParams q;
+    memset(&q, 0, sizeof(q));
+    q.pred = pred;
+    q.n_frames = n_frames; q.rows = rows; q.nc = num_classes; q.max_det = max_det;
+    q.conf_thres = conf_thres; q.iou_thres = iou_thres;
+    // class_words: ceil(num_classes / 32) words (the bits of classes >= num_classes are ignored); NULL = every class
+    for (int w = 0; w < (num_classes + 31) / 32; ++w) q.class_words[w] = class_words ? class_words[w] : 0xffffffffu;
+    const double gain = std::min((double)net_height / img_height, (double)net_width / img_width);
+    q.gain = (float)gain;
+    q.pad_x = (float)(((double)net_width - img_width * gain) / 2.0);
+    q.pad_y = (float)(((double)net_height - img_height * gain) / 2.0);
+    q.img_w = (float)img_width; q.img_h = (float)img_height;
+    q.dets = dets; q.counts = counts;
+    ProfScope ps(e, (hipStream_t)stream, "detect_nms_classes", 0.0, (double)n_frames * rows * (5 + num_classes) * 4.0);
+    HIPCHK(e, launch_detect_nms_classes(q, (hipStream_t)stream));
+    return PA_OK;
+}
+
 int pa_project_boxes(pa_engine* e, const double* log_rows, int32_t n_rows, double* boxes, void* stream) {
     if (!e || !log_rows || !boxes || n_rows < 1) return fail(e, PA_ERR_INVALID_ARG, "pa_project_boxes: bad argument");
     HIPCHK(e, launch_project_boxes(log_rows, boxes, n_rows, (hipStream_t)stream));

@@ -368,12 +368,15 @@ struct DetectParams {
     int32_t n_frames, rows, nc, max_det;
     float conf_thres, iou_thres;
     uint32_t class_mask;
+    uint32_t class_words[3];   // launch_detect_nms_classes: bit c % 32 of word c / 32 = class c allowed (nc <= DETECT_MAX_CLASSES)
     float pad_x, pad_y, gain;  // letterbox of the network input inside the image (scale_boxes)
     float img_w, img_h;
     float* dets;         // [n_frames][max_det][6]: cls cx cy w h conf, label-file order (lowest confidence first)
     int32_t* counts;     // [n_frames]
 };
 hipError_t launch_detect_nms(const DetectParams& q, hipStream_t s);
+constexpr int DETECT_MAX_CLASSES = 80;
+hipError_t launch_detect_nms_classes(const DetectParams& q, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // small kernels (misc.hip)

@@ -529,7 +529,8 @@ struct pa_detector {
     std::vector<long long> wino_off;    // per layer: float offset into wino_weights, -1 = the layer runs in its direct form
     std::vector<int> wino_bn;           // per layer: output channels per workgroup its filters were laid out for
     int compute_dtype = PA_DTYPE_F32;   // PA_DTYPE_EMULATED_F32: the layers listed in split_off run on psgemm.hip
-    unsigned short* stem_frag = nullptr;       // PA_DTYPE_EMULATED_F32: the stem's W / 255 as stem6x6_bf16_kernel's 27 register fragments (x0 then holds bf16 integers)
+    unsigned short* stem_frag = nullptr;       // PA_DTYPE_EMULATED_F32, PA_DTYPE_BF16: every stem row's W / 255 as stem6x6_bf16_kernel's 27 register fragments (x0 then holds bf16 integers)
+    std::vector<long long> stem_frag_off;      // per layer: element offset of its fragments in stem_frag, -1 = not a stem row on the bf16 kernel
     unsigned short* split_weights = nullptr;   // those layers' weights as three bf16 slices in the kernel's stage-image order
     std::vector<long long> split_off;   // per layer: element offset into split_weights, -1 = the layer keeps its exact fp32 kernel
     unsigned short* bf_weights = nullptr;      // PA_DTYPE_BF16: every convolution's weights as one RNE bf16 plane (bgemm.hip's stage images)
@@ -685,11 +686,18 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
             if (!chk(hipMemcpy(h->wino_weights, ug.data(), total * sizeof(float), hipMemcpyHostToDevice), "upload Winograd filters")) return PA_ERR_HIP;
         }
     }
-    // the 6x6 / 2 stem's W / 255 as stem6x6_bf16_kernel's 27 register fragments, three bf16 slices each (PA_DTYPE_EMULATED_F32, PA_DTYPE_BF16)
-    auto make_stem_frag = [&](const pa_net_layer& L) -> bool {
+    // the 6x6 / 2 stem's W / 255 as stem6x6_bf16_kernel's 27 register fragments, three bf16 slices each (PA_DTYPE_EMULATED_F32, PA_DTYPE_BF16),
+    // per stem row (a network wider than 32 stem channels has one row per 32 of them); uploaded once all rows have theirs
+    std::vector<unsigned short> stem_frags;
+    h->stem_frag_off.assign(n_layers, -1);
+    const size_t frag_elems = (size_t)9 * 3 * 64 * 8;
+    auto make_stem_frag = [&](int i) {
+        const pa_net_layer& L = h->layers[i];
         // lane layout of the direct kernel: W[ch][c][ky][3 half + j] sits at half * cout * 56 + ch * 56 + ky * 9 + j * 3 + c.
         // -> [step][slice][lane][8]: lane = 32 khalf + ch supplies k = 16 step + 8 khalf + i, k = 24 ky + 4 kx + c
-        std::vector<unsigned short> frag((size_t)9 * 3 * 64 * 8, 0);
+        h->stem_frag_off[i] = (long long)stem_frags.size();
+        stem_frags.resize(stem_frags.size() + frag_elems, 0);
+        unsigned short* frag = stem_frags.data() + h->stem_frag_off[i];
         auto rne = [](double v) {   // bf16 nearest-even of a double, and its value
             float f = (float)v;
             uint32_t u;
@@ -710,9 +718,11 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
                         r -= val(hq);
                     }
                 }
-        if (!chk(hipMalloc(&h->stem_frag, frag.size() * sizeof(unsigned short)), "hipMalloc stem fragments")) return false;
-        if (!chk(hipMemcpy(h->stem_frag, frag.data(), frag.size() * sizeof(unsigned short), hipMemcpyHostToDevice), "upload stem fragments")) return false;
-        return true;
+    };
+    auto upload_stem_frags = [&]() -> bool {
+        if (stem_frags.empty()) return true;
+        if (!chk(hipMalloc(&h->stem_frag, stem_frags.size() * sizeof(unsigned short)), "hipMalloc stem fragments")) return false;
+        return chk(hipMemcpy(h->stem_frag, stem_frags.data(), stem_frags.size() * sizeof(unsigned short), hipMemcpyHostToDevice), "upload stem fragments");
     };
     h->split_off.assign(n_layers, -1);
     h->bf_off.assign(n_layers, -1);
@@ -728,10 +738,9 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         for (int i = 0; i < n_layers; ++i) {
             const pa_net_layer& L = h->layers[i];
             if (L.kind == 3) {
-                if (L.cout != 32 || L.ksize != 6 || L.stride != 2) return nobf(i, "the stem kernel takes the 6x6 / 2, 32-channel stem only");
+                if (L.cout != 32 || L.ksize != 6 || L.stride != 2) return nobf(i, "the stem kernel takes 6x6 / 2 rows of 32 channels only");
                 if (h->buf_elem[L.out_buf] != 2) return nobf(i, "the stem writes a buffer a decode row reads");
-                if (h->stem_frag) return nobf(i, "a second stem");
-                if (!make_stem_frag(L)) return PA_ERR_HIP;
+                make_stem_frag(i);
             } else if (L.kind == 0) {
                 if (h->buf_elem[L.in_buf] != 2 || (L.res_buf >= 0 && h->buf_elem[L.res_buf] != 2))
                     return nobf(i, "the convolution reads a buffer a decode row reads (fp32)");
@@ -754,6 +763,7 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
             if (!chk(hipMalloc(&h->bf_weights, total * sizeof(unsigned short)), "hipMalloc bf16 weights")) return PA_ERR_HIP;
             if (!chk(hipMemcpy(h->bf_weights, bw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload bf16 weights")) return PA_ERR_HIP;
         }
+        if (!upload_stem_frags()) return PA_ERR_HIP;
     }
     if (compute_dtype == PA_DTYPE_EMULATED_F32) {
         // the 1x1 and the stride-2 3x3 convolutions (and, with PA_DET_EMU_S1=1, the stride-1 3x3 ones in place of their Winograd
@@ -767,8 +777,8 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         size_t total = 0;
         for (int i = 0; i < n_layers; ++i) {
             const pa_net_layer& L = h->layers[i];
-            if (L.kind == 3 && emu_stem && L.cout == 32 && L.ksize == 6 && L.stride == 2 && !h->stem_frag) {
-                if (!make_stem_frag(L)) return PA_ERR_HIP;
+            if (L.kind == 3 && emu_stem) {   // every stem row: x0 holds the pixel integers for all of them
+                make_stem_frag(i);
                 continue;
             }
             if (L.kind != 0 || L.cin % 32 || L.cout % 32) continue;
@@ -788,6 +798,7 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
             if (!chk(hipMalloc(&h->split_weights, total * sizeof(unsigned short)), "hipMalloc split weights")) return PA_ERR_HIP;
             if (!chk(hipMemcpy(h->split_weights, sw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload split weights")) return PA_ERR_HIP;
         }
+        if (!upload_stem_frags()) return PA_ERR_HIP;
     }
     h->bufs.assign(n_bufs, nullptr);
     h->buf_floats.assign(buf_floats_per_image, buf_floats_per_image + n_bufs);
@@ -884,7 +895,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             const int oh = h->net_h / 2, ow = h->net_w / 2;
             pa::StemBf16Params q;
             q.x = X0B;
-            q.wfrag = h->stem_frag;
+            q.wfrag = h->stem_frag + h->stem_frag_off[li];
             q.bias = h->weights + L.b_off;
             q.out = reinterpret_cast<float*>(SLICE(L.out_buf, L.out_coff));
             q.n = n; q.net_h = h->net_h; q.net_w = h->net_w; q.oh = oh; q.ow = ow;

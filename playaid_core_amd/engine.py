@@ -397,17 +397,30 @@ class Engine:
     def detect_postprocess(self, pred, net_hw, img_hw, conf_thres: float = 0.25, iou_thres: float = 0.45,
                            classes=(2, 3), max_det: int = 2):
         """pred float32[n, rows, 5 + nc] (decoded head rows) -> (dets float32[n, max_det, 6], counts int32[n]) on
-        the device; dets rows are ``cls cx cy w h conf`` in label-file order."""
+        the device; dets rows are ``cls cx cy w h conf`` in label-file order. ``classes``: the class ids kept (0..79), or None
+        for every class (``detect.py`` without ``--classes``). nc <= 32 with ids < 32 runs ``pa_detect_postprocess``, anything
+        wider ``pa_detect_postprocess_classes`` (same arithmetic)."""
         pd = self._dev(pred, torch.float32)
         n, rows, width = pd.shape
-        mask = 0
-        for c in classes:
-            mask |= 1 << int(c)
+        nc = width - 5
+        ids = list(range(nc)) if classes is None else [int(c) for c in classes]
+        if any(not 0 <= c < 80 for c in ids):
+            raise ValueError(f"class ids must be in 0..79: {ids}")
         dets = torch.empty((n, max_det, 6), dtype=torch.float32, device=self.device)
         counts = torch.empty((n,), dtype=torch.int32, device=self.device)
-        self._check(self._lib.pa_detect_postprocess(self._h, _ptr(pd), n, rows, width - 5, conf_thres, iou_thres, mask, max_det,
-                                                    int(net_hw[0]), int(net_hw[1]), int(img_hw[0]), int(img_hw[1]), _ptr(dets),
-                                                    _ptr(counts), self._stream()))
+        geo = (int(net_hw[0]), int(net_hw[1]), int(img_hw[0]), int(img_hw[1]))
+        if nc <= 32 and all(c < 32 for c in ids):
+            mask = 0
+            for c in ids:
+                mask |= 1 << c
+            self._check(self._lib.pa_detect_postprocess(self._h, _ptr(pd), n, rows, nc, conf_thres, iou_thres, mask, max_det, *geo,
+                                                        _ptr(dets), _ptr(counts), self._stream()))
+        else:
+            words = (C.c_uint32 * 3)()
+            for c in ids:
+                words[c >> 5] |= 1 << (c & 31)
+            self._check(self._lib.pa_detect_postprocess_classes(self._h, _ptr(pd), n, rows, nc, conf_thres, iou_thres, words, max_det,
+                                                                *geo, _ptr(dets), _ptr(counts), self._stream()))
         return dets, counts
 
     def clean_detections(self, dets: torch.Tensor, counts: torch.Tensor, n_decoded_frames: int):

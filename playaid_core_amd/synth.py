@@ -528,3 +528,70 @@ def make_yolov5s_state_dict(seed: int = 1357, nc: int = 6) -> Dict[str, np.ndarr
     anchors = np.array([[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]], np.float32).reshape(3, 3, 2)
     sd["model.24.anchors"] = anchors / np.array([8, 16, 32], np.float32)[:, None, None]
     return sd
+
+
+def make_yolov5_state_dict(size="s", seed: int = 1357, nc: int = 6) -> Dict[str, np.ndarray]:
+    """``make_yolov5s_state_dict`` for any YOLOv5 v6.0 / v7.0 P5 size: ``size`` is one of "n", "s", "m", "l", "x" or a
+    ``(depth_multiple, width_multiple)`` pair; widths and bottlenecks per C3 block as ``parse_model`` makes them from
+    ``models/yolov5{size}.yaml`` (``yolov5.p5_graph``). Same key layout, distributions and name-derived seeds, so "s" gives
+    the arrays of ``make_yolov5s_state_dict``."""
+    from .yolov5 import P5_SIZES, p5_graph
+
+    gd, gw = P5_SIZES[size] if isinstance(size, str) else size
+    g = p5_graph(gd, gw)
+    c, rep = g["widths"], g["repeats"]
+    sd: Dict[str, np.ndarray] = {}
+
+    def conv(prefix, c1, c2, k, gain=1.0):
+        fan = c1 * k * k
+        a = math.sqrt(3.0 / fan) * 1.5 * gain
+        sd[prefix + ".conv.weight"] = uniform((c2, c1, k, k), _name_seed(prefix + ".conv.weight", seed), -a, a)
+        sd[prefix + ".bn.weight"] = uniform((c2,), _name_seed(prefix + ".bn.weight", seed), 0.5, 1.5)
+        sd[prefix + ".bn.bias"] = uniform((c2,), _name_seed(prefix + ".bn.bias", seed), -0.1, 0.1)
+        sd[prefix + ".bn.running_mean"] = uniform((c2,), _name_seed(prefix + ".bn.running_mean", seed), -0.1, 0.1)
+        sd[prefix + ".bn.running_var"] = uniform((c2,), _name_seed(prefix + ".bn.running_var", seed), 0.5, 1.5)
+
+    s_rep = p5_graph(*P5_SIZES["s"])["repeats"]
+
+    def c3(i, c1, c2):
+        prefix, c_ = f"model.{i}", int(c2 * 0.5)   # C3(e=0.5)
+        conv(prefix + ".cv1", c1, c_, 1)
+        conv(prefix + ".cv2", c1, c_, 1)
+        conv(prefix + ".cv3", 2 * c_, c2, 1)
+        # deeper blocks than s's: the bottlenecks' gain shrinks so that n of them grow the signal as much as s's do (with
+        # s's gain a 12-bottleneck block saturates the network, and the head sees nothing but 0 and 1)
+        g = (s_rep[i] / rep[i]) ** 0.5
+        for j in range(rep[i]):
+            conv(f"{prefix}.m.{j}.cv1", c_, c_, 1, g)
+            conv(f"{prefix}.m.{j}.cv2", c_, c_, 3, g)
+
+    conv("model.0", 3, c[0], 6)
+    conv("model.1", c[0], c[1], 3)
+    c3(2, c[1], c[1])
+    conv("model.3", c[1], c[2], 3)
+    c3(4, c[2], c[2])
+    conv("model.5", c[2], c[3], 3)
+    c3(6, c[3], c[3])
+    conv("model.7", c[3], c[4], 3)
+    c3(8, c[4], c[4])
+    conv("model.9.cv1", c[4], c[4] // 2, 1)
+    conv("model.9.cv2", 4 * (c[4] // 2), c[4], 1)
+    conv("model.10", c[4], c[3], 1)
+    c3(13, 2 * c[3], c[3])
+    conv("model.14", c[3], c[2], 1)
+    c3(17, 2 * c[2], c[2])
+    conv("model.18", c[2], c[2], 3)
+    c3(20, 2 * c[2], c[3])
+    conv("model.21", c[3], c[3], 3)
+    c3(23, 2 * c[3], c[4])
+    no = 5 + nc
+    for i, (ch, s) in enumerate(((c[2], 8), (c[3], 16), (c[4], 32))):
+        a = math.sqrt(3.0 / ch)
+        sd[f"model.24.m.{i}.weight"] = uniform((3 * no, ch, 1, 1), _name_seed(f"model.24.m.{i}.weight", seed), -a, a)
+        b = uniform((3, no), _name_seed(f"model.24.m.{i}.bias", seed), -0.05, 0.05)
+        b[:, 4] += math.log(8 / (640 / s) ** 2)
+        b[:, 5:] += math.log(0.6 / (nc - 0.99999))
+        sd[f"model.24.m.{i}.bias"] = b.reshape(-1)
+    anchors = np.array([[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]], np.float32).reshape(3, 3, 2)
+    sd["model.24.anchors"] = anchors / np.array([8, 16, 32], np.float32)[:, None, None]
+    return sd

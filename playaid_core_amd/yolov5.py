@@ -228,6 +228,218 @@ def build_yolov5s_table(sd: Mapping, net_hw: Tuple[int, int], nc: int):
     return T.layers, buf_floats, np.concatenate(T.weights), rows
 
 
+# -- every YOLOv5 v6.0 / v7.0 P5 size (n / s / m / l / x, or any multiples) --------------------------------------------------
+# models/yolov5{n,s,m,l,x}.yaml: one graph, scaled by depth_multiple (gd) and width_multiple (gw)
+P5_SIZES = {"n": (0.33, 0.25), "s": (0.33, 0.50), "m": (0.67, 0.75), "l": (1.00, 1.00), "x": (1.33, 1.25)}
+C3_LAYERS = (2, 4, 6, 8, 13, 17, 20, 23)          # the C3 blocks of the graph (first four: the backbone's, with shortcuts)
+_C3_BASE = {2: 3, 4: 6, 6: 9, 8: 3, 13: 3, 17: 3, 20: 3, 23: 3}   # their yaml repeats before depth_multiple
+
+
+def make_divisible(x: float, divisor: int = 8) -> int:
+    """utils/general.py::make_divisible: the smallest multiple of divisor >= x."""
+    return int(np.ceil(x / divisor) * divisor)
+
+
+def p5_graph(gd: float, gw: float) -> Dict[str, object]:
+    """What models/yolo.py::parse_model makes of the P5 yaml at (gd, gw): widths c1..c5 (make_divisible(c * gw, 8)) and the
+    bottlenecks per C3 block (max(round(n * gd), 1))."""
+    widths = tuple(make_divisible(c * gw, 8) for c in (64, 128, 256, 512, 1024))
+    return {"widths": widths, "repeats": {i: max(round(n * gd), 1) for i, n in _C3_BASE.items()}}
+
+
+def graph_of(sd: Mapping) -> Dict[str, object]:
+    """The graph a P5 state dict holds, read from its shapes: widths c1..c5, bottlenecks per C3 block, nc."""
+    out = lambda key: int(_np(sd[key]).shape[0])
+    if "model.0.conv.conv.weight" in sd:
+        raise ValueError("a v5.0-or-older model (Focus stem): only the v6.0 / v7.0 6x6 stem is supported")
+    if "model.33.m.3.weight" in sd or "model.24.m.0.weight" not in sd:
+        raise ValueError("not a P5 Detect head on model.24 (P6 models with four scales are not supported)")
+    widths = tuple(out(f"model.{i}.conv.weight") for i in (0, 1, 3, 5, 7))
+    repeats = {}
+    for i in C3_LAYERS:
+        n = 0
+        while f"model.{i}.m.{n}.cv1.conv.weight" in sd:
+            n += 1
+        repeats[i] = n
+    no3 = out("model.24.m.0.weight")
+    if no3 % 3 or no3 // 3 < 6:
+        raise ValueError(f"Detect head with {no3} output channels is not 3 x (5 + nc)")
+    return {"widths": widths, "repeats": repeats, "nc": no3 // 3 - 5}
+
+
+def _c32(c: int) -> int:
+    return -(-c // 32) * 32
+
+
+def build_yolov5_table(sd: Mapping, net_hw: Tuple[int, int], nc: int, real_masks: List = None):
+    """``build_yolov5s_table`` for any YOLOv5 v6.0 / v7.0 P5 state dict: the widths and the bottlenecks per C3 block come from
+    its shapes. Channel counts that are not multiples of 32 (c1 = 16 / 48 / 80 of n / m / x, C3 hidden widths) are padded to
+    the next multiple: a slice holds its real channels first and zeros behind them, and every weight row, weight column and
+    bias of a padded position is exactly 0 (SiLU(0) = 0, so the padding stays 0 through every layer and moves no result).
+    A concatenation buffer is its producers' padded slices side by side; the consumer's weight columns follow that layout.
+    The stem is one kind-3 row per 32 output channels (out_coff = 32 g). Detect slices hold max(64, 3 (5 + nc) rounded up to
+    32) channels. For an s state dict the layers and the weight blob are those of ``build_yolov5s_table``, byte for byte.
+    real_masks: if a list, gets (row index, real output rows bool[cout], real input columns bool[cin]) per kind-0 / kind-3 row."""
+    H, W = net_hw
+    assert H % 32 == 0 and W % 32 == 0
+    g = graph_of(sd)
+    if g["nc"] != nc:
+        raise ValueError(f"the Detect head holds {g['nc']} classes, not nc = {nc}")
+    if any(n < 1 for n in g["repeats"].values()):
+        raise ValueError(f"a C3 block without bottlenecks: {g['repeats']}")
+    T = _Table()
+    size = {2: (H // 2, W // 2), 4: (H // 4, W // 4), 8: (H // 8, W // 8), 16: (H // 16, W // 16), 32: (H // 32, W // 32)}
+
+    def B(scale, pad, c):
+        return T.buf(size[scale][0], size[scale][1], pad, c)
+
+    def S(buf, coff, *reals):
+        """a slice of buf at coff holding the real channel groups `reals`, each padded to a multiple of 32, side by side"""
+        segs, o = [], 0
+        for r in reals:
+            segs.append((o, r))
+            o += _c32(r)
+        return (buf, coff, o, tuple(segs))
+
+    def lay(w, b, src, dst, k, s, act=2, res=None, res_after=0):
+        """w [co, ci, k, k] / b [co] of the real channels -> the padded layout of the slices src / dst"""
+        wp = np.zeros((dst[2], src[2], k, k), np.float64)
+        bp = np.zeros(dst[2], np.float64)
+        rows, cols = np.zeros(dst[2], bool), np.zeros(src[2], bool)
+        i = 0
+        for o, r in dst[3]:
+            j = 0
+            for oc, c in src[3]:
+                wp[o:o + r, oc:oc + c] = w[i:i + r, j:j + c]
+                j += c
+            assert j == w.shape[1], (w.shape, src)
+            bp[o:o + r] = b[i:i + r]
+            rows[o:o + r] = True
+            i += r
+        assert i == w.shape[0], (w.shape, dst)
+        for oc, c in src[3]:
+            cols[oc:oc + c] = True
+        if real_masks is not None:
+            real_masks.append((len(T.layers), rows, cols))
+        T.conv(wp, bp, src[:3], dst[:3], k, s, act, None if res is None else res[:3], res_after)
+
+    def C3(prefix, src, dst, scale, n, shortcut):
+        """as in build_yolov5s_table: X = [cv1 | cv2], the bottlenecks in place on X's first half, cv3 on X"""
+        w1, b1 = _fold(sd, prefix + ".cv1")
+        w2, b2 = _fold(sd, prefix + ".cv2")
+        w3, b3 = _fold(sd, prefix + ".cv3")
+        c_ = w1.shape[0]
+        X = B(scale, 0, 2 * _c32(c_))
+        R = B(scale, 1, _c32(c_))
+        lay(np.concatenate([w1, w2]), np.concatenate([b1, b2]), src, S(X, 0, c_, c_), 1, 1)
+        for j in range(n):
+            wa, ba = _fold(sd, f"{prefix}.m.{j}.cv1")
+            lay(wa, ba, S(X, 0, c_), S(R, 0, c_), 1, 1)
+            wb, bb = _fold(sd, f"{prefix}.m.{j}.cv2")
+            lay(wb, bb, S(R, 0, c_), S(X, 0, c_), 3, 1, res=S(X, 0, c_) if shortcut else None, res_after=1)
+        lay(w3, b3, S(X, 0, c_, c_), dst, 1, 1)
+
+    def conv(prefix, src, dst, k, s):
+        w, b = _fold(sd, prefix)
+        lay(w, b, src, dst, k, s)
+
+    ch = lambda key: int(_np(sd[key]).shape[0])
+    c1, c2, c3, c4, c5 = g["widths"]
+    rep = g["repeats"]
+    c6, c9, c10 = ch("model.6.cv3.conv.weight"), ch("model.9.cv1.conv.weight"), ch("model.10.conv.weight")
+    c14, c18, c21 = ch("model.14.conv.weight"), ch("model.18.conv.weight"), ch("model.21.conv.weight")
+    c4o = ch("model.4.cv3.conv.weight")
+    # concatenation buffers of the head (the backbone writes its skip connections straight into them)
+    C12 = B(16, 1, _c32(c10) + _c32(c6))     # [up(model.10) | model.6]
+    C16 = B(8, 1, _c32(c14) + _c32(c4o))     # [up(model.14) | model.4]
+    C19 = B(16, 0, _c32(c18) + _c32(c14))    # [model.18 | model.14]
+    C22 = B(32, 0, _c32(c21) + _c32(c10))    # [model.21 | model.10]
+    # backbone: the stem as one row per 32 output channels, each in the direct kernel's lane layout (build_yolov5s_table)
+    B0 = B(2, 1, _c32(c1))
+    w0, b0 = _fold(sd, "model.0")
+    w0p, b0p = np.zeros((_c32(c1), 3, 6, 6)), np.zeros(_c32(c1))
+    w0p[:c1], b0p[:c1] = w0, b0
+    for gi in range(_c32(c1) // 32):
+        stem = np.zeros((2, 32, 56), np.float64)
+        for half in range(2):
+            stem[half, :, :54] = w0p[32 * gi:32 * gi + 32, :, :, 3 * half:3 * half + 3].transpose(0, 2, 3, 1).reshape(32, 54)
+        L = _lib.pa_net_layer()
+        L.kind, L.cin, L.cout, L.ksize, L.stride, L.in_h, L.in_w = 3, 3, 32, 6, 2, H, W
+        L.in_buf, L.res_buf = -1, -1
+        L.out_buf, L.out_coff, L.out_cstride, L.out_pad = B0, 32 * gi, _c32(c1), 1
+        L.act = 2
+        if real_masks is not None:
+            real_masks.append((len(T.layers), np.arange(32 * gi, 32 * gi + 32) < c1, np.ones(3, bool)))
+        L.w_off, L.b_off = T.put(stem), T.put(b0p[32 * gi:32 * gi + 32])
+        T.layers.append(L)
+    B1 = B(4, 0, _c32(c2))
+    conv("model.1", S(B0, 0, c1), S(B1, 0, c2), 3, 2)
+    B2 = B(4, 1, _c32(c2))
+    C3("model.2", S(B1, 0, c2), S(B2, 0, c2), 4, rep[2], True)
+    B3 = B(8, 0, _c32(c3))
+    conv("model.3", S(B2, 0, c2), S(B3, 0, c3), 3, 2)
+    C3("model.4", S(B3, 0, c3), S(C16, _c32(c14), c4o), 8, rep[4], True)
+    B5 = B(16, 0, _c32(c4))
+    conv("model.5", S(C16, _c32(c14), c4o), S(B5, 0, c4), 3, 2)
+    C3("model.6", S(B5, 0, c4), S(C12, _c32(c10), c6), 16, rep[6], True)
+    B7 = B(32, 0, _c32(c5))
+    conv("model.7", S(C12, _c32(c10), c6), S(B7, 0, c5), 3, 2)
+    c8 = ch("model.8.cv3.conv.weight")
+    B8 = B(32, 0, _c32(c8))
+    C3("model.8", S(B7, 0, c5), S(B8, 0, c8), 32, rep[8], True)
+    # SPPF: x | pool(x) | pool(pool(x)) | pool(pool(pool(x))) side by side
+    p9 = _c32(c9)
+    S9 = B(32, 0, 4 * p9)
+    conv("model.9.cv1", S(B8, 0, c8), S(S9, 0, c9), 1, 1)
+    for k in range(3):
+        T.move(4, (S9, k * p9, p9), (S9, (k + 1) * p9, p9))
+    c9o = ch("model.9.cv2.conv.weight")
+    B9 = B(32, 0, _c32(c9o))
+    conv("model.9.cv2", S(S9, 0, c9, c9, c9, c9), S(B9, 0, c9o), 1, 1)
+    # head
+    conv("model.10", S(B9, 0, c9o), S(C22, _c32(c21), c10), 1, 1)
+    T.move(5, (C22, _c32(c21), _c32(c10)), (C12, 0, _c32(c10)))
+    c13 = ch("model.13.cv3.conv.weight")
+    B13 = B(16, 0, _c32(c13))
+    C3("model.13", S(C12, 0, c10, c6), S(B13, 0, c13), 16, rep[13], False)
+    conv("model.14", S(B13, 0, c13), S(C19, _c32(c18), c14), 1, 1)
+    T.move(5, (C19, _c32(c18), _c32(c14)), (C16, 0, _c32(c14)))
+    c17 = ch("model.17.cv3.conv.weight")
+    B17 = B(8, 1, _c32(c17))
+    C3("model.17", S(C16, 0, c14, c4o), S(B17, 0, c17), 8, rep[17], False)
+    conv("model.18", S(B17, 0, c17), S(C19, 0, c18), 3, 2)
+    c20 = ch("model.20.cv3.conv.weight")
+    B20 = B(16, 1, _c32(c20))
+    C3("model.20", S(C19, 0, c18, c14), S(B20, 0, c20), 16, rep[20], False)
+    conv("model.21", S(B20, 0, c20), S(C22, 0, c21), 3, 2)
+    c23 = ch("model.23.cv3.conv.weight")
+    B23 = B(32, 0, _c32(c23))
+    C3("model.23", S(C22, 0, c21, c10), S(B23, 0, c23), 32, rep[23], False)
+    # Detect: one 1x1 convolution per scale into a head slice of hd channels, then the decode
+    no = 5 + nc
+    hd = max(64, _c32(3 * no))
+    anchors = _np(sd["model.24.anchors"]).astype(np.float64)
+    rows = 0
+    for i, (feat, c, scale) in enumerate(((B17, c17, 8), (B20, c20, 16), (B23, c23, 32))):
+        D = B(scale, 0, hd)
+        w = _np(sd[f"model.24.m.{i}.weight"]).astype(np.float64)
+        b = _np(sd[f"model.24.m.{i}.bias"]).astype(np.float64)
+        lay(w, b, S(feat, 0, c), (D, 0, hd, ((0, 3 * no),)), 1, 1, act=0)
+        L = _lib.pa_net_layer()
+        L.kind, L.cin, L.cout, L.ksize, L.stride = 6, hd, 3 * no, 1, 1
+        L.in_h, L.in_w = size[scale]
+        L.in_buf, L.in_coff, L.in_cstride, L.in_pad = D, 0, hd, 0
+        L.out_buf, L.res_buf = -1, -1
+        L.aux[0] = float(STRIDES[i])
+        for a in range(3):
+            L.aux[1 + 2 * a] = float(anchors[i, a, 0] * STRIDES[i])
+            L.aux[2 + 2 * a] = float(anchors[i, a, 1] * STRIDES[i])
+        T.layers.append(L)
+        rows += 3 * size[scale][0] * size[scale][1]
+    buf_floats = [(h + 2 * p) * (w + 2 * p) * c for (h, w, p, c) in T.bufs]
+    return T.layers, buf_floats, np.concatenate(T.weights), rows
+
+
 def buffer_geometry(layers) -> Dict[int, Tuple[int, int, int, int]]:
     """buffer -> (h, w, pad, channels per pixel) as the table's rows address it (every row touching a buffer agrees)."""
     geo = {}
@@ -242,13 +454,14 @@ def buffer_geometry(layers) -> Dict[int, Tuple[int, int, int, int]]:
 
 
 class YoloV5Detector:
-    """``pa_detector_*`` handle for a YOLOv5s state dict. ``net_hw``: the network input (what ``letterbox(auto=True)`` picks
-    for the clip: 384 x 640 for 16:9 frames at ``--imgsz 640``)."""
+    """``pa_detector_*`` handle for a YOLOv5 v6.0 / v7.0 P5 state dict of any size (n / s / m / l / x or custom multiples; up to
+    80 classes). ``net_hw``: the network input (what ``letterbox(auto=True)`` picks for the clip: 384 x 640 for 16:9 frames at
+    ``--imgsz 640``). ``load_from_checkpoint`` takes an ultralytics ``.pt`` directly."""
 
     def __init__(self, state_dict: Mapping, nc: int, net_hw: Tuple[int, int] = (384, 640), max_images: int = 64, device: str = "cuda:0",
-                 compute_dtype: str = "f32", buf_slack: int = 0):
+                 compute_dtype: str = "f32", buf_slack: int = 0, names: List[str] = None):
         """buf_slack: floats added to every buffer's share per image (tests: a table whose buffers are larger than the geometry
-        their rows address, which the public table API allows)."""
+        their rows address, which the public table API allows). names: the class names, if known (``self.names``)."""
         self._lib = _lib.load()
         if compute_dtype not in ("f32", "emulated_f32", "bf16"):
             raise ValueError("compute_dtype must be 'f32', 'emulated_f32' or 'bf16'")
@@ -257,7 +470,8 @@ class YoloV5Detector:
             raise _lib.HipLibraryError("no HIP device visible to PyTorch-ROCm; the detection network has no CPU fallback")
         self.device = torch.device(device)
         self.nc, self.net_hw, self.max_images = nc, tuple(net_hw), max_images
-        layers, buf_floats, weights, rows = build_yolov5s_table(state_dict, self.net_hw, nc)
+        self.names = list(names) if names is not None else None
+        layers, buf_floats, weights, rows = build_yolov5_table(state_dict, self.net_hw, nc)
         buf_floats = [b + buf_slack for b in buf_floats]
         self.rows = rows
         self.layers, self.weights = layers, weights
@@ -286,6 +500,18 @@ class YoloV5Detector:
                 self.flops_per_image += 2.0 * oh * ow * L.cout * L.ksize * L.ksize * L.cin
             elif L.kind == 3:
                 self.flops_per_image += 2.0 * oh * ow * L.cout * 108
+
+    @classmethod
+    def load_from_checkpoint(cls, path, net_hw: Tuple[int, int] = (384, 640), max_images: int = 64, device: str = "cuda:0",
+                             compute_dtype: str = "f32") -> "YoloV5Detector":
+        """An ultralytics YOLOv5 v6.x / v7.0 ``.pt`` (or a bare state dict saved with ``torch.save``), read without the YOLOv5
+        checkout (``yolov5_checkpoint.load_yolov5_checkpoint``: what it refuses, and why, is listed there)."""
+        from .yolov5_checkpoint import load_yolov5_checkpoint
+
+        sd, meta = load_yolov5_checkpoint(path)
+        det = cls(sd, meta["nc"], net_hw, max_images=max_images, device=device, compute_dtype=compute_dtype, names=meta["names"])
+        det.meta = meta
+        return det
 
     def close(self):
         if getattr(self, "_h", None):
@@ -352,7 +578,8 @@ class YoloV5Detector:
         return [_lib.DET_FORMS[f] for f in forms]
 
     def detections(self, engine, frames, conf_thres: float = 0.25, iou_thres: float = 0.45, classes=(2, 3), max_det: int = 2):
-        """-> (dets float32[n, max_det, 6], counts int32[n]) on the device: ``detect.py``'s label rows (``ai_runner.py:209-217``)."""
+        """-> (dets float32[n, max_det, 6], counts int32[n]) on the device: ``detect.py``'s label rows (``ai_runner.py:209-217``).
+        classes: the class ids kept (0..79), None = every class (``detect.py`` without ``--classes``)."""
         fd = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames)).to(self.device)
         pred = self.forward(fd)
         return engine.detect_postprocess(pred, self.net_hw, (fd.shape[1], fd.shape[2]), conf_thres, iou_thres, classes, max_det)
