@@ -1463,8 +1463,17 @@ __global__ __launch_bounds__(256) void slice_upload_kernel(const uint8_t* __rest
         const uintptr_t ga = (uintptr_t)(frames_host + so);
         const uint32_t* g4 = reinterpret_cast<const uint32_t*>(ga & ~(uintptr_t)3);
         const uint32_t sh = (uint32_t)(ga & 3);
-        // bytes of the frame buffer left from the aligned address on: never read past its end
+        // bytes of the frame buffer left from the aligned address on: never read past its end. A buffer whose size is not a
+        // multiple of 4 ends inside a dword; that dword is gathered byte by byte (it holds the last pixels of the last frame's
+        // rows that reach the last column), the bytes behind the end read as 0
         const long long left = frames_bytes - (so - (long long)sh);
+        auto ld = [&](int j) -> uint32_t {
+            if (4ll * (j + 1) <= left) return g4[j];
+            const uint8_t* b = reinterpret_cast<const uint8_t*>(g4 + j);
+            uint32_t v = 0;
+            for (int k = 0; k < 4 && 4ll * j + k < left; ++k) v |= (uint32_t)b[k] << (8 * k);
+            return v;
+        };
         uint32_t* dst = reinterpret_cast<uint32_t*>(windows + w.offset + (size_t)y * w.pitch);
         // the link's latency is microseconds: every lane requests up to six dwords (a 1.5 KB row per pass) before the
         // first one is used
@@ -1473,8 +1482,8 @@ __global__ __launch_bounds__(256) void slice_upload_kernel(const uint8_t* __rest
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
                 const int j = j0 + lane + 64 * u;
-                lo[u] = j < row_dwords ? g4[j] : 0u;
-                hi[u] = (sh && j < row_dwords && 4ll * (j + 1) < (long long)sh + row_bytes && 4ll * (j + 2) <= left) ? g4[j + 1] : 0u;
+                lo[u] = j < row_dwords ? ld(j) : 0u;
+                hi[u] = (sh && j < row_dwords && 4ll * (j + 1) < (long long)sh + row_bytes) ? ld(j + 1) : 0u;
             }
 #pragma unroll
             for (int u = 0; u < 6; ++u) {

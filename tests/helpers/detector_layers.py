@@ -270,12 +270,41 @@ class _Trace:
             del self.cache[key]
 
 
+def check_model_input(det, frames_np, tag, x0=None, idx=None, want=None):
+    """The model input of a detector of any compute dtype on frames uint8[n,H,W,3]: the stem's 2-pixel border and channel 3
+    zero, the interior bitwise ``oracle.yolov5.letterbox`` -- fp32 / 255 ("f32"), or 255 x that as bf16 pixel integers
+    ("emulated_f32", "bf16"). x0: the stored input (``det.trace(frames, -1, -1)``; fetched when None). idx: the images compared
+    (default ``sample_images``). want: the oracle's letterbox of those images, [len(idx)][3][H][W], when the caller has it.
+    -> the interior of those images as stored, float32 [len(idx)][net_h][net_w][3]. Raises LayerFault."""
+    from oracle import yolov5 as oy
+
+    n = frames_np.shape[0]
+    idx = sample_images(n) if idx is None else np.asarray(idx)
+    if x0 is None:
+        x0, _ = det.trace(torch.from_numpy(np.ascontiguousarray(frames_np)).to(det.device), -1, -1, 0, det.max_images)
+    if det.compute_dtype == "bf16" and x0.dtype != torch.bfloat16:
+        raise LayerFault(f"{tag} input: stored as {x0.dtype}, not bf16")
+    if bool(x0[..., 3].any()) or bool(x0[:, :2].any()) or bool(x0[:, -2:].any()) or bool(x0[:, :, :2].any()) or bool(x0[:, :, -2:].any()):
+        raise LayerFault(f"{tag} input: border or channel 3 not zero")
+    x0h = x0[torch.as_tensor(idx, device=x0.device)].float().cpu().numpy()
+    if want is None:
+        want = np.stack([oy.letterbox(frames_np[i], det.net_hw) for i in idx])
+    want = np.asarray(want).transpose(0, 2, 3, 1)
+    got = x0h[:, 2:-2, 2:-2, :3]
+    if det.compute_dtype in ("emulated_f32", "bf16"):
+        if not np.array_equal(got, np.rint(want.astype(np.float64) * 255).astype(np.float32)):
+            raise LayerFault(f"{tag} input: not the letterbox's pixel integers")
+        if det.compute_dtype == "emulated_f32" and not np.array_equal(got / np.float32(255), want):
+            raise LayerFault(f"{tag} input: not the letterbox's pixel integers")
+    elif not np.array_equal(got, want):
+        raise LayerFault(f"{tag} input: not bitwise the letterbox")
+    return got
+
+
 def check_detector(det, frames_np, tag, log=print):
     """Walks every row of det's table on frames uint8[n,H,W,3] and checks it; returns
     {"forms": [per row], "ratios": {form: worst conv ratio}, "decode": worst decode ratio}. Raises LayerFault (naming row,
     kind and form) on the first failure."""
-    from oracle import yolov5 as oy
-
     n = frames_np.shape[0]
     frames = torch.from_numpy(np.ascontiguousarray(frames_np)).to(det.device)
     layers, blob, nc = det.layers, det.weights, det.nc
@@ -286,16 +315,7 @@ def check_detector(det, frames_np, tag, log=print):
     emu_stem = det.compute_dtype == "emulated_f32"
     # the model input
     x0, _ = tr.get(-1, -1)
-    if bool(x0[..., 3].any()) or bool(x0[:, :2].any()) or bool(x0[:, -2:].any()) or bool(x0[:, :, :2].any()) or bool(x0[:, :, -2:].any()):
-        raise LayerFault(f"{tag} input: border or channel 3 not zero")
-    x0h = host(x0)
-    want = np.stack([oy.letterbox(frames_np[i], det.net_hw) for i in idx]).transpose(0, 2, 3, 1)
-    got = x0h[:, 2:-2, 2:-2, :3]
-    if emu_stem:
-        if not np.array_equal(got, np.rint(want.astype(np.float64) * 255).astype(np.float32)) or not np.array_equal(got / np.float32(255), want):
-            raise LayerFault(f"{tag} input: not the letterbox's pixel integers")
-    elif not np.array_equal(got, want):
-        raise LayerFault(f"{tag} input: not bitwise the letterbox")
+    got = check_model_input(det, frames_np, tag, x0=x0, idx=idx)
     x_in = got.astype(np.float64) / 255.0 if emu_stem else got.astype(np.float64)
     ratios, dec_worst, row0 = {}, 0.0, 0
     per_row = {}

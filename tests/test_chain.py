@@ -12,7 +12,19 @@ F32 = np.float32
 NET = (384, 640)
 
 
-def test_chain_from_mjpeg_bytes_to_labels(engine, state_dict):
+# (frame height, width, seed of the clip's frames): 16:9, and a 4:3 clip that sits in the same 384 x 640 input at gain 0.64 between
+# two 64-column grey borders
+CLIPS = [(720, 1280, 7), (600, 800, 7)]
+
+
+def letterbox_geometry(net, h, w):
+    """``scale_boxes``' gain and pads of an h x w frame in the network input (oracle/detect.py: scale_and_normalise)."""
+    gain = min(net[0] / h, net[1] / w)
+    return gain, (net[1] - w * gain) / 2, (net[0] - h * gain) / 2
+
+
+@pytest.mark.parametrize("h,w,seed", CLIPS, ids=[f"{h}x{w}" for h, w, _ in CLIPS])
+def test_chain_from_mjpeg_bytes_to_labels(engine, state_dict, h, w, seed):
     import torch
 
     from oracle import detect as odet
@@ -24,8 +36,10 @@ def test_chain_from_mjpeg_bytes_to_labels(engine, state_dict):
     from playaid_core_amd.fighter import YoloCrop
     from playaid_core_amd.yolov5 import YoloV5Detector
 
-    n, h, w = 20, 720, 1280
-    blobs = synth.encode_jpeg_frames(synth.make_frames(n, h, w), quality=95)
+    n = 20
+    gain, pad_x, pad_y = letterbox_geometry(NET, h, w)
+    assert (gain, pad_x, pad_y) == {720: (0.5, 0.0, 12.0), 600: (0.64, 64.0, 0.0)}[h]
+    blobs = synth.encode_jpeg_frames(synth.make_frames(n, h, w, seed=seed), quality=95)
     # 1. decode: device frames == the oracle's, bit for bit
     data = np.frombuffer(b"".join(blobs), np.uint8)
     ends = np.cumsum([len(b) for b in blobs])
@@ -59,8 +73,8 @@ def test_chain_from_mjpeg_bytes_to_labels(engine, state_dict):
         boxes = synth.make_boxes(n, h, w)
         cand = np.zeros((n, 6, 11), F32)
         for i in range(n):
-            for p in range(2):  # network-input pixels: gain 0.5, 12 px letterbox (720p in 384 x 640)
-                cx, cy, bw, bh = boxes[i, p] * np.array([w, h, w, h]) * 0.5 + np.array([0, 12, 0, 0])
+            for p in range(2):  # network-input pixels: the letterbox's gain and borders (720p in 384 x 640: 0.5, 12 rows above)
+                cx, cy, bw, bh = boxes[i, p] * np.array([w, h, w, h]) * gain + np.array([pad_x, pad_y, 0, 0])
                 for k in range(3):
                     cand[i, 3 * p + k, :5] = [cx + k, cy - k, bw, bh, 0.95 - 0.1 * k]
                     cand[i, 3 * p + k, 5 + 2 + p] = 0.9

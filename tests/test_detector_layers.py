@@ -6,6 +6,7 @@ references, bars and the walk live in tests/helpers/detector_layers.py (its docs
 bottleneck (``X += conv3x3(R)``) takes as its residual the output slice as the row before left it.
 
 Cases, frames of 720p, 1080p and 270 x 480 (enlarged) mixed, both dtypes:
+  * net 384 x 640 on 480 x 640 frames (left and right borders) and net 640 x 384 on 853 x 481 frames (portrait, unequal borders);
   * net 384 x 640: 1 and 3 frames of a 4-image handle; 64 of 64 (configs[1]), every image on the exact and the bitwise
     checks, a float64 sample of seven images on the convolutions (``sample_images``);
   * nets 320 x 320, 352 x 608, 64 x 96, 3 frames: maps whose sides are not multiples of four (10 x 10; 22 x 38 and 11 x 19;
@@ -54,6 +55,10 @@ CASES = {
     "352x608": ((352, 608), 3, [(3, 1080, 1920)], 0),
     "64x96": ((64, 96), 3, [(3, 270, 480)], 0),
     "384x640_padded": ((384, 640), 4, [(3, 720, 1280)], 4096),
+    # frames that are not 16:9 (tests/test_frame_geometry.py walks the letterbox alone over more of them): 4:3 with 64 grey
+    # columns on each side, and a portrait frame in a portrait input with 11 / 12 grey columns
+    "384x640_4:3": ((384, 640), 3, [(3, 480, 640)], 0),
+    "640x384_portrait": ((640, 384), 3, [(3, 853, 481)], 0),
 }
 _SEEN = {}   # dtype -> {form: worst ratio}, and the forms per case, for the coverage test
 

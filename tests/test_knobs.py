@@ -1,6 +1,7 @@
 """The library's A/B knobs change HOW a result is computed, never what it is: every setting measured
 this round must reproduce the default process's outputs -- bit for bit where the knob only moves work between streams, within
-fp32 rounding (1e-5 on log-probabilities, 2e-4 on scores, 4e-2 px on boxes: the paths' own bars) where it swaps a kernel."""
+fp32 rounding (1e-5 on log-probabilities, 2e-4 on scores, 4e-2 px on boxes: the paths' own bars) where it swaps a kernel.
+The crop stage's knob, PA_FUSED_LDS, is pinned bit for bit in tests/test_frame_geometry.py (test_fused_lds_budgets_give_the_same_bytes)."""
 import os
 import subprocess
 import sys
