@@ -31,6 +31,7 @@ SOURCES = [
     ("misc.hip", []),
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("detect.hip", ["-ffp-contract=off"]),
+    ("conv_rows.hip", []),
     ("lstm.hip", []),
     ("convnet.hip", []),
     ("transformer.hip", []),
@@ -51,7 +52,7 @@ def _newer(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = os.environ.get("HIPCC", "hipcc")
-    headers = [os.path.join(CSRC, "pa_kernels.h"), os.path.join(CSRC, "jpeg_dct.h"), os.path.join(HERE, "..", "include", "playaid_hip.h")]
+    headers = [os.path.join(CSRC, "pa_kernels.h"), os.path.join(CSRC, "conv_rows.h"), os.path.join(CSRC, "jpeg_dct.h"), os.path.join(HERE, "..", "include", "playaid_hip.h")]
     objs = []
     rebuilt = False
     for src, extra in SOURCES:

@@ -1,0 +1,113 @@
+// conv_rows.h: a table's convolution row -> launch parameters, and the per-form weight planes. Host code only.
+#include "conv_rows.h"
+
+namespace pa {
+
+GemmParams conv_row_params(const ConvRow& r) {
+    const int oh = r.in_h / r.stride, ow = r.in_w / r.stride;
+    const int in_hb = r.in_h + 2 * r.in_pad, in_wb = r.in_w + 2 * r.in_pad;
+    const int out_hb = oh + 2 * r.out_pad, out_wb = ow + 2 * r.out_pad;
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = r.images * oh * ow;
+    p.N = r.cout;
+    p.taps = r.ksize * r.ksize;
+    p.kw_taps = r.ksize;
+    p.chunk = r.cin;
+    p.ktot = p.taps * p.chunk;
+    p.howo = oh * ow;
+    p.wo = ow;
+    p.in_px_stride = r.in_px_stride;
+    p.in_row_stride = in_wb * r.in_px_stride;
+    p.in_img_stride = in_hb * in_wb * r.in_px_stride;
+    p.stride = r.stride;
+    p.off_y = p.off_x = r.in_pad - (r.ksize - 1) / 2;
+    p.out_px_stride = r.out_px_stride;
+    p.out_row_stride = out_wb * r.out_px_stride;
+    p.out_img_stride = out_hb * out_wb * r.out_px_stride;
+    p.out_pad = r.out_pad;
+    p.relu = r.act;
+    p.res_after = r.res_after;
+    p.splitk = 1;
+    return p;
+}
+
+WinoParams wino_params(const GemmParams& p, int n_img, int height, int width, int cin, const float* filters, int bn) {
+    WinoParams q;
+    memset(&q, 0, sizeof(q));
+    q.act = p.act; q.wgt = filters; q.bias = p.bias; q.residual = p.residual; q.out = p.out;
+    q.n_img = n_img; q.height = height; q.width = width; q.cin = cin; q.cout = p.N; q.bn = bn;
+    q.in_px_stride = p.in_px_stride; q.in_row_stride = p.in_row_stride; q.in_img_stride = p.in_img_stride;
+    q.out_px_stride = p.out_px_stride; q.out_row_stride = p.out_row_stride; q.out_img_stride = p.out_img_stride; q.out_pad = p.out_pad;
+    q.relu = p.relu; q.res_after = p.res_after;
+    return q;
+}
+
+GemmTile im2col_tile(long long M, int N) {
+    const long long t128 = (M + 127) / 128 * (N / 64);   // 128 x 64 tiles; half as many 128 x 128 ones
+    return (N % 128 == 0 && t128 / 2 >= 512) ? TILE_128x128 : (t128 >= 512 ? TILE_128x64 : TILE_64x64);
+}
+
+FormWeights::~FormWeights() {
+    (void)hipFree(wino);
+    (void)hipFree(psgemm);
+    (void)hipFree(bgemm);
+}
+
+namespace {
+
+template <typename T>
+hipError_t upload_plane(T** dst, const std::vector<T>& host, const char* alloc_what, const char* copy_what, const char** what) {
+    if (host.empty()) return hipSuccess;
+    *what = alloc_what;
+    const hipError_t e = hipMalloc(dst, host.size() * sizeof(T));
+    if (e != hipSuccess) return e;
+    *what = copy_what;
+    return hipMemcpy(*dst, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+}  // namespace
+
+hipError_t FormWeights::prepare(const std::vector<FormRow>& rows, const float* blob, const char** what) {
+    const size_t n = rows.size();
+    wino_off.assign(n, -1);
+    wino_bn.assign(n, 0);
+    psgemm_off.assign(n, -1);
+    bgemm_off.assign(n, -1);
+    size_t n_wino = 0, n_ps = 0, n_bg = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const FormRow& r = rows[i];
+        const int ktot = r.ksize * r.ksize * r.cin;
+        if (r.forms & FORM_WINO) {
+            wino_off[i] = (long long)n_wino;
+            wino_bn[i] = wino_pick_bn(r.cout, r.wino_tiles);
+            n_wino += wino_weight_floats(r.cin, r.cout);
+        }
+        if (r.forms & FORM_PSGEMM) {
+            psgemm_off[i] = (long long)n_ps;
+            n_ps += psgemm_weight_elems(r.cout, ktot, r.residual);
+        }
+        if (r.forms & FORM_BGEMM) {
+            bgemm_off[i] = (long long)n_bg;
+            n_bg += r.packed ? r.packed_elems : bgemm_weight_elems(r.cout, ktot, r.residual);
+            n_bg = (n_bg + 127) & ~(size_t)127;   // (every plane 256-byte aligned)
+        }
+    }
+    std::vector<float> ug(n_wino);
+    std::vector<unsigned short> ps(n_ps), bg(n_bg, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const FormRow& r = rows[i];
+        const float* w = blob + r.w_off;
+        const int ktot = r.ksize * r.ksize * r.cin;
+        if (wino_off[i] >= 0) wino_transform_weights(w, r.cin, r.cout, wino_bn[i], ug.data() + wino_off[i]);
+        if (psgemm_off[i] >= 0) psgemm_pack_weights(w, r.cout, ktot, r.residual, ps.data() + psgemm_off[i]);
+        if (bgemm_off[i] >= 0 && r.packed) memcpy(bg.data() + bgemm_off[i], r.packed, r.packed_elems * sizeof(unsigned short));
+        else if (bgemm_off[i] >= 0) bgemm_pack_weights(w, r.cout, ktot, r.residual, bg.data() + bgemm_off[i]);
+    }
+    hipError_t e = upload_plane(&wino, ug, "hipMalloc Winograd filters", "upload Winograd filters", what);
+    if (e == hipSuccess) e = upload_plane(&psgemm, ps, "hipMalloc split weights", "upload split weights", what);
+    if (e == hipSuccess) e = upload_plane(&bgemm, bg, "hipMalloc bf16 weights", "upload bf16 weights", what);
+    return e;
+}
+
+}  // namespace pa

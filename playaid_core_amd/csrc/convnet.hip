@@ -13,7 +13,7 @@
 // convolution on the one-slice bf16 GEMM (bgemm.hip), in its split-K form where the unsplit grid would leave most of the chip idle,
 // the pool on a bf16 twin of the fp32 one (fp32 out). Rounding model: include/playaid_hip.h next to pa_convnet_create_dtype.
 // Nothing here is specific to ResNet-50; the table in playaid_core_amd/resnet_transformer_detector.py is.
-#include "pa_kernels.h"
+#include "conv_rows.h"
 #include "../../include/playaid_hip.h"
 #include <algorithm>
 #include <cstdlib>
@@ -66,16 +66,12 @@ struct pa_convnet {
     std::vector<size_t> buf_floats;  // per crop (elements)
     float* weights = nullptr;
     size_t n_weights = 0;
-    float* wino_weights = nullptr;      // the stride-1 3x3 layers' filters in the Winograd kernel's layout (wino.hip)
-    std::vector<long long> wino_off;    // per layer: float offset into wino_weights, -1 = direct form
-    std::vector<int> wino_bn;           // per layer: output channels per workgroup its filters were laid out for
-    int compute_dtype = PA_DTYPE_F32;          // PA_DTYPE_EMULATED_F32: the layers listed in split_off run on psgemm.hip
-    unsigned short* split_weights = nullptr;   // those layers' weights as three bf16 slices (psgemm_pack_weights)
-    std::vector<long long> split_off;          // per layer: element offset into split_weights, -1 = the exact kernel
+    int compute_dtype = PA_DTYPE_F32;
+    // per row: the stride-1 3x3 layers' Winograd filters; PA_DTYPE_EMULATED_F32: the psgemm.hip layers' three bf16 slices;
+    // PA_DTYPE_BF16: the stem's [64][224] or bgemm_pack_weights' plane, RNE bf16
+    pa::FormWeights fw;
     // PA_DTYPE_BF16: every stem and convolution row stores bf16 (the buffers it writes hold 2-byte elements), the pool fp32
     std::vector<char> buf_bf16;                // per buffer: 1 = bf16 elements
-    unsigned short* bg_weights = nullptr;      // per row: the stem's [64][224] or bgemm_pack_weights' plane, RNE bf16
-    std::vector<long long> bg_off;             // per row: element offset into bg_weights, -1 = none
     float* bg_slab = nullptr;                  // bgemm split-K partials: BGEMM_SLAB_ITEMS workgroups x 128 x 128 fp32
     int32_t* bg_tickets = nullptr;             // BGEMM_TICKETS of them, zero between launches
     float* x0 = nullptr;  // [max_crops][134][134][4] model input of the stem (bf16 elements under PA_DTYPE_BF16)
@@ -97,12 +93,12 @@ void out_geom(const pa_conv_desc& d, int* hw, int* c) {
     else { *hw = d.in_hw / d.stride; *c = d.cout; }
 }
 
-unsigned short cn_bf16_rne(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
+// every call that can fail with a HIP error inside a function that returns a PA_* code for handle h
+#define CN_HIP(call)                                                                                  \
+    do {                                                                                              \
+        hipError_t e__ = (call);                                                                      \
+        if (e__ != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
 
 bool is_bf16(const pa_convnet* h, int buf) { return h->compute_dtype == PA_DTYPE_BF16 && (buf < 0 || h->buf_bf16[buf]); }
 
@@ -113,33 +109,17 @@ int bg_split_knob() {
     return v;
 }
 
-// a convolution row's GemmParams for n crops: conv mode, strides and counts in elements, no pointers (create validates the
-// geometry before anything is allocated; convnet_run fills them in)
-pa::GemmParams conv_geometry(const pa_conv_desc& d, int n) {
-    const int out_hw = d.in_hw / d.stride;
-    const int in_w = d.in_hw + 2 * d.in_pad, out_w = out_hw + 2 * d.out_pad;
-    pa::GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.M = n * out_hw * out_hw;
-    p.N = d.cout;
-    p.taps = d.ksize * d.ksize;
-    p.kw_taps = d.ksize;
-    p.chunk = d.cin;
-    p.ktot = p.taps * p.chunk;
-    p.howo = out_hw * out_hw;
-    p.wo = out_hw;
-    p.in_px_stride = d.cin;
-    p.in_row_stride = in_w * d.cin;
-    p.in_img_stride = in_w * in_w * d.cin;
-    p.stride = d.stride;
-    p.off_y = p.off_x = d.in_pad - (d.ksize - 1) / 2;
-    p.out_px_stride = d.cout;
-    p.out_row_stride = out_w * d.cout;
-    p.out_img_stride = out_w * out_w * d.cout;
-    p.out_pad = d.out_pad;
-    p.relu = d.relu;
-    p.splitk = 1;
-    return p;
+// PA_CONVNET_WINO=0 (read once, at the first convolution row of the first create that is not bf16) keeps the stride-1 3x3 rows in their direct form (A/B)
+int wino_knob() {
+    static const int v = getenv("PA_CONVNET_WINO") ? atoi(getenv("PA_CONVNET_WINO")) : 1;
+    return v;
+}
+
+// a convolution row at n crops: square maps, whole pixels (create validates its GemmParams before anything is allocated;
+// convnet_run fills in the pointers)
+pa::ConvRow conv_row(const pa_conv_desc& d, int n) {
+    return {/*images*/ n, /*in h, w, pad, px stride*/ d.in_hw, d.in_hw, d.in_pad, d.cin, /*cin, cout, ksize, stride*/ d.cin, d.cout, d.ksize, d.stride,
+            /*out pad, px stride*/ d.out_pad, d.cout, /*act, res_after*/ d.relu, 0};
 }
 
 }  // namespace
@@ -227,7 +207,7 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
             if (d.kind != 1 && (!h->buf_bf16[d.in_buf] || (d.kind == 0 && d.res_buf >= 0 && !h->buf_bf16[d.res_buf])))
                 return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": reads an fp32 buffer (bf16 rows read bf16)");
             if (d.kind != 0) continue;
-            const pa::GemmParams p = conv_geometry(d, max_crops);
+            const pa::GemmParams p = pa::conv_row_params(conv_row(d, max_crops));
             const unsigned long long in_bytes = (unsigned long long)max_crops * p.in_img_stride * 2ull;
             const unsigned long long out_bytes = (unsigned long long)max_crops * p.out_img_stride * 2ull;
             if (pa::psgemm_pick_bn(d.cout, d.res_buf >= 0) == 0 || p.M >= (1 << 24) || p.howo >= (1 << 16) || in_bytes >= (1ull << 31) ||
@@ -246,75 +226,40 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
     h->n_weights = n_weights;
     if (!chk(hipMalloc(&h->weights, n_weights * sizeof(float)), "hipMalloc weights")) return PA_ERR_HIP;
     if (!chk(hipMemcpy(h->weights, weights_host, n_weights * sizeof(float), hipMemcpyHostToDevice), "upload weights")) return PA_ERR_HIP;
-    h->wino_off.assign(n_descs, -1);
-    h->wino_bn.assign(n_descs, 0);
-    if (compute_dtype != PA_DTYPE_BF16) {
-        // stride-1 3x3 convolutions on maps of 8 x 8 and larger run as Winograd F(2x2, 3x3) (wino.hip, as in the engine's
-        // ResNet-18: the 4 x 4 maps stay on the direct kernel); PA_CONVNET_WINO=0 keeps the direct form (A/B)
-        static const int use_wino = getenv("PA_CONVNET_WINO") ? atoi(getenv("PA_CONVNET_WINO")) : 1;
-        size_t total = 0;
-        for (int i = 0; i < n_descs; ++i) {
-            const pa_conv_desc& d = h->descs[i];
-            if (use_wino && d.kind == 0 && d.ksize == 3 && d.stride == 1 && d.in_pad == 1 && d.in_hw >= 8 && d.in_hw % 4 == 0 && d.cin % 8 == 0) {
-                h->wino_off[i] = (long long)total;
-                h->wino_bn[i] = pa::wino_pick_bn(d.cout, (long long)max_crops * (d.in_hw / 4) * (d.in_hw / 4));
-                total += pa::wino_weight_floats(d.cin, d.cout);
-            }
+    // which rows take which form; the planes themselves are FormWeights' business
+    std::vector<pa::FormRow> rows(n_descs);
+    std::vector<std::vector<unsigned short>> stems;
+    for (int i = 0; i < n_descs; ++i) {
+        const pa_conv_desc& d = h->descs[i];
+        pa::FormRow& r = rows[i];
+        if (d.kind == 1 && compute_dtype == PA_DTYPE_BF16) {
+            // the stem's [64][224] weights rounded to nearest even once, as laid out: a slot of the bgemm plane packed here
+            stems.emplace_back(64 * 224);
+            for (int k = 0; k < 64 * 224; ++k) stems.back()[k] = pa::bf16_rne(weights_host[d.w_off + k]);
+            r.forms = pa::FORM_BGEMM;
+            r.packed = stems.back().data();
+            r.packed_elems = stems.back().size();
         }
-        if (total) {
-            std::vector<float> ug(total);
-            for (int i = 0; i < n_descs; ++i)
-                if (h->wino_off[i] >= 0) pa::wino_transform_weights(weights_host + h->descs[i].w_off, h->descs[i].cin, h->descs[i].cout, h->wino_bn[i], ug.data() + h->wino_off[i]);
-            if (!chk(hipMalloc(&h->wino_weights, total * sizeof(float)), "hipMalloc Winograd filters")) return PA_ERR_HIP;
-            if (!chk(hipMemcpy(h->wino_weights, ug.data(), total * sizeof(float), hipMemcpyHostToDevice), "upload Winograd filters")) return PA_ERR_HIP;
-        }
-    }
-    h->split_off.assign(n_descs, -1);
-    if (compute_dtype == PA_DTYPE_EMULATED_F32) {
-        // every convolution that is not in Winograd form and whose 128-pixel tiles can fill at least half the chip at max_crops runs on
-        // the emulated-fp32 persistent GEMM (psgemm.hip; below that its one-workgroup-per-CU grid is mostly empty and the exact
-        // engine's 64 x 64 tiles are faster: profiles/r06_pgemm_split_layers.txt, ResNet-18's 8 x 8 and 4 x 4 maps)
-        size_t total = 0;
-        for (int i = 0; i < n_descs; ++i) {
-            const pa_conv_desc& d = h->descs[i];
-            if (d.kind != 0 || h->wino_off[i] >= 0 || d.cin % 32 || d.cout % 32) continue;
+        if (d.kind != 0) continue;
+        r = pa::FormRow{0, d.cin, d.cout, d.ksize, d.res_buf >= 0, d.w_off};
+        if (compute_dtype == PA_DTYPE_BF16) {
+            r.forms = pa::FORM_BGEMM;  // every convolution's weights rounded to nearest even once, in bgemm's plane layout
+        } else if (wino_knob() && d.ksize == 3 && d.stride == 1 && d.in_pad == 1 && d.in_hw >= 8 && d.in_hw % 4 == 0 && d.cin % 8 == 0) {
+            // stride-1 3x3 convolutions on maps of 8 x 8 and larger run as Winograd F(2x2, 3x3) (wino.hip, as in the engine's
+            // ResNet-18: the 4 x 4 maps stay on the direct kernel)
+            r.forms = pa::FORM_WINO;
+            r.wino_tiles = (long long)max_crops * (d.in_hw / 4) * (d.in_hw / 4);
+        } else if (compute_dtype == PA_DTYPE_EMULATED_F32 && d.cin % 32 == 0 && d.cout % 32 == 0) {
+            // every convolution that is not in Winograd form and whose 128-pixel tiles can fill at least half the chip at max_crops runs on
+            // the emulated-fp32 persistent GEMM (psgemm.hip; below that its one-workgroup-per-CU grid is mostly empty and the exact
+            // engine's 64 x 64 tiles are faster: profiles/r06_pgemm_split_layers.txt, ResNet-18's 8 x 8 and 4 x 4 maps)
             const int ohw = d.in_hw / d.stride, bn = pa::psgemm_pick_bn(d.cout, d.res_buf >= 0);
-            if (bn == 0 || (long long)(((long long)max_crops * ohw * ohw + 127) / 128) * (d.cout / bn) < 128) continue;
-            h->split_off[i] = (long long)total;
-            total += pa::psgemm_weight_elems(d.cout, d.ksize * d.ksize * d.cin, d.res_buf >= 0);
-        }
-        if (total) {
-            std::vector<unsigned short> sw(total);
-            for (int i = 0; i < n_descs; ++i)
-                if (h->split_off[i] >= 0) {
-                    const pa_conv_desc& d = h->descs[i];
-                    pa::psgemm_pack_weights(weights_host + d.w_off, d.cout, d.ksize * d.ksize * d.cin, d.res_buf >= 0, sw.data() + h->split_off[i]);
-                }
-            if (!chk(hipMalloc(&h->split_weights, total * sizeof(unsigned short)), "hipMalloc split weights")) return PA_ERR_HIP;
-            if (!chk(hipMemcpy(h->split_weights, sw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload split weights")) return PA_ERR_HIP;
+            if (bn != 0 && (long long)(((long long)max_crops * ohw * ohw + 127) / 128) * (d.cout / bn) >= 128) r.forms = pa::FORM_PSGEMM;
         }
     }
-    h->bg_off.assign(n_descs, -1);
+    const char* what = "";
+    if (!chk(h->fw.prepare(rows, weights_host, &what), what)) return PA_ERR_HIP;
     if (compute_dtype == PA_DTYPE_BF16) {
-        // the weights rounded to nearest even once: the stem's [64][224] as laid out, every convolution in bgemm's plane layout
-        size_t total = 0;
-        for (int i = 0; i < n_descs; ++i) {
-            const pa_conv_desc& d = h->descs[i];
-            if (d.kind == 2) continue;
-            h->bg_off[i] = (long long)total;
-            total += d.kind == 1 ? 64 * 224 : pa::bgemm_weight_elems(d.cout, d.ksize * d.ksize * d.cin, d.res_buf >= 0);
-            total = (total + 127) & ~(size_t)127;   // (every plane 256-byte aligned)
-        }
-        std::vector<unsigned short> bw(total, 0);
-        for (int i = 0; i < n_descs; ++i) {
-            const pa_conv_desc& d = h->descs[i];
-            if (d.kind == 1)
-                for (int k = 0; k < 64 * 224; ++k) bw[h->bg_off[i] + k] = cn_bf16_rne(weights_host[d.w_off + k]);
-            else if (d.kind == 0)
-                pa::bgemm_pack_weights(weights_host + d.w_off, d.cout, d.ksize * d.ksize * d.cin, d.res_buf >= 0, bw.data() + h->bg_off[i]);
-        }
-        if (!chk(hipMalloc(&h->bg_weights, total * sizeof(unsigned short)), "hipMalloc bf16 weights")) return PA_ERR_HIP;
-        if (!chk(hipMemcpy(h->bg_weights, bw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload bf16 weights")) return PA_ERR_HIP;
         const size_t slab_bytes = (size_t)pa::BGEMM_SLAB_ITEMS * 128 * 128 * sizeof(float);
         if (!chk(hipMalloc(&h->bg_slab, slab_bytes), "hipMalloc split-K slab")) return PA_ERR_HIP;
         if (!chk(hipMalloc(&h->bg_tickets, pa::BGEMM_TICKETS * sizeof(int32_t)), "hipMalloc split-K tickets")) return PA_ERR_HIP;
@@ -336,9 +281,6 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
 void pa_convnet_destroy(pa_convnet* h) {
     if (!h) return;
     (void)hipFree(h->weights);
-    (void)hipFree(h->wino_weights);
-    (void)hipFree(h->split_weights);
-    (void)hipFree(h->bg_weights);
     (void)hipFree(h->bg_slab);
     (void)hipFree(h->bg_tickets);
     (void)hipFree(h->x0);
@@ -353,11 +295,6 @@ namespace {
 // What pa_convnet_forward enqueues for n crops, up to and including layer `last` (-1: the input conversion alone); records
 // each layer's form. Arguments are checked by the callers.
 int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t s) {
-#define CN_HIP(call)                                                                                  \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
     const bool bf = h->compute_dtype == PA_DTYPE_BF16;
     CN_HIP(pa::launch_nchw_to_padded(x, h->x0, n, bf ? 1 : 0, s));
     for (int li = 0; li <= last; ++li) {
@@ -366,7 +303,7 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
             pa::StemPoolParams sp;
             memset(&sp, 0, sizeof(sp));
             sp.x = h->x0;
-            sp.wgt = bf ? (const void*)(h->bg_weights + h->bg_off[li]) : (const void*)(h->weights + d.w_off);
+            sp.wgt = bf ? (const void*)(h->fw.bgemm + h->fw.bgemm_off[li]) : (const void*)(h->weights + d.w_off);
             sp.bias = h->weights + d.b_off;
             sp.out = h->bufs[d.out_buf];
             sp.crops = n;
@@ -390,7 +327,7 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
             CN_HIP(hipGetLastError());
             continue;
         }
-        pa::GemmParams p = conv_geometry(d, n);
+        pa::GemmParams p = pa::conv_row_params(conv_row(d, n));
         p.act = h->bufs[d.in_buf];
         p.wgt = h->weights + d.w_off;
         p.bias = h->weights + d.b_off;
@@ -404,29 +341,20 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
                 p.slab = h->bg_slab;
                 p.tickets = h->bg_tickets;
             }
-            const hipError_t pe = pa::launch_bgemm(p, h->bg_weights + h->bg_off[li], (size_t)n * p.out_img_stride, 0, false, s);
+            const hipError_t pe = pa::launch_bgemm(p, h->fw.bgemm + h->fw.bgemm_off[li], (size_t)n * p.out_img_stride, 0, false, s);
             if (pe != hipSuccess)
                 return cn_fail(h, PA_ERR_HIP, "layer " + std::to_string(li) + " (bf16): " +
                                                   (pe == hipErrorInvalidValue ? std::string("the bf16 GEMM refuses its shape") : hipGetErrorString(pe)));
             h->forms[li] = S > 1 ? PA_CN_FORM_BGEMM_SPLITK : PA_CN_FORM_BGEMM;
             continue;
         }
-        // tile: the largest shape that still gives the chip ~two workgroups per CU
-        const long long t128 = (long long)((p.M + 127) / 128) * (p.N / 64);
-        const pa::GemmTile tile = (p.N % 128 == 0 && t128 / 2 >= 512) ? pa::TILE_128x128 : (t128 >= 512 ? pa::TILE_128x64 : pa::TILE_64x64);
+        const pa::GemmTile tile = pa::im2col_tile(p.M, p.N);
         hipError_t pe = hipErrorInvalidValue;
         int32_t form = PA_CN_FORM_PSGEMM;
-        if (h->split_off[li] >= 0) pe = pa::launch_psgemm(p, h->split_weights + h->split_off[li], (size_t)n * p.out_img_stride, 0, s);
-        if (pe == hipErrorInvalidValue && h->wino_off[li] >= 0) {
+        if (h->fw.psgemm_off[li] >= 0) pe = pa::launch_psgemm(p, h->fw.psgemm + h->fw.psgemm_off[li], (size_t)n * p.out_img_stride, 0, s);
+        if (pe == hipErrorInvalidValue && h->fw.wino_off[li] >= 0) {
             form = PA_CN_FORM_WINO;
-            pa::WinoParams q;
-            memset(&q, 0, sizeof(q));
-            q.act = p.act; q.wgt = h->wino_weights + h->wino_off[li]; q.bias = p.bias; q.residual = p.residual; q.out = p.out;
-            q.n_img = n; q.height = d.in_hw; q.width = d.in_hw; q.cin = d.cin; q.cout = d.cout; q.bn = h->wino_bn[li];
-            q.in_px_stride = p.in_px_stride; q.in_row_stride = p.in_row_stride; q.in_img_stride = p.in_img_stride;
-            q.out_px_stride = p.out_px_stride; q.out_row_stride = p.out_row_stride; q.out_img_stride = p.out_img_stride; q.out_pad = p.out_pad;
-            q.relu = p.relu;
-            pe = pa::launch_wino3x3(q, s);
+            pe = pa::launch_wino3x3(pa::wino_params(p, n, d.in_hw, d.in_hw, d.cin, h->fw.wino + h->fw.wino_off[li], h->fw.wino_bn[li]), s);
         }
         if (pe == hipErrorInvalidValue && d.ksize == 3 && d.stride == 1 && d.in_pad == 1) {
             form = PA_CN_FORM_PATCH;
@@ -439,7 +367,6 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
         if (pe != hipSuccess) return cn_fail(h, PA_ERR_HIP, "layer " + std::to_string(li) + ": " + hipGetErrorString(pe));
         h->forms[li] = form;
     }
-#undef CN_HIP
     return PA_OK;
 }
 
@@ -454,11 +381,6 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
     hipStream_t s = (hipStream_t)stream;
     const int rc = convnet_run(h, x, n, (int)h->descs.size() - 1, s);
     if (rc != PA_OK) return rc;
-#define CN_HIP(call)                                                                                  \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess) return cn_fail(h, PA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
-    } while (0)
     // the last layer's output buffer as stored, zero border included when it has one (a pooled vector has none; under
     // PA_DTYPE_BF16 the last row is a pool, fp32)
     const pa_conv_desc& last = h->descs.back();
@@ -468,7 +390,6 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
     const int per_crop = (ohw + 2 * opad) * (ohw + 2 * opad) * oc;
     if (out_floats_per_crop != per_crop) return cn_fail(h, PA_ERR_INVALID_ARG, "pa_convnet_forward: out_floats_per_crop does not match the last layer");
     CN_HIP(hipMemcpyAsync(out, h->bufs[last.out_buf], (size_t)n * per_crop * sizeof(float), hipMemcpyDeviceToDevice, s));
-#undef CN_HIP
     return PA_OK;
 }
 

@@ -12,7 +12,7 @@
 // small launch per time step adds h(t-1) W_hh^T + b_hh, applies the gates (torch order i, f, g, o) and writes
 // h(t), c(t). All fp32; gates with expf / tanhf. This is a side path (7-row batches, launch-latency bound), not
 // the hot loop: no MFMA tiling here on purpose.
-#include "pa_kernels.h"
+#include "conv_rows.h"
 #include "../../include/playaid_hip.h"
 #include <cstdio>
 #include <cstdlib>
@@ -368,8 +368,10 @@ hipError_t launch_linear_f32(const float* X, int ld, const float* W, const float
         p.out_px_stride = ldc; p.out_row_stride = 0; p.out_img_stride = 0;
         p.relu = relu;
         p.splitk = 1;
-        const long long t128 = (long long)((M + 127) / 128) * (N / 64);
-        return launch_igemm(p, t128 >= 512 ? TILE_128x64 : TILE_64x64, s);
+        // the shared rule with a 128 x 64 ceiling: 128 x 128 tiles were never measured for these layers (and the rule names them
+        // only where it would otherwise name 128 x 64: ceil(M / 128) * (N / 64) >= 1024)
+        const GemmTile tile = im2col_tile(M, N);
+        return launch_igemm(p, tile == TILE_128x128 ? TILE_128x64 : tile, s);
     }
     hipLaunchKernelGGL(linear_f32_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, s, X, ld, W, bias, Cm, ldc, M, N, K, relu);
     return hipGetLastError();

@@ -3,7 +3,7 @@
 // one forward on the caller's stream. No torch types, no hidden synchronisation
 // in the enqueue calls.
 #include "../../include/playaid_hip.h"
-#include "pa_kernels.h"
+#include "conv_rows.h"
 
 #include <algorithm>
 #include <cmath>
@@ -190,12 +190,7 @@ int upload(pa_engine* e, float** dst, const std::vector<float>& host) {
 int upload_bf16(pa_engine* e, float** dst, const std::vector<float>& host) {
     std::vector<uint16_t> h(host.size());
     if (!e->adopt)
-        for (size_t i = 0; i < host.size(); ++i) {
-            uint32_t u;
-            memcpy(&u, &host[i], 4);
-            u += 0x7fffu + ((u >> 16) & 1u);
-            h[i] = (uint16_t)(u >> 16);
-        }
+        for (size_t i = 0; i < host.size(); ++i) h[i] = bf16_rne(host[i]);
     return arena_put(e, reinterpret_cast<void**>(dst), h.data(), h.size() * sizeof(uint16_t));
 }
 
@@ -288,20 +283,9 @@ void choose_tile(int M, int N, int nk, GemmTile* tile, int* splitk) {
     // Aim for >= 2 workgroups per CU (512) so that the un-pipelined K loop of
     // one workgroup hides behind another's; fall back to split-K when even the
     // smallest tile cannot fill the chip.
-    const int t128x128 = (N % 128 == 0) ? ((M + 127) / 128) * (N / 128) : 0;
-    const int t128x64 = ((M + 127) / 128) * (N / 64);
-    const int t64x64 = ((M + 63) / 64) * (N / 64);
-    int tiles;
-    if (t128x128 >= 512) {
-        *tile = TILE_128x128;
-        tiles = t128x128;
-    } else if (t128x64 >= 512) {
-        *tile = TILE_128x64;
-        tiles = t128x64;
-    } else {
-        *tile = TILE_64x64;
-        tiles = t64x64;
-    }
+    *tile = im2col_tile(M, N);
+    const int tm = (M + 127) / 128;
+    const int tiles = *tile == TILE_128x128 ? tm * (N / 128) : *tile == TILE_128x64 ? tm * (N / 64) : ((M + 63) / 64) * (N / 64);
     int sk = 1;
     while (tiles * sk < 512 && nk / (sk * 2) >= 8) sk *= 2;
     *splitk = sk;
@@ -397,44 +381,29 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
     p.out_img_stride = (int)out_crop;
     p.out_pad = L.out_pad;
     p.relu = L.relu;
-    if (bf_ds && L.ds_fused) {
-        p.residual = at(L.ds_out, crop0 * out_crop);  // written by the block's opener
-    } else if (bf_ds) {
-        GemmParams d;
-        memset(&d, 0, sizeof(d));
-        const int w2 = L.in2_hw + 2;  // zero-bordered block input
-        d.act = at(L.in2, (size_t)crop0 * w2 * w2 * L.in2_c);
+    // the block's 1x1/2 downsample branch as a GEMM of its own: the zero-bordered block input -> ds_out, laid out like this layer's output
+    // (add_conv builds the block so that this layer's output is in2_hw / in2_stride on a side with whole pixels of cout channels:
+    // the branch's M, howo, wo and output strides come out equal to p's)
+    auto branch_gemm = [&]() {
+        GemmParams d = conv_row_params({/*images*/ ncrops, /*in h, w, pad, px stride*/ L.in2_hw, L.in2_hw, 1, L.in2_c,
+                                        /*cin, cout, ksize, stride*/ L.in2_c, L.cout, 1, L.in2_stride,
+                                        /*out pad, px stride*/ L.out_pad, L.cout, /*act, res_after*/ 0, 0});
+        d.act = at(L.in2, (size_t)crop0 * (L.in2_hw + 2) * (L.in2_hw + 2) * L.in2_c);
         d.wgt = L.ds_wgt;
         d.out = at(L.ds_out, crop0 * out_crop);
         d.slab = p.slab;
-        d.M = p.M; d.N = p.N;
-        d.taps = 1; d.kw_taps = 1; d.chunk = L.in2_c; d.ktot = L.in2_c;
-        d.howo = p.howo; d.wo = p.wo;
-        d.in_px_stride = L.in2_c; d.in_row_stride = w2 * L.in2_c; d.in_img_stride = w2 * w2 * L.in2_c;
-        d.stride = L.in2_stride; d.off_y = 1; d.off_x = 1;
-        d.out_px_stride = p.out_px_stride; d.out_row_stride = p.out_row_stride; d.out_img_stride = p.out_img_stride;
-        d.out_pad = p.out_pad;
-        d.relu = 0; d.splitk = 1;
+        return d;
+    };
+    if (bf_ds && L.ds_fused) {
+        p.residual = at(L.ds_out, crop0 * out_crop);  // written by the block's opener
+    } else if (bf_ds) {
+        const GemmParams d = branch_gemm();
         ProfScope ps(e, s, prof_name, 2.0 * d.M * d.N * L.in2_c,
                      2.0 * ((double)ncrops * L.in2_hw * L.in2_hw * L.in2_c / (L.in2_stride * L.in2_stride) + (double)d.M * d.N + (double)d.N * L.in2_c));
         HIPCHK(e, launch_igemm_bf16(d, TILE_128x64, s));  // (128x128 / 256x128 tiles measured 2-7 us slower here)
         p.residual = d.out;
     } else if (f32_ds) {
-        GemmParams d;
-        memset(&d, 0, sizeof(d));
-        const int w2 = L.in2_hw + 2;  // zero-bordered block input
-        d.act = L.in2 + (size_t)crop0 * w2 * w2 * L.in2_c;
-        d.wgt = L.ds_wgt;
-        d.out = L.ds_out + crop0 * out_crop;
-        d.slab = p.slab;
-        d.M = p.M; d.N = p.N;
-        d.taps = 1; d.kw_taps = 1; d.chunk = L.in2_c; d.ktot = L.in2_c;
-        d.howo = p.howo; d.wo = p.wo;
-        d.in_px_stride = L.in2_c; d.in_row_stride = w2 * L.in2_c; d.in_img_stride = w2 * w2 * L.in2_c;
-        d.stride = L.in2_stride; d.off_y = 1; d.off_x = 1;
-        d.out_px_stride = p.out_px_stride; d.out_row_stride = p.out_row_stride; d.out_img_stride = p.out_img_stride;
-        d.out_pad = p.out_pad;
-        d.relu = 0; d.splitk = 1;
+        const GemmParams d = branch_gemm();
         ProfScope ps(e, s, prof_name, ds_done ? 0.0 : 2.0 * d.M * d.N * L.in2_c,
                      ds_done ? 0.0 : 4.0 * ((double)ncrops * L.in2_hw * L.in2_hw * L.in2_c / (L.in2_stride * L.in2_stride) + (double)d.M * d.N + (double)d.N * L.in2_c));
         if (ds_done) {
@@ -499,13 +468,7 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
         }
         HIPCHK(e, pe);
     } else if (L.wino_wgt && !p.act2) {
-        WinoParams q;
-        memset(&q, 0, sizeof(q));
-        q.act = p.act; q.wgt = L.wino_wgt; q.bias = p.bias; q.residual = p.residual; q.out = p.out;
-        q.n_img = ncrops; q.height = L.out_hw; q.width = L.out_hw; q.cin = L.cin; q.cout = L.cout; q.bn = L.wino_bn;
-        q.in_px_stride = p.in_px_stride; q.in_row_stride = p.in_row_stride; q.in_img_stride = p.in_img_stride;
-        q.out_px_stride = p.out_px_stride; q.out_row_stride = p.out_row_stride; q.out_img_stride = p.out_img_stride; q.out_pad = p.out_pad;
-        q.relu = p.relu;
+        WinoParams q = wino_params(p, ncrops, L.out_hw, L.out_hw, L.cin, L.wino_wgt, L.wino_bn);
         if (e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
             q.slab = e->slab + slab_off;
             q.slab_floats = e->slab_floats > slab_off ? std::min(e->slab_floats - slab_off, e->slab_floats / 2) : 0;

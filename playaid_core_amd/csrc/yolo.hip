@@ -18,7 +18,7 @@
 // the un-padded size, a 114-grey border up to the network input (a multiple of 32), BGR -> RGB, / 255.
 // PA_DTYPE_BF16 (include/playaid_hip.h states its rounding model): bf16 buffers (fp32 for the ones a decode row reads), the bf16
 // stem with a bf16 store, every convolution on the one-slice bf16 GEMM (bgemm.hip), the pools and the up-sampling on bf16.
-#include "pa_kernels.h"
+#include "conv_rows.h"
 #include "../../include/playaid_hip.h"
 #include <cstdlib>
 #include <cstring>
@@ -525,16 +525,12 @@ struct pa_detector {
     std::vector<int32_t> forms;         // per layer: the pa_det_form the last forward or trace launched it as
     float* weights = nullptr;
     size_t n_weights = 0;
-    float* wino_weights = nullptr;      // the stride-1 3x3 layers' filters in the Winograd kernel's layout (wino.hip)
-    std::vector<long long> wino_off;    // per layer: float offset into wino_weights, -1 = the layer runs in its direct form
-    std::vector<int> wino_bn;           // per layer: output channels per workgroup its filters were laid out for
-    int compute_dtype = PA_DTYPE_F32;   // PA_DTYPE_EMULATED_F32: the layers listed in split_off run on psgemm.hip
+    // per layer: the stride-1 3x3 layers' Winograd filters (-1: the layer runs in its direct form); PA_DTYPE_EMULATED_F32: the
+    // psgemm.hip layers' three bf16 slices (-1: the layer keeps its exact fp32 kernel); PA_DTYPE_BF16: every convolution's bgemm plane
+    pa::FormWeights fw;
+    int compute_dtype = PA_DTYPE_F32;
     unsigned short* stem_frag = nullptr;       // PA_DTYPE_EMULATED_F32, PA_DTYPE_BF16: every stem row's W / 255 as stem6x6_bf16_kernel's 27 register fragments (x0 then holds bf16 integers)
     std::vector<long long> stem_frag_off;      // per layer: element offset of its fragments in stem_frag, -1 = not a stem row on the bf16 kernel
-    unsigned short* split_weights = nullptr;   // those layers' weights as three bf16 slices in the kernel's stage-image order
-    std::vector<long long> split_off;   // per layer: element offset into split_weights, -1 = the layer keeps its exact fp32 kernel
-    unsigned short* bf_weights = nullptr;      // PA_DTYPE_BF16: every convolution's weights as one RNE bf16 plane (bgemm.hip's stage images)
-    std::vector<long long> bf_off;      // per layer: element offset into bf_weights, -1 = not a convolution
     hipStream_t side = nullptr;         // PA_DET_LANES=2: the second half batch's stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     float* x0 = nullptr;       // letter-boxed input [max_images][net_h + 4][net_w + 4][4]
@@ -549,9 +545,6 @@ const char* pa_detector_last_error(const pa_detector* h) { return h ? h->last_er
 void pa_detector_destroy(pa_detector* h) {
     if (!h) return;
     (void)hipFree(h->weights);
-    (void)hipFree(h->wino_weights);
-    (void)hipFree(h->split_weights);
-    (void)hipFree(h->bf_weights);
     (void)hipFree(h->stem_frag);
     (void)hipFree(h->x0);
     (void)hipFree(h->anchors);
@@ -657,33 +650,24 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
     h->n_weights = n_weights;
     if (!chk(hipMalloc(&h->weights, n_weights * sizeof(float)), "hipMalloc weights")) return PA_ERR_HIP;
     if (!chk(hipMemcpy(h->weights, weights_host, n_weights * sizeof(float), hipMemcpyHostToDevice), "upload weights")) return PA_ERR_HIP;
+    std::vector<pa::FormRow> frows(n_layers);   // which rows take which form; the planes themselves are FormWeights' business
     {
         // stride-1 3x3 convolutions on maps whose sides are multiples of four run as Winograd F(2x2, 3x3) (wino.hip: 4 / 9 of
-        // the direct form's multiply-adds, the same fp32 matrix instructions); their filters are transformed here, once, in
+        // the direct form's multiply-adds, the same fp32 matrix instructions); their filters are transformed once, at create, in
         // fp64. PA_DET_WINO=0 keeps the direct patch-resident kernel (A/B)
         // (read per create, not once per process: scripts/yolov5_parity.py makes detectors with one layer at a time in this form
         // to see which of them moves the boxes; PA_DET_WINO_MASK = bit k set <=> the k-th eligible layer runs as Winograd)
         const int use_wino = getenv("PA_DET_WINO") ? atoi(getenv("PA_DET_WINO")) : 1;
         const unsigned long wino_mask = getenv("PA_DET_WINO_MASK") ? strtoul(getenv("PA_DET_WINO_MASK"), nullptr, 0) : ~0ul;
-        h->wino_off.assign(n_layers, -1);
-        h->wino_bn.assign(n_layers, 0);
-        size_t total = 0;
         int eligible = 0;
         for (int i = 0; i < n_layers; ++i) {
             const pa_net_layer& L = h->layers[i];
+            if (L.kind == 0) frows[i] = pa::FormRow{0, L.cin, L.cout, L.ksize, L.res_buf >= 0, L.w_off};
             if (use_wino && compute_dtype != PA_DTYPE_BF16 && L.kind == 0 && L.ksize == 3 && L.stride == 1 && L.in_pad == 1 && L.in_h % 4 == 0 && L.in_w % 4 == 0 && L.cin % 8 == 0 &&
                 ((wino_mask >> (eligible++ & 63)) & 1ul)) {
-                h->wino_off[i] = (long long)total;
-                h->wino_bn[i] = pa::wino_pick_bn(L.cout, (long long)max_images * (L.in_h / 4) * (L.in_w / 4));
-                total += pa::wino_weight_floats(L.cin, L.cout);
+                frows[i].forms |= pa::FORM_WINO;
+                frows[i].wino_tiles = (long long)max_images * (L.in_h / 4) * (L.in_w / 4);
             }
-        }
-        if (total) {
-            std::vector<float> ug(total);
-            for (int i = 0; i < n_layers; ++i)
-                if (h->wino_off[i] >= 0) pa::wino_transform_weights(weights_host + h->layers[i].w_off, h->layers[i].cin, h->layers[i].cout, h->wino_bn[i], ug.data() + h->wino_off[i]);
-            if (!chk(hipMalloc(&h->wino_weights, total * sizeof(float)), "hipMalloc Winograd filters")) return PA_ERR_HIP;
-            if (!chk(hipMemcpy(h->wino_weights, ug.data(), total * sizeof(float), hipMemcpyHostToDevice), "upload Winograd filters")) return PA_ERR_HIP;
         }
     }
     // the 6x6 / 2 stem's W / 255 as stem6x6_bf16_kernel's 27 register fragments, three bf16 slices each (PA_DTYPE_EMULATED_F32, PA_DTYPE_BF16),
@@ -698,13 +682,6 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         h->stem_frag_off[i] = (long long)stem_frags.size();
         stem_frags.resize(stem_frags.size() + frag_elems, 0);
         unsigned short* frag = stem_frags.data() + h->stem_frag_off[i];
-        auto rne = [](double v) {   // bf16 nearest-even of a double, and its value
-            float f = (float)v;
-            uint32_t u;
-            memcpy(&u, &f, 4);
-            u += 0x7fffu + ((u >> 16) & 1u);
-            return (unsigned short)(u >> 16);
-        };
         auto val = [](unsigned short hq) { const uint32_t u = (uint32_t)hq << 16; float f; memcpy(&f, &u, 4); return (double)f; };
         for (int st = 0; st < 9; ++st)
             for (int ln = 0; ln < 64; ++ln)
@@ -713,19 +690,12 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
                     if (c == 3) continue;
                     double r = (double)weights_host[L.w_off + (size_t)(kx / 3) * L.cout * 56 + (size_t)ch * 56 + ky * 9 + (kx % 3) * 3 + c] / 255.0;
                     for (int sl = 0; sl < 3; ++sl) {
-                        const unsigned short hq = rne(r);
+                        const unsigned short hq = pa::bf16_rne((float)r);
                         frag[((size_t)(st * 3 + sl) * 64 + ln) * 8 + e] = hq;
                         r -= val(hq);
                     }
                 }
     };
-    auto upload_stem_frags = [&]() -> bool {
-        if (stem_frags.empty()) return true;
-        if (!chk(hipMalloc(&h->stem_frag, stem_frags.size() * sizeof(unsigned short)), "hipMalloc stem fragments")) return false;
-        return chk(hipMemcpy(h->stem_frag, stem_frags.data(), stem_frags.size() * sizeof(unsigned short), hipMemcpyHostToDevice), "upload stem fragments");
-    };
-    h->split_off.assign(n_layers, -1);
-    h->bf_off.assign(n_layers, -1);
     h->buf_elem.assign(n_bufs, 4);
     if (compute_dtype == PA_DTYPE_BF16) {
         // bf16 storage: 2 bytes per element in every buffer but those a decode row reads (the Detect heads store fp32 there);
@@ -734,7 +704,6 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         for (const pa_net_layer& L : h->layers)
             if (L.kind == 6) h->buf_elem[L.in_buf] = 4;
         auto nobf = [&](int i, const char* why) { return bad(i, (std::string("no bf16 form: ") + why).c_str()); };
-        size_t total = 0;
         for (int i = 0; i < n_layers; ++i) {
             const pa_net_layer& L = h->layers[i];
             if (L.kind == 3) {
@@ -745,25 +714,12 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
                 if (h->buf_elem[L.in_buf] != 2 || (L.res_buf >= 0 && h->buf_elem[L.res_buf] != 2))
                     return nobf(i, "the convolution reads a buffer a decode row reads (fp32)");
                 if (h->buf_elem[L.out_buf] == 4 && L.res_buf >= 0) return nobf(i, "an fp32 head output with a residual");
-                const size_t n_el = pa::bgemm_weight_elems(L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0);
-                if (n_el == 0) return nobf(i, "channel counts the one-slice GEMM does not tile");
-                h->bf_off[i] = (long long)total;
-                total += n_el;
+                if (pa::bgemm_weight_elems(L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0) == 0) return nobf(i, "channel counts the one-slice GEMM does not tile");
+                frows[i].forms |= pa::FORM_BGEMM;
             } else if (L.kind == 4 || L.kind == 5) {
                 if (h->buf_elem[L.in_buf] != 2 || h->buf_elem[L.out_buf] != 2) return nobf(i, "a pool / up-sampling on a buffer a decode row reads (fp32)");
             }
         }
-        if (total) {
-            std::vector<unsigned short> bw(total);
-            for (int i = 0; i < n_layers; ++i)
-                if (h->bf_off[i] >= 0) {
-                    const pa_net_layer& L = h->layers[i];
-                    pa::bgemm_pack_weights(weights_host + L.w_off, L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0, bw.data() + h->bf_off[i]);
-                }
-            if (!chk(hipMalloc(&h->bf_weights, total * sizeof(unsigned short)), "hipMalloc bf16 weights")) return PA_ERR_HIP;
-            if (!chk(hipMemcpy(h->bf_weights, bw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload bf16 weights")) return PA_ERR_HIP;
-        }
-        if (!upload_stem_frags()) return PA_ERR_HIP;
     }
     if (compute_dtype == PA_DTYPE_EMULATED_F32) {
         // the 1x1 and the stride-2 3x3 convolutions (and, with PA_DET_EMU_S1=1, the stride-1 3x3 ones in place of their Winograd
@@ -774,7 +730,6 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
         // pixels split in registers -- lived here until commit dd6847f and was 1.42x slower than the exact kernel
         // (profiles/r06_detect_stem_emulated_ab.txt).
         const int emu_stem = getenv("PA_DET_EMU_STEM") ? atoi(getenv("PA_DET_EMU_STEM")) : 1;
-        size_t total = 0;
         for (int i = 0; i < n_layers; ++i) {
             const pa_net_layer& L = h->layers[i];
             if (L.kind == 3 && emu_stem) {   // every stem row: x0 holds the pixel integers for all of them
@@ -782,23 +737,15 @@ int pa_detector_create_dtype(int32_t device, const pa_net_layer* layers, int32_t
                 continue;
             }
             if (L.kind != 0 || L.cin % 32 || L.cout % 32) continue;
-            if (L.ksize == 3 && L.stride == 1 && !emu_s1 && h->wino_off[i] >= 0) continue;
-            const size_t n_el = pa::psgemm_weight_elems(L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0);
-            if (n_el == 0) continue;
-            h->split_off[i] = (long long)total;
-            total += n_el;
+            if (L.ksize == 3 && L.stride == 1 && !emu_s1 && (frows[i].forms & pa::FORM_WINO)) continue;
+            if (pa::psgemm_weight_elems(L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0) != 0) frows[i].forms |= pa::FORM_PSGEMM;
         }
-        if (total) {
-            std::vector<unsigned short> sw(total);
-            for (int i = 0; i < n_layers; ++i)
-                if (h->split_off[i] >= 0) {
-                    const pa_net_layer& L = h->layers[i];
-                    pa::psgemm_pack_weights(weights_host + L.w_off, L.cout, L.ksize * L.ksize * L.cin, L.res_buf >= 0, sw.data() + h->split_off[i]);
-                }
-            if (!chk(hipMalloc(&h->split_weights, total * sizeof(unsigned short)), "hipMalloc split weights")) return PA_ERR_HIP;
-            if (!chk(hipMemcpy(h->split_weights, sw.data(), total * sizeof(unsigned short), hipMemcpyHostToDevice), "upload split weights")) return PA_ERR_HIP;
-        }
-        if (!upload_stem_frags()) return PA_ERR_HIP;
+    }
+    const char* what = "";
+    if (!chk(h->fw.prepare(frows, weights_host, &what), what)) return PA_ERR_HIP;
+    if (!stem_frags.empty()) {
+        if (!chk(hipMalloc(&h->stem_frag, stem_frags.size() * sizeof(unsigned short)), "hipMalloc stem fragments")) return PA_ERR_HIP;
+        if (!chk(hipMemcpy(h->stem_frag, stem_frags.data(), stem_frags.size() * sizeof(unsigned short), hipMemcpyHostToDevice), "upload stem fragments")) return PA_ERR_HIP;
     }
     h->bufs.assign(n_bufs, nullptr);
     h->buf_floats.assign(buf_floats_per_image, buf_floats_per_image + n_bufs);
@@ -1008,36 +955,14 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             continue;
         }
         const int oh = L.in_h / L.stride, ow = L.in_w / L.stride;
-        const int in_wb = L.in_w + 2 * L.in_pad, in_hb = L.in_h + 2 * L.in_pad;
-        const int out_wb = ow + 2 * L.out_pad, out_hb = oh + 2 * L.out_pad;
-        pa::GemmParams p;
-        memset(&p, 0, sizeof(p));
+        pa::GemmParams p = pa::conv_row_params({/*images*/ n, /*in h, w, pad, px stride*/ L.in_h, L.in_w, L.in_pad, L.in_cstride,
+                                                /*cin, cout, ksize, stride*/ L.cin, L.cout, L.ksize, L.stride,
+                                                /*out pad, px stride*/ L.out_pad, L.out_cstride, /*act, res_after*/ L.act, L.res_after});
         p.act = BUF(L.in_buf) + L.in_coff;
         p.wgt = h->weights + L.w_off;
         p.bias = h->weights + L.b_off;
         p.residual = L.res_buf >= 0 ? BUF(L.res_buf) + L.res_coff : nullptr;
         p.out = BUF(L.out_buf) + L.out_coff;
-        p.M = n * oh * ow;
-        p.N = L.cout;
-        p.taps = L.ksize * L.ksize;
-        p.kw_taps = L.ksize;
-        p.chunk = L.cin;
-        p.ktot = p.taps * p.chunk;
-        p.howo = oh * ow;
-        p.wo = ow;
-        p.in_px_stride = L.in_cstride;
-        p.in_row_stride = in_wb * L.in_cstride;
-        p.in_img_stride = in_hb * in_wb * L.in_cstride;
-        p.stride = L.stride;
-        p.off_y = p.off_x = L.in_pad - (L.ksize - 1) / 2;
-        p.out_px_stride = L.out_cstride;
-        p.out_row_stride = out_wb * L.out_cstride;
-        p.out_img_stride = out_hb * out_wb * L.out_cstride;
-        p.out_pad = L.out_pad;
-        p.relu = L.act;
-        p.res_after = L.res_after;
-        p.splitk = 1;
-        const long long t128 = (long long)((p.M + 127) / 128) * (p.N / 64);
         hipError_t pe;
         static const int use_pgemm = getenv("PA_DET_PGEMM") ? atoi(getenv("PA_DET_PGEMM")) : 1;  // 0: the one-tile-per-workgroup engine (A/B)
         static const int use_patch = getenv("PA_DET_PATCH") ? atoi(getenv("PA_DET_PATCH")) : 1;  // 0: im2col for the 3x3 convolutions (A/B)
@@ -1078,7 +1003,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             p.residual = L.res_buf >= 0 ? reinterpret_cast<const float*>(SLICE(L.res_buf, L.res_coff)) : nullptr;
             p.out = reinterpret_cast<float*>(SLICE(L.out_buf, L.out_coff));
             const bool out_f32 = h->buf_elem[L.out_buf] == 4;
-            const unsigned short* w = h->bf_weights + h->bf_off[li];
+            const unsigned short* w = h->fw.bgemm + h->fw.bgemm_off[li];
             const size_t out_elems = (size_t)n * p.out_img_stride - (size_t)L.out_coff;
             if (!out_f32) try_up();
             pe = pa::launch_bgemm(p, w, out_elems, up_floats, out_f32, s);
@@ -1094,27 +1019,20 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             h->forms[fused_up ? li - 1 : li] = form;
             continue;
         }
-        if (h->split_off[li] >= 0) {
+        if (h->fw.psgemm_off[li] >= 0) {
             // emulated fp32 (psgemm.hip); out_floats: from the layer's first output channel to the end of the images in flight
             try_up();
-            pe = pa::launch_psgemm(p, h->split_weights + h->split_off[li], (size_t)n * p.out_img_stride - (size_t)L.out_coff, up_floats, s);
+            pe = pa::launch_psgemm(p, h->fw.psgemm + h->fw.psgemm_off[li], (size_t)n * p.out_img_stride - (size_t)L.out_coff, up_floats, s);
             if (fused_up && pe == hipErrorInvalidValue) {
                 p.up_out = nullptr;
                 fused_up = false;
-                pe = pa::launch_psgemm(p, h->split_weights + h->split_off[li], (size_t)n * p.out_img_stride - (size_t)L.out_coff, 0, s);
+                pe = pa::launch_psgemm(p, h->fw.psgemm + h->fw.psgemm_off[li], (size_t)n * p.out_img_stride - (size_t)L.out_coff, 0, s);
             }
             form = fused_up ? PA_DET_FORM_PSGEMM_UP : PA_DET_FORM_PSGEMM;
             up_done();
         }
-        if (pe == hipErrorInvalidValue && h->wino_off[li] >= 0) {
-            pa::WinoParams q;
-            memset(&q, 0, sizeof(q));
-            q.act = p.act; q.wgt = h->wino_weights + h->wino_off[li]; q.bias = p.bias; q.residual = p.residual; q.out = p.out;
-            q.n_img = n; q.height = L.in_h; q.width = L.in_w; q.cin = L.cin; q.cout = L.cout; q.bn = h->wino_bn[li];
-            q.in_px_stride = p.in_px_stride; q.in_row_stride = p.in_row_stride; q.in_img_stride = p.in_img_stride;
-            q.out_px_stride = p.out_px_stride; q.out_row_stride = p.out_row_stride; q.out_img_stride = p.out_img_stride; q.out_pad = p.out_pad;
-            q.relu = p.relu; q.res_after = p.res_after;
-            pe = pa::launch_wino3x3(q, s);
+        if (pe == hipErrorInvalidValue && h->fw.wino_off[li] >= 0) {
+            pe = pa::launch_wino3x3(pa::wino_params(p, n, L.in_h, L.in_w, L.cin, h->fw.wino + h->fw.wino_off[li], h->fw.wino_bn[li]), s);
             form = PA_DET_FORM_WINO;
         }
         if (pe == hipErrorInvalidValue && use_patch && L.ksize == 3 && L.stride == 1 && L.in_pad == 1) {
@@ -1134,8 +1052,7 @@ static int detector_run(pa_detector* h, const uint8_t* frames, int32_t n, int32_
             form = fused_up ? PA_DET_FORM_PGEMM_UP : PA_DET_FORM_PGEMM;
             up_done();
         } else if (p.N % 64 == 0) {
-            const pa::GemmTile tile = (p.N % 128 == 0 && t128 / 2 >= 512) ? pa::TILE_128x128 : (t128 >= 512 ? pa::TILE_128x64 : pa::TILE_64x64);
-            pe = pa::launch_igemm(p, tile, s);
+            pe = pa::launch_igemm(p, pa::im2col_tile(p.M, p.N), s);
             form = PA_DET_FORM_IGEMM;
         }   // (32 output channels: the persistent and the patch kernel only -- the table builder keeps such layers on them)
         if (pe != hipSuccess) return fail(PA_ERR_HIP, "layer " + std::to_string(li) + ": " + hipGetErrorString(pe));
