@@ -518,6 +518,48 @@ int pa_mjpeg_debug_counters(unsigned long long* out8_host);
 int pa_mjpeg_decode(pa_mjpeg* h, const uint8_t* data_host, const int64_t* spans_host, int32_t n, int32_t height, int32_t width,
                     int32_t rgb, uint8_t* frames_dev, int32_t* status_dev, void* stream);
 
+/* ---- a2 / a3: baseline JPEG encode on the device --------------------------------- */
+
+/* The file half of YOLOv5's `--save-crop` hand-off (ai_runner.py:191-194, 208, 291-295: crops/<Fighter>/<video>_<n>.jpg)
+ * and the writer of Motion-JPEG clips: n packed uint8 [h][w][3] images in HBM -> n complete baseline JPEG files in HBM,
+ * byte for byte what libjpeg(-turbo) writes for the same pixels (Pillow's Image.save(quality, subsampling) without
+ * `optimize`): JFIF 1.1 APP0, two DQT segments from jpeg_set_quality(q, force_baseline), SOF0, the four standard Huffman
+ * tables K.3-K.6 (DC0, AC0, DC1, AC1), one interleaved scan without restart markers, FF bytes stuffed, the last byte
+ * filled with 1-bits, FFD9. Samples: jccolor.c, edge blocks by repeating the last row / column, 4:2:0 by jcsample.c's
+ * h2v2_downsample (dummy luma blocks of a half-empty MCU: AC 0, DC of the block before), jfdctint.c, jcdctmgr.c.
+ *
+ * A handle owns the scratch of one call: max_blocks 8x8 blocks (all components, all images of a call; 130 bytes each)
+ * and scratch_bytes for the un-stuffed entropy-coded streams (each image's rounded up to 64 bytes). pa_jpegenc_encode
+ * only ENQUEUES on `stream` -- about ten launches, no host synchronisation, no waiting between workgroups; calls on one
+ * handle must be stream-ordered with each other.
+ * images / images_bytes: device bytes exactly as pa_save_one_box_crops(jpeg_quality = 0) / pa_square_crops leave them;
+ * desc (device) as pa_crop_image; bgr = 1 for OpenCV's channel order, 0 for R, G, B; quality 1..100; subsampling 0 (4:4:4)
+ * or 2 (4:2:0); max_height / max_width bound every image of the call (they size the grids). The files land back to back
+ * in `files`, each at a 16-byte aligned offset, in input order; out[n] (device) says where. An entry with
+ * height = width = 0 gets nbytes = 0. An image that does not fit -- the handle's blocks or stream scratch, files_capacity,
+ * a descriptor larger than max_height x max_width or outside images_bytes -- gets nbytes = -1, is counted for
+ * pa_jpegenc_overflows, and nothing of it is written; the images before it stay valid (the ones behind it fail as well:
+ * offsets are running sums). Bad arguments return PA_ERR_INVALID_ARG without touching the device. */
+typedef struct pa_jpeg_file {
+    int64_t offset;   /* first byte of the file in `files` (16-byte aligned) */
+    int32_t nbytes;   /* file length; 0: empty entry; -1: did not fit */
+    int32_t reserved;
+} pa_jpeg_file;
+typedef struct pa_jpegenc pa_jpegenc;
+int pa_jpegenc_create(int32_t device, int32_t max_images, int64_t max_blocks, size_t scratch_bytes, pa_jpegenc** out);
+void pa_jpegenc_destroy(pa_jpegenc* h);
+const char* pa_jpegenc_last_error(const pa_jpegenc* h);
+/* Host only, no device: the 623 header bytes (SOI .. SOS) of such a file. */
+int pa_jpeg_header(int32_t height, int32_t width, int32_t quality, int32_t subsampling, uint8_t* out_host, size_t cap, int32_t* nbytes);
+/* Host only: an upper bound of a file's length: header + 2 * 209 bytes per coded block (1665 bits, every byte stuffed)
+ * + 2; 0 for bad arguments. */
+size_t pa_jpeg_file_bytes_bound(int32_t height, int32_t width, int32_t subsampling);
+int pa_jpegenc_encode(pa_jpegenc* h, const uint8_t* images, size_t images_bytes, const pa_crop_image* desc, int32_t n, int32_t max_height,
+                      int32_t max_width, int32_t bgr, int32_t quality, int32_t subsampling, uint8_t* files, size_t files_capacity,
+                      pa_jpeg_file* out, void* stream);
+/* Images that did not fit since the last query (the count is reset); synchronises `stream`. */
+int pa_jpegenc_overflows(pa_jpegenc* h, int32_t* count_host, void* stream);
+
 /* pa_backbone_frames for frames that are NOT consecutive in the clip (a resolution bucket of a
  * mixed-resolution stream, BASELINE.json configs[4]): frame_ids[n] (device, int32, 0-based)
  * says where each frame's features go in the cache. The call does not touch host-side clip

@@ -38,6 +38,7 @@ SOURCES = [
     ("jpeg.hip", ["-ffp-contract=off"]),
     ("mjpeg.hip", []),
     ("savebox.hip", ["-ffp-contract=off"]),
+    ("jpegenc.hip", ["-ffp-contract=off"]),
     ("yolo.hip", ["-ffp-contract=off"]),
     ("pa_api.hip", []),
 ]

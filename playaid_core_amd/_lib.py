@@ -81,6 +81,10 @@ class pa_crop_image(C.Structure):
     _fields_ = [("offset", C.c_int64), ("height", C.c_int32), ("width", C.c_int32)]
 
 
+class pa_jpeg_file(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("nbytes", C.c_int32), ("reserved", C.c_int32)]
+
+
 class pa_crop_window(C.Structure):
     _fields_ = [("offset", C.c_int64), ("pitch", C.c_int32), ("rows", C.c_int32), ("src_offset", C.c_int64),
                 ("src_pitch", C.c_int32), ("row_bytes", C.c_int32)]
@@ -212,6 +216,14 @@ SYMBOLS = [
     ("pa_mjpeg_last_sync_rounds", C.c_int, [_P]),
     ("pa_mjpeg_debug_counters", C.c_int, [_P]),
     ("pa_mjpeg_decode", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("pa_jpegenc_create", C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.POINTER(_P)]),
+    ("pa_jpegenc_destroy", None, [_P]),
+    ("pa_jpegenc_last_error", C.c_char_p, [_P]),
+    ("pa_jpeg_header", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t, C.POINTER(C.c_int32)]),
+    ("pa_jpeg_file_bytes_bound", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ("pa_jpegenc_encode", C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
+                                    _P, _P]),
+    ("pa_jpegenc_overflows", C.c_int, [_P, C.POINTER(C.c_int32), _P]),
 ]
 
 _lib = None

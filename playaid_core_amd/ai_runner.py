@@ -130,6 +130,50 @@ class ClipSource:
                 labels.append(open(fp).read() if os.path.exists(fp) else "")
         return cls(frames, labels, name)
 
+    @classmethod
+    def from_cache(cls, video_path_or_frames, cache_dir: str, name: str = None) -> "ClipSource":
+        """The detector's cache directory as the reference's runner finds it (``ai_runner.py:156-159, 291-295``; written by
+        YOLOv5's ``detect.py --save-txt --save-conf --save-crop`` or by ``ai_cache.write_detector_cache``): the label text of
+        ``<cache_dir>/labels/<video>_<n>.txt`` and, as ``crop_images``, ``<cache_dir>/crops/<Fighter>/<video>_<n>.jpg`` read
+        the way ``cv2.imread`` reads them (libjpeg-turbo's decode, BGR). ``video_path_or_frames``: the video's path -- only
+        its name is used, the crop files carry the pixels, and the clip is as long as its last label file -- or the
+        frames themselves (uint8[n, H, W, 3]; ``name`` then names the files)."""
+        from PIL import Image  # lazily, like synth.py: the product path proper never needs it
+
+        if isinstance(video_path_or_frames, (str, os.PathLike)):
+            name = name or os.path.splitext(os.path.basename(os.path.normpath(str(video_path_or_frames))))[0]
+            frames = None
+        else:
+            frames = video_path_or_frames
+            name = name or "clip"
+        labels_dir, crops_dir = os.path.join(cache_dir, "labels"), os.path.join(cache_dir, "crops")
+        if not os.path.isdir(labels_dir):
+            raise FileNotFoundError(f"{labels_dir}: no detector output for {name}")
+        if frames is None:
+            nums = [int(f[len(name) + 1:-4]) for f in os.listdir(labels_dir)
+                    if f.startswith(name + "_") and f.endswith(".txt") and f[len(name) + 1:-4].isdigit()]
+            if not nums:
+                raise FileNotFoundError(f"{labels_dir}: no label file of {name}")
+            frames = np.zeros((max(nums), 0, 0, 3), np.uint8)
+        n = frames.shape[0]
+        labels = []
+        for i in range(n):
+            fp = os.path.join(labels_dir, f"{name}_{i + 1}.txt")
+            labels.append(open(fp).read() if os.path.exists(fp) else "")
+        class_ids = sorted({int(l.split(" ")[0]) for t in labels for l in t.splitlines() if l})
+        crop_images = []
+        for i in range(n):
+            row = []
+            for c in class_ids:
+                fp = os.path.join(crops_dir, constants.CHAR_LIST[c], f"{name}_{i + 1}.jpg")
+                if os.path.exists(fp):
+                    with Image.open(fp) as im:
+                        row.append(np.ascontiguousarray(np.asarray(im.convert("RGB"))[..., ::-1]))
+                else:
+                    row.append(None)
+            crop_images.append(row)
+        return cls(frames, labels, name, crop_images=crop_images)
+
     def save(self, path: str):
         frames = self.frames if isinstance(self.frames, np.ndarray) else self.frames.cpu().numpy()
         np.savez(path, frames=frames, labels=np.array(self.labels))
@@ -377,7 +421,7 @@ class AIRunner:
                 j = int(src[i, p])
                 if missing[i, p]:
                     assert i == n - 1, f"Failed to get frame crops/{fighter}/{self.video_name}_{i + 1}.jpg"
-                    j = int(np.nonzero(~missing[:, p])[0][-1])  # never reported (frame max_frames has no window)
+                    j = int(src[int(np.nonzero(~missing[:, p])[0][-1]), p])  # never reported (frame max_frames has no window); a tail copy's own source
                 same = cl.pixel_frame[j, p] == j and np.array_equal(cl.pixel_box[j, p], boxes[i, p])
                 img = self.clip.crop_images[j][p] if same or missing[i, p] else None
                 if img is None:

@@ -156,6 +156,26 @@ def write_avi_mjpeg(path: str, jpeg_frames: Sequence[bytes], fps: float, width: 
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
+def write_frames_mjpeg(path: str, frames_dev, fps: float, quality: int = 95, subsampling: int = 2, bgr: bool = True, encoder=None) -> List[bytes]:
+    """Frames uint8[n, H, W, 3] (BGR like the decoder's output; a device tensor, or a numpy array that is uploaded) ->
+    a Motion-JPEG ``.avi`` whose frames were encoded ON THE DEVICE (``jpeg_encode.JpegEncoder``: libjpeg's bytes at
+    that quality, 4:2:0 like ``cv2.VideoWriter``), through ``write_avi_mjpeg``. Returns the frames' JPEG files.
+    ``encoder``: a ``JpegEncoder`` to re-use (one that holds the frames is made otherwise)."""
+    from .jpeg_encode import JpegEncoder
+
+    n, h, w, _ = frames_dev.shape
+    own = encoder is None
+    if own:
+        encoder = JpegEncoder.for_frames(max(n, 1), h, w, subsampling)
+    try:
+        files = encoder.encode_frames(frames_dev, quality=quality, subsampling=subsampling, bgr=bgr)
+    finally:
+        if own:
+            encoder.close()
+    write_avi_mjpeg(path, files, fps, w, h)
+    return files
+
+
 def jpeg_frame_size(buf: np.ndarray) -> Tuple[int, int]:
     """(height, width) from the first SOF0 / SOF1 segment of a JPEG file."""
     d = np.ascontiguousarray(buf, dtype=np.uint8)
