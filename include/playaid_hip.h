@@ -560,6 +560,44 @@ int pa_jpegenc_encode(pa_jpegenc* h, const uint8_t* images, size_t images_bytes,
 /* Images that did not fit since the last query (the count is reset); synchronises `stream`. */
 int pa_jpegenc_overflows(pa_jpegenc* h, int32_t* count_host, void* stream);
 
+/* ---- a2 / a3 (read side): the crop cache's JPEG files of mixed sizes, decoded on the device ---- */
+
+/* The other half of the cache boundary pa_jpegenc_encode writes: the reference reads every cached crop back with cv2.imread
+ * (ai_runner.py:191-194, 445-446). n baseline JPEG FILES OF DIFFERENT SIZES AND SAMPLINGS -- save_one_box crops (any size,
+ * 4:4:4) and the repaired gaps' 128 x 128 4:2:0 files (:420) sit in one folder -- go straight into the packed crop-image layout
+ * pa_backbone_crop_images / pa_runner_inputs consume: rows packed, each image at a 16-byte aligned offset, one pa_crop_image
+ * per image. Per image it takes what pa_mjpeg_decode takes per call: 4:4:4, 4:2:2, 4:2:0 or grey (three equal channels, as
+ * cv2.imread gives), restart markers or none, standard or optimised tables. The arithmetic is libjpeg-turbo's, including one
+ * rule no video frame meets: 2:1 sub-sampled chroma at most 2 samples wide is replicated, not filtered (jdsample.c).
+ *
+ * pa_jpegdec_plan is host only and needs no device: the marker segments of the n files spans_host[i] = bytes [start, end)
+ * of data_host -> desc_host[i] (height, width, offset = running sum of (h * w * 3 + 15) & ~15 in input order), the total
+ * *images_bytes and *blocks, the sum of all components' 8x8 blocks padded to whole MCUs, which a handle's max_blocks must
+ * cover. An empty span (start == end: no file for that frame and fighter) gives height = width = 0 and takes no bytes. A
+ * file the decoder does not take (progressive, arithmetic, 12-bit, multi-scan, 4 components, truncated header) returns
+ * PA_ERR_INVALID_ARG and names the image index and the reason in `why`. desc_host, images_bytes, blocks may be NULL.
+ *
+ * A handle owns the scratch of one call: up to max_images files, max_blocks blocks and max_bytes compressed bytes (the range
+ * of data_host that covers the call's spans). pa_jpegdec_decode parses on the host, then only ENQUEUES on `stream`: the upload
+ * of that byte range, the descriptors to desc_dev (device pa_crop_image[n]), the pixels to images_dev (16-byte aligned; BGR
+ * for bgr = 1, RGB for 0) and, if not NULL, the per-image status bits of pa_mjpeg_decode to status_dev (device int32[n]).
+ * The number of launches does not depend on n. Spans may come in any order and may repeat; data_host must stay untouched
+ * until `stream` has passed the call; calls on one handle must be stream-ordered with each other. PA_ERR_CAPACITY, with
+ * nothing enqueued, when n, the blocks, the bytes or images_capacity exceed what the handle or the caller provided;
+ * header problems fail the call like pa_jpegdec_plan (pa_jpegdec_last_error). A corrupt entropy-coded stream flags its own
+ * image, whose pixels are undefined; nothing is written out of bounds and the other images are not affected.
+ * pa_jpegdec_set_sync_rounds: as pa_mjpeg_set_sync_rounds (1..16 passes enqueued, default 16: a pass over an image that has
+ * settled returns at once; 0 = exact mode, which synchronises `stream` once per pass). */
+typedef struct pa_jpegdec pa_jpegdec;
+int pa_jpegdec_create(int32_t device, int32_t max_images, int64_t max_blocks, size_t max_bytes, pa_jpegdec** out);
+void pa_jpegdec_destroy(pa_jpegdec* h);
+const char* pa_jpegdec_last_error(const pa_jpegdec* h);
+int pa_jpegdec_set_sync_rounds(pa_jpegdec* h, int32_t rounds);
+int pa_jpegdec_plan(const uint8_t* data_host, const int64_t* spans_host, int32_t n, pa_crop_image* desc_host, size_t* images_bytes,
+                    int64_t* blocks, char* why, size_t why_bytes);
+int pa_jpegdec_decode(pa_jpegdec* h, const uint8_t* data_host, const int64_t* spans_host, int32_t n, int32_t bgr, uint8_t* images_dev,
+                      size_t images_capacity, pa_crop_image* desc_dev, int32_t* status_dev, void* stream);
+
 /* pa_backbone_frames for frames that are NOT consecutive in the clip (a resolution bucket of a
  * mixed-resolution stream, BASELINE.json configs[4]): frame_ids[n] (device, int32, 0-based)
  * says where each frame's features go in the cache. The call does not touch host-side clip

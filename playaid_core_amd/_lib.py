@@ -224,6 +224,12 @@ SYMBOLS = [
     ("pa_jpegenc_encode", C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_size_t,
                                     _P, _P]),
     ("pa_jpegenc_overflows", C.c_int, [_P, C.POINTER(C.c_int32), _P]),
+    ("pa_jpegdec_create", C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_size_t, C.POINTER(_P)]),
+    ("pa_jpegdec_destroy", None, [_P]),
+    ("pa_jpegdec_last_error", C.c_char_p, [_P]),
+    ("pa_jpegdec_set_sync_rounds", C.c_int, [_P, C.c_int32]),
+    ("pa_jpegdec_plan", C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),
+    ("pa_jpegdec_decode", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P]),
 ]
 
 _lib = None

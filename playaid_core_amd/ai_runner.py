@@ -79,6 +79,9 @@ class ClipSource:
         self.labels = list(labels)
         self.name = name
         self.crop_images = crop_images
+        # from_cache(decoder=...): the crop files decoded on the device -- (packed uint8 device tensor, descriptors int64[n * F, 2]
+        # device tensor in (frame, fighter) order, the same descriptors on the host); an entry without a file is 0 x 0
+        self.packed_crops = None
 
     VIDEO_EXTENSIONS = (".avi", ".mjpeg", ".mjpg")
 
@@ -131,14 +134,18 @@ class ClipSource:
         return cls(frames, labels, name)
 
     @classmethod
-    def from_cache(cls, video_path_or_frames, cache_dir: str, name: str = None) -> "ClipSource":
+    def from_cache(cls, video_path_or_frames, cache_dir: str, name: str = None, decoder=None) -> "ClipSource":
         """The detector's cache directory as the reference's runner finds it (``ai_runner.py:156-159, 291-295``; written by
         YOLOv5's ``detect.py --save-txt --save-conf --save-crop`` or by ``ai_cache.write_detector_cache``): the label text of
         ``<cache_dir>/labels/<video>_<n>.txt`` and, as ``crop_images``, ``<cache_dir>/crops/<Fighter>/<video>_<n>.jpg`` read
         the way ``cv2.imread`` reads them (libjpeg-turbo's decode, BGR). ``video_path_or_frames``: the video's path -- only
         its name is used, the crop files carry the pixels, and the clip is as long as its last label file -- or the
-        frames themselves (uint8[n, H, W, 3]; ``name`` then names the files)."""
-        from PIL import Image  # lazily, like synth.py: the product path proper never needs it
+        frames themselves (uint8[n, H, W, 3]; ``name`` then names the files).
+
+        ``decoder`` (a ``jpeg_decode.JpegDecoder``): the crop files are read as bytes and decoded ON THE DEVICE
+        (``pa_jpegdec_decode``), files of every size and sampling in one call; the clip then keeps the packed buffer and its
+        descriptors (``packed_crops``) instead of ``crop_images``, and no decoded pixel is ever held on the host. Without one
+        the files are decoded with Pillow on the host, one by one."""
 
         if isinstance(video_path_or_frames, (str, os.PathLike)):
             name = name or os.path.splitext(os.path.basename(os.path.normpath(str(video_path_or_frames))))[0]
@@ -161,6 +168,26 @@ class ClipSource:
             fp = os.path.join(labels_dir, f"{name}_{i + 1}.txt")
             labels.append(open(fp).read() if os.path.exists(fp) else "")
         class_ids = sorted({int(l.split(" ")[0]) for t in labels for l in t.splitlines() if l})
+        if decoder is not None:
+            from .jpeg_decode import JpegDecodeError
+
+            paths = [os.path.join(crops_dir, constants.CHAR_LIST[c], f"{name}_{i + 1}.jpg") for i in range(n) for c in class_ids]
+            blobs = []
+            for fp in paths:
+                if os.path.exists(fp):
+                    with open(fp, "rb") as fh:
+                        blobs.append(fh.read())
+                else:
+                    blobs.append(None)
+            try:
+                images, desc, _ = decoder.decode_files(blobs, bgr=True)
+            except JpegDecodeError as exc:
+                raise ValueError(f"{paths[exc.index]}: {exc}") from exc
+            clip = cls(frames, labels, name)
+            clip.packed_crops = (images, desc, desc.cpu().numpy().reshape(n, len(class_ids), 2))
+            return clip
+        from PIL import Image  # lazily, like synth.py: the product path proper never needs it
+
         crop_images = []
         for i in range(n):
             row = []
@@ -319,11 +346,15 @@ class AIRunner:
                     if im is not None:
                         hs.append(im.shape[0])
                         ws.append(im.shape[1])
+            if self.clip.packed_crops is not None:
+                hd = self.clip.packed_crops[2]
+                hs.append(int((hd[..., 1] & 0xFFFFFFFF).max()))
+                ws.append(int((hd[..., 1] >> 32).max()))
             eng = eng.reconfigured(frame_delta=self.frame_delta, fighter_class_ids=tuple(self._class_ids),
                                    max_clip_frames=max(self.max_frames, 64), max_frame_height=max(hs), max_frame_width=max(ws))
         boxes, src, missing = self._boxes()
         n = self.max_frames
-        if self.clip.crop_images is not None:
+        if self.clip.crop_images is not None or self.clip.packed_crops is not None:
             self._results = self._run_clip_from_crop_images(eng, boxes, src, missing)
             return self._results
         for p, fighter in enumerate(self.fighters):
@@ -411,9 +442,14 @@ class AIRunner:
         runner-input branch on the device (``pa_backbone_crop_images``). A crop that the label repair made up
         by duplicating the last detection (``ai_runner.py:270-289``) re-uses that detection's image, like the
         file copy the reference makes; an interpolated gap (``:389-418``) is re-cut from the video by the
-        reference and therefore needs ``frames`` -- not available from crop images alone."""
+        reference and therefore needs ``frames`` -- not available from crop images alone.
+
+        A clip whose crop files were decoded on the device (``ClipSource.from_cache(decoder=...)``) does the same bookkeeping
+        on the descriptors: a tail copy re-uses descriptor ``[j][p]``, the pixels stay where the decoder put them."""
         n = self.max_frames
         cl = self.cleaned
+        packed = self.clip.packed_crops
+        present = (packed[2][..., 1] != 0) if packed is not None else None
         images = []
         for i in range(n):
             row = []
@@ -423,14 +459,22 @@ class AIRunner:
                     assert i == n - 1, f"Failed to get frame crops/{fighter}/{self.video_name}_{i + 1}.jpg"
                     j = int(src[int(np.nonzero(~missing[:, p])[0][-1]), p])  # never reported (frame max_frames has no window); a tail copy's own source
                 same = cl.pixel_frame[j, p] == j and np.array_equal(cl.pixel_box[j, p], boxes[i, p])
-                img = self.clip.crop_images[j][p] if same or missing[i, p] else None
+                if packed is not None:
+                    img = (j, p) if (same or missing[i, p]) and present[j, p] else None
+                else:
+                    img = self.clip.crop_images[j][p] if same or missing[i, p] else None
                 if img is None:
                     raise NotImplementedError(
                         f"crop of {fighter} for frame {i + 1} was interpolated by the label repair; the reference re-cuts it "
                         "from the video (ai_runner.py:404-418): give the ClipSource its frames as well")
                 row.append(img)
             images.append(row)
-        out = eng.infer_clip_from_crop_images(images, want_crops=True)
+        if packed is not None:
+            F = len(self.fighters)
+            idx = torch.tensor([j * F + p for row in images for (j, p) in row], dtype=torch.int64, device=packed[1].device)
+            out = eng.infer_clip_from_packed_crop_images(packed[0], packed[1][idx].contiguous(), n, want_crops=True)
+        else:
+            out = eng.infer_clip_from_crop_images(images, want_crops=True)
         st = out["crop_status"].copy()
         st[missing] = 0
         bad = np.argwhere(st != 0)
