@@ -48,7 +48,8 @@ typedef enum pa_status {
     PA_ERR_BAD_WEIGHTS = -3,  /* blob size / magic / shape mismatch */
     PA_ERR_CAPACITY = -4,     /* more frames/windows than the engine was created for */
     PA_ERR_NO_DEVICE = -5,
-    PA_ERR_NOT_READY = -6     /* head asked for frames whose features are not cached */
+    PA_ERR_NOT_READY = -6,    /* head asked for frames whose features are not cached */
+    PA_ERR_BAD_LABELS = -7    /* pa_eval_read: labels outside [0, num_actions) were met (and skipped); the totals are filled */
 } pa_status;
 
 /* per-crop status words written by the preprocess stage */
@@ -889,6 +890,47 @@ int pa_stream_gate_open(pa_engine* e);
 
 /* Blocks until all work enqueued on `stream` is done (hipStreamSynchronize). */
 int pa_stream_sync(pa_engine* e, void* stream);
+
+/* ---- scoring ------------------------------------------------------------ */
+
+/* Scores log-probabilities against labels on the device: the NLL loss and multiclass top-1 accuracy of the reference's
+ * validation_step / test_step (cnn_action_detector.py:131-163, the same in the other two models) and the confusion matrix,
+ * "% correct" and "mean confidence" of visualizations/cnn_action_detector_vis.py:89-153, accumulated over any number of
+ * pa_eval_update calls (an epoch) and read once. The handle belongs to no engine: it takes the log-probabilities of any
+ * of the three models. Not thread-safe; the calls of one handle go to one stream (or to streams the caller orders).
+ *
+ * pa_eval_update: logp float32[n][ld] (device; ld >= num_actions, columns >= num_actions are never read), row i is
+ * scored against labels[i * label_stride] (int32, device). label_stride 1 = a plain label array; 4 with
+ * labels = &records->action_id = a pa_record array, so that another run's predictions serve as the labels (agreement of
+ * two arithmetics with nothing on the host). The prediction of a row is its first maximum (torch.argmax, pa_record's
+ * action_id). A label PA_EVAL_IGNORE (F.nll_loss's default ignore_index; frames without ground truth) skips the row and
+ * counts it in `ignored`; any other label outside [0, num_actions) skips the row and counts it in `bad_labels`.
+ * Otherwise rows += 1, correct += (prediction == label), nll_sum += -logp[i][label], conf_sum += exp(logp[i][prediction])
+ * (both taken in double), confusion[label][prediction] += 1 (row = actual, column = predicted, as sklearn lays it out).
+ * n == 0 is a no-op. Enqueue only.
+ *
+ * Determinism: the integers are exact in any order; the two double sums use no floating-point atomics (ordered slabs:
+ * one partial per workgroup, folded in a fixed order by a second launch), so the same calls in the same order give the
+ * same bits.
+ *
+ * pa_eval_read is the only call that waits: it copies the totals (and, when confusion_host is not NULL, the
+ * int64[num_actions * num_actions] matrix) to the host behind everything enqueued on `stream`. It returns
+ * PA_ERR_BAD_LABELS when bad_labels != 0 -- the totals and the matrix are filled all the same. pa_eval_reset zeroes the
+ * state (enqueued). pa_eval_create / pa_eval_update check their arguments before any device call (null handle or
+ * pointers, device < 0, num_actions outside 1..4096, ld < num_actions, n < 0, label_stride < 1: PA_ERR_INVALID_ARG); a create that
+ * stops at the device (PA_ERR_NO_DEVICE / PA_ERR_HIP) still hands the handle back, to be destroyed by the caller. */
+typedef struct pa_eval pa_eval;
+typedef struct pa_eval_totals {
+    int64_t rows, correct, ignored, bad_labels;
+    double nll_sum, conf_sum;
+} pa_eval_totals;
+#define PA_EVAL_IGNORE (-100)
+int pa_eval_create(int32_t device, int32_t num_actions, pa_eval** out);
+void pa_eval_destroy(pa_eval* h);
+int pa_eval_reset(pa_eval* h, void* stream);
+int pa_eval_update(pa_eval* h, const float* logp_dev, int32_t ld, int32_t n, const int32_t* labels_dev, int32_t label_stride,
+                   void* stream);
+int pa_eval_read(pa_eval* h, pa_eval_totals* totals_host, int64_t* confusion_host, void* stream);
 
 #ifdef __cplusplus
 }

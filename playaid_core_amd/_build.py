@@ -35,6 +35,7 @@ SOURCES = [
     ("lstm.hip", []),
     ("convnet.hip", []),
     ("transformer.hip", []),
+    ("metrics.hip", []),
     ("jpeg.hip", ["-ffp-contract=off"]),
     ("mjpeg.hip", []),
     ("savebox.hip", ["-ffp-contract=off"]),

@@ -37,6 +37,8 @@ PA_ERR_BAD_WEIGHTS = -3
 PA_ERR_CAPACITY = -4
 PA_ERR_NO_DEVICE = -5
 PA_ERR_NOT_READY = -6
+PA_ERR_BAD_LABELS = -7
+PA_EVAL_IGNORE = -100
 
 PA_CROP_OK = 0
 PA_CROP_EMPTY = 1
@@ -99,6 +101,11 @@ class pa_net_layer(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("kind", "cin", "cout", "ksize", "stride", "in_h", "in_w", "in_buf", "in_coff", "in_cstride", "in_pad",
                                         "out_buf", "out_coff", "out_cstride", "out_pad", "res_buf", "res_coff", "act", "res_after",
                                         "reserved")] + [("w_off", C.c_int64), ("b_off", C.c_int64), ("aux", C.c_float * 8)]
+
+
+class pa_eval_totals(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("correct", C.c_int64), ("ignored", C.c_int64), ("bad_labels", C.c_int64),
+                ("nll_sum", C.c_double), ("conf_sum", C.c_double)]
 
 
 class pa_kernel_stat(C.Structure):
@@ -230,6 +237,11 @@ SYMBOLS = [
     ("pa_jpegdec_set_sync_rounds", C.c_int, [_P, C.c_int32]),
     ("pa_jpegdec_plan", C.c_int, [_P, _P, C.c_int32, _P, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]),
     ("pa_jpegdec_decode", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P]),
+    ("pa_eval_create", C.c_int, [C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("pa_eval_destroy", None, [_P]),
+    ("pa_eval_reset", C.c_int, [_P, _P]),
+    ("pa_eval_update", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    ("pa_eval_read", C.c_int, [_P, C.POINTER(pa_eval_totals), _P, _P]),
 ]
 
 _lib = None

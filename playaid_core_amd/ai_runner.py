@@ -82,6 +82,8 @@ class ClipSource:
         # from_cache(decoder=...): the crop files decoded on the device -- (packed uint8 device tensor, descriptors int64[n * F, 2]
         # device tensor in (frame, fighter) order, the same descriptors on the host); an entry without a file is 0 x 0
         self.packed_crops = None
+        # from_ground_truth: ground_truth[fighter][i] = the hand-labelled action string of frame i (AIRunner.evaluate's labels)
+        self.ground_truth = None
 
     VIDEO_EXTENSIONS = (".avi", ".mjpeg", ".mjpg")
 
@@ -200,6 +202,38 @@ class ClipSource:
                     row.append(None)
             crop_images.append(row)
         return cls(frames, labels, name, crop_images=crop_images)
+
+    @classmethod
+    def from_ground_truth(cls, video_path_or_frames, csv_path: str, lines=None, first_frame: int = 0, name: str = None) -> "ClipSource":
+        """A hand-labelled clip (``ult_action_dataset.py:429-559``: CSV rows ``frame_num, fighter, action, cx, cy, w, h``) as a
+        clip with the boxes GIVEN: the label text of every frame (``cls cx cy w h conf``, conf 1.0) is written from the CSV's
+        boxes, so the clip runs without a detector. ``video_path_or_frames``: a video the device decodes (``from_video``) or
+        the frames (uint8[n, H, W, 3] BGR). CSV ``frame_num`` ``first_frame + i`` is frame i of the clip (the reference seeks
+        ``VideoCapture`` positions, ``:463``). A frame or fighter the CSV does not list gets no label line -- the runner's label
+        repair then treats it like a frame the detector lost -- and ``ground_truth[fighter][i]`` (action strings, kept on the
+        clip for ``AIRunner.evaluate``) has no entry for it, which scores as ``-100``."""
+        from .ult_action_dataset import load_ground_truth_labels
+
+        gt, _ = load_ground_truth_labels(csv_path, lines)
+        if isinstance(video_path_or_frames, (str, os.PathLike)):
+            clip = cls.from_video(str(video_path_or_frames), labels=None, labels_dir=os.path.dirname(os.path.abspath(csv_path)))
+            # (whatever label files lie there are not used: the text below replaces them)
+        else:
+            clip = cls(video_path_or_frames, [""] * video_path_or_frames.shape[0], name or "clip")
+        if name:
+            clip.name = name
+        n = clip.frames.shape[0]
+        text = [[] for _ in range(n)]
+        clip.ground_truth = {}
+        for fighter in sorted(gt, key=constants.CHAR_LIST.index):
+            clip.ground_truth[fighter] = {}
+            for f, (_, _, action, cx, cy, w, h) in sorted(gt[fighter].items()):
+                i = f - first_frame
+                if 0 <= i < n:
+                    text[i].append(str(YoloCrop(cx, cy, w, h, confidence=1.0, class_id=constants.CHAR_LIST.index(fighter))))
+                    clip.ground_truth[fighter][i] = action
+        clip.labels = ["".join(l + "\n" for l in lines_) for lines_ in text]
+        return clip
 
     def save(self, path: str):
         frames = self.frames if isinstance(self.frames, np.ndarray) else self.frames.cpu().numpy()
@@ -531,6 +565,40 @@ class AIRunner:
                 frame_data.crop = str(self._crops[frame_num - 1][p])
                 frame_data.action = predicted_action
                 frame_data.predicted_action_confidence = confidence
+
+    def evaluate(self, actions=None, ground_truth_csv: str = None, lines=None, first_frame: int = 0):
+        """Scores the open clip's predictions against ground truth: NLL loss, top-1 accuracy, mean confidence and confusion
+        matrix over every (frame in [1, max_frames), fighter) -- the figures of the reference's ``test_step``
+        (``cnn_action_detector.py:148-163``) and ``visualizations/cnn_action_detector_vis.py:89-153`` (``metrics.finish``).
+        The clip runs as ``run_action_recognition`` runs it (same crop mode, JPEG round trip and label repair: ``_run_clip``);
+        its log-probabilities are scored by the device accumulator (``pa_eval_update``) in one call and read once.
+
+        Ground truth, one of: ``actions[p][f - 1]`` = the action string of fighter slot p in frame f (the shape
+        ``ClipWindowDataset`` takes; None entries are unlabelled), ``ground_truth_csv`` (``load_ground_truth_labels``; ``lines`` /
+        ``first_frame`` as there and in ``label_table``), or neither for a clip made by ``ClipSource.from_ground_truth``.
+        Action strings map through the model's action list; unlabelled frames are ``-100`` and counted in ``ignored``."""
+        from .metrics import EvalState
+        from .ult_action_dataset import label_table, load_ground_truth_labels
+
+        if actions is not None and ground_truth_csv is not None:
+            raise ValueError("evaluate: actions= or ground_truth_csv=, not both")
+        if ground_truth_csv is not None:
+            actions, first = load_ground_truth_labels(ground_truth_csv, lines)[0], first_frame
+        elif actions is None:
+            actions, first = getattr(self.clip, "ground_truth", None), 0
+            if actions is None:
+                raise ValueError("evaluate: no ground truth (actions=, ground_truth_csv= or a ClipSource.from_ground_truth clip)")
+        else:
+            first = 0
+        table = label_table(self, actions, self.model.actions, first_frame=first)
+        res = self._run_clip()
+        eng = self.model.engine
+        logp = torch.from_numpy(np.ascontiguousarray(res["logp"][: self.max_frames - 1], dtype=np.float32)).to(eng.device)
+        with EvalState(len(self.model.actions), eng.device) as st:
+            st.update(logp.view(-1, logp.shape[-1]), torch.from_numpy(table.reshape(-1)).to(eng.device))
+            out = st.compute()
+        out["labels"] = table
+        return out
 
     def load_ai_output(self):
         if not os.path.exists(self.ai_output_file):

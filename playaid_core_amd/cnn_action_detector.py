@@ -5,8 +5,18 @@ Mirror of ``playaid/models/cnn_action_detector.py:46-92`` for inference:
 ``x: float32[B,S,3,128,128]`` in [0,1] -> ``float32[B,len(actions)]``
 log-probabilities, ``.actions``. The arithmetic (ResNet-18 per frame, Conv1d
 over the S features, MLP, log_softmax) runs in the HIP library through
-``pa_infer_windows``; there is no PyTorch fallback. Training hooks of the
-reference (``:94-207``) are out of scope.
+``pa_infer_windows``; there is no PyTorch fallback.
+
+Scoring is mirrored too (it is inference): ``validation_step`` / ``test_step``
+(``:131-163``) score the window's CENTRE label -- NLL loss and multiclass top-1
+accuracy -- into a device accumulator (``metrics.EvalState``, ``pa_eval_*``)
+without reading anything back per step; ``metrics("val" | "test")`` is the one
+read and returns the figures under the reference's log names
+(``val_action_loss``, ``val_action_acc``, ...) plus the confusion matrix and
+mean confidence of ``visualizations/cnn_action_detector_vis.py:89-153``;
+``reset_metrics(split)`` starts a new epoch. Not mirrored: ``training_step``,
+``training_epoch_end``, ``configure_optimizers`` and the data hooks
+(``:94-129,165-207``).
 """
 from __future__ import annotations
 
@@ -15,6 +25,7 @@ from typing import List, Mapping, Optional
 import torch
 
 from .engine import Engine
+from .metrics import SplitMetrics
 from .weights import infer_geometry
 
 
@@ -86,3 +97,28 @@ class CNNActionDetector:
         return out if x.is_cuda else out.cpu()
 
     __call__ = forward
+
+    # -- scoring (cnn_action_detector.py:131-163) ---------------------------------
+    def _split_metrics(self) -> SplitMetrics:
+        if getattr(self, "_metrics", None) is None:
+            self._metrics = SplitMetrics(self.num_actions, self._engine.device)
+        return self._metrics
+
+    def _score(self, split: str, batch):
+        input, char_label, action_label, _ = batch
+        centered_action_label = action_label[:, input.shape[1] // 2]
+        logp = self._engine.infer_windows(input)  # stays on the device: nothing is read back per step
+        self._split_metrics().step(split, logp, centered_action_label)
+
+    def validation_step(self, batch, batch_idx):
+        self._score("val", batch)
+
+    def test_step(self, batch, batch_idx):
+        self._score("test", batch)
+
+    def metrics(self, split: str = "val"):
+        """The epoch's figures so far (``metrics.finish``) plus ``<split>_action_loss`` / ``<split>_action_acc``; waits."""
+        return self._split_metrics().metrics(split)
+
+    def reset_metrics(self, split: str = None):
+        self._split_metrics().reset(split)

@@ -759,6 +759,7 @@ const char* pa_status_string(int status) {
         case PA_ERR_CAPACITY: return "request exceeds the capacity the engine was created with";
         case PA_ERR_NO_DEVICE: return "no usable HIP device";
         case PA_ERR_NOT_READY: return "features of a required frame are not in the cache";
+        case PA_ERR_BAD_LABELS: return "labels outside [0, num_actions) were skipped";
         default: return "unknown status";
     }
 }
@@ -1854,6 +1855,75 @@ int pa_stream_gate_open(pa_engine* e) {
 int pa_stream_sync(pa_engine* e, void* stream) {
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     return PA_OK;
+}
+
+}  // extern "C"
+
+// ===============================================================================
+// Scoring (csrc/metrics.hip): a handle of its own, owned by no engine
+// ===============================================================================
+
+struct pa_eval {
+    int actions = 0;
+    // one allocation: counts {rows, correct, ignored, bad_labels} | sums {nll_sum, conf_sum} (= pa_eval_totals) | confusion [A][A] | slab
+    unsigned char* state = nullptr;
+    size_t state_bytes = 0;  // what pa_eval_reset zeroes: everything but the slab
+    unsigned long long* counts() const { return reinterpret_cast<unsigned long long*>(state); }
+    double* sums() const { return reinterpret_cast<double*>(state + 4 * sizeof(int64_t)); }
+    unsigned long long* confusion() const { return reinterpret_cast<unsigned long long*>(state + sizeof(pa_eval_totals)); }
+    double* slab() const { return reinterpret_cast<double*>(state + state_bytes); }
+};
+
+static_assert(sizeof(pa_eval_totals) == 48, "pa_eval_totals is four int64 and two doubles, read back in one copy");
+
+extern "C" {
+
+int pa_eval_create(int32_t device, int32_t num_actions, pa_eval** out) {
+    if (!out) return PA_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (device < 0 || num_actions < 1 || num_actions > 4096) return PA_ERR_INVALID_ARG;
+    pa_eval* h = new pa_eval();
+    *out = h;
+    h->actions = num_actions;
+    h->state_bytes = sizeof(pa_eval_totals) + (size_t)num_actions * num_actions * sizeof(int64_t);
+    if (hipSetDevice(device) != hipSuccess) return PA_ERR_NO_DEVICE;
+    void* p = nullptr;
+    if (hipMalloc(&p, h->state_bytes + 2 * EVAL_SLAB_PARTS * sizeof(double)) != hipSuccess) return PA_ERR_HIP;
+    h->state = static_cast<unsigned char*>(p);
+    if (hipMemset(h->state, 0, h->state_bytes) != hipSuccess) return PA_ERR_HIP;
+    return PA_OK;
+}
+
+void pa_eval_destroy(pa_eval* h) {
+    if (!h) return;
+    (void)hipFree(h->state);
+    delete h;
+}
+
+int pa_eval_reset(pa_eval* h, void* stream) {
+    if (!h) return PA_ERR_INVALID_ARG;
+    if (!h->state) return PA_ERR_NO_DEVICE;
+    return hipMemsetAsync(h->state, 0, h->state_bytes, (hipStream_t)stream) == hipSuccess ? PA_OK : PA_ERR_HIP;
+}
+
+int pa_eval_update(pa_eval* h, const float* logp_dev, int32_t ld, int32_t n, const int32_t* labels_dev, int32_t label_stride,
+                   void* stream) {
+    if (!h || !logp_dev || !labels_dev || ld < h->actions || n < 0 || label_stride < 1) return PA_ERR_INVALID_ARG;
+    if (!h->state) return PA_ERR_NO_DEVICE;
+    return launch_eval_rows(logp_dev, ld, n, h->actions, labels_dev, label_stride, h->counts(), h->sums(), h->confusion(), h->slab(),
+                            (hipStream_t)stream) == hipSuccess ? PA_OK : PA_ERR_HIP;
+}
+
+int pa_eval_read(pa_eval* h, pa_eval_totals* totals_host, int64_t* confusion_host, void* stream) {
+    if (!h || !totals_host) return PA_ERR_INVALID_ARG;
+    if (!h->state) return PA_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(totals_host, h->state, sizeof(pa_eval_totals), hipMemcpyDeviceToHost, s) != hipSuccess) return PA_ERR_HIP;
+    if (confusion_host && hipMemcpyAsync(confusion_host, h->confusion(), (size_t)h->actions * h->actions * sizeof(int64_t),
+                                         hipMemcpyDeviceToHost, s) != hipSuccess)
+        return PA_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return PA_ERR_HIP;
+    return totals_host->bad_labels != 0 ? PA_ERR_BAD_LABELS : PA_OK;
 }
 
 }  // extern "C"

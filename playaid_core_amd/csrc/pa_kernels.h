@@ -419,4 +419,11 @@ struct HeadParams {
 };
 hipError_t launch_head_mlp(const HeadParams& p, hipStream_t s);
 
+// metrics.hip: scores n rows of log-probabilities logp[n][ld] (A columns read) against labels[i * label_stride] and adds the
+// result to running device state -- counts {rows, correct, ignored, bad_labels}, sums {nll_sum, conf_sum} (double), confusion
+// [A][A] (row = label, column = prediction). slab: 2 * EVAL_SLAB_PARTS doubles of scratch (one partial pair per workgroup).
+constexpr int EVAL_SLAB_PARTS = 1024;
+hipError_t launch_eval_rows(const float* logp, int ld, int n, int A, const int32_t* labels, int label_stride, unsigned long long* counts,
+                            double* sums, unsigned long long* confusion, double* slab, hipStream_t s);
+
 }  // namespace pa

@@ -662,11 +662,8 @@ class Engine:
             "status": r[..., 3].copy(),
         }
 
-    def infer_clip(self, frames, boxes, want_crops: bool = False, src=None):
-        """Host convenience: upload, run, download. -> dict with logp[n-1,F,A],
-        action_id, prob, char_id, status[n,F] (and crops_rgb[n,F,128,128,3]).
-        ``src`` (int[n,F], optional): the frame each crop is cut from when that is not its own
-        (``pa_backbone_frames_src``); the clip then has ``boxes.shape[0]`` frames."""
+    def _enqueue_clip(self, frames, boxes, want_crops: bool = False, src=None):
+        """Upload and enqueue a whole clip; -> device tensors (records, logp, crop status, crops or None). Nothing is waited for."""
         fd = self._dev(frames, torch.uint8)
         bd = self._dev(boxes, torch.float64)
         n = bd.shape[0] if src is not None else fd.shape[0]
@@ -685,6 +682,14 @@ class Engine:
                 self.backbone_frames_src(fd, bd[f0 : f0 + cnt], sd[f0 : f0 + cnt], f0,
                                          crops[f0 : f0 + cnt] if want_crops else None, status[f0 : f0 + cnt])
             self.head_frames(1, n, records, logp)
+        return records, logp, status, crops
+
+    def infer_clip(self, frames, boxes, want_crops: bool = False, src=None):
+        """Host convenience: upload, run, download. -> dict with logp[n-1,F,A],
+        action_id, prob, char_id, status[n,F] (and crops_rgb[n,F,128,128,3]).
+        ``src`` (int[n,F], optional): the frame each crop is cut from when that is not its own
+        (``pa_backbone_frames_src``); the clip then has ``boxes.shape[0]`` frames."""
+        records, logp, status, crops = self._enqueue_clip(frames, boxes, want_crops, src)
         torch.cuda.synchronize(self.device)
         out = self.decode_records(records)
         out["logp"] = logp.cpu().numpy()
@@ -692,6 +697,47 @@ class Engine:
         if want_crops:
             out["crops_rgb"] = crops.cpu().numpy()
         return out
+
+    # -- scoring (pa_eval_*, metrics.py) ------------------------------------------
+    def evaluate_clip(self, frames, boxes, labels, src=None, state=None):
+        """``infer_clip`` scored against ``labels`` int32[n-1, F] (``metrics.IGNORE`` = -100 where a frame has no ground truth):
+        enqueues exactly what ``infer_clip`` enqueues, then ONE ``pa_eval_update`` over ``logp.view(-1, A)`` on the same stream
+        -- records and log-probabilities stay on the device -- and one read. -> ``metrics.finish``'s dict (loss, accuracy,
+        mean_confidence, confusion, ...) plus ``records`` (the ``decode_records`` fields of the clip). ``state``: an
+        ``EvalState`` to accumulate into across clips (the figures then cover everything it has seen); default a fresh one."""
+        from .metrics import EvalState
+
+        records, logp, status, _ = self._enqueue_clip(frames, boxes, False, src)
+        ld = self._dev(labels, torch.int32)
+        if tuple(ld.shape) != tuple(logp.shape[:2]):
+            raise ValueError(f"labels are int32[{logp.shape[0]}, {self.F}], got {tuple(ld.shape)}")
+        own = state is None
+        st = EvalState(self.A, self.device) if own else state
+        try:
+            st.update(logp.view(-1, self.A), ld.reshape(-1))
+            out = st.compute()
+        finally:
+            if own:
+                st.close()
+        out["records"] = self.decode_records(records)
+        out["records"]["crop_status"] = status.cpu().numpy()
+        return out
+
+    def agreement(self, records_a: torch.Tensor, logp_b: torch.Tensor):
+        """Run A's predictions as the labels of run B: ``records_a`` int32[..., 4] (a ``pa_record`` array on the device, as
+        ``alloc_records`` / ``infer_clip_device`` leave it; its ``action_id`` is read in place through ``label_stride=4``),
+        ``logp_b`` float32[..., A] with as many rows. -> the same dict; ``accuracy`` is the fraction of labels that agree,
+        the confusion matrix's off-diagonals are the flips (row = A's action, column = B's)."""
+        from .metrics import EvalState
+
+        if records_a.dtype != torch.int32 or records_a.shape[-1] != 4 or not records_a.is_cuda or not records_a.is_contiguous():
+            raise ValueError("agreement: records_a is a contiguous int32[..., 4] device tensor (pa_record rows)")
+        lb = logp_b.reshape(-1, logp_b.shape[-1])
+        if lb.shape[0] != records_a.numel() // 4 or lb.shape[1] != self.A:
+            raise ValueError(f"agreement: {records_a.numel() // 4} records against logp of shape {tuple(logp_b.shape)}")
+        with EvalState(self.A, self.device) as st:
+            st.update(self._dev(lb, torch.float32), records_a.view(-1)[1:], label_stride=4)
+            return st.compute()
 
     def features_export(self, frame0: int, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if out is None:

@@ -11,7 +11,13 @@ frame slot; that is reproduced as is.
 The ResNet-50 runs on the engine's fp32 convolution kernels through a layer table (``pa_convnet_*``,
 ``csrc/convnet.hip``): BatchNorm folded in fp64 here, 1x1 convolutions as GEMMs on the im2col engine, the stride-1
 3x3 ones on the patch-resident kernel, the stem on ``stem_pool_kernel``. The encoder and the classifier run in
-``csrc/transformer.hip`` (``pa_encoder_*``). No PyTorch fallback; training hooks (``:143-260``) are out of scope.
+``csrc/transformer.hip`` (``pa_encoder_*``). No PyTorch fallback.
+
+Scoring is mirrored (``validation_step`` / ``test_step``, ``:179-205``): this model's reference flattens its ``[B, S, A]`` output
+and ``action_label`` to ``B * S`` rows and scores every one of them (not the centre label the CNN model scores) -- NLL loss and
+multiclass top-1 accuracy, accumulated on the device (``metrics.EvalState``) with nothing read back per step;
+``metrics(split)`` is the one read (``val_action_loss``, ``val_action_acc``, ... plus confusion matrix and mean confidence),
+``reset_metrics(split)`` clears a split. Not mirrored: ``training_step``, the optimiser and the data hooks (``:143-177,207-260``).
 
 ``compute_dtype="bf16"`` (never the default) runs the ResNet-50 with bf16 storage and bf16 products: the stem on
 ``stem_pool_kernel``'s bf16 form, every convolution on the one-slice bf16 GEMM (``csrc/bgemm.hip``, split-K on the small maps),
@@ -28,6 +34,7 @@ import torch
 
 from . import _lib
 from .engine import EngineError, _ptr
+from .metrics import SplitMetrics
 
 HIDDEN_DIM, NUM_FREQ, NUM_HEADS, NUM_LAYERS, FF_DIM = 247, 4, 8, 3, 2048
 D_MODEL = HIDDEN_DIM + 1 + 2 * NUM_FREQ
@@ -351,6 +358,9 @@ class ResnetTransformerDetector:
         if getattr(self, "_h", None):
             self._lib.pa_encoder_destroy(self._h)
             self._h = None
+        if getattr(self, "_metrics", None) is not None:
+            self._metrics.close()
+            self._metrics = None
         if getattr(self, "_net", None) is not None:
             self._net.close()
             self._net = None
@@ -371,3 +381,27 @@ class ResnetTransformerDetector:
         return out if frames.is_cuda else out.cpu()
 
     __call__ = forward
+
+    # -- scoring (resnet_transformer_detector.py:179-205) -----------------------------
+    def _split_metrics(self) -> SplitMetrics:
+        if getattr(self, "_metrics", None) is None:
+            self._metrics = SplitMetrics(self.num_actions, self.device)
+        return self._metrics
+
+    def _score(self, split: str, batch):
+        input, char_label, action_label, _ = batch
+        logp = self.forward(input.to(self.device))  # a device input: the rows stay on the device, nothing waits
+        self._split_metrics().step(split, logp.reshape(-1, self.num_actions), action_label.reshape(-1))  # "b s f -> (b s) f"
+
+    def validation_step(self, batch, batch_idx):
+        self._score("val", batch)
+
+    def test_step(self, batch, batch_idx):
+        self._score("test", batch)
+
+    def metrics(self, split: str = "val"):
+        """The epoch's figures so far (``metrics.finish``) plus ``<split>_action_loss`` / ``<split>_action_acc``; waits."""
+        return self._split_metrics().metrics(split)
+
+    def reset_metrics(self, split: str = None):
+        self._split_metrics().reset(split)

@@ -8,7 +8,13 @@ the recurrence runs over the WINDOWS of a call and the frames of a window are it
 
 The backbone runs on the engine's convolution kernels (``pa_backbone_windows``: the fc rows are zero-padded from 300
 to the engine's 1000, the Conv1d head of the engine is unused), the recurrent head and decoder in
-``csrc/lstm.hip`` (``pa_lstm_forward``). No PyTorch fallback; training hooks (``:97-260``) are out of scope.
+``csrc/lstm.hip`` (``pa_lstm_forward``). No PyTorch fallback.
+
+Scoring is mirrored (``validation_step`` / ``test_step``, ``:132-160``): this model's reference scores EVERY row of its
+``[B*S, A]`` output against ``action_label.view(B * S)`` (not the centre label the CNN model scores) -- NLL loss and multiclass
+top-1 accuracy, accumulated on the device (``metrics.EvalState``) with nothing read back per step; ``metrics(split)`` is the
+one read (``val_action_loss``, ``val_action_acc``, ... plus confusion matrix and mean confidence), ``reset_metrics(split)``
+clears a split. Not mirrored: ``training_step``, the optimiser and the data hooks (``:97-130,162-260``).
 """
 from __future__ import annotations
 
@@ -20,6 +26,7 @@ import torch
 
 from . import _lib
 from .engine import Engine, EngineError, _ptr
+from .metrics import SplitMetrics
 from .synth import resnet18_param_shapes
 
 INPUT_DIM, HIDDEN_DIM, NUM_LAYERS = 300, 512, 3
@@ -153,6 +160,9 @@ class RNNActionDetector:
         if getattr(self, "_h", None):
             self._lib.pa_lstm_destroy(self._h)
             self._h = None
+        if getattr(self, "_metrics", None) is not None:
+            self._metrics.close()
+            self._metrics = None
         if getattr(self, "_engine", None) is not None:
             self._engine.close()
             self._engine = None
@@ -185,3 +195,31 @@ class RNNActionDetector:
             raise EngineError(rc, self._lib.pa_lstm_last_error(self._h).decode())
 
     __call__ = forward
+
+    # -- scoring (rnn_action_detector.py:132-160) -----------------------------------
+    def _split_metrics(self) -> SplitMetrics:
+        if getattr(self, "_metrics", None) is None:
+            self._metrics = SplitMetrics(self.num_actions, self._engine.device)
+        return self._metrics
+
+    def _score(self, split: str, batch):
+        input, char_label, action_label, _ = batch
+        batch_size, seq_length = input.shape[0], input.shape[1]
+        action_label = action_label.reshape(batch_size * seq_length)
+        logp = self.forward(self._engine._dev(input, torch.float32))  # a device input: the rows stay on the device, nothing waits
+        self._split_metrics().step(split, logp, action_label)
+
+    def validation_step(self, batch, batch_idx):
+        self._score("val", batch)
+
+    def test_step(self, batch, batch_idx):
+        self._score("test", batch)
+
+    def metrics(self, split: str = "val"):
+        """The epoch's figures so far (``metrics.finish``) plus ``<split>_action_loss`` / ``<split>_action_acc``; waits."""
+        out = self._split_metrics().metrics(split)
+        self.check()  # (the read synchronised the stream: a barrier time-out of any step's LSTM kernel shows here)
+        return out
+
+    def reset_metrics(self, split: str = None):
+        self._split_metrics().reset(split)

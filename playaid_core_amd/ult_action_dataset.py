@@ -13,9 +13,15 @@ the same sampler with the runner's own range (frames are 1-indexed crop files, `
 Not built, by scope (training only): the random choice of (fighter, action, frame), the frame-delta
 choice, ``synth_difficulty`` augmentation, the synthetic-stage compositing of the "simple" split, ``preceding_actions`` (the
 reference's own loop over them is empty: ``range(a, a)``, ``ult_action_dataset.py:284-286``).
+
+For scoring (``metrics.py``, ``AIRunner.evaluate``): ``load_ground_truth_labels`` reads a hand-labelled clip's CSV as the
+reference does (``ult_action_dataset.py:512-559``) and ``label_table`` turns action strings -- per-fighter lists or that CSV's
+labels -- into the ``int32[max_frames - 1, F]`` table the device accumulator takes, ``-100`` where a frame has no ground truth.
 """
 from __future__ import annotations
 
+import csv
+from collections import defaultdict
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -24,6 +30,68 @@ import torch
 from . import constants
 from .anim_ontology import MOVE_TO_CLASS_ID
 from .dataset_utils import action_sample_from_frame_middle_out
+
+
+def _action_id(animations: Sequence[str], action: str) -> int:
+    # ult_action_dataset.py:352-357 (an action outside the list maps to "Unknown", which must then be in the list)
+    return animations.index(action) if action in animations else animations.index("Unknown")
+
+
+def load_ground_truth_labels(csv_path: str, lines=None):
+    """``UltActionRecogDataset.load_ground_truth_labels`` (``ult_action_dataset.py:512-559``) on ``csv_path``: rows
+    ``frame_num, fighter, action, cx, cy, w, h``; line 1 (the header) is skipped, and with ``lines`` (a set of 1-based line
+    numbers, the reference's train / validation split) only those lines are kept -- None keeps every line.
+    -> ``(labels[fighter][frame_num] = (frame_num, fighter, action, cx, cy, w, h), action_to_frames[fighter][action] = [frame_num])``.
+    ``frame_num`` is the frame's ``VideoCapture`` position (``:463``): 0 is the first frame."""
+    labels = defaultdict(dict)
+    action_to_frames = {}
+    with open(csv_path, newline="") as f:
+        reader = csv.reader(f)
+        for row in reader:
+            if reader.line_num == 1 or (lines is not None and reader.line_num not in lines):
+                continue
+            if not row:
+                continue
+            frame_num, fighter_name, action = int(row[0]), row[1], row[2]
+            labels[fighter_name][frame_num] = (frame_num, fighter_name, action, float(row[3]), float(row[4]), float(row[5]), float(row[6]))
+            if fighter_name not in action_to_frames:
+                action_to_frames[fighter_name] = defaultdict(list)
+            action_to_frames[fighter_name][action].append(frame_num)
+    return dict(labels), dict(action_to_frames)
+
+
+def label_table(runner_or_names, actions, animations: Optional[Sequence[str]] = None, n_rows: Optional[int] = None,
+                first_frame: int = 0) -> np.ndarray:
+    """-> ``int32[max_frames - 1, F]``: row i, column p = the action id of fighter slot p in the runner's frame i + 1 (the rows
+    of ``Engine.evaluate_clip`` / ``infer_clip``'s ``logp``), ``-100`` (``metrics.IGNORE``) where there is no ground truth.
+
+    ``runner_or_names``: an ``AIRunner`` (its ``fighters`` and ``max_frames``) or the fighter names in slot order (then ``n_rows``,
+    or as many rows as the labels reach). ``actions``: per-fighter sequences ``actions[p][i]`` of action strings (the shape
+    ``ClipWindowDataset`` takes; None = no ground truth), or ``load_ground_truth_labels``' ``labels[fighter][frame_num]`` mapping --
+    frame_num ``first_frame + i`` is row i (the CSV counts ``VideoCapture`` positions, the runner's frame i + 1 is position i).
+    Strings go through the dataset's rule: one outside ``animations`` (default: the ontology's 63) is ``"Unknown"``, which must
+    then be in the list (ValueError otherwise, as in the reference)."""
+    animations = list(animations) if animations is not None else list(MOVE_TO_CLASS_ID.keys())
+    if hasattr(runner_or_names, "fighters"):
+        names = list(runner_or_names.fighters)
+        n_rows = runner_or_names.max_frames - 1 if n_rows is None else n_rows
+    else:
+        names = list(runner_or_names)
+    by_name = isinstance(actions, dict)
+    cols = []
+    for p, name in enumerate(names):
+        if by_name:
+            cols.append({f - first_frame: rec[2] if isinstance(rec, (tuple, list)) else rec for f, rec in actions.get(name, {}).items()})
+        else:
+            cols.append({i: a for i, a in enumerate(actions[p]) if a is not None})
+    if n_rows is None:
+        n_rows = max([max(c) + 1 for c in cols if c] or [0])
+    out = np.full((n_rows, len(names)), -100, dtype=np.int32)
+    for p, col in enumerate(cols):
+        for i, a in col.items():
+            if 0 <= i < n_rows:
+                out[i, p] = _action_id(animations, a)
+    return out
 
 
 class ClipWindowDataset:
@@ -50,8 +118,7 @@ class ClipWindowDataset:
         return (self.runner.max_frames - 1) * len(self.runner.fighters)
 
     def _action_id(self, action: str) -> int:
-        # ult_action_dataset.py:352-357 (an action outside the list maps to "Unknown", which must then be in the list)
-        return self.animations.index(action) if action in self.animations else self.animations.index("Unknown")
+        return _action_id(self.animations, action)
 
     def __getitem__(self, idx: int):
         n_per = self.runner.max_frames - 1
