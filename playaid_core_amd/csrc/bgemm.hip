@@ -1,4 +1,5 @@
-// One-slice bf16 form of the persistent implicit-GEMM convolution (psgemm.hip's launcher conventions and loader / consumer split):
+// One-slice bf16 form of the persistent implicit-GEMM convolution (psgemm.hip's launcher conventions and loader / consumer split; the
+// tile schedule, the pixel walk, the issue cursor, the loaders' ring and the weights' stage image are pgemm_common.h's):
 // the detection network's PA_DTYPE_BF16 convolutions -- every 1x1, stride-2 3x3 and stride-1 3x3 row of its table.
 //
 // What changes against psgemm.hip's emulated-fp32 kernel:
@@ -13,14 +14,14 @@
 //     and rounds once to nearest even on the store (8 bytes per lane and 4 channels); the fused 2x up-sampled copy is the same
 //     bf16 value. OUT_F32: the Detect heads' fp32 store instead (no residual, no up-sampling).
 // Loader waves 4-7: per k-step 2 activation pieces (128 rows x 64 bytes = 8 KiB) and BN / 64 weight pieces (at least one) of 1 KiB
-// each, counted waits as in psgemm.hip.
+// each, counted waits (loader_ring).
 //
 // Split-K form (SPLIT, the ResNet-50 table's small maps: launch_bgemm with p.splitk = S > 1): one workgroup per (output tile, k-slice),
 // slice s covering k-steps [s nk / S, (s + 1) nk / S); slice 0's accumulators start from the bias, the others' from zero. Each
 // consumer wave writes its 32 pixels x BN channels of fp32 partials to the slab and draws the ticket of (tile, wave); the last of
 // the S waves to arrive sums the S partials IN SPLIT ORDER (its own read back from the slab as well, so the sum does not depend on
 // who was last), resets the ticket and runs the unsplit epilogue (residual, activation, one rounding on the store).
-#include "pa_kernels.h"
+#include "pgemm_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -34,32 +35,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) const u32x4 lds_cu4;
 typedef __attribute__((address_space(3))) float lds_f;
-
-__device__ __forceinline__ i32x4 bg_rsrc(const void* base, unsigned num_bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32) & 0xffff), (int)num_bytes, 0x00020000};
-}
-
-// 16 bytes per lane, L2 / HBM -> LDS at lds_addr + 16 * lane (psgemm.hip's ps_dma16: M0 written and read in one statement)
-__device__ __forceinline__ void bg_dma16(i32x4 rsrc, int voff_bytes, int soff_bytes, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 :
-                 : "v"(voff_bytes), "s"(rsrc), "s"(soff_bytes), "s"(lds_addr)
-                 : "memory");
-}
-
-__device__ __forceinline__ int bg_sdiv(int n, int d, unsigned magic, int& rem) {   // (psgemm.hip's ps_sdiv)
-    int q = (int)__umulhi((unsigned)n, magic);
-    int r = n - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
 
 // four fp32 values -> four bf16, round to nearest even (v_cvt_pk_bf16_f32), element 0 in the low half of word 0
 __device__ __forceinline__ u32x2 bg_pack4(f32x4 v) {
@@ -91,16 +69,13 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
     constexpr int OE = OUT_F32 ? 4 : 2;           // output element bytes
     __shared__ __attribute__((aligned(1024))) unsigned char lds[NSTAGE * STAGE + BN * 4];
 
-    // --- this workgroup's tiles (psgemm.hip): one channel column, every lm-th pixel tile of its XCD's contiguous share ----
+    // --- this workgroup's tiles: one channel column, every step-th pixel tile of its XCD's contiguous share ----
     // (SPLIT: the one tile w_tile = tile_m * TN + tile_n of workgroup w_tile * S + slice, k-steps ks_lo .. ks_lo + nk - 1)
-    const int b = blockIdx.x, xcd = b & 7, local = b >> 3, per = p.pg_per;
-    const int TN = p.tiles_n, TM = p.tiles_m;
+    const int b = blockIdx.x, TN = p.tiles_n;
     const int S = SPLIT ? p.splitk : 1;
     const int w_tile = SPLIT ? b / S : 0, slice = SPLIT ? b - w_tile * S : 0;
-    const int LM = SPLIT ? 1 : per / TN;
-    const int tile_n = SPLIT ? w_tile % TN : local % TN, lm = SPLIT ? 0 : local / TN;
-    const int t_lo = SPLIT ? w_tile / TN : (int)(((long long)xcd * TM) >> 3), t_hi = SPLIT ? t_lo + 1 : (int)(((long long)(xcd + 1) * TM) >> 3);
-    const int nt = t_lo + lm < t_hi ? (t_hi - t_lo - lm + LM - 1) / LM : 0;
+    const TileRun run = SPLIT ? TileRun{w_tile % TN, w_tile / TN, 1, w_tile / TN + 1, 1} : tile_run(p);
+    const int tile_n = run.tile_n, nt = run.nt;
     if (nt == 0) return;
     const int nk_all = p.ktot >> 5;
     const int ks_lo = SPLIT ? slice * nk_all / S : 0;
@@ -121,101 +96,53 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
         const int lw = wave_id - 4, ltid = tid - 256;
         const int row0 = ltid >> 2;                          // 0..63: four lanes per 64-byte row
         const int colq = (ltid & 3) ^ ((row0 >> 2) & 3);     // LDS chunk c of activation row r holds logical chunk c ^ ((r >> 2) & 3)
-        const i32x4 act_rs = bg_rsrc(p.act, 0xffffffffu);
-        const i32x4 wgt_rs = bg_rsrc(wsp + (size_t)tile_n * nk_all * (B_BYTES / 2), 0xffffffffu);
-        // pixel addressing in bytes (psgemm.hip's, with a lane's distance from the run's first pixel up to 63)
+        const pgemm_i32x4 act_rs = lds_dma_rsrc(p.act, 0xffffffffu);
+        const pgemm_i32x4 wgt_rs = lds_dma_rsrc(wsp + (size_t)tile_n * nk_all * (B_BYTES / 2), 0xffffffffu);
+        // pixel addressing in bytes (pixel_walk, with a lane's distance from the run's first pixel up to 63: its own wrap counts)
         const int in_ps = p.in_px_stride * p.stride * 2, in_rs = p.in_row_stride * p.stride * 2;
         const int in_wrap_x = in_rs - p.wo * in_ps;
         const int in_wrap_y = p.in_img_stride * 2 - p.pg_ho * in_rs;
         const int in_org = (p.off_y * p.in_row_stride + p.off_x * p.in_px_stride) * 2;
-        const int nwx = 1 + 62 / p.wo, nwy = (p.pg_ho - 1 + nwx) / p.pg_ho;
+        PixelGeom geom = pixel_geom(p);
+        geom.nwx = 1 + 62 / p.wo;
+        geom.nwy = (p.pg_ho - 1 + geom.nwx) / p.pg_ho;
         int in_lane = row0 * in_ps + colq * 16;
         asm volatile("" : "+v"(in_lane));
         int in_last;   // pixel M - 1: what the rows past M of a partial last tile read (computed, dropped)
         {
-            int rem, ox;
-            const int img = bg_sdiv(p.M - 1, p.howo, p.pg_magic_howo, rem);
-            const int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox);
-            in_last = img * (p.in_img_stride * 2) + oy * in_rs + ox * in_ps + in_org + colq * 16;
+            int oy, ox;
+            in_last = pixel_base(geom, p.M - 1, p.in_img_stride * 2, in_rs, in_ps, oy, ox) + in_org + colq * 16;
         }
         auto in_offset = [&](int m_base) {
-            int rem, ox_b;
-            const int img_b = bg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-            int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-            int off = img_b * (p.in_img_stride * 2) + oy * in_rs + ox_b * in_ps + in_org + in_lane;
-            int ox = ox_b + row0;
-            for (int w = 0; w < nwx; ++w) {
-                const bool c = ox >= p.wo;
-                ox -= c ? p.wo : 0;
-                off += c ? in_wrap_x : 0;
-                oy += c ? 1 : 0;
-            }
-            for (int w = 0; w < nwy; ++w) {
-                const bool c = oy >= p.pg_ho;
-                oy -= c ? p.pg_ho : 0;
-                off += c ? in_wrap_y : 0;
-            }
+            const int off = pixel_walk(geom, m_base, row0, p.in_img_stride * 2, in_rs, in_ps, in_wrap_x, in_wrap_y, in_org + in_lane);
             return m_base + row0 < p.M ? off : in_last;
         };
-        int i_tile = t_lo + lm, i_ks = ks_lo, i_ky = 0, i_kx = 0, i_kc = 0;
+        IssueCursor cur{run.first, ks_lo, 0, 0, 0};
         if (SPLIT) {   // the slice's first k-step: tap (ky, kx), channel offset kc
             const int k0 = ks_lo * 32, tap = k0 / p.chunk;
-            i_kc = k0 - tap * p.chunk;
-            i_ky = tap / p.kw_taps;
-            i_kx = tap - i_ky * p.kw_taps;
+            cur.kc = k0 - tap * p.chunk;
+            cur.ky = tap / p.kw_taps;
+            cur.kx = tap - cur.ky * p.kw_taps;
         }
         int a_off[2];
         auto rows_of = [&](int tile_m) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) a_off[i] = in_offset(tile_m * BM + 64 * i);
         };
-        rows_of(i_tile);
+        rows_of(cur.tile);
         int b_lane = lw * PB * 1024 + lane * 16;
         asm volatile("" : "+v"(b_lane));
         auto issue = [&](int slot) {
             const unsigned sb = lds_base + slot * STAGE;
-            const int tapoff = (i_ky * p.in_row_stride + i_kx * p.in_px_stride + i_kc) * 2;
+            const int tapoff = cur.tap_offset(p) * 2;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) bg_dma16(act_rs, a_off[i], tapoff, sb + lw * 1024 + i * 4096);
-            const int koff = i_ks * B_BYTES;
+            for (int i = 0; i < 2; ++i) lds_dma16(act_rs, a_off[i], tapoff, sb + lw * 1024 + i * 4096);
+            const int koff = cur.ks * B_BYTES;
 #pragma unroll
-            for (int j = 0; j < PB; ++j) bg_dma16(wgt_rs, b_lane, koff + j * 1024, sb + A_BYTES + (lw * PB + j) * 1024);
-            i_kc += 32;
-            if (i_kc == p.chunk) {
-                i_kc = 0;
-                if (++i_kx == p.kw_taps) { i_kx = 0; ++i_ky; }
-            }
-            if (++i_ks == ks_lo + nk) {   // (SPLIT: behind the slice's last issue; nothing is issued after it)
-                i_ks = 0; i_ky = 0; i_kx = 0; i_kc = 0;
-                i_tile += LM;
-                rows_of(i_tile < t_hi ? i_tile : t_hi - 1);
-            }
+            for (int j = 0; j < PB; ++j) lds_dma16(wgt_rs, b_lane, koff + j * 1024, sb + A_BYTES + (lw * PB + j) * 1024);
+            cur.advance(p, ks_lo + nk, run, rows_of);   // (SPLIT: past the slice's last k-step nothing is issued)
         };
-        // in front of barrier g + 1 exactly the copies of the (at most NSTAGE - 2) stages issued after stage g + 1 may be outstanding
-        auto wait_stage = [&](int younger) {
-            if (NSTAGE >= 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NLD) : "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        };
-        static_assert(NSTAGE >= 2 && NSTAGE <= 4, "wait_stage covers rings of two to four stages");
-        int slot = 0;
-#pragma unroll
-        for (int s = 0; s < NSTAGE; ++s)
-            if (s < total) issue(s);
-        {
-            const int younger = (total < NSTAGE ? total : NSTAGE) - 1;
-            if (younger >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NLD) : "memory");
-            else wait_stage(younger);
-        }
-        __builtin_amdgcn_s_barrier();   // stage 0 (and bias_s) in LDS
-        for (int g = 0; g + 1 < total; ++g) {
-            const int inflight = (g + NSTAGE < total ? g + NSTAGE : total) - (g + 2);
-            wait_stage(inflight);
-            __builtin_amdgcn_s_barrier();   // stage g + 1 landed; every consumer's reads of stage g have returned
-            if (g + NSTAGE < total) issue(slot);
-            slot = slot + 1 == NSTAGE ? 0 : slot + 1;
-        }
-        __builtin_amdgcn_s_barrier();   // (the consumers' barrier of the last k-step)
+        loader_ring<NSTAGE, NLD>(total, issue);
         return;
     }
 
@@ -223,54 +150,24 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
     const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)out_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t res_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.residual : p.out), 0, (int)out_bytes, 0x00020000);
     const int ch0 = tile_n * BN + 4 * lh;
-    const int nwx = p.pg_nwx, nwy = p.pg_nwy;
+    const PixelGeom geom = pixel_geom(p);
     // output, in BYTES: O(m) = (img * OIS + (oy + pad) * ORS + (ox + pad) * OPS + ch0) * OE
     const int out_wrap_x = (p.out_row_stride - p.wo * p.out_px_stride) * OE;
     const int out_wrap_y = (p.out_img_stride - p.pg_ho * p.out_row_stride) * OE;
     int out_lane = (lr * p.out_px_stride + p.out_pad * (p.out_row_stride + p.out_px_stride) + ch0) * OE;
     asm volatile("" : "+v"(out_lane));
     auto out_offset = [&](int m_base) -> unsigned {
-        int rem, ox_b;
-        const int img_b = bg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-        int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-        int off = (img_b * p.out_img_stride + oy * p.out_row_stride + ox_b * p.out_px_stride) * OE + out_lane;
-        int ox = ox_b + lr;
-        for (int w = 0; w < nwx; ++w) {
-            const bool c = ox >= p.wo;
-            ox -= c ? p.wo : 0;
-            off += c ? out_wrap_x : 0;
-            oy += c ? 1 : 0;
-        }
-        for (int w = 0; w < nwy; ++w) {
-            const bool c = oy >= p.pg_ho;
-            oy -= c ? p.pg_ho : 0;
-            off += c ? out_wrap_y : 0;
-        }
+        const int off = pixel_walk(geom, m_base, lr, p.out_img_stride * OE, p.out_row_stride * OE, p.out_px_stride * OE, out_wrap_x, out_wrap_y, out_lane);
         return m_base + lr < p.M ? (unsigned)off : 0x80000000u;   // past M: beyond num_records, dropped
     };
-    // the nearest-neighbour x2 up-sampled copy (psgemm.hip): the same walk with doubled row and pixel strides, bf16
+    // the nearest-neighbour x2 up-sampled copy: the same walk with doubled row and pixel strides, bf16
     const __amdgpu_buffer_rsrc_t up_rs = __builtin_amdgcn_make_buffer_rsrc(p.up_out ? p.up_out : p.out, 0, (int)(p.up_out ? up_bytes : out_bytes), 0x00020000);
     const int up_rs_b = 2 * p.up_row_stride * 2, up_ps_b = 2 * p.up_px_stride * 2;
     const int up_wrap_x = up_rs_b - p.wo * up_ps_b, up_wrap_y = p.up_img_stride * 2 - p.pg_ho * up_rs_b;
     int up_lane = lr * up_ps_b + (p.up_pad * (p.up_row_stride + p.up_px_stride) + ch0) * 2;
     asm volatile("" : "+v"(up_lane));
     auto up_offset = [&](int m_base) -> unsigned {
-        int rem, ox_b;
-        const int img_b = bg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-        int oy = bg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-        int off = img_b * p.up_img_stride * 2 + oy * up_rs_b + ox_b * up_ps_b + up_lane;
-        int ox = ox_b + lr;
-        for (int w = 0; w < nwx; ++w) {
-            const bool c = ox >= p.wo;
-            ox -= c ? p.wo : 0;
-            off += c ? up_wrap_x : 0;
-            oy += c ? 1 : 0;
-        }
-        for (int w = 0; w < nwy; ++w) {
-            const bool c = oy >= p.pg_ho;
-            oy -= c ? p.pg_ho : 0;
-            off += c ? up_wrap_y : 0;
-        }
+        const int off = pixel_walk(geom, m_base, lr, p.up_img_stride * 2, up_rs_b, up_ps_b, up_wrap_x, up_wrap_y, up_lane);
         return m_base + lr < p.M ? (unsigned)off : 0x80000000u;
     };
 
@@ -331,7 +228,7 @@ __global__ __launch_bounds__(512, 2) void bgemm_kernel(const GemmParams p, const
     // matrix instructions of this one run. Every k-step of every tile, one barrier each (the loaders' count).
     auto step = [&](const u32x4 (&ca)[2], const u32x4 (&cw)[CB][2], u32x4 (&na)[2], u32x4 (&nw)[CB][2]) {
         if (ks == 0) {
-            const int tile_m = t_lo + lm + t * LM;
+            const int tile_m = run.tile(t);
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
@@ -421,49 +318,20 @@ int bgemm_pick_bn(int N, int residual) { return psgemm_pick_bn(N, residual); }
 
 size_t bgemm_weight_elems(int N, int ktot, int residual) {
     const int bn = bgemm_pick_bn(N, residual);
-    if (bn == 0 || ktot % 32 != 0 || N <= 0 || ktot <= 0) return 0;
-    return (size_t)(N / bn) * (ktot / 32) * (bg_b_pieces(bn) * 512);
+    return stage_weight_elems(N, ktot, bn, bg_b_pieces(bn));
 }
 
-static inline unsigned short bg_bf16_rne(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)(u >> 16);   // inf / nan: truncate
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
-// w [N][ktot] fp32 (K contiguous, BatchNorm folded) -> one RNE bf16 plane in the kernel's stage images:
-// [tile_n][k-step][row r][chunk c'][8], chunk c' of row r holding k 8 (c' ^ ((r >> 2) & 3)) .. + 7 (32-channel tiles: + 2 KiB of zeros)
+// w [N][ktot] fp32 (K contiguous, BatchNorm folded) -> one RNE bf16 plane in the kernel's stage images (32-channel tiles: + 2 KiB of zeros)
 void bgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned short* out) {
-    const int bn = bgemm_pick_bn(N, residual), nk = ktot / 32, tn_n = N / bn;
-    const size_t stage = (size_t)bg_b_pieces(bn) * 512;   // elements
-    memset(out, 0, bgemm_weight_elems(N, ktot, residual) * sizeof(unsigned short));
-    for (int tn = 0; tn < tn_n; ++tn)
-        for (int ks = 0; ks < nk; ++ks) {
-            unsigned short* img = out + ((size_t)tn * nk + ks) * stage;
-            for (int r = 0; r < bn; ++r)
-                for (int c = 0; c < 4; ++c) {
-                    const int cp = c ^ ((r >> 2) & 3);
-                    for (int j = 0; j < 8; ++j) img[((size_t)r * 4 + cp) * 8 + j] = bg_bf16_rne(w[(size_t)(tn * bn + r) * ktot + ks * 32 + c * 8 + j]);
-                }
-        }
-}
-
-// workgroups per XCD of the unsplit persistent grid over tiles_m x tiles_n tiles (the grid is 8 x that): one channel column each,
-// lm pixel tiles of its XCD's share in turn, about 32 per XCD. launch_bgemm launches it; bgemm_pick_split judges it.
-static int bg_unsplit_per(int tiles_m, int tiles_n) {
-    const int share = (tiles_m + 7) / 8;
-    int lm = 32 / tiles_n;
-    lm = lm < 1 ? 1 : (lm > share ? share : lm);
-    return lm * tiles_n;
+    const int bn = bgemm_pick_bn(N, residual);
+    pack_stage_weights(w, N, ktot, bn, 1, bg_b_pieces(bn), out);
 }
 
 int bgemm_pick_split(const GemmParams& p, int force) {
     const int bn = bgemm_pick_bn(p.N, p.residual != nullptr);
     if (bn == 0 || p.M <= 0 || force == 0 || force == 1) return 1;
     const int tn = p.N / bn, tm = (p.M + 127) / 128;
-    const int grid = 8 * bg_unsplit_per(tm, tn);   // the unsplit grid launch_bgemm would launch
+    const int grid = 8 * unsplit_per(tm, tn);   // the unsplit grid launch_bgemm would launch
     if (grid >= 128) return 1;   // at least half the CUs (256 on an MI355X) busy
     const int tiles = tm * tn, nk = p.ktot / 32;
     auto fits = [&](int S) { return tiles * S <= BGEMM_SLAB_ITEMS && 4 * tiles <= BGEMM_TICKETS && nk / S >= 4; };
@@ -487,9 +355,7 @@ int bgemm_pick_split(const GemmParams& p, int force) {
 hipError_t launch_bgemm(const GemmParams& p_in, const unsigned short* wsp, size_t out_elems, size_t up_elems, bool out_f32, hipStream_t s) {
     GemmParams p = p_in;
     const int bn = bgemm_pick_bn(p.N, p.residual != nullptr);
-    if (p.gather || p.k2_steps || bn == 0 || p.chunk % 32 != 0 || p.M <= 0 || p.M >= (1 << 24) || p.howo <= 0 || p.howo >= (1 << 16) ||
-        p.ktot != p.taps * p.chunk || !wsp || out_elems == 0 || p.howo % p.wo != 0 || (out_f32 && (p.residual || p.up_out)))
-        return hipErrorInvalidValue;
+    if (bn == 0 || !wsp || out_elems == 0 || (out_f32 && (p.residual || p.up_out)) || persistent_plan(p) != hipSuccess) return hipErrorInvalidValue;
     const unsigned long long oe = out_f32 ? 4 : 2;
     const unsigned long long images = (unsigned long long)((p.M + p.howo - 1) / p.howo);
     // the input span the loaders address with int byte offsets: every image of the range, its border and channel slice included
@@ -500,15 +366,8 @@ hipError_t launch_bgemm(const GemmParams& p_in, const unsigned short* wsp, size_
         return hipErrorInvalidValue;
     p.tiles_n = p.N / bn;
     p.tiles_m = (p.M + 127) / 128;
-    const int per = bg_unsplit_per(p.tiles_m, p.tiles_n);
-    const int grid = per * 8;
-    auto magic = [](int d) { return (unsigned)std::min<unsigned long long>(((1ull << 32) + d - 1) / d, 0xffffffffull); };
-    p.pg_per = per;
-    p.pg_ho = p.howo / p.wo;
-    p.pg_magic_howo = magic(p.howo);
-    p.pg_magic_wo = magic(p.wo);
-    p.pg_nwx = 1 + 30 / p.wo;
-    p.pg_nwy = (p.pg_ho - 1 + p.pg_nwx) / p.pg_ho;
+    p.pg_per = unsplit_per(p.tiles_m, p.tiles_n);
+    const int grid = p.pg_per * 8;
     const unsigned out_bytes = (unsigned)(out_elems * oe), up_bytes = (unsigned)(up_elems * 2);
     if (p.splitk > 1) {
         // split-K: workgroup w_tile * S + slice; the slab holds BGEMM_SLAB_ITEMS workgroups, the tickets 4 per tile

@@ -8,10 +8,11 @@
 
 namespace pa {
 
-// fp32 -> bf16, round to nearest even (host side: weights at create)
+// fp32 -> bf16, round to nearest even (host side: weights at create); inf and NaN by truncation (a quiet NaN stays one)
 inline unsigned short bf16_rne(float x) {
     uint32_t u;
     memcpy(&u, &x, 4);
+    if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)(u >> 16);
     u += 0x7fffu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }

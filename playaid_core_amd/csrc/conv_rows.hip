@@ -1,5 +1,7 @@
-// conv_rows.h: a table's convolution row -> launch parameters, and the per-form weight planes. Host code only.
+// conv_rows.h: a table's convolution row -> launch parameters, and the per-form weight planes; behind them the single-layer
+// convolution operator of the C ABI (pa_conv2d) on the persistent GEMM kernels. Host code only.
 #include "conv_rows.h"
+#include "../../include/playaid_hip.h"
 
 namespace pa {
 
@@ -111,3 +113,51 @@ hipError_t FormWeights::prepare(const std::vector<FormRow>& rows, const float* b
 }
 
 }  // namespace pa
+
+extern "C" {
+
+size_t pa_conv_weight_bytes(int32_t cin, int32_t cout, int32_t ksize, int32_t compute_dtype, int32_t has_residual) {
+    if (cin <= 0 || cout <= 0 || (ksize != 1 && ksize != 3) || cin % 32 != 0 || cout % 32 != 0) return 0;
+    if (compute_dtype == PA_DTYPE_F32) return (size_t)cout * ksize * ksize * cin * sizeof(float);
+    if (compute_dtype == PA_DTYPE_EMULATED_F32) return pa::psgemm_weight_elems(cout, ksize * ksize * cin, has_residual) * sizeof(unsigned short);
+    return 0;
+}
+
+int pa_conv_pack_weights(const float* w_host, int32_t cin, int32_t cout, int32_t ksize, int32_t compute_dtype, int32_t has_residual, void* out_host) {
+    const size_t bytes = pa_conv_weight_bytes(cin, cout, ksize, compute_dtype, has_residual);
+    if (!w_host || !out_host || bytes == 0) return PA_ERR_INVALID_ARG;
+    if (compute_dtype == PA_DTYPE_F32) memcpy(out_host, w_host, bytes);
+    else pa::psgemm_pack_weights(w_host, cout, ksize * ksize * cin, has_residual, static_cast<unsigned short*>(out_host));
+    return PA_OK;
+}
+
+int pa_conv2d(const float* x, const void* w, const float* bias, const float* residual, float* out, int32_t n, int32_t height, int32_t width, int32_t cin,
+              int32_t cout, int32_t ksize, int32_t stride, int32_t in_pad, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad, int32_t act,
+              int32_t res_after, int32_t compute_dtype, void* stream) {
+    if (!x || !w || !out || n <= 0 || height <= 0 || width <= 0 || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || height % stride || width % stride ||
+        in_pad < (ksize - 1) / 2 || in_px_stride < cin || out_px_stride < cout || out_pad < 0 || act < 0 || act > 2 ||
+        pa_conv_weight_bytes(cin, cout, ksize, compute_dtype, residual != nullptr) == 0)
+        return PA_ERR_INVALID_ARG;
+    // 16-byte units: the loaders' LDS-DMA reads and the epilogue's dwordx4 stores / residual loads move four floats at an address
+    auto misaligned = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) != 0; };
+    if (in_px_stride % 4 || out_px_stride % 4 || misaligned(x) || misaligned(w) || misaligned(out) || misaligned(residual) ||
+        (reinterpret_cast<unsigned long long>(bias) & 3ull))
+        return PA_ERR_INVALID_ARG;
+    const int oh = height / stride, ow = width / stride;
+    const int in_wb = width + 2 * in_pad, in_hb = height + 2 * in_pad, out_wb = ow + 2 * out_pad, out_hb = oh + 2 * out_pad;
+    if ((long long)n * in_hb * in_wb * in_px_stride >= (1ll << 29) || (long long)n * out_hb * out_wb * out_px_stride >= (1ll << 29)) return PA_ERR_CAPACITY;
+    pa::GemmParams p = pa::conv_row_params({/*images*/ n, /*in h, w, pad, px stride*/ height, width, in_pad, in_px_stride, /*cin, cout, ksize, stride*/ cin, cout, ksize, stride,
+                                            /*out pad, px stride*/ out_pad, out_px_stride, /*act, res_after*/ act, res_after});
+    p.act = x;
+    p.wgt = static_cast<const float*>(w);
+    p.bias = bias;
+    p.residual = residual;
+    p.out = out;
+    hipError_t e;
+    if (compute_dtype == PA_DTYPE_EMULATED_F32) e = pa::launch_psgemm(p, static_cast<const unsigned short*>(w), (size_t)n * p.out_img_stride, 0, static_cast<hipStream_t>(stream));
+    else if (residual) return PA_ERR_INVALID_ARG;   // (the exact persistent kernel has no residual epilogue: Winograd / the patch kernel take those layers)
+    else e = pa::launch_pgemm(p, 0, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? PA_OK : (e == hipErrorInvalidValue ? PA_ERR_INVALID_ARG : PA_ERR_HIP);
+}
+
+}  // extern "C"

@@ -51,7 +51,7 @@ struct GemmParams {
     int32_t* splitk_used;
     int32_t skip_w;         // 1: k % 4 == 3 always meets a zero weight (stem channel pad): those MFMAs are skipped
     int32_t tiles_m, tiles_n;
-    // persistent GEMM (pigemm.hip), filled by its launcher: workgroups per XCD, output rows per image, ceil(2^32 / howo) and
+    // persistent GEMMs (pgemm_common.h), filled by persistent_plan and the launchers: workgroups per XCD, output rows per image, ceil(2^32 / howo) and
     // ceil(2^32 / wo) for the scalar divisions, how often 31 consecutive pixels can wrap a row / that many rows an image
     // (beside tiles_m / tiles_n: the kernel's first scalar loads fetch them together)
     int32_t pg_per, pg_ho, pg_nwx, pg_nwy;

@@ -14,7 +14,8 @@
 //     stores run straight from the accumulators -- no transposition, no barrier, nothing between two tiles but the stores.
 // Same k order as igemm.hip (tap, channel chunk, eight-wide group, lane half); the bias is the value the accumulators start
 // from instead of a last addition, so results agree with igemm.hip to the rounding of that one reordering.
-#include "pa_kernels.h"
+// The tile schedule, the pixel walk and the issue cursor are pgemm_common.h's, shared with psgemm.hip and bgemm.hip.
+#include "pgemm_common.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -39,17 +40,6 @@ __device__ __forceinline__ void pg_dma16(__amdgpu_buffer_rsrc_t rsrc, int voff_b
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voff_bytes, soff_bytes, 0, 0);
 }
 
-// n / d and the remainder for a WAVE-UNIFORM 0 <= n < 2^25 with magic = min(ceil(2^32 / d), 2^32 - 1), 1 <= d < 2^16: the
-// estimate is off by at most one either way (n * (magic * d - 2^32) < 2^32 * d * 2^-7); everything on the scalar unit
-__device__ __forceinline__ int pg_sdiv(int n, int d, unsigned magic, int& rem) {
-    int q = (int)__umulhi((unsigned)n, magic);
-    int r = n - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
-
 // (vmcnt is six bits: a count past 63 waits at 63 -- for more than it must, never for less)
 template <int N> __device__ __forceinline__ void pg_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N > 63 ? 63 : N) : "memory"); }
 
@@ -62,7 +52,7 @@ template <int N> __device__ __forceinline__ void pg_wait_vm() { asm volatile("s_
 // v_mfma_f32_32x32x2_f32 an LDS read is free, a lone vector instruction costs ~12 cycles of the SIMD, a transcendental 16 (and
 // v_mul_lo_u32, which the per-lane divisions were made of, is a quarter-rate instruction too) -- so the bookkeeping is kept off
 // the vector unit:
-//   * pixel index -> (image, row, column) of the tile's FIRST pixel on the scalar unit (pg_sdiv); a lane adds its pixel's
+//   * pixel index -> (image, row, column) of the tile's FIRST pixel on the scalar unit (pgemm_sdiv); a lane adds its pixel's
 //     distance and folds the row / image wraps in with compares and selects (no multiply, no division per lane);
 //   * a k-step's copies differ from the tile's first in a scalar byte offset only (buffer_load's soffset);
 //   * the LDS read addresses of a k-step are eight adds in one burst (a burst costs about what a lone instruction does);
@@ -89,13 +79,9 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     constexpr int STAGE = (BM + BN) * 32;
     __shared__ __attribute__((aligned(16))) float lds[3 * STAGE];
 
-    // --- this workgroup's tiles: one channel column, every lm-th pixel tile of its XCD's contiguous share -------------
-    const int b = blockIdx.x, xcd = b & 7, local = b >> 3, per = p.pg_per;
-    const int TN = p.tiles_n, TM = p.tiles_m;
-    const int LM = per / TN;  // workgroups per XCD and channel column (the launcher makes per a multiple of TN)
-    const int tile_n = local % TN, lm = local / TN;
-    const int t_lo = (int)(((long long)xcd * TM) >> 3), t_hi = (int)(((long long)(xcd + 1) * TM) >> 3);
-    const int nt = t_lo + lm < t_hi ? (t_hi - t_lo - lm + LM - 1) / LM : 0;
+    // --- this workgroup's tiles: one channel column, every step-th pixel tile of its XCD's contiguous share -------------
+    const TileRun run = tile_run(p);
+    const int tile_n = run.tile_n, nt = run.nt;
     {   // the arguments the loop needs are asked for BEFORE the early exit below: one round trip of scalar loads instead of two
         const float *pa_ = p.act, *pw_ = p.wgt, *pb_ = p.bias;
         float* po_ = p.out;
@@ -137,31 +123,14 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     const int in_org = (p.off_y * p.in_row_stride + p.off_x * p.in_px_stride) * 4;
     int in_lane = row0 * in_ps + colq * 16;
     asm volatile("" : "+v"(in_lane));   // (kept as a register: the compiler would fold it back into a per-tile multiply)
+    const PixelGeom geom = pixel_geom(p);
     int in_last;   // pixel M - 1: what the rows past M of a partial last tile read (computed, dropped)
     {
-        int rem, ox;
-        const int img = pg_sdiv(p.M - 1, p.howo, p.pg_magic_howo, rem);
-        const int oy = pg_sdiv(rem, p.wo, p.pg_magic_wo, ox);
-        in_last = img * (p.in_img_stride * 4) + oy * in_rs + ox * in_ps + in_org + colq * 16;
+        int oy, ox;
+        in_last = pixel_base(geom, p.M - 1, p.in_img_stride * 4, in_rs, in_ps, oy, ox) + in_org + colq * 16;
     }
-    const int nwx = p.pg_nwx, nwy = p.pg_nwy;   // most row wraps over 31 pixels, most image wraps over that many rows
     auto in_offset = [&](int m_base) {   // byte offset of this lane's row of the 32-pixel run starting at the uniform m_base
-        int rem, ox_b;
-        const int img_b = pg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-        int oy = pg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-        int off = img_b * (p.in_img_stride * 4) + oy * in_rs + ox_b * in_ps + in_org + in_lane;
-        int ox = ox_b + row0;
-        for (int w = 0; w < nwx; ++w) {
-            const bool c = ox >= p.wo;
-            ox -= c ? p.wo : 0;
-            off += c ? in_wrap_x : 0;
-            oy += c ? 1 : 0;
-        }
-        for (int w = 0; w < nwy; ++w) {
-            const bool c = oy >= p.pg_ho;
-            oy -= c ? p.pg_ho : 0;
-            off += c ? in_wrap_y : 0;
-        }
+        const int off = pixel_walk(geom, m_base, row0, p.in_img_stride * 4, in_rs, in_ps, in_wrap_x, in_wrap_y, in_org + in_lane);
         return m_base + row0 < p.M ? off : in_last;
     };
     // output, in floats: O(m) = img * OIS + (oy + pad) * ORS + (ox + pad) * OPS + ch0
@@ -169,60 +138,31 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     const int out_wrap_y = p.out_img_stride - p.pg_ho * p.out_row_stride;
     int out_lane = lr * p.out_px_stride + p.out_pad * (p.out_row_stride + p.out_px_stride) + ch0;
     asm volatile("" : "+v"(out_lane));
-    // offset of this lane's pixel of the 32-pixel run at m_base in a buffer whose pixel (img, oy, ox) sits at img * is + oy * rs + ox * ps
-    auto pix_offset = [&](int m_base, int is, int rs, int ps, int wrap_x, int wrap_y, int lane_const) {
-        int rem, ox_b;
-        const int img_b = pg_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-        int oy = pg_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-        int off = img_b * is + oy * rs + ox_b * ps + lane_const;
-        int ox = ox_b + lr;
-        for (int w = 0; w < nwx; ++w) {
-            const bool c = ox >= p.wo;
-            ox -= c ? p.wo : 0;
-            off += c ? wrap_x : 0;
-            oy += c ? 1 : 0;
-        }
-        for (int w = 0; w < nwy; ++w) {
-            const bool c = oy >= p.pg_ho;
-            oy -= c ? p.pg_ho : 0;
-            off += c ? wrap_y : 0;
-        }
-        return off;
-    };
-    auto out_offset = [&](int m_base) { return pix_offset(m_base, p.out_img_stride, p.out_row_stride, p.out_px_stride, out_wrap_x, out_wrap_y, out_lane); };
+    auto out_offset = [&](int m_base) { return pixel_walk(geom, m_base, lr, p.out_img_stride, p.out_row_stride, p.out_px_stride, out_wrap_x, out_wrap_y, out_lane); };
     // the up-sampled copy: pixel (oy, ox) -> (2 oy, 2 ox) .. (2 oy + 1, 2 ox + 1): the same walk with doubled row and pixel strides
     const int up_rs = 2 * p.up_row_stride, up_ps = 2 * p.up_px_stride;
     const int up_wrap_x = up_rs - p.wo * up_ps, up_wrap_y = p.up_img_stride - p.pg_ho * up_rs;
     int up_lane = lr * up_ps + p.up_pad * (p.up_row_stride + p.up_px_stride) + ch0;
     asm volatile("" : "+v"(up_lane));
-    // issue cursor: tile, its row offsets, (ky, kx, kc) of its next k-step
-    int i_tile = t_lo + lm, i_ks = 0, i_ky = 0, i_kx = 0, i_kc = 0;
+    // issue cursor: tile, (ky, kx, kc) of its next k-step; the tile's row offsets
+    IssueCursor cur{run.first, 0, 0, 0, 0};
     int a_off[A_ROWS];   // bytes
     auto rows_of = [&](int tile_m) {
 #pragma unroll
         for (int i = 0; i < A_ROWS; ++i) a_off[i] = in_offset(tile_m * BM + 32 * i);
     };
-    rows_of(i_tile);
+    rows_of(cur.tile);
     stamp(61);
     auto issue = [&](int slot) {
         float* As_w = lds + slot * STAGE + wave_id * 256;
         float* Bs_w = As_w + BM * 32;
-        const int tapoff = (i_ky * p.in_row_stride + i_kx * p.in_px_stride + i_kc) * 4;
+        const int tapoff = cur.tap_offset(p) * 4;
 #pragma unroll
         for (int i = 0; i < A_ROWS; ++i) pg_dma16(act_rs, a_off[i], tapoff, As_w + i * 1024);
-        const int koff = ((i_ky * p.kw_taps + i_kx) * p.chunk + i_kc) * 4;
+        const int koff = ((cur.ky * p.kw_taps + cur.kx) * p.chunk + cur.kc) * 4;
 #pragma unroll
         for (int i = 0; i < B_ROWS; ++i) pg_dma16(wgt_rs, b_off[i], koff, Bs_w + i * 1024);
-        i_kc += 32;
-        if (i_kc == p.chunk) {
-            i_kc = 0;
-            if (++i_kx == p.kw_taps) { i_kx = 0; ++i_ky; }
-        }
-        if (++i_ks == nk) {  // on to the workgroup's next tile (past the last one: rows of a tile nobody computes; never issued)
-            i_ks = 0; i_ky = 0; i_kx = 0; i_kc = 0;
-            i_tile += LM;
-            rows_of(i_tile < t_hi ? i_tile : t_hi - 1);
-        }
+        cur.advance(p, nk, run, rows_of);
     };
 
     // LDS read addresses of the four eight-wide k groups within a stage (bytes; the 32-row block is an immediate of the read)
@@ -323,7 +263,7 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     // (a wave's LDS reads of a stage are complete before it reaches the next barrier, behind which the stage is overwritten:
     // every one of them fed a matrix instruction)
     for (int t = 0; t < nt; ++t) {
-        const int tile_m = t_lo + lm + t * LM;
+        const int tile_m = run.tile(t);
         if (t < 15) stamp(2 + 4 * t);
         pre(0, t);
         kstep(slot * (STAGE * 4), std::true_type{});
@@ -358,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
                 // (rows past M of a partial last tile were computed on pixel M - 1 and are dropped)
                 // INVARIANT the counted waits rely on: a wave whose rows are all past M issues NO stores here (hipcc branches
                 // around them), so its vmcnt(NLD + k * NST) would under-wait if another k-step of this workgroup followed. None
-                // does: a workgroup walks its tiles in ASCENDING order (t_lo + lm, + LM, ...) and only the launch's last tile
+                // does: a workgroup walks its tiles in ASCENDING order (TileRun: first, + step, ...) and only the launch's last tile
                 // (tiles_m - 1) can be partial, so a partial tile is always the last thing its workgroup computes. Any other
                 // tile order must first make the store count independent of the predicate (launch_pgemm checks the premise). That the
                 // compiler emits exactly NST 16-byte stores per tile is checked on the built object
@@ -368,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
                 if (UP) { out4[gq] = f32x4{lo.x, lo.y, hi.x, hi.y}; }
             }
             if (UP && live) {   // (a launch with an up-sampled copy has no partial tile followed by a k-step either: same invariant)
-                float* u_px = p.up_out + pix_offset(m_base, p.up_img_stride, up_rs, up_ps, up_wrap_x, up_wrap_y, up_lane);
+                float* u_px = p.up_out + pixel_walk(geom, m_base, lr, p.up_img_stride, up_rs, up_ps, up_wrap_x, up_wrap_y, up_lane);
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     float* u = u_px + (q4 >> 1) * p.up_row_stride + (q4 & 1) * p.up_px_stride;
@@ -385,9 +325,7 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
 // Conv mode of GemmParams (no gather, no second source, no residual, no split-K); bm = 128 | 64 | 0 (chosen here).
 hipError_t launch_pgemm(const GemmParams& p_in, int bm, hipStream_t s) {
     GemmParams p = p_in;
-    if (p.gather || p.k2_steps || p.residual || p.chunk % 32 != 0 || p.N % 32 != 0 || p.M <= 0 || p.M >= (1 << 24) || p.howo >= (1 << 16) ||
-        p.ktot != p.taps * p.chunk || (bm != 128 && bm != 64 && bm != 0))
-        return hipErrorInvalidValue;
+    if (p.residual || p.N % 32 != 0 || (bm != 128 && bm != 64 && bm != 0) || persistent_plan(p) != hipSuccess) return hipErrorInvalidValue;
     const int bn = p.N % 64 == 0 ? 64 : 32;   // 32: output channels that are not a multiple of 64 (128-row tiles only)
     if (bn == 32) bm = 128;
     p.tiles_n = p.N / bn;
@@ -417,15 +355,7 @@ hipError_t launch_pgemm(const GemmParams& p_in, int bm, hipStream_t s) {
     if ((long long)(p.tiles_m - 1) * bm >= p.M || (long long)p.tiles_m * bm < p.M) return hipErrorInvalidValue;
     const int per = lm * p.tiles_n;
     const int grid = per * 8;
-    // the kernel's pixel arithmetic (pg_sdiv and the wrap loops)
-    auto magic = [](int d) { return (unsigned)std::min<unsigned long long>(((1ull << 32) + d - 1) / d, 0xffffffffull); };
-    if (p.howo % p.wo != 0 || p.howo >= (1 << 16)) return hipErrorInvalidValue;
     p.pg_per = per;
-    p.pg_ho = p.howo / p.wo;
-    p.pg_magic_howo = magic(p.howo);
-    p.pg_magic_wo = magic(p.wo);
-    p.pg_nwx = 1 + 30 / p.wo;                         // column c + 31 <= wo - 1 + 31 wraps at most this often
-    p.pg_nwy = (p.pg_ho - 1 + p.pg_nwx) / p.pg_ho;    // and row r + nwx that often
     const bool silu = p.relu == 2;
     // diagnostic: PA_PG_STAMP_FILE=<path> PA_PG_STAMP_SHAPE=M,K,N [PA_PG_STAMP_SKIP=n]: the (n + 1)-th launch of that shape runs
     // the stamped kernel and its per-wave clock stamps are written to the file (synchronises; scripts/pgemm_stamps.py)

@@ -12,7 +12,8 @@
 // This is the reference's arithmetic (playaid/ai_runner.py:191-224's network, cnn_action_detector.py:29-43) to fp32 rounding,
 // never the default: compute_dtype PA_DTYPE_EMULATED_F32 selects it, `value` / `dtype` of bench.py stay on the exact path.
 //
-// Layout of the work (pigemm.hip's persistent scheme, re-cut for a matrix pipe that is 2.7x faster):
+// Layout of the work (pigemm.hip's persistent scheme, re-cut for a matrix pipe that is 2.7x faster; the tile schedule, the pixel
+// walk, the issue cursor and the loaders' ring are pgemm_common.h's, shared with pigemm.hip and bgemm.hip):
 //   * 512 threads, ONE workgroup per CU: waves 0-3 CONSUME (LDS reads, split, matrix instructions, epilogue), waves 4-7 LOAD (every
 //     LDS-DMA copy, the pixel address arithmetic, the counted waits) -- one of each per SIMD. A tile is 128 pixels x BN channels
 //     (BN = 128 | 64 | 32) and consumer wave w owns pixels 32 w .. 32 w + 31 x ALL BN channels: every activation value is split
@@ -39,7 +40,7 @@
 //     handed to the loader waves through 64 KB of LDS staging, and stores transposed to whole cache lines -- same speed and 5-15 %
 //     slower: on the short-K layers the stores cost their bytes, 4.6 TB/s of mixed traffic, not issue slots.
 //     profiles/r06_pgemm_split_defer.txt)
-#include "pa_kernels.h"
+#include "pgemm_common.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -61,36 +62,10 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) const f32x4 lds_cf4;
 typedef __attribute__((address_space(3))) const u32x4 lds_cu4;
 typedef __attribute__((address_space(3))) float lds_f;
-
-__device__ __forceinline__ i32x4 ps_rsrc(const void* base, unsigned num_bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32) & 0xffff), (int)num_bytes, 0x00020000};
-}
-
-// 16 bytes per lane, L2 / HBM -> LDS at lds_addr + 16 * lane (buffer_load_dwordx4 ... lds; M0 = destination). As inline assembly
-// (wino.hip's reasons): hipcc then knows nothing of these copies and the kernel's own counted waits are the only ones. M0 is written
-// and read in the SAME statement (it is compiler-reserved and cannot be declared; nothing else here lives in it: tests/test_abi.py).
-__device__ __forceinline__ void ps_dma16(i32x4 rsrc, int voff_bytes, int soff_bytes, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 :
-                 : "v"(voff_bytes), "s"(rsrc), "s"(soff_bytes), "s"(lds_addr)
-                 : "memory");
-}
-
-// n / d and the remainder for a WAVE-UNIFORM 0 <= n < 2^25 (pigemm.hip's pg_sdiv)
-__device__ __forceinline__ int ps_sdiv(int n, int d, unsigned magic, int& rem) {
-    int q = (int)__umulhi((unsigned)n, magic);
-    int r = n - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-    rem = r;
-    return q;
-}
 
 __device__ __forceinline__ unsigned ps_cvt_pk_bf16(float a, float b) {   // (lo = a, hi = b), round to nearest even
     unsigned r;
@@ -154,13 +129,9 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
     constexpr int NM = 6 * CB;                    // matrix instructions per half k-step
     __shared__ __attribute__((aligned(1024))) unsigned char lds[NSTAGE * STAGE + BN * 4];
 
-    // --- this workgroup's tiles: one channel column, every lm-th pixel tile of its XCD's contiguous share (as pigemm.hip) ----
-    const int b = blockIdx.x, xcd = b & 7, local = b >> 3, per = p.pg_per;
-    const int TN = p.tiles_n, TM = p.tiles_m;
-    const int LM = per / TN;
-    const int tile_n = local % TN, lm = local / TN;
-    const int t_lo = (int)(((long long)xcd * TM) >> 3), t_hi = (int)(((long long)(xcd + 1) * TM) >> 3);
-    const int nt = t_lo + lm < t_hi ? (t_hi - t_lo - lm + LM - 1) / LM : 0;
+    // --- this workgroup's tiles: one channel column, every step-th pixel tile of its XCD's contiguous share ----
+    const TileRun run = tile_run(p);
+    const int tile_n = run.tile_n, nt = run.nt;
     if (nt == 0) return;
     const int nk = p.ktot >> 5;
     const int total = nt * nk;
@@ -169,7 +140,7 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const unsigned lds_base = (unsigned)(size_t)(lds_f*)(float*)lds;
-    const int nwx = p.pg_nwx, nwy = p.pg_nwy;
+    const PixelGeom geom = pixel_geom(p);
 
     // bias of the column -> LDS (the accumulators of every tile start from it)
     float* const bias_s = (float*)(lds + NSTAGE * STAGE);
@@ -183,9 +154,9 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
         const int lw = wave_id - 4, ltid = tid - 256;
         const int row0 = ltid >> 3;
         const int colq = (ltid & 7) ^ ((row0 >> 1) & 7);   // LDS chunk c of activation row r holds logical chunk c ^ ((r >> 1) & 7)
-        const i32x4 act_rs = ps_rsrc(p.act, 0xffffffffu);
-        const i32x4 wgt_rs = ps_rsrc(wsp + (size_t)tile_n * nk * (B_BYTES / 2), 0xffffffffu);
-        // pixel addressing (pigemm.hip: scalar base of a 32-pixel run + the lane's distance, wraps folded in), in bytes
+        const pgemm_i32x4 act_rs = lds_dma_rsrc(p.act, 0xffffffffu);
+        const pgemm_i32x4 wgt_rs = lds_dma_rsrc(wsp + (size_t)tile_n * nk * (B_BYTES / 2), 0xffffffffu);
+        // pixel addressing (pixel_walk: scalar base of a 32-pixel run + the lane's distance, wraps folded in), in bytes
         const int in_ps = p.in_px_stride * p.stride * 4, in_rs = p.in_row_stride * p.stride * 4;
         const int in_wrap_x = in_rs - p.wo * in_ps;
         const int in_wrap_y = p.in_img_stride * 4 - p.pg_ho * in_rs;
@@ -194,84 +165,33 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
         asm volatile("" : "+v"(in_lane));
         int in_last;   // pixel M - 1: what the rows past M of a partial last tile read (computed, dropped)
         {
-            int rem, ox;
-            const int img = ps_sdiv(p.M - 1, p.howo, p.pg_magic_howo, rem);
-            const int oy = ps_sdiv(rem, p.wo, p.pg_magic_wo, ox);
-            in_last = img * (p.in_img_stride * 4) + oy * in_rs + ox * in_ps + in_org + colq * 16;
+            int oy, ox;
+            in_last = pixel_base(geom, p.M - 1, p.in_img_stride * 4, in_rs, in_ps, oy, ox) + in_org + colq * 16;
         }
         auto in_offset = [&](int m_base) {
-            int rem, ox_b;
-            const int img_b = ps_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-            int oy = ps_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-            int off = img_b * (p.in_img_stride * 4) + oy * in_rs + ox_b * in_ps + in_org + in_lane;
-            int ox = ox_b + row0;
-            for (int w = 0; w < nwx; ++w) {
-                const bool c = ox >= p.wo;
-                ox -= c ? p.wo : 0;
-                off += c ? in_wrap_x : 0;
-                oy += c ? 1 : 0;
-            }
-            for (int w = 0; w < nwy; ++w) {
-                const bool c = oy >= p.pg_ho;
-                oy -= c ? p.pg_ho : 0;
-                off += c ? in_wrap_y : 0;
-            }
+            const int off = pixel_walk(geom, m_base, row0, p.in_img_stride * 4, in_rs, in_ps, in_wrap_x, in_wrap_y, in_org + in_lane);
             return m_base + row0 < p.M ? off : in_last;
         };
-        int i_tile = t_lo + lm, i_ks = 0, i_ky = 0, i_kx = 0, i_kc = 0;
+        IssueCursor cur{run.first, 0, 0, 0, 0};
         int a_off[4];
         auto rows_of = [&](int tile_m) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) a_off[i] = in_offset(tile_m * BM + 32 * i);
         };
-        rows_of(i_tile);
+        rows_of(cur.tile);
         int b_lane = lw * PB * 1024 + lane * 16;
         asm volatile("" : "+v"(b_lane));
         auto issue = [&](int slot) {
             const unsigned sb = lds_base + slot * STAGE;
-            const int tapoff = (i_ky * p.in_row_stride + i_kx * p.in_px_stride + i_kc) * 4;
+            const int tapoff = cur.tap_offset(p) * 4;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) ps_dma16(act_rs, a_off[i], tapoff, sb + lw * 1024 + i * 4096);
-            const int koff = i_ks * B_BYTES;
+            for (int i = 0; i < 4; ++i) lds_dma16(act_rs, a_off[i], tapoff, sb + lw * 1024 + i * 4096);
+            const int koff = cur.ks * B_BYTES;
 #pragma unroll
-            for (int j = 0; j < PB; ++j) ps_dma16(wgt_rs, b_lane, koff + j * 1024, sb + A_BYTES + (lw * PB + j) * 1024);
-            i_kc += 32;
-            if (i_kc == p.chunk) {
-                i_kc = 0;
-                if (++i_kx == p.kw_taps) { i_kx = 0; ++i_ky; }
-            }
-            if (++i_ks == nk) {
-                i_ks = 0; i_ky = 0; i_kx = 0; i_kc = 0;
-                i_tile += LM;
-                rows_of(i_tile < t_hi ? i_tile : t_hi - 1);
-            }
+            for (int j = 0; j < PB; ++j) lds_dma16(wgt_rs, b_lane, koff + j * 1024, sb + A_BYTES + (lw * PB + j) * 1024);
+            cur.advance(p, nk, run, rows_of);
         };
-        // the stage in front of barrier g + 1 must have landed: exactly the copies of the (at most NSTAGE - 2) stages issued after it may be outstanding
-        auto wait_stage = [&](int younger) {
-            if (NSTAGE >= 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NLD) : "memory");
-            else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        };
-        static_assert(NSTAGE >= 2 && NSTAGE <= 4, "wait_stage covers rings of two to four stages");
-        int slot = 0;
-#pragma unroll
-        for (int s = 0; s < NSTAGE; ++s)
-            if (s < total) issue(s);
-        {
-            const int younger = (total < NSTAGE ? total : NSTAGE) - 1;   // stages 1 .. behind stage 0
-            if (younger >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NLD) : "memory");
-            else wait_stage(younger);
-        }
-        __builtin_amdgcn_s_barrier();   // stage 0 (and bias_s) in LDS
-        for (int g = 0; g + 1 < total; ++g) {
-            // stages issued so far: min(g + NSTAGE, total); behind stage g + 1: min(g + NSTAGE, total) - (g + 2)
-            const int inflight = (g + NSTAGE < total ? g + NSTAGE : total) - (g + 2);
-            wait_stage(inflight);
-            __builtin_amdgcn_s_barrier();   // stage g + 1 landed; every consumer's reads of stage g have returned
-            if (g + NSTAGE < total && !(PA_PS_ABL & 1)) issue(slot);
-            slot = slot + 1 == NSTAGE ? 0 : slot + 1;
-        }
-        __builtin_amdgcn_s_barrier();   // (the consumers' barrier of the last k-step)
+        loader_ring<NSTAGE, NLD, !(PA_PS_ABL & 1)>(total, issue);
         return;
     }
 
@@ -285,22 +205,7 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
     int out_lane = (lr * p.out_px_stride + p.out_pad * (p.out_row_stride + p.out_px_stride) + ch0) * 4;
     asm volatile("" : "+v"(out_lane));
     auto out_offset = [&](int m_base) -> unsigned {
-        int rem, ox_b;
-        const int img_b = ps_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-        int oy = ps_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-        int off = (img_b * p.out_img_stride + oy * p.out_row_stride + ox_b * p.out_px_stride) * 4 + out_lane;
-        int ox = ox_b + lr;
-        for (int w = 0; w < nwx; ++w) {
-            const bool c = ox >= p.wo;
-            ox -= c ? p.wo : 0;
-            off += c ? out_wrap_x : 0;
-            oy += c ? 1 : 0;
-        }
-        for (int w = 0; w < nwy; ++w) {
-            const bool c = oy >= p.pg_ho;
-            oy -= c ? p.pg_ho : 0;
-            off += c ? out_wrap_y : 0;
-        }
+        const int off = pixel_walk(geom, m_base, lr, p.out_img_stride * 4, p.out_row_stride * 4, p.out_px_stride * 4, out_wrap_x, out_wrap_y, out_lane);
         return m_base + lr < p.M ? (unsigned)off : 0x80000000u;   // past M: beyond num_records, dropped (the launcher keeps buffers under 2 GB)
     };
 
@@ -312,22 +217,7 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
     int up_lane = lr * up_ps_b + (p.up_pad * (p.up_row_stride + p.up_px_stride) + ch0) * 4;
     asm volatile("" : "+v"(up_lane));
     auto up_offset = [&](int m_base) -> unsigned {
-        int rem, ox_b;
-        const int img_b = ps_sdiv(m_base, p.howo, p.pg_magic_howo, rem);
-        int oy = ps_sdiv(rem, p.wo, p.pg_magic_wo, ox_b);
-        int off = img_b * p.up_img_stride * 4 + oy * up_rs_b + ox_b * up_ps_b + up_lane;
-        int ox = ox_b + lr;
-        for (int w = 0; w < nwx; ++w) {
-            const bool c = ox >= p.wo;
-            ox -= c ? p.wo : 0;
-            off += c ? up_wrap_x : 0;
-            oy += c ? 1 : 0;
-        }
-        for (int w = 0; w < nwy; ++w) {
-            const bool c = oy >= p.pg_ho;
-            oy -= c ? p.pg_ho : 0;
-            off += c ? up_wrap_y : 0;
-        }
+        const int off = pixel_walk(geom, m_base, lr, p.up_img_stride * 4, up_rs_b, up_ps_b, up_wrap_x, up_wrap_y, up_lane);
         return m_base + lr < p.M ? (unsigned)off : 0x80000000u;
     };
 
@@ -450,7 +340,7 @@ __global__ __launch_bounds__(512, 2) void psgemm_kernel(const GemmParams p, cons
 #endif
     int slot = 0, g = 0;
     for (int t = 0; t < nt; ++t) {
-        const int tile_m = t_lo + lm + t * LM;
+        const int tile_m = run.tile(t);
 #ifdef PA_PS_STAMP
         const unsigned long long st_ks = p.clk ? __builtin_amdgcn_s_memtime() : 0ull;
 #endif
@@ -545,46 +435,13 @@ int psgemm_pick_bn(int N, int residual) {
 
 size_t psgemm_weight_elems(int N, int ktot, int residual) {
     const int bn = psgemm_pick_bn(N, residual);
-    if (bn == 0 || ktot % 32 != 0 || N <= 0 || ktot <= 0) return 0;
-    return (size_t)(N / bn) * (ktot / 32) * (ps_b_pieces(bn) * 512);
+    return stage_weight_elems(N, ktot, bn, ps_b_pieces(bn));
 }
 
-static inline unsigned short ps_bf16_rne(float x) {
-    uint32_t u;
-    memcpy(&u, &x, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)(u >> 16);   // inf / nan: truncate
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-static inline float ps_bf16_f(unsigned short h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// w [N][ktot] fp32 (K contiguous: [cout][tap][cin], BatchNorm folded) -> the kernel's stage images (host):
-// [tile_n][k-step][plane s][row r][chunk c'][8] bf16, plane s = the s-th bf16 slice, chunk c' of row r holding k 8 (c' ^ ((r >> 2) & 3)) ..
+// w [N][ktot] fp32 -> the kernel's stage images (host): three planes, the exact decomposition of every weight into bf16 slices
 void psgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned short* out) {
-    const int bn = psgemm_pick_bn(N, residual), nk = ktot / 32, tn_n = N / bn;
-    const size_t stage = (size_t)ps_b_pieces(bn) * 512;   // elements
-    memset(out, 0, psgemm_weight_elems(N, ktot, residual) * sizeof(unsigned short));
-    for (int tn = 0; tn < tn_n; ++tn)
-        for (int ks = 0; ks < nk; ++ks) {
-            unsigned short* img = out + ((size_t)tn * nk + ks) * stage;
-            for (int r = 0; r < bn; ++r)
-                for (int c = 0; c < 4; ++c) {
-                    const int cp = c ^ ((r >> 2) & 3);
-                    for (int j = 0; j < 8; ++j) {
-                        float x = w[(size_t)(tn * bn + r) * ktot + ks * 32 + c * 8 + j];
-                        for (int s = 0; s < 3; ++s) {
-                            const unsigned short hq = ps_bf16_rne(x);
-                            img[((size_t)(s * bn + r) * 4 + cp) * 8 + j] = hq;
-                            x -= ps_bf16_f(hq);
-                        }
-                    }
-                }
-        }
+    const int bn = psgemm_pick_bn(N, residual);
+    pack_stage_weights(w, N, ktot, bn, 3, ps_b_pieces(bn), out);
 }
 
 // Conv mode of GemmParams (no gather, no second source, no split-K); p.wgt is ignored, wsp = psgemm_pack_weights' image of it.
@@ -592,25 +449,11 @@ void psgemm_pack_weights(const float* w, int N, int ktot, int residual, unsigned
 hipError_t launch_psgemm(const GemmParams& p_in, const unsigned short* wsp, size_t out_floats, size_t up_floats, hipStream_t s) {
     GemmParams p = p_in;
     const int bn = psgemm_pick_bn(p.N, p.residual != nullptr);
-    if (p.gather || p.k2_steps || bn == 0 || p.chunk % 32 != 0 || p.M <= 0 || p.M >= (1 << 24) || p.howo >= (1 << 16) ||
-        p.ktot != p.taps * p.chunk || !wsp || out_floats == 0 || out_floats >= (1ull << 29))
-        return hipErrorInvalidValue;
+    if (bn == 0 || !wsp || out_floats == 0 || out_floats >= (1ull << 29) || persistent_plan(p) != hipSuccess) return hipErrorInvalidValue;
     p.tiles_n = p.N / bn;
     p.tiles_m = (p.M + 127) / 128;
-    // one workgroup per CU = 32 per XCD, a multiple of the channel columns, no more per column than the XCD's share of pixel tiles
-    const int share = (p.tiles_m + 7) / 8;
-    int lm = 32 / p.tiles_n;
-    lm = lm < 1 ? 1 : (lm > share ? share : lm);
-    const int per = lm * p.tiles_n;
-    const int grid = per * 8;
-    auto magic = [](int d) { return (unsigned)std::min<unsigned long long>(((1ull << 32) + d - 1) / d, 0xffffffffull); };
-    if (p.howo % p.wo != 0) return hipErrorInvalidValue;
-    p.pg_per = per;
-    p.pg_ho = p.howo / p.wo;
-    p.pg_magic_howo = magic(p.howo);
-    p.pg_magic_wo = magic(p.wo);
-    p.pg_nwx = 1 + 30 / p.wo;
-    p.pg_nwy = (p.pg_ho - 1 + p.pg_nwx) / p.pg_ho;
+    p.pg_per = unsplit_per(p.tiles_m, p.tiles_n);
+    const int grid = p.pg_per * 8;
     const unsigned out_bytes = (unsigned)(out_floats * 4);
 #ifdef PA_PS_STAMP
     // PA_PS_STAMP_FILE=<path>: every launch appends "M K N grid | median over consumer waves of: shader cycles, 100 MHz ticks, cycles in k-steps, k-steps, tiles" (synchronises)
@@ -676,73 +519,3 @@ hipError_t launch_psgemm(const GemmParams& p_in, const unsigned short* wsp, size
 }
 
 }  // namespace pa
-
-#include "../../include/playaid_hip.h"
-
-extern "C" {
-
-size_t pa_conv_weight_bytes(int32_t cin, int32_t cout, int32_t ksize, int32_t compute_dtype, int32_t has_residual) {
-    if (cin <= 0 || cout <= 0 || (ksize != 1 && ksize != 3) || cin % 32 != 0 || cout % 32 != 0) return 0;
-    if (compute_dtype == PA_DTYPE_F32) return (size_t)cout * ksize * ksize * cin * sizeof(float);
-    if (compute_dtype == PA_DTYPE_EMULATED_F32) return pa::psgemm_weight_elems(cout, ksize * ksize * cin, has_residual) * sizeof(unsigned short);
-    return 0;
-}
-
-int pa_conv_pack_weights(const float* w_host, int32_t cin, int32_t cout, int32_t ksize, int32_t compute_dtype, int32_t has_residual, void* out_host) {
-    const size_t bytes = pa_conv_weight_bytes(cin, cout, ksize, compute_dtype, has_residual);
-    if (!w_host || !out_host || bytes == 0) return PA_ERR_INVALID_ARG;
-    if (compute_dtype == PA_DTYPE_F32) memcpy(out_host, w_host, bytes);
-    else pa::psgemm_pack_weights(w_host, cout, ksize * ksize * cin, has_residual, static_cast<unsigned short*>(out_host));
-    return PA_OK;
-}
-
-int pa_conv2d(const float* x, const void* w, const float* bias, const float* residual, float* out, int32_t n, int32_t height, int32_t width, int32_t cin,
-              int32_t cout, int32_t ksize, int32_t stride, int32_t in_pad, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad, int32_t act,
-              int32_t res_after, int32_t compute_dtype, void* stream) {
-    if (!x || !w || !out || n <= 0 || height <= 0 || width <= 0 || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || height % stride || width % stride ||
-        in_pad < (ksize - 1) / 2 || in_px_stride < cin || out_px_stride < cout || out_pad < 0 || act < 0 || act > 2 ||
-        pa_conv_weight_bytes(cin, cout, ksize, compute_dtype, residual != nullptr) == 0)
-        return PA_ERR_INVALID_ARG;
-    // 16-byte units: the loaders' LDS-DMA reads and the epilogue's dwordx4 stores / residual loads move four floats at an address
-    auto misaligned = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) != 0; };
-    if (in_px_stride % 4 || out_px_stride % 4 || misaligned(x) || misaligned(w) || misaligned(out) || misaligned(residual) ||
-        (reinterpret_cast<unsigned long long>(bias) & 3ull))
-        return PA_ERR_INVALID_ARG;
-    const int oh = height / stride, ow = width / stride;
-    const int in_wb = width + 2 * in_pad, in_hb = height + 2 * in_pad, out_wb = ow + 2 * out_pad, out_hb = oh + 2 * out_pad;
-    if ((long long)n * in_hb * in_wb * in_px_stride >= (1ll << 29) || (long long)n * out_hb * out_wb * out_px_stride >= (1ll << 29)) return PA_ERR_CAPACITY;
-    pa::GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.act = x;
-    p.wgt = static_cast<const float*>(w);
-    p.bias = bias;
-    p.residual = residual;
-    p.out = out;
-    p.M = n * oh * ow;
-    p.N = cout;
-    p.taps = ksize * ksize;
-    p.kw_taps = ksize;
-    p.chunk = cin;
-    p.ktot = p.taps * p.chunk;
-    p.howo = oh * ow;
-    p.wo = ow;
-    p.in_px_stride = in_px_stride;
-    p.in_row_stride = in_wb * in_px_stride;
-    p.in_img_stride = in_hb * in_wb * in_px_stride;
-    p.stride = stride;
-    p.off_y = p.off_x = in_pad - (ksize - 1) / 2;
-    p.out_px_stride = out_px_stride;
-    p.out_row_stride = out_wb * out_px_stride;
-    p.out_img_stride = out_hb * out_wb * out_px_stride;
-    p.out_pad = out_pad;
-    p.relu = act;
-    p.res_after = res_after;
-    p.splitk = 1;
-    hipError_t e;
-    if (compute_dtype == PA_DTYPE_EMULATED_F32) e = pa::launch_psgemm(p, static_cast<const unsigned short*>(w), (size_t)n * p.out_img_stride, 0, static_cast<hipStream_t>(stream));
-    else if (residual) return PA_ERR_INVALID_ARG;   // (the exact persistent kernel has no residual epilogue: Winograd / the patch kernel take those layers)
-    else e = pa::launch_pgemm(p, 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? PA_OK : (e == hipErrorInvalidValue ? PA_ERR_INVALID_ARG : PA_ERR_HIP);
-}
-
-}  // extern "C"

@@ -32,6 +32,7 @@ def test_weight_slices_are_an_exact_decomposition_in_the_stage_image_order():
         assert img.size == (cout // bn) * nk * pieces * 512
         img = img.reshape(cout // bn, nk, pieces * 512)
         wk = np.ascontiguousarray(w.transpose(0, 2, 3, 1)).reshape(cout, ktot)   # K order: (ky, kx, cin)
+        assert np.array_equal(conv.pack_weights(w, "f32").view(np.float32).reshape(cout, ktot), wk), "the exact kernel reads the weights as they are"
         planes = []
         rem = wk.copy()
         for _ in range(3):
@@ -118,6 +119,9 @@ SHAPES = [
     (20, 24, 40, 256, 256, 1, 1),    # two 128-channel columns, 150 pixel tiles
     (12, 96, 160, 64, 128, 3, 2),    # stride-2 3x3, 18 k-steps
     (9, 96, 160, 32, 32, 3, 1),      # 32-channel tiles, nine k-steps, 1080 tiles
+    # small maps: a run of 32 pixels wraps many rows and images
+    (40, 2, 2, 64, 64, 1, 1),        # 2 x 2 maps: a 32-pixel run spans eight images (16 row wraps)
+    (3, 6, 10, 64, 128, 3, 2),       # stride 2 onto a 3 x 5 map
 ]
 
 
@@ -126,6 +130,21 @@ SHAPES = [
 def test_emulated_conv_matches_conv2d_in_float64(shape):
     n, h, w, cin, cout, k, stride = shape
     err = _case(n, h, w, cin, cout, k, stride, seed=h * 131 + cin + k)
+    assert err <= 2e-5, (shape, err)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [
+    (40, 2, 2, 64, 64, 1, 1),        # a 32-pixel run spans eight images: 16 row wraps
+    (7, 4, 4, 512, 512, 3, 1),       # one partial tile
+    (5, 12, 20, 512, 512, 1, 1),     # a partial last tile after nine full ones
+    (1, 8, 12, 96, 96, 1, 1),        # 32-channel tiles, less than one pixel tile
+    (3, 6, 10, 64, 128, 3, 2),       # stride 2, output map 3 x 5
+])
+def test_exact_conv_matches_conv2d_in_float64_on_small_maps(shape):
+    """The exact fp32 kernel's pixel walk on maps narrower than a 32-pixel run (inside the library it takes maps at least 20 wide)."""
+    n, h, w, cin, cout, k, stride = shape
+    err = _case(n, h, w, cin, cout, k, stride, seed=h * 131 + cin + k, dtype="f32")
     assert err <= 2e-5, (shape, err)
 
 
