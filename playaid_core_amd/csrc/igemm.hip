@@ -31,7 +31,7 @@
 //     contiguous run of tiles (same A rows, neighbouring weight panels) in that
 //     XCD's private L2;
 //   * deterministic split-K (slabs + ordered reduce) for the small-M layers.
-#include "pa_kernels.h"
+#include "tile_common.h"
 #include <cstdio>
 #include <cstdlib>
 
@@ -41,34 +41,6 @@ namespace pa {
 #define PA_COUNTED_VMCNT 0
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in VGPRs (HIP's float4 class did not)
-
-
-// 16-byte global -> LDS DMA, buffer form (buffer_load_dwordx4 ... offen lds). LDS destination =
-// wave-uniform `lds_base` + lane*16, source = descriptor base + `off` floats. The FLAT form
-// (global_load_lds) makes hipcc assume "a FLAT access may be pending" and turn every later wait
-// into s_waitcnt vmcnt(0) lgkmcnt(0); behind the MUBUF form the waits stay counted.
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, int off, float* lds_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, off * 4, 0, 0, 0);
-}
-
-// m -> (img, oy, ox) with shifts when the output plane is a power of two
-// (every layer of this network), integer division otherwise.
-__device__ __forceinline__ void split_m(const GemmParams& p, int m, int& img, int& oy, int& ox) {
-    if (p.howo_shift >= 0) {
-        img = m >> p.howo_shift;
-        const int rem = m & (p.howo - 1);
-        oy = rem >> p.wo_shift;
-        ox = rem & (p.wo - 1);
-    } else {
-        img = m / p.howo;
-        const int rem = m - img * p.howo;
-        oy = rem / p.wo;
-        ox = rem - oy * p.wo;
-    }
-}
-
 // ABL: timing-only ablation bits for scripts/ablate_igemm.sh (results are wrong when != 0):
 //   1 no global->LDS loads, 4 no barriers in the loop, 8 no MFMAs.
 // SKIPW: every 4th k carries a zero weight (the stem's channel pad, k = ky*32 + kx*4 + c with c < 3),
@@ -77,128 +49,24 @@ template <int BM, int BN, int BK, bool GATHER, int ABL = 0, bool SKIPW = false>
 __global__ __launch_bounds__(256) void igemm_f32_kernel(const GemmParams p) {
     constexpr int MI = BM / 64;  // 32x32 MFMA tiles per wave along M
     constexpr int NI = BN / 64;
+    using Stage = Im2colStage<4, BK, BM, BN, GATHER>;  // tile decode, staging offsets, k-step cursor (tile_common.h)
     constexpr int LDS_STRIDE = BK;       // floats per LDS row (unpadded: LDS-DMA writes are lane-linear)
-    constexpr int CH = BK / 4;           // 16-byte chunks per row (8 or 16)
-    constexpr int PASS_ROWS = 256 / CH;  // rows staged by one pass of the 256 threads (32 or 16)
-    constexpr int WAVE_ROWS = 64 / CH;   // rows written by one LDS-DMA wave instruction (8 or 4)
-    constexpr int A_ROWS = BM / PASS_ROWS;  // staging rows per thread
-    constexpr int B_ROWS = BN / PASS_ROWS;
+    constexpr int A_ROWS = Stage::A_ROWS, B_ROWS = Stage::B_ROWS;  // staging rows per thread
     constexpr int STAGE = (BM + BN) * LDS_STRIDE;  // floats per LDS stage
     __shared__ __attribute__((aligned(16))) float lds[3 * STAGE];
 
-    // XCD-aware (bijective) remap: blocks with equal b % 8 share an XCD.
-    const int nwg = gridDim.x;
-    const int b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    const int tiles_mn = p.tiles_m * p.tiles_n;
-    const int z = wg / tiles_mn;
-    const int t_id = wg - z * tiles_mn;
-    const int tile_m = t_id / p.tiles_n;
-    const int tile_n = t_id - tile_m * p.tiles_n;
-
+    Stage st;
+    st.setup(p);
+    const int tile_m = st.tile_m, tile_n = st.tile_n, z = st.z;
+    const int ks_begin = st.ks_begin, ks_end = st.ks_end;
     const int tid = threadIdx.x;
-    const int row0 = tid / CH;  // staging row of this thread within a pass
-    // LDS chunk c of staging row r receives logical chunk c ^ swz(r), swz(r) = (r>>1)&7 for
-    // 128-byte rows (BK 32) and r&15 for 256-byte rows (BK 64); r = row0 + PASS_ROWS*i, so the
-    // term only depends on row0.
-    const int colq = (tid & (CH - 1)) ^ (BK == 32 ? ((row0 >> 1) & 7) : (row0 & 15));
-
-    int a_off[A_ROWS];
-    int b_off[B_ROWS];
-#pragma unroll
-    for (int i = 0; i < A_ROWS; ++i) {
-        int m = tile_m * BM + row0 + PASS_ROWS * i;
-        m = m < p.M ? m : p.M - 1;
-        if (GATHER) {
-            a_off[i] = m * p.taps;
-        } else {
-            int img, oy, ox;
-            split_m(p, m, img, oy, ox);
-            a_off[i] = img * p.in_img_stride + oy * p.stride * p.in_row_stride +
-                       ox * p.stride * p.in_px_stride + colq * 4;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < B_ROWS; ++i) b_off[i] = (tile_n * BN + row0 + PASS_ROWS * i) * p.ktot + colq * 4;
-    // optional second source for the last k2_steps k-steps (the 1x1/2 downsample branch of a
-    // residual block, fused into conv2's accumulation as extra K)
-    int a_off2[A_ROWS];
-#pragma unroll
-    for (int i = 0; i < A_ROWS; ++i) {
-        a_off2[i] = 0;
-        if (!GATHER && p.act2) {
-            int m = tile_m * BM + row0 + PASS_ROWS * i;
-            m = m < p.M ? m : p.M - 1;
-            int img, oy, ox;
-            split_m(p, m, img, oy, ox);
-            a_off2[i] = img * p.in2_img_stride + (oy * p.stride2 + p.off2) * p.in2_row_stride +
-                        (ox * p.stride2 + p.off2) * p.in2_px_stride + colq * 4;
-        }
-    }
-    const int nk_main = (p.ktot - p.k2_steps * BK) / BK;
-
-    const int nk = p.ktot / BK;
-    const int ks_begin = z * p.ksteps_per_split;
-    int ks_end = ks_begin + p.ksteps_per_split;
-    ks_end = ks_end < nk ? ks_end : nk;
-
-    // k-step cursor, advanced incrementally (one division at entry only)
-    int cur_kc, cur_kx, cur_ky;
-    int issue_ks = ks_begin;  // absolute index of the next k-step to issue
-    {
-        const int cpt = p.chunk / BK;
-        const int ksm = ks_begin < nk_main ? ks_begin : nk_main;
-        const int tap = ksm / cpt;
-        cur_kc = (ksm - tap * cpt) * BK;
-        cur_ky = tap / p.kw_taps;
-        cur_kx = tap - cur_ky * p.kw_taps;
-    }
-
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const __amdgpu_buffer_rsrc_t act_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.act), 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wgt), 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t act2_rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.act2 ? p.act2 : p.act), 0, -1, 0x00020000);
-
-    // Issue the LDS-DMA loads of the k-step under the cursor into stage BUF, then
-    // advance the cursor. Each wave instruction fills WAVE_ROWS rows (1 KiB).
-#define PA_ISSUE_STAGE(BUF)                                                                                   \
-    {                                                                                                         \
-        float* As_w = lds + (BUF) * STAGE + wave_id * 256;                                                    \
-        float* Bs_w = As_w + BM * LDS_STRIDE;                                                                 \
-        if (issue_ks >= nk_main) {                                                                            \
-            const int kc2 = (issue_ks - nk_main) * BK;                                                        \
-            _Pragma("unroll") for (int i = 0; i < A_ROWS; ++i)                                                \
-                glds16(act2_rs, a_off2[i] + kc2, As_w + i * 1024);                                            \
-            const int koff2 = nk_main * BK + kc2;                                                             \
-            _Pragma("unroll") for (int i = 0; i < B_ROWS; ++i)                                                \
-                glds16(wgt_rs, b_off[i] + koff2, Bs_w + i * 1024);                                            \
-        } else {                                                                                              \
-            const int tap = cur_ky * p.kw_taps + cur_kx;                                                      \
-            if (GATHER) {                                                                                     \
-                _Pragma("unroll") for (int i = 0; i < A_ROWS; ++i) {                                          \
-                    const int row = p.gather[a_off[i] + tap];                                                 \
-                    glds16(act_rs, row * p.in_px_stride + cur_kc + colq * 4, As_w + i * 1024);        \
-                }                                                                                             \
-            } else {                                                                                          \
-                const int tapoff = (cur_ky + p.off_y) * p.in_row_stride + (cur_kx + p.off_x) * p.in_px_stride + cur_kc; \
-                _Pragma("unroll") for (int i = 0; i < A_ROWS; ++i)                                            \
-                    glds16(act_rs, a_off[i] + tapoff, As_w + i * 1024);                                       \
-            }                                                                                                 \
-            const int koff = tap * p.chunk + cur_kc;                                                          \
-            _Pragma("unroll") for (int i = 0; i < B_ROWS; ++i)                                                \
-                glds16(wgt_rs, b_off[i] + koff, Bs_w + i * 1024);                                             \
-            cur_kc += BK;                                                                                     \
-            if (cur_kc == p.chunk) {                                                                          \
-                cur_kc = 0;                                                                                   \
-                if (++cur_kx == p.kw_taps) {                                                                  \
-                    cur_kx = 0;                                                                               \
-                    ++cur_ky;                                                                                 \
-                }                                                                                             \
-            }                                                                                                 \
-        }                                                                                                     \
-        ++issue_ks;                                                                                           \
+    // Issue the LDS-DMA loads of the k-step under the cursor into stage BUF, then advance the cursor. Each wave instruction
+    // fills 1 KiB (8 or 4 rows).
+#define PA_ISSUE_STAGE(BUF)                                                \
+    {                                                                      \
+        float* As_w = lds + (BUF) * STAGE + wave_id * 256;                 \
+        st.issue(p, As_w, As_w + BM * LDS_STRIDE);                         \
     }
 
     const int lane = tid & 63;
@@ -323,8 +191,8 @@ __global__ __launch_bounds__(256) void igemm_f32_kernel(const GemmParams p) {
             if (PA_COUNTED_VMCNT) {
                 // leave the stage issued in THIS step in flight across the barrier: only the older
                 // stage (needed next step) must have landed. __syncthreads() would drain to vmcnt(0).
-                if (ks + 2 < ks_end) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_ROWS + B_ROWS) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (ks + 2 < ks_end) wait_vmcnt<A_ROWS + B_ROWS>();
+                else wait_vmcnt<0>();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
             } else {
@@ -368,52 +236,49 @@ __global__ __launch_bounds__(256) void igemm_f32_kernel(const GemmParams p) {
         if (!direct_out) {
             *reinterpret_cast<f32x4*>(p.slab + ((size_t)z * p.M + m) * p.N + tile_n * BN + c4) = v;
         } else {
-            v += p.res_after ? bias4 : bias4 + res_t[i];
-            if (p.relu == 1) {
-                v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-                v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-            } else if (p.relu == 2) {
-                v.x = silu_fast(v.x); v.y = silu_fast(v.y);
-                v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-            }
-            if (p.res_after) v += res_t[i];
-            *reinterpret_cast<f32x4*>(p.out + o_t[i]) = v;
+            *reinterpret_cast<f32x4*>(p.out + o_t[i]) = epilogue4(v, bias4, res_t[i], p.relu, p.res_after);
         }
     }
 }
 
-// Ordered (deterministic) split-K reduction with the fused epilogue.
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) {
+// Ordered (deterministic) split-K reduction with the fused epilogue: the fp32 slabs summed in split order, + bias, + residual,
+// activation, stored as OutT. The sum is (slabs + bias) + residual -- the tile epilogues add slabs + (bias + residual) -- so of
+// epilogue4 only act4 is shared. float: ReLU / SiLU, residual before or after the activation; bf16_t (igemm_bf16.hip's layers): bf16
+// residual before the activation, any non-zero relu is ReLU. (The body stands in the kernel itself: behind a helper that takes the
+// parameters by reference both instances need two more registers.)
+template <typename OutT> __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) {
+    constexpr bool BF16 = sizeof(OutT) == 2;
+    const OutT* residual = reinterpret_cast<const OutT*>(p.residual);
+    OutT* out = reinterpret_cast<OutT*>(p.out);
     const int n4 = p.N >> 2;
     const size_t total = (size_t)p.M * n4;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int m = (int)(i / n4);
         const int n = (int)(i - (size_t)m * n4) * 4;
-        float4 s = *reinterpret_cast<const float4*>(p.slab + (size_t)m * p.N + n);
-        for (int z = 1; z < p.splitk; ++z) {
-            const float4 v = *reinterpret_cast<const float4*>(p.slab + ((size_t)z * p.M + m) * p.N + n);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
+        f32x4 s = *reinterpret_cast<const f32x4*>(p.slab + (size_t)m * p.N + n);
+        for (int z = 1; z < p.splitk; ++z) s += *reinterpret_cast<const f32x4*>(p.slab + ((size_t)z * p.M + m) * p.N + n);
         int img, oy, ox;
         split_m(p, m, img, oy, ox);
         const size_t o = (size_t)img * p.out_img_stride + (size_t)(oy + p.out_pad) * p.out_row_stride +
                          (size_t)(ox + p.out_pad) * p.out_px_stride + n;
-        if (p.bias) {
-            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            s.x += bv.x; s.y += bv.y; s.z += bv.z; s.w += bv.w;
+        if (p.bias) s += *reinterpret_cast<const f32x4*>(p.bias + n);
+        if constexpr (BF16) {
+            if (residual) {
+                const ushort4 rv = *reinterpret_cast<const ushort4*>(residual + o);
+                s += f32x4{bf16_to_f32(rv.x), bf16_to_f32(rv.y), bf16_to_f32(rv.z), bf16_to_f32(rv.w)};
+            }
+            s = act4(s, p.relu ? 1 : 0);
+            ushort4 ov;
+            ov.x = f32_to_bf16(s.x); ov.y = f32_to_bf16(s.y); ov.z = f32_to_bf16(s.z); ov.w = f32_to_bf16(s.w);
+            *reinterpret_cast<ushort4*>(out + o) = ov;
+        } else {
+            f32x4 rv = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (residual) rv = *reinterpret_cast<const f32x4*>(residual + o);
+            if (!p.res_after) s += rv;
+            s = act4(s, p.relu);
+            if (p.res_after) s += rv;
+            *reinterpret_cast<f32x4*>(out + o) = s;
         }
-        float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (p.residual) rv = *reinterpret_cast<const float4*>(p.residual + o);
-        if (!p.res_after) { s.x += rv.x; s.y += rv.y; s.z += rv.z; s.w += rv.w; }
-        if (p.relu == 1) {
-            s.x = s.x > 0.f ? s.x : 0.f; s.y = s.y > 0.f ? s.y : 0.f;
-            s.z = s.z > 0.f ? s.z : 0.f; s.w = s.w > 0.f ? s.w : 0.f;
-        } else if (p.relu == 2) {
-            s.x = silu_fast(s.x); s.y = silu_fast(s.y);
-            s.z = silu_fast(s.z); s.w = silu_fast(s.w);
-        }
-        if (p.res_after) { s.x += rv.x; s.y += rv.y; s.z += rv.z; s.w += rv.w; }
-        *reinterpret_cast<float4*>(p.out + o) = s;
     }
 }
 
@@ -450,37 +315,20 @@ static hipError_t launch_tile(const GemmParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-static void tile_dims(GemmTile tile, int* bm, int* bn, int* bk) {
-    switch (tile) {
-        case TILE_128x128: *bm = 128; *bn = 128; *bk = 32; break;
-        case TILE_128x64: *bm = 128; *bn = 64; *bk = 32; break;
-        case TILE_64x64: *bm = 64; *bn = 64; *bk = 32; break;
-        case TILE_128x64_K64: *bm = 128; *bn = 64; *bk = 64; break;
-        default: *bm = 64; *bn = 64; *bk = 64; break;
-    }
-}
-
 hipError_t launch_igemm(const GemmParams& p_in, GemmTile tile, hipStream_t s) {
     GemmParams p = p_in;
-    int bm, bn, bk;
-    tile_dims(tile, &bm, &bn, &bk);
-    if (p.chunk % bk != 0 || p.k2_steps) {  // 32-wide taps (stem) or a fused second source: BK=32 shapes only
+    TileDims d = tile_dims(tile, 4);
+    if (p.chunk % d.bk != 0 || p.k2_steps) {  // 32-wide taps (stem) or a fused second source: BK=32 shapes only
         tile = tile == TILE_128x64_K64 ? TILE_128x64 : TILE_64x64;
-        tile_dims(tile, &bm, &bn, &bk);
+        d = tile_dims(tile, 4);
     }
+    const int bm = d.bm, bn = d.bn, bk = d.bk;
     if (p.N % bn != 0 || p.chunk % bk != 0 || p.ktot != p.taps * p.chunk + p.k2_steps * 32 || p.M <= 0) return hipErrorInvalidValue;
     if (p.k2_steps && (bk != 32 || !p.act2 || p.gather)) return hipErrorInvalidValue;
-    auto ilog2 = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-    p.howo_shift = ilog2(p.howo);
-    p.wo_shift = ilog2(p.wo);
-    if (p.howo_shift < 0 || p.wo_shift < 0) p.howo_shift = p.wo_shift = -1;
+    fill_pow2_shifts(p);
     p.tiles_m = (p.M + bm - 1) / bm;
     p.tiles_n = p.N / bn;
-    const int nk = p.ktot / bk;
-    if (p.splitk < 1) p.splitk = 1;
-    if (p.splitk > nk) p.splitk = nk;
-    p.ksteps_per_split = (nk + p.splitk - 1) / p.splitk;
-    p.splitk = (nk + p.ksteps_per_split - 1) / p.ksteps_per_split;  // no empty splits
+    plan_splitk(p.ktot / bk, p.splitk, p.ksteps_per_split);
     hipError_t err;
     switch (tile) {
         case TILE_128x128: err = launch_tile<128, 128, 32>(p, s); break;
@@ -495,11 +343,12 @@ hipError_t launch_igemm(const GemmParams& p_in, GemmTile tile, hipStream_t s) {
     return hipSuccess;
 }
 
-hipError_t launch_splitk_reduce(const GemmParams& p, hipStream_t s) {
+hipError_t launch_splitk_reduce(const GemmParams& p, hipStream_t s, bool out_bf16) {
     const size_t total = (size_t)p.M * (p.N >> 2);
     int grid = (int)((total + 255) / 256);
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, p);
+    if (out_bf16) hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(grid), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

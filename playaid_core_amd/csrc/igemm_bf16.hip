@@ -1,6 +1,7 @@
 // bf16 implicit-GEMM convolution for gfx950 (BASELINE.json configs[2]: "bf16 conv path").
 //
-// Same structure as igemm.hip -- zero-bordered NHWC activations, im2col rows and weight rows
+// The im2col design of igemm.hip, whose tile decode, staging offsets, k-step cursor and DMA issue both kernels take from
+// tile_common.h (Im2colStage) -- zero-bordered NHWC activations, im2col rows and weight rows
 // copied global -> LDS with global_load_lds_dwordx4 into a three-stage ring, XOR swizzle on the
 // DMA source address, 2x2 waves over a BM x BN tile, fused bias / residual / ReLU epilogue (here straight from the
 // accumulators: the weights are the matrix instruction's row operand, a lane owns one pixel and stores 16 bytes),
@@ -14,45 +15,9 @@
 // bound by LDS fill and, across the layer, by HBM (bf16 ridge ~315 FLOP/B).
 //
 // Only conv mode (no gather): the temporal Conv1d head and the fc stay in fp32.
-#include "pa_kernels.h"
+#include "tile_common.h"
 
 namespace pa {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint16_t bf16_t;  // storage
-
-namespace {
-
-// 16-byte global -> LDS DMA, buffer form (see igemm.hip); source = descriptor base + `off` bf16 elements.
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, int off, float* lds_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, off * 2, 0, 0, 0);
-}
-
-__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-__device__ __forceinline__ bf16_t f2bf(float f) {  // round to nearest even (inputs are finite)
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
-
-__device__ __forceinline__ void split_m(const GemmParams& p, int m, int& img, int& oy, int& ox) {
-    if (p.howo_shift >= 0) {
-        img = m >> p.howo_shift;
-        const int rem = m & (p.howo - 1);
-        oy = rem >> p.wo_shift;
-        ox = rem & (p.wo - 1);
-    } else {
-        img = m / p.howo;
-        const int rem = m - img * p.howo;
-        oy = rem / p.wo;
-        ox = rem - oy * p.wo;
-    }
-}
-
-}  // namespace
 
 // BK in bf16 elements: 64 (128-byte LDS rows) or 128 (256-byte rows).
 //
@@ -65,115 +30,45 @@ template <int BM, int BN, int BK, bool DS = false>
 __global__ __launch_bounds__(256) void igemm_bf16_kernel(const GemmParams p) {
     constexpr int MI = BM / 64;
     constexpr int NI = BN / 64;
+    using Stage = Im2colStage<2, BK, BM, BN, false>;
     constexpr int ROW_F = BK / 2;          // floats (4-byte words) per LDS row: 32 or 64
-    constexpr int CH = BK / 8;             // 16-byte chunks per row: 8 or 16
-    constexpr int KG = CH / 2;             // 16-wide k groups per row (one MFMA each)
-    constexpr int PASS_ROWS = 256 / CH;
-    constexpr int A_ROWS = BM / PASS_ROWS;
-    constexpr int B_ROWS = BN / PASS_ROWS;
+    constexpr int KG = Stage::CH / 2;      // 16-wide k groups per row (one MFMA each)
+    constexpr int PASS_ROWS = Stage::PASS_ROWS, A_ROWS = Stage::A_ROWS, B_ROWS = Stage::B_ROWS;
     constexpr int STAGE = (BM + BN + (DS ? BN : 0)) * ROW_F;  // floats per LDS stage
     static_assert(!DS || BK == 64, "the centre tap is found by 64-deep k-steps");
     __shared__ __attribute__((aligned(16))) float lds[3 * STAGE];
 
-    const bf16_t* act = reinterpret_cast<const bf16_t*>(p.act);
-    const bf16_t* act2 = reinterpret_cast<const bf16_t*>(p.act2);
-    const bf16_t* wgt = reinterpret_cast<const bf16_t*>(p.wgt);
     const bf16_t* residual = reinterpret_cast<const bf16_t*>(p.residual);
     bf16_t* out = reinterpret_cast<bf16_t*>(p.out);
 
-    // XCD-aware (bijective) remap: blocks with equal b % 8 share an XCD.
-    const int nwg = gridDim.x;
-    const int b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    const int tiles_mn = p.tiles_m * p.tiles_n;
-    const int z = wg / tiles_mn;
-    const int t_id = wg - z * tiles_mn;
-    const int tile_m = t_id / p.tiles_n;
-    const int tile_n = t_id - tile_m * p.tiles_n;
-
+    Stage st;
+    st.setup(p);
+    const int tile_m = st.tile_m, tile_n = st.tile_n, z = st.z;
+    const int ks_begin = st.ks_begin, ks_end = st.ks_end;
     const int tid = threadIdx.x;
-    const int row0 = tid / CH;
-    const int colq = (tid & (CH - 1)) ^ (CH == 8 ? ((row0 >> 1) & 7) : (row0 & 15));  // source-side swizzle
-
-    int a_off[A_ROWS], a_off2[A_ROWS], b_off[B_ROWS];
-#pragma unroll
-    for (int i = 0; i < A_ROWS; ++i) {
-        int m = tile_m * BM + row0 + PASS_ROWS * i;
-        m = m < p.M ? m : p.M - 1;
-        int img, oy, ox;
-        split_m(p, m, img, oy, ox);
-        a_off[i] = img * p.in_img_stride + oy * p.stride * p.in_row_stride + ox * p.stride * p.in_px_stride + colq * 8;
-        a_off2[i] = 0;
-        if (p.act2)
-            a_off2[i] = img * p.in2_img_stride + (oy * p.stride2 + p.off2) * p.in2_row_stride +
-                        (ox * p.stride2 + p.off2) * p.in2_px_stride + colq * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < B_ROWS; ++i) b_off[i] = (tile_n * BN + row0 + PASS_ROWS * i) * p.ktot + colq * 8;
     int b2_off[DS ? B_ROWS : 1];
     if constexpr (DS) {
 #pragma unroll
-        for (int i = 0; i < B_ROWS; ++i) b2_off[i] = (tile_n * BN + row0 + PASS_ROWS * i) * p.chunk + colq * 8;
-    }
-
-    const int nk_main = (p.ktot - p.k2_steps * BK) / BK;
-    const int nk = p.ktot / BK;
-    const int ks_begin = z * p.ksteps_per_split;
-    int ks_end = ks_begin + p.ksteps_per_split;
-    ks_end = ks_end < nk ? ks_end : nk;
-
-    int cur_kc, cur_kx, cur_ky;
-    int issue_ks = ks_begin;
-    {
-        const int cpt = p.chunk / BK;
-        const int ksm = ks_begin < nk_main ? ks_begin : nk_main;
-        const int tap = ksm / cpt;
-        cur_kc = (ksm - tap * cpt) * BK;
-        cur_ky = tap / p.kw_taps;
-        cur_kx = tap - cur_ky * p.kw_taps;
+        for (int i = 0; i < B_ROWS; ++i) b2_off[i] = (tile_n * BN + st.row0 + PASS_ROWS * i) * p.chunk + st.colq * 8;
     }
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const __amdgpu_buffer_rsrc_t act_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(act), 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(wgt), 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t act2_rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(act2 ? act2 : act), 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt2_rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DS ? p.wgt2 : p.wgt), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wgt2_rs = glds_rsrc(DS ? p.wgt2 : p.wgt);
     bool newest_ctr = false;  // DS: the stage issued last carried the second weight tile
 
+    // the k-step under the cursor into stage BUF; DS: behind the centre tap's copies the second weight tile's
 #define PA_ISSUE_STAGE(BUF)                                                                                   \
     {                                                                                                         \
         float* As_w = lds + (BUF) * STAGE + wave_id * 256;                                                    \
         float* Bs_w = As_w + BM * ROW_F;                                                                      \
-        if (issue_ks >= nk_main) {                                                                            \
-            const int kc2 = (issue_ks - nk_main) * BK;                                                        \
-            _Pragma("unroll") for (int i = 0; i < A_ROWS; ++i) glds16(act2_rs, a_off2[i] + kc2, As_w + i * 1024); \
-            const int koff2 = nk_main * BK + kc2;                                                             \
-            _Pragma("unroll") for (int i = 0; i < B_ROWS; ++i) glds16(wgt_rs, b_off[i] + koff2, Bs_w + i * 1024); \
-        } else {                                                                                              \
-            const int tap = cur_ky * p.kw_taps + cur_kx;                                                      \
-            const int tapoff = (cur_ky + p.off_y) * p.in_row_stride + (cur_kx + p.off_x) * p.in_px_stride + cur_kc; \
-            _Pragma("unroll") for (int i = 0; i < A_ROWS; ++i) glds16(act_rs, a_off[i] + tapoff, As_w + i * 1024); \
-            const int koff = tap * p.chunk + cur_kc;                                                          \
-            _Pragma("unroll") for (int i = 0; i < B_ROWS; ++i) glds16(wgt_rs, b_off[i] + koff, Bs_w + i * 1024); \
+        st.issue(p, As_w, Bs_w, [&](int ky, int kx, int kc) {                                                 \
             if constexpr (DS) {                                                                               \
-                newest_ctr = cur_ky == 1 && cur_kx == 1;                                                      \
+                newest_ctr = ky == 1 && kx == 1;                                                              \
                 if (newest_ctr) {                                                                             \
                     float* B2s_w = Bs_w + BN * ROW_F;                                                         \
-                    _Pragma("unroll") for (int i = 0; i < B_ROWS; ++i) glds16(wgt2_rs, b2_off[i] + cur_kc, B2s_w + i * 1024); \
+                    _Pragma("unroll") for (int i = 0; i < B_ROWS; ++i) glds16(wgt2_rs, (b2_off[i] + kc) * 2, 0, B2s_w + i * 1024); \
                 }                                                                                             \
             }                                                                                                 \
-            cur_kc += BK;                                                                                     \
-            if (cur_kc == p.chunk) {                                                                          \
-                cur_kc = 0;                                                                                   \
-                if (++cur_kx == p.kw_taps) {                                                                  \
-                    cur_kx = 0;                                                                               \
-                    ++cur_ky;                                                                                 \
-                }                                                                                             \
-            }                                                                                                 \
-        }                                                                                                     \
-        ++issue_ks;                                                                                           \
+        });                                                                                                   \
     }
 
     const int lane = tid & 63;
@@ -202,7 +97,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const GemmParams p) {
 
     const int a_rd_off = (wm * (BM / 2) + lr) * ROW_F;
     const int b_rd_off = BM * ROW_F + (wn * (BN / 2) + lr) * ROW_F;
-    const int swz = CH == 8 ? ((lr >> 1) & 7) : (lr & 15);
+    const int swz = Stage::CH == 8 ? ((lr >> 1) & 7) : (lr & 15);
 
     const bool direct_out = p.splitk <= 1;
 
@@ -221,28 +116,19 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const GemmParams p) {
     // at the top of this k-step -- are outstanding. A __syncthreads() here would drain vmcnt to 0 and with it the
     // whole ring (every copy would be waited for one k-step after its issue: the round-2 profile of this kernel).
     constexpr int NCOPY = A_ROWS + B_ROWS;
-    static_assert(NCOPY == 12 || NCOPY == 8 || NCOPY == 6 || NCOPY == 4, "extend the counted wait below");
-    static_assert(!DS || NCOPY + B_ROWS == 12 || NCOPY + B_ROWS == 8, "extend the counted wait below");
-#define PA_WAIT_COUNT(N_)                                                        \
-    {                                                                            \
-        if constexpr ((N_) == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); \
-        else if constexpr ((N_) == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); \
-        else if constexpr ((N_) == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); \
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                    \
-    }
     // all but the newest stage's copies have landed
 #define PA_WAIT_NEWEST()                                                         \
     {                                                                            \
         if constexpr (DS) {                                                      \
-            if (newest_ctr) PA_WAIT_COUNT(NCOPY + B_ROWS) else PA_WAIT_COUNT(NCOPY) \
-        } else PA_WAIT_COUNT(NCOPY)                                              \
+            if (newest_ctr) wait_vmcnt<NCOPY + B_ROWS>(); else wait_vmcnt<NCOPY>(); \
+        } else wait_vmcnt<NCOPY>();                                              \
     }
     if (ks_begin < ks_end) PA_ISSUE_STAGE(0);
     if (ks_begin + 1 < ks_end) PA_ISSUE_STAGE(1);
     if (ks_begin + 1 < ks_end) {
         PA_WAIT_NEWEST();
     } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
     }
     __builtin_amdgcn_s_barrier();
     if (ks_begin < ks_end) PA_LOAD_FRAGS(0, lds, 0);
@@ -293,7 +179,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const GemmParams p) {
                 if (issued) {
                     PA_WAIT_NEWEST();
                 } else {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    wait_vmcnt<0>();
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -313,7 +199,6 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const GemmParams p) {
 #undef PA_LOAD_FRAGS
 #undef PA_ISSUE_STAGE
 #undef PA_WAIT_NEWEST
-#undef PA_WAIT_COUNT
 
     // Epilogue, straight from the accumulators. The WEIGHTS are the matrix instruction's row operand, so a lane owns
     // ONE pixel (tile row wm BM/2 + 32 mi + lr) and, per 32-channel block, the runs 8 j + 4 lh + 0..3 (element e = 4 j + i).
@@ -373,7 +258,7 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const GemmParams p) {
                             a_ = a_ > 0.f ? a_ : 0.f;                                                          \
                             c_ = c_ > 0.f ? c_ : 0.f;                                                          \
                         }                                                                                      \
-                        pk_[k] = (uint32_t)f2bf(a_) | ((uint32_t)f2bf(c_) << 16);                              \
+                        pk_[k] = (uint32_t)f32_to_bf16(a_) | ((uint32_t)f32_to_bf16(c_) << 16);                              \
                     }                                                                                          \
                     if (mrow[mi] < p.M) *reinterpret_cast<uint4*>((DST) + o_) = make_uint4(pk_[0], pk_[1], pk_[2], pk_[3]); \
                 }                                                                                              \
@@ -388,42 +273,6 @@ __global__ __launch_bounds__(256) void igemm_bf16_kernel(const GemmParams p) {
 #undef PA_STORE_TILE
 }
 
-// Ordered split-K reduction (fp32 slabs) with the fused epilogue, bf16 out.
-__global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const GemmParams p) {
-    const bf16_t* residual = reinterpret_cast<const bf16_t*>(p.residual);
-    bf16_t* out = reinterpret_cast<bf16_t*>(p.out);
-    const int n4 = p.N >> 2;
-    const size_t total = (size_t)p.M * n4;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int m = (int)(i / n4);
-        const int n = (int)(i - (size_t)m * n4) * 4;
-        float4 s = *reinterpret_cast<const float4*>(p.slab + (size_t)m * p.N + n);
-        for (int z = 1; z < p.splitk; ++z) {
-            const float4 v = *reinterpret_cast<const float4*>(p.slab + ((size_t)z * p.M + m) * p.N + n);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        int img, oy, ox;
-        split_m(p, m, img, oy, ox);
-        const size_t o = (size_t)img * p.out_img_stride + (size_t)(oy + p.out_pad) * p.out_row_stride +
-                         (size_t)(ox + p.out_pad) * p.out_px_stride + n;
-        if (p.bias) {
-            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            s.x += bv.x; s.y += bv.y; s.z += bv.z; s.w += bv.w;
-        }
-        if (residual) {
-            const ushort4 rv = *reinterpret_cast<const ushort4*>(residual + o);
-            s.x += bf2f(rv.x); s.y += bf2f(rv.y); s.z += bf2f(rv.z); s.w += bf2f(rv.w);
-        }
-        if (p.relu) {
-            s.x = s.x > 0.f ? s.x : 0.f; s.y = s.y > 0.f ? s.y : 0.f;
-            s.z = s.z > 0.f ? s.z : 0.f; s.w = s.w > 0.f ? s.w : 0.f;
-        }
-        ushort4 ov;
-        ov.x = f2bf(s.x); ov.y = f2bf(s.y); ov.z = f2bf(s.z); ov.w = f2bf(s.w);
-        *reinterpret_cast<ushort4*>(out + o) = ov;
-    }
-}
-
 template <int BM, int BN, int BK, bool DS = false>
 static hipError_t launch_tile_bf16(const GemmParams& p, hipStream_t s) {
     const int grid = p.tiles_m * p.tiles_n * p.splitk;
@@ -436,42 +285,25 @@ static hipError_t launch_tile_bf16(const GemmParams& p, hipStream_t s) {
 hipError_t launch_igemm_bf16(const GemmParams& p_in, GemmTile tile, hipStream_t s) {
     GemmParams p = p_in;
     if (p.gather) return hipErrorInvalidValue;
-    auto dims = [](GemmTile t, int* bm, int* bn, int* bk) {
-        switch (t) {
-            case TILE_256x128: *bm = 256; *bn = 128; *bk = 64; break;
-            case TILE_128x128: *bm = 128; *bn = 128; *bk = 64; break;
-            case TILE_128x64: *bm = 128; *bn = 64; *bk = 64; break;
-            case TILE_64x64: *bm = 64; *bn = 64; *bk = 64; break;
-            case TILE_128x64_K64: *bm = 128; *bn = 64; *bk = 128; break;
-            default: *bm = 64; *bn = 64; *bk = 128; break;
-        }
-    };
-    int bm, bn, bk;
-    dims(tile, &bm, &bn, &bk);
-    if (p.chunk % bk != 0 || (p.k2_steps && bk != 64)) {  // 64-channel layers / fused second source: 128-byte rows only
+    TileDims d = tile_dims(tile, 2);
+    if (p.chunk % d.bk != 0 || (p.k2_steps && d.bk != 64)) {  // 64-channel layers / fused second source: 128-byte rows only
         tile = tile == TILE_128x64_K64 ? TILE_128x64 : (tile == TILE_64x64_K64 ? TILE_64x64 : tile);
-        dims(tile, &bm, &bn, &bk);
+        d = tile_dims(tile, 2);
     }
+    const int bm = d.bm, bn = d.bn, bk = d.bk;
     if (p.N % bn != 0 || p.chunk % bk != 0 || p.ktot != p.taps * p.chunk + p.k2_steps * 64 || p.M <= 0) return hipErrorInvalidValue;
     if (p.k2_steps && (bk != 64 || !p.act2)) return hipErrorInvalidValue;
-    auto ilog2 = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
-    p.howo_shift = ilog2(p.howo);
-    p.wo_shift = ilog2(p.wo);
-    if (p.howo_shift < 0 || p.wo_shift < 0) p.howo_shift = p.wo_shift = -1;
+    fill_pow2_shifts(p);
     p.tiles_m = (p.M + bm - 1) / bm;
     p.tiles_n = p.N / bn;
     const int nk = p.ktot / bk;
-    if (p.splitk < 1) p.splitk = 1;
-    if (p.splitk > nk) p.splitk = nk;
+    plan_splitk(nk, p.splitk, p.ksteps_per_split);
     if (p.out2) {  // second 1x1 product on the centre tap (see the kernel): 3x3 taps, 64-deep k-steps, one K split
         if (!p.wgt2 || p.taps != 9 || p.kw_taps != 3 || p.k2_steps || bk != 64 || p.splitk != 1 ||
             (tile != TILE_128x128 && tile != TILE_128x64))
             return hipErrorInvalidValue;
-        p.ksteps_per_split = nk;
         return tile == TILE_128x128 ? launch_tile_bf16<128, 128, 64, true>(p, s) : launch_tile_bf16<128, 64, 64, true>(p, s);
     }
-    p.ksteps_per_split = (nk + p.splitk - 1) / p.splitk;
-    p.splitk = (nk + p.ksteps_per_split - 1) / p.ksteps_per_split;
     hipError_t err;
     switch (tile) {
         case TILE_256x128: err = launch_tile_bf16<256, 128, 64>(p, s); break;
@@ -482,13 +314,7 @@ hipError_t launch_igemm_bf16(const GemmParams& p_in, GemmTile tile, hipStream_t 
         default: err = launch_tile_bf16<64, 64, 128>(p, s); break;
     }
     if (err != hipSuccess) return err;
-    if (p.splitk > 1) {
-        const size_t total = (size_t)p.M * (p.N >> 2);
-        int grid = (int)((total + 255) / 256);
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(grid), dim3(256), 0, s, p);
-        return hipGetLastError();
-    }
+    if (p.splitk > 1) return launch_splitk_reduce(p, s, true);
     return hipSuccess;
 }
 

@@ -11,7 +11,7 @@
 // bytes; 512 threads; phase A one thread per 2x2 pixel quad (colour conversion + down-sampling), phase B one thread per
 // 8x8 block with the block in registers (384 blocks per crop, one round), phase C one thread per 2x2 quad again (up-sampling + colour
 // conversion + the crop / model-input stores). Off unless pa_set_crop_jpeg_quality was called.
-#include "pa_kernels.h"
+#include "tile_common.h"
 #include "jpeg_dct.h"
 
 namespace pa {
@@ -129,10 +129,7 @@ __global__ __launch_bounds__(512) void jpeg_roundtrip_kernel(const JpegParams p)
             const float f0 = (float)(p.bgr ? b : r) / 255.0f, f1 = (float)g / 255.0f, f2 = (float)(p.bgr ? r : b) / 255.0f;
             const size_t oo = ((size_t)crop * 134 + (y + 3)) * 134 + (x + 3);
             if (p.x0_bf16) {
-                uint32_t u[3] = {__float_as_uint(f0), __float_as_uint(f1), __float_as_uint(f2)};
-#pragma unroll
-                for (int k = 0; k < 3; ++k) u[k] = (u[k] + 0x7fffu + ((u[k] >> 16) & 1u)) >> 16;
-                reinterpret_cast<uint2*>(p.x0)[oo] = make_uint2(u[0] | (u[1] << 16), u[2]);
+                reinterpret_cast<uint2*>(p.x0)[oo] = make_uint2(pack_bf16x2(f0, f1), f32_to_bf16(f2));
             } else {
                 reinterpret_cast<float4*>(p.x0)[oo] = make_float4(f0, f1, f2, 0.f);
             }

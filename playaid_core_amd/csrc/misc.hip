@@ -3,7 +3,7 @@
 // the MLP + log-softmax + argmax tail. All are streaming / reduction work:
 // 16-byte accesses where the layout allows, wave64 shuffle reductions, no LDS
 // beyond one staged row.
-#include "pa_kernels.h"
+#include "tile_common.h"
 #include "../../include/playaid_hip.h"
 
 namespace pa {
@@ -24,10 +24,7 @@ __global__ __launch_bounds__(256) void nchw_to_padded_kernel(const float* __rest
         v.w = 0.f;
         const size_t o = ((size_t)img * 134 + (y + 3)) * 134 + (xx + 3);
         if (out_bf16) {  // bf16 conv path: the stem multiplies bf16 pixels (round to nearest even)
-            uint32_t u[3] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z)};
-#pragma unroll
-            for (int k = 0; k < 3; ++k) u[k] = (u[k] + 0x7fffu + ((u[k] >> 16) & 1u)) >> 16;
-            reinterpret_cast<uint2*>(out)[o] = make_uint2(u[0] | (u[1] << 16), u[2]);
+            reinterpret_cast<uint2*>(out)[o] = make_uint2(pack_bf16x2(v.x, v.y), f32_to_bf16(v.z));
         } else {
             reinterpret_cast<float4*>(out)[o] = v;
         }

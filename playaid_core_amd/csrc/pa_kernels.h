@@ -142,7 +142,8 @@ struct StemPoolParams {
     int32_t out_bf16;
 };
 hipError_t launch_stem_pool(const StemPoolParams& p, hipStream_t s);
-hipError_t launch_splitk_reduce(const GemmParams& p, hipStream_t s);
+// ordered split-K reduce of the slabs with the fused epilogue (igemm.hip); out_bf16: bf16 residual and output (igemm_bf16.hip)
+hipError_t launch_splitk_reduce(const GemmParams& p, hipStream_t s, bool out_bf16 = false);
 // stride-1 3x3 convolution with the input patch resident in LDS across the nine taps (patchconv.hip); bm = 128 | 64
 hipError_t launch_conv3x3_patch(const GemmParams& p, int bm, hipStream_t s);
 // the same kernel over rectangular blocks of output pixels (8 x 16, 8 x 8 or 4 x 4, whichever divides the map): any map whose

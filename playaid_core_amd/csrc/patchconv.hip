@@ -12,13 +12,13 @@
 // register ring two steps ahead. With no per-step stage there is no per-step barrier: ONE
 // barrier per 9 k-steps (288 MFMAs per wave at 128x64) when the patch buffers swap.
 //
-// Everything else follows igemm.hip: 2x2 waves over a BM x 64 tile, v_mfma_f32_32x32x2_f32,
+// Everything else follows igemm.hip, the shared pieces through tile_common.h: 2x2 waves over a BM x 64 tile, v_mfma_f32_32x32x2_f32,
 // 16-byte chunks XOR-swizzled by (pixel >> 1) & 7 on the DMA source so that ds_read_b128 of
 // consecutive pixels is conflict-free, fused bias / residual / ReLU epilogue, ordered split-K
 // over channel chunks. k is summed in (chunk, tap, channel) order -- a different rounding order
 // than igemm.hip's (tap, chunk, channel), equally deterministic. Layers with the fused 1x1/2
 // second source (block 0 conv2 of layers 2-4) and the stride-2 convs stay on igemm.hip.
-#include "pa_kernels.h"
+#include "tile_common.h"
 #ifdef PA_STAMP_BUILD
 #include <cstdio>
 #include <cstdlib>
@@ -27,34 +27,7 @@
 
 namespace pa {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// 16-byte global -> LDS DMA in its buffer form (buffer_load_dwordx4 ... offen lds): LDS
-// destination = wave-uniform `lds_base` + lane*16, source = descriptor base + voff + soff bytes.
-// The FLAT form (global_load_lds) makes hipcc treat every later wait as "a FLAT access may be
-// pending" and emit s_waitcnt vmcnt(0) lgkmcnt(0); with the MUBUF form the waits for the weight
-// ring stay counted (vmcnt(10) instead of a full drain twice per chunk).
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, int voff_bytes, int soff_bytes, float* lds_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voff_bytes,
-                                             soff_bytes, 0, 0);
-}
-
-__device__ __forceinline__ void split_m(const GemmParams& p, int m, int& img, int& oy, int& ox) {
-    if (p.howo_shift >= 0) {
-        img = m >> p.howo_shift;
-        const int rem = m & (p.howo - 1);
-        oy = rem >> p.wo_shift;
-        ox = rem & (p.wo - 1);
-    } else {
-        img = m / p.howo;
-        const int rem = m - img * p.howo;
-        oy = rem / p.wo;
-        ox = rem - oy * p.wo;
-    }
-}
 
 // m / d for 0 <= m < 2^24, 1 <= d < 2^16
 __device__ __forceinline__ int pc_div(int m, int d) {
@@ -99,11 +72,7 @@ __global__ __launch_bounds__(KS2 ? 512 : 256, 2) void conv3x3_patch_kernel(const
     const int half = KS2 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;
     float* const patch0 = pc_lds + half * 2 * PP;
 
-    // XCD-aware (bijective) remap: blocks with equal b % 8 share an XCD.
-    const int nwg = gridDim.x;
-    const int b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int tiles_mn = p.tiles_m * p.tiles_n;
     const int z = KS2 ? half : wg / tiles_mn;   // which share of K this group of four waves sums
     const int t_id = KS2 ? wg : wg - (wg / tiles_mn) * tiles_mn;
@@ -114,11 +83,7 @@ __global__ __launch_bounds__(KS2 ? 512 : 256, 2) void conv3x3_patch_kernel(const
         // A contiguous run of tiles gives an XCD 1/8 of the pixels and ALL channel columns = the whole filter bank
         // (layer 4: 9.4 MB of weights x 8 XCDs = 75 of the 85 MB fetched per launch, rocprofv3 FETCH_SIZE). Arranging
         // the XCDs as an xcd_m x xcd_n grid over (pixel tiles, channel tiles) fetches acts / xcd_m + weights / xcd_n each.
-        const int local = b >> 3;                      // this workgroup's rank inside its XCD
-        const int tn_per = p.tiles_n / p.xcd_n, tm_per = p.tiles_m / p.xcd_m;
-        const int lm = local / tn_per;
-        tile_m = (xcd / p.xcd_n) * tm_per + lm;
-        tile_n = (xcd % p.xcd_n) * tn_per + (local - lm * tn_per);
+        xcd_grid_tile(blockIdx.x & 7, blockIdx.x >> 3, p.xcd_m, p.xcd_n, p.tiles_m, p.tiles_n, tile_m, tile_n);
     }
 
     const int tid = threadIdx.x & 255;
@@ -186,18 +151,16 @@ __global__ __launch_bounds__(KS2 ? 512 : 256, 2) void conv3x3_patch_kernel(const
                          (ox * p.stride2 + p.off2) * p.in2_px_stride + colq * 4) * 4;
         }
     }
-    const __amdgpu_buffer_rsrc_t act2_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.act2 ? p.act2 : p.act), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t act2_rsrc = glds_rsrc(p.act2 ? p.act2 : p.act);
     // pass Q of the gathered tile of second-source step J into buffer PB
-#define PC_TILE2_PASS(J, PB, Q) blds16(act2_rsrc, a_off2[Q], (j0 + (J)) * 128, patch0 + (PB) * PP + (Q) * 1024 + wave_id * 256)
+#define PC_TILE2_PASS(J, PB, Q) glds16(act2_rsrc, a_off2[Q], (j0 + (J)) * 128, patch0 + (PB) * PP + (Q) * 1024 + wave_id * 256)
 
     // One DMA pass (32 pixels x 128 B, one piece per wave) of chunk CH's patch into buffer PB.
-    const __amdgpu_buffer_rsrc_t act_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.act), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t act_rsrc = glds_rsrc(p.act);
 #define PC_PATCH_PASS(CH, PB, Q)                                                                   \
     {                                                                                              \
     if (BLK) {                                                                                     \
-        blds16(act_rsrc, voffb[Q], (CH) * 128, patch0 + (PB) * PP + (Q) * 1024 + wave_id * 256);   \
+        glds16(act_rsrc, voffb[Q], (CH) * 128, patch0 + (PB) * PP + (Q) * 1024 + wave_id * 256);   \
     } else {                                                                                       \
         int px_ = p0 + row0 + 32 * (Q);                                                            \
         px_ = px_ < p.total_px ? px_ : p.total_px - 1;                                             \
@@ -206,7 +169,7 @@ __global__ __launch_bounds__(KS2 ? 512 : 256, 2) void conv3x3_patch_kernel(const
         const int rem_ = pp_ - im_ * p.img_px_patch;                                                   \
         const int rw_ = (rem_ * p.magic_pitch) >> 16;           /* its padded row and column */        \
         const int key_ = ((p.swz_a * (rw_ + band_row0) + rem_ - rw_ * p.patch_pitch) >> 1) & 7;        \
-        blds16(act_rsrc, (px_ * p.in_px_stride + ((tid & 7) ^ key_) * 4) * 4, (CH) * 128,              \
+        glds16(act_rsrc, (px_ * p.in_px_stride + ((tid & 7) ^ key_) * 4) * 4, (CH) * 128,              \
                patch0 + (PB) * PP + (Q) * 1024 + wave_id * 256);                                   \
     }                                                                                              \
     }
@@ -459,23 +422,8 @@ __global__ __launch_bounds__(KS2 ? 512 : 256, 2) void conv3x3_patch_kernel(const
             if (!direct_out) {
                 *reinterpret_cast<f32x4*>(p.slab + ((size_t)z * p.M + m) * p.N + ch0 + 8 * g) = v;
             } else {
-                if (BLK) {  // the detection network's epilogues: SiLU, residual after the activation
-                    v += p.res_after ? bias4[g] : bias4[g] + res4[g];
-                    if (p.relu == 1) {
-                        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-                        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-                    } else if (p.relu == 2) {
-                        v.x = silu_fast(v.x); v.y = silu_fast(v.y);
-                        v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-                    }
-                    if (p.res_after) v += res4[g];
-                } else {
-                    v += bias4[g] + res4[g];
-                    if (p.relu) {
-                        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-                        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-                    }
-                }
+                // BLK, the detection network's epilogues: SiLU, residual after the activation; else residual, then ReLU
+                v = BLK ? epilogue4(v, bias4[g], res4[g], p.relu, p.res_after) : epilogue4(v, bias4[g], res4[g], p.relu ? 1 : 0, 0);
                 *reinterpret_cast<f32x4*>(p.out + o_px + 8 * g) = v;
             }
         }
@@ -499,11 +447,7 @@ hipError_t launch_conv3x3_patch(const GemmParams& p_in, int bm, hipStream_t s) {
         p.k2_steps < 0 || p.k2_steps > 8 || p.k2_steps == 1 || p.ktot != 9 * p.chunk + 32 * p.k2_steps ||
         (p.k2_steps && !p.act2) || (bm != 128 && bm != 64))
         return hipErrorInvalidValue;
-    auto ilog2 = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
-    p.howo_shift = ilog2(p.howo);
-    p.wo_shift = ilog2(p.wo);
-    if (p.howo_shift < 0 || p.wo_shift < 0) p.howo_shift = p.wo_shift = -1;
-    const int ho = p.howo / p.wo;
+    fill_pow2_shifts(p);
     p.patch_pitch = p.in_row_stride / p.in_px_stride;  // W + 2
     p.img_px = p.in_img_stride / p.in_px_stride;       // (H + 2) * (W + 2)
     int patch_px;
@@ -522,7 +466,6 @@ hipError_t launch_conv3x3_patch(const GemmParams& p_in, int bm, hipStream_t s) {
         p.p0_row = 0;
         patch_px = imgs * p.img_px;
     }
-    (void)ho;
     p.patch_slots = (patch_px + 31) & ~31;  // whole 32-pixel DMA passes (no partially masked wave instruction)
     p.swz_a = p.wo & 15;
     p.magic_pitch = (65536 + p.patch_pitch - 1) / p.patch_pitch;  // x / pitch == (x * magic) >> 16 for x < 1024
@@ -538,12 +481,8 @@ hipError_t launch_conv3x3_patch(const GemmParams& p_in, int bm, hipStream_t s) {
     p.tiles_m = (p.M + bm - 1) / bm;
     p.tiles_n = p.N / 64;
     const int n_ch = p.chunk / 32;
-    if (p.splitk < 1) p.splitk = 1;
-    if (p.splitk > n_ch) p.splitk = n_ch;
-    p.ksteps_per_split = (n_ch + p.splitk - 1) / p.splitk;  // chunks per split
-    p.splitk = (n_ch + p.ksteps_per_split - 1) / p.ksteps_per_split;
+    plan_splitk(n_ch, p.splitk, p.ksteps_per_split);  // (chunks per split)
     if (p.patch_slots > (bm == 128 ? PatchCap<128>::slots : PatchCap<64>::slots)) return hipErrorInvalidValue;
-    const size_t lds_bytes = 0;
     // a two-way split of 64-row tiles is done inside 512-thread workgroups (no slabs, no reduce
     // kernel) when the chunks and second-source steps divide evenly; PA_PATCH_KS2=0 disables (A/B)
     static const int want_ks2 = getenv("PA_PATCH_KS2") ? atoi(getenv("PA_PATCH_KS2")) : 1;
@@ -553,24 +492,8 @@ hipError_t launch_conv3x3_patch(const GemmParams& p_in, int bm, hipStream_t s) {
         p.ksteps_per_split = n_ch / 2;
     }
     const int grid = p.tiles_m * p.tiles_n * p.splitk;
-    p.xcd_m = p.xcd_n = 0;
-    if (p.splitk == 1 && grid % 8 == 0) {
-        // bytes an XCD fetches for an (a x b) arrangement: input activations / a + weights / b; keep the default
-        // (a = 8: contiguous runs) unless another divisor pair is at least 10 % cheaper
-        const double act = (double)p.total_px * p.chunk * 4.0, wgt = (double)p.N * p.ktot * 4.0;
-        double best = act / 8 + wgt;
-        static const int use_grid = getenv("PA_XCD_GRID") ? atoi(getenv("PA_XCD_GRID")) : 1;
-        for (int a = 4; a >= 1 && use_grid; a >>= 1) {
-            const int bb = 8 / a;
-            if (p.tiles_m % a || p.tiles_n % bb) continue;
-            const double cost = act / a + wgt / bb;
-            if (cost < 0.9 * best) {
-                best = cost;
-                p.xcd_m = a;
-                p.xcd_n = bb;
-            }
-        }
-    }
+    static const int use_grid = getenv("PA_XCD_GRID") ? atoi(getenv("PA_XCD_GRID")) : 1;  // 0: contiguous runs always (A/B)
+    pick_xcd_grid(p, p.splitk == 1 && grid % 8 == 0 && use_grid);
 #ifdef PA_STAMP_BUILD
     // timeline stamps of every workgroup of launch number PA_STAMP_CALL, written to PA_STAMP_FILE
     static int stamp_calls = 0;
@@ -583,7 +506,7 @@ hipError_t launch_conv3x3_patch(const GemmParams& p_in, int bm, hipStream_t s) {
     }
 #endif
 #define PC_LAUNCH(BM_, K2_, KS2_, GRID_, THREADS_) \
-    hipLaunchKernelGGL((conv3x3_patch_kernel<BM_, K2_, KS2_>), dim3(GRID_), dim3(THREADS_), lds_bytes, s, p)
+    hipLaunchKernelGGL((conv3x3_patch_kernel<BM_, K2_, KS2_>), dim3(GRID_), dim3(THREADS_), 0, s, p)
     if (ks2) {
         if (p.k2_steps) PC_LAUNCH(64, true, true, grid, 512); else PC_LAUNCH(64, false, true, grid, 512);
     } else if (bm == 128) {
@@ -628,9 +551,8 @@ hipError_t launch_conv3x3_patch_blocked(const GemmParams& p_in, hipStream_t s) {
     else if (p.wo % 8 == 0 && ho % 8 == 0) { br = 8; bc = 8; bm = ((p.M + 127) / 128) * (p.N / 64) >= 512 || bn == 32 ? 128 : 64; }
     else if (p.wo % 4 == 0 && ho % 4 == 0 && bn == 64) { br = 4; bc = 4; bm = 64; }
     else return hipErrorInvalidValue;
-    auto ilog2 = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return sh; };
     p.blk_rows = br; p.blk_cols = bc;
-    p.blk_shift_c = ilog2(bc); p.blk_shift_px = ilog2(br * bc);
+    p.blk_shift_c = ilog2_exact(bc); p.blk_shift_px = ilog2_exact(br * bc);
     p.blk_per_row = p.wo / bc;
     p.blk_per_img = (ho / br) * p.blk_per_row;
     p.n_blocks = p.M / (br * bc);
@@ -652,17 +574,7 @@ hipError_t launch_conv3x3_patch_blocked(const GemmParams& p_in, hipStream_t s) {
     p.splitk = 1;
     p.ksteps_per_split = p.chunk / 32;
     const int grid = p.tiles_m * p.tiles_n;
-    p.xcd_m = p.xcd_n = 0;
-    if (grid % 8 == 0) {  // (as launch_conv3x3_patch: the XCDs as a grid over pixel and channel tiles when that fetches less)
-        const double act = (double)p.total_px * p.chunk * 4.0, wgt = (double)p.N * p.ktot * 4.0;
-        double best = act / 8 + wgt;
-        for (int a = 4; a >= 1; a >>= 1) {
-            const int bb = 8 / a;
-            if (p.tiles_m % a || p.tiles_n % bb) continue;
-            const double cost = act / a + wgt / bb;
-            if (cost < 0.9 * best) { best = cost; p.xcd_m = a; p.xcd_n = bb; }
-        }
-    }
+    pick_xcd_grid(p, grid % 8 == 0);
     if (bn == 32) hipLaunchKernelGGL((conv3x3_patch_kernel<128, false, false, true, 32>), dim3(grid), dim3(256), 0, s, p);
     else if (bm == 128) hipLaunchKernelGGL((conv3x3_patch_kernel<128, false, false, true>), dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((conv3x3_patch_kernel<64, false, false, true>), dim3(grid), dim3(256), 0, s, p);

@@ -4,7 +4,8 @@
 // igemm_bf16.hip stages an im2col tile and a weight tile per 64-deep k-step, so every activation
 // byte crosses L2 -> LDS nine times and a 128 x 64 tile pays 24 KB of LDS fill for 8 matrix
 // instructions per wave: the matrix pipe idles at ~0.19 (rocprofv3, round 1). This kernel turns the
-// K loop inside out like the fp32 patch kernel (patchconv.hip), with what bf16 rates demand on top:
+// K loop inside out like the fp32 patch kernel (patchconv.hip; the pieces both share with the im2col kernels are
+// tile_common.h's), with what bf16 rates demand on top:
 //
 //  * tile = 64*WAVES output pixels x 64 output channels; one wave = 64 pixels x 64 channels
 //    (2 x 2 accumulators of v_mfma_f32_32x32x16_bf16): the weight stage of a k-step is shared by
@@ -26,46 +27,11 @@
 //    (keys brute-forced by scripts/lds_swizzle_search.py).
 //
 // fp32 accumulation, bias + residual + ReLU in fp32, one rounding to bf16 at the store.
-#include "pa_kernels.h"
+#include "tile_common.h"
 
 namespace pa {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint16_t bf16_t;  // storage
-
 namespace {
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int voff_bytes, int soff_bytes, uint8_t* lds_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voff_bytes,
-                                             soff_bytes, 0, 0);
-}
-
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {  // round to nearest even (finite inputs)
-    uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
-    ua += 0x7fffu + ((ua >> 16) & 1u);
-    ub += 0x7fffu + ((ub >> 16) & 1u);
-    return (ua >> 16) | (ub & 0xffff0000u);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    // counted wait: all but the N youngest vector-memory operations of this wave are done
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-}
 
 // Geometry of one map width. A tile is 64*WAVES consecutive output pixels in (image, row, column)
 // raster order: a band of rows of one image (W = 32), or whole images (W <= 16).
@@ -133,10 +99,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_bf16_patch_kernel(const Ge
     // XCD-aware (bijective) remap: blocks with equal b % 8 share an XCD and get a contiguous run of work
     // items; item v = (tile group, channel column): the columns of one tile group sit on one XCD (they
     // read the same patches), the weights of a column stay in that XCD's L2 for the whole group.
-    const int nwg = gridDim.x;
-    const int b = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7;
-    const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
+    const int v = xcd_remap(blockIdx.x, gridDim.x);
     const int grp = v / p.tiles_n;
     const int tile_n = v - grp * p.tiles_n;
     const int tile_first = grp * p.tiles_per_img;                      // (field reused: tiles per workgroup)
@@ -150,9 +113,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_bf16_patch_kernel(const Ge
     const int lr = lane & 31, lh = lane >> 5;
 
     // out-of-range bytes of the activation buffer (the last tile's patch pieces run past it) read as zero
-    const __amdgpu_buffer_rsrc_t act_rs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.act), 0, p.total_px * C * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wgt), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t act_rs = glds_rsrc(p.act, p.total_px * C * 2);
+    const __amdgpu_buffer_rsrc_t wgt_rs = glds_rsrc(p.wgt);
 
     // byte offset of tile t's patch origin (its first padded pixel) in the activation buffer
     auto patch_origin = [&](int t) -> int {
@@ -208,11 +170,11 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_bf16_patch_kernel(const Ge
                 const int kx_ = job_ / NGRP, grp_ = job_ - kx_ * NGRP;                                               \
                 const int n_ = 16 * grp_ + (lane >> 2);                                                              \
                 const int voff_ = wvoff_base + 16 * grp_ * p.ktot * 2 + (((lane & 3) ^ ((n_ >> 2) & 3)) << 4);       \
-                dma16(wgt_rs, voff_, (((KY) * 3 + kx_) * C + (CH) * 32) * 2, wring + (SLOT) * WSTAGE_BYTES + job_ * 1024); \
+                glds16(wgt_rs, voff_, (((KY) * 3 + kx_) * C + (CH) * 32) * 2, wring + (SLOT) * WSTAGE_BYTES + job_ * 1024); \
             } else {                                                                                                 \
                 int q_ = job_ - NWJ + (HALF_IDX) * HALF;                                                             \
                 q_ = q_ < G::NPIECE ? q_ : G::NPIECE - 1;                                                            \
-                dma16(act_rs, pvoff[HALF_IDX][i_], (PSOFF), lds + (PB) * G::PATCH_BYTES + q_ * 1024);                \
+                glds16(act_rs, pvoff[HALF_IDX][i_], (PSOFF), lds + (PB) * G::PATCH_BYTES + q_ * 1024);                \
             }                                                                                                        \
         }                                                                                                            \
     }
@@ -291,22 +253,22 @@ __global__ __launch_bounds__(64 * WAVES) void conv3x3_bf16_patch_kernel(const Ge
     // ---- prologue: patch of the first tile's chunk 0, weight stages 0 and 1 ----------------------------
     {
         const int ps0 = patch_origin(tile_first);
-        for (int q = wave; q < G::NPIECE; q += WAVES) dma16(act_rs, patch_voff(q), ps0, lds + q * 1024);
+        for (int q = wave; q < G::NPIECE; q += WAVES) glds16(act_rs, patch_voff(q), ps0, lds + q * 1024);
         if constexpr (WRES) {
             // the whole filter bank: piece j = (chunk * 9 + tap) * 4 + group of 16 output channels
             for (int j = wave; j < 2 * 9 * 4; j += WAVES) {
                 const int tc = j >> 2, grp_ = j & 3, chn = tc / 9, tap = tc - chn * 9;
                 const int n = 16 * grp_ + (lane >> 2);
                 const int voff = wvoff_base + 16 * grp_ * p.ktot * 2 + (((lane & 3) ^ ((n >> 2) & 3)) << 4);
-                dma16(wgt_rs, voff, (tap * C + chn * 32) * 2, wring + j * 1024);
+                glds16(wgt_rs, voff, (tap * C + chn * 32) * 2, wring + j * 1024);
             }
         } else {
             for (int job = wave; job < NWJ; job += WAVES) {
                 const int kx = job / NGRP, grp_ = job - kx * NGRP;
                 const int n = 16 * grp_ + (lane >> 2);
                 const int voff = wvoff_base + 16 * grp_ * p.ktot * 2 + (((lane & 3) ^ ((n >> 2) & 3)) << 4);
-                dma16(wgt_rs, voff, ((0 * 3 + kx) * C) * 2, wring + 0 * WSTAGE_BYTES + job * 1024);
-                dma16(wgt_rs, voff, ((1 * 3 + kx) * C) * 2, wring + 1 * WSTAGE_BYTES + job * 1024);
+                glds16(wgt_rs, voff, ((0 * 3 + kx) * C) * 2, wring + 0 * WSTAGE_BYTES + job * 1024);
+                glds16(wgt_rs, voff, ((1 * 3 + kx) * C) * 2, wring + 1 * WSTAGE_BYTES + job * 1024);
             }
         }
         wait_vmcnt<0>();

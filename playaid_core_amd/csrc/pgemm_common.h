@@ -4,6 +4,7 @@
 // own matrix loop, LDS layout, epilogue and launcher.
 #pragma once
 #include "conv_rows.h"
+#include "tile_common.h"
 
 #include <algorithm>
 #include <cstring>

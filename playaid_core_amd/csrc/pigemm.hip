@@ -25,23 +25,16 @@
 
 namespace pa {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float lds_f32;
 typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
 
-// 16 bytes per lane, HBM/L2 -> LDS: voff = the lane's byte offset (a register that lives as long as the tile), soff = the
-// k-step's byte offset (scalar): no vector instruction between two copies
-__device__ __forceinline__ void pg_dma16(__amdgpu_buffer_rsrc_t rsrc, int voff_bytes, int soff_bytes, float* lds_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, voff_bytes, soff_bytes, 0, 0);
-}
-
+// The copies are tile_common.h's glds16 (the builtin): voff = the lane's byte offset (a register that lives as long as the tile),
+// soff = the k-step's byte offset (scalar): no vector instruction between two copies.
 // (vmcnt is six bits: a count past 63 waits at 63 -- for more than it must, never for less)
-template <int N> __device__ __forceinline__ void pg_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N > 63 ? 63 : N) : "memory"); }
+template <int N> __device__ __forceinline__ void pg_wait_vm() { wait_vmcnt<(N > 63 ? 63 : N)>(); }
 
 }  // namespace
 
@@ -104,8 +97,7 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     const int lane = tid & 63, lr = lane & 31, lh = lane >> 5;
     const int wm = BN == 64 ? wave_id >> 1 : wave_id, wn = BN == 64 ? wave_id & 1 : 0;
 
-    const __amdgpu_buffer_rsrc_t act_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.act), 0, -1, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wgt), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t act_rs = glds_rsrc(p.act), wgt_rs = glds_rsrc(p.wgt);
 
     const int ch0 = tile_n * BN + wn * 32 + 4 * lh;
     f32x2 nl2e = f32x2{-1.44269504088896341f, -1.44269504088896341f}, one2 = f32x2{1.f, 1.f};
@@ -158,10 +150,10 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
         float* Bs_w = As_w + BM * 32;
         const int tapoff = cur.tap_offset(p) * 4;
 #pragma unroll
-        for (int i = 0; i < A_ROWS; ++i) pg_dma16(act_rs, a_off[i], tapoff, As_w + i * 1024);
+        for (int i = 0; i < A_ROWS; ++i) glds16(act_rs, a_off[i], tapoff, As_w + i * 1024);
         const int koff = ((cur.ky * p.kw_taps + cur.kx) * p.chunk + cur.kc) * 4;
 #pragma unroll
-        for (int i = 0; i < B_ROWS; ++i) pg_dma16(wgt_rs, b_off[i], koff, Bs_w + i * 1024);
+        for (int i = 0; i < B_ROWS; ++i) glds16(wgt_rs, b_off[i], koff, Bs_w + i * 1024);
         cur.advance(p, nk, run, rows_of);
     };
 

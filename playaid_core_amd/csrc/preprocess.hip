@@ -23,7 +23,7 @@
 // element, consecutive lanes on consecutive bytes. Five small kernels keep every
 // size general (any box, any frame): a fused LDS kernel for crops whose bands fit 48 KB,
 // a multi-pass fallback over global scratch for the rest.
-#include "pa_kernels.h"
+#include "tile_common.h"
 #ifdef PA_STAMP_BUILD
 #include <cstdio>
 #include <vector>
@@ -679,10 +679,7 @@ __device__ __forceinline__ void write_crop_pixel(const PreprocParams& p, int cro
         const int dy = i >> 7, dx = i & 127;
         const size_t o = ((size_t)crop * 134 + (dy + 3)) * 134 + (dx + 3);
         if (p.crops_f32_is_bf16) {  // bf16 conv path: the /255 quotient rounded to bf16 (nearest even)
-            uint32_t u[3] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z)};
-#pragma unroll
-            for (int k = 0; k < 3; ++k) u[k] = (u[k] + 0x7fffu + ((u[k] >> 16) & 1u)) >> 16;
-            reinterpret_cast<uint2*>(p.crops_f32)[o] = make_uint2(u[0] | (u[1] << 16), u[2]);
+            reinterpret_cast<uint2*>(p.crops_f32)[o] = make_uint2(pack_bf16x2(v.x, v.y), f32_to_bf16(v.z));
         } else {
             reinterpret_cast<float4*>(p.crops_f32)[o] = v;
         }

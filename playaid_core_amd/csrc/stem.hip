@@ -17,7 +17,7 @@
 //     address, because the DMA destination is lane-linear), which makes the reads conflict-free.
 // The summation order (ky, pixel pair, channel) is the one igemm.hip uses for the stem, so the
 // two kernels produce bit-identical outputs.
-#include "pa_kernels.h"
+#include "tile_common.h"
 #ifdef PA_STAMP_BUILD
 #include <cstdio>
 #include <cstdlib>
@@ -25,9 +25,6 @@
 #endif
 
 namespace pa {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -39,12 +36,6 @@ constexpr int PATCH_ROWS = 9;              // 2 output rows x stride 2 + 7 taps 
 constexpr int PATCH_CH = PATCH_ROWS * IN_W;  // 16-byte chunks per patch (1206)
 constexpr int STAGE_CH = 1280;             // chunks per LDS stage (5 passes of 256 lanes)
 constexpr int KTOT = 224;                  // weight row stride of the igemm layout (7 ky x 32)
-
-// 16-byte global -> LDS DMA, buffer form (see igemm.hip: behind the FLAT form hipcc turns every
-// later wait into vmcnt(0) lgkmcnt(0)); source = descriptor base + `off` floats.
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rsrc, int off, float* lds_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, off * 4, 0, 0, 0);
-}
 
 }  // namespace
 
@@ -69,11 +60,9 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemParams p) {
     // XCD-aware start: workgroups b and b+8 share an XCD; give each XCD a contiguous run of
     // tiles per sweep so neighbouring row pairs (which share 5 of 9 input rows) meet in one L2.
     const int nwg = gridDim.x;
-    const int b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = b & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+    const int wg = xcd_remap(blockIdx.x, nwg);
 
-    const __amdgpu_buffer_rsrc_t x_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x_rs = glds_rsrc(p.x);  // (LDS-DMA in its buffer form: tile_common.h)
 #define PA_STEM_ISSUE(TILE, BUF)                                                                   \
     {                                                                                              \
         const int img_ = (TILE) >> 5, oy0_ = ((TILE) & 31) * 2;                                    \
@@ -81,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemParams p) {
         float* dst_ = lds + (BUF) * (STAGE_CH * 4) + wave_id * 256;                                \
         _Pragma("unroll") for (int i = 0; i < 5; ++i) {                                            \
             const int j = tid + 256 * i;                                                           \
-            if (j < PATCH_CH) glds16(x_rs, src_ + (j ^ ((j >> 4) & 1)) * 4, dst_ + i * 1024);      \
+            if (j < PATCH_CH) glds16(x_rs, (src_ + (j ^ ((j >> 4) & 1)) * 4) * 4, 0, dst_ + i * 1024); \
         }                                                                                          \
     }
 
@@ -173,13 +162,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemParams p) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(tbuf + row * TS + c4);
                 const size_t o = ((size_t)img * OUT_W * OUT_W + (size_t)(oy0 + (row >> 6) + 1) * OUT_W + (row & 63) + 1) * COUT + c4;
                 if (p.out_bf16) {  // bf16 conv path: round to nearest even, 4 channels = 8 bytes
-                    uint32_t u[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) u[k] = (u[k] + 0x7fffu + ((u[k] >> 16) & 1u)) >> 16;
-                    uint2 pk;
-                    pk.x = u[0] | (u[1] << 16);
-                    pk.y = u[2] | (u[3] << 16);
-                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.out) + o) = pk;
+                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.out) + o) = make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w));
                 } else {
                     *reinterpret_cast<f32x4*>(p.out + o) = v;
                 }

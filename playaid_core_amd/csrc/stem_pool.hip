@@ -15,14 +15,9 @@
 // maxpool_kernel. BF16 = true (the bf16 conv path, BASELINE.json configs[2]) takes the crop as bf16
 // NHWC4 pixels and multiplies on v_mfma_f32_32x32x16_bf16: 28 matrix instructions per tile and wave
 // instead of 168 fp32 ones (consecutive lanes then read consecutive 16-byte chunks: no swizzle needed).
-#include "pa_kernels.h"
+#include "tile_common.h"
 
 namespace pa {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -37,10 +32,6 @@ template <bool BF16> struct StemGeom {
     static constexpr int PASSES = (PATCH_CH + 255) / 256;
     static constexpr int STAGE_CH = PASSES * 256;
 };
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, int off_bytes, float* lds_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_base, 16, off_bytes, 0, 0, 0);
-}
 
 __device__ __forceinline__ f32x4 max4(f32x4 a, f32x4 b) {
     return f32x4{fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)};
@@ -66,13 +57,11 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
     // XCD-aware order of the runs: workgroups b and b+8 share an XCD; neighbouring runs (same crop, shared
     // halo rows) meet in one L2
     const int nwg = gridDim.x;
-    const int b = blockIdx.x;
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = b & 7;
-    const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (b >> 3);
+    const int wg = xcd_remap(blockIdx.x, nwg);
     const int runs_per_crop = 32 / p.run;
     const int runs_total = p.crops * runs_per_crop;
 
-    const __amdgpu_buffer_rsrc_t x_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, -1, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x_rs = glds_rsrc(p.x);
     // patch of row pair R of crop IMG -> stage BUF (chunk j of the patch lands in LDS chunk j; the fp32 image is
     // XOR-swizzled on the source side, see stem.hip)
 #define SP_ISSUE(IMG, R, BUF)                                                                      \
@@ -82,7 +71,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
         _Pragma("unroll") for (int i = 0; i < G::PASSES; ++i) {                                    \
             const int j = tid + 256 * i;                                                           \
             const int js = BF16 ? j : (j ^ ((j >> 4) & 1));                                        \
-            if (j < G::PATCH_CH) dma16(x_rs, (src_ + js) * 16, dst_ + i * 1024);                   \
+            if (j < G::PATCH_CH) glds16(x_rs, (src_ + js) * 16, 0, dst_ + i * 1024);               \
         }                                                                                          \
     }
 
@@ -238,13 +227,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
                 if (store) {
                     const size_t o = (((size_t)crop * POOL_W + rr + 1) * POOL_W + px + 1) * COUT + c4;
                     if (p.out_bf16) {  // round to nearest even, 4 channels = 8 bytes
-                        uint32_t u[4] = {__float_as_uint(m.x), __float_as_uint(m.y), __float_as_uint(m.z), __float_as_uint(m.w)};
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) u[k] = (u[k] + 0x7fffu + ((u[k] >> 16) & 1u)) >> 16;
-                        uint2 pk;
-                        pk.x = u[0] | (u[1] << 16);
-                        pk.y = u[2] | (u[3] << 16);
-                        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.out) + o) = pk;
+                        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.out) + o) = make_uint2(pack_bf16x2(m.x, m.y), pack_bf16x2(m.z, m.w));
                     } else {
                         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + o) = m;
                     }

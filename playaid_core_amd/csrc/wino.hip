@@ -48,7 +48,7 @@
 // image's result is independent of the batch size only while no split engages (layers 1-2 of the ResNet); where it does
 // (layers 3-4 at 64-128 crops) the input channels are summed in a different grouping at different batch sizes and an image's
 // values move by fp32 rounding (bounded at 2e-5 by tests/test_wino.py::test_wino_split_k_results_move_by_rounding_only_across_batch_sizes).
-#include "pa_kernels.h"
+#include "tile_common.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -56,14 +56,12 @@
 
 namespace pa {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #ifndef WN_SCALAR_T
 #define WN_SCALAR_T 0   // 1: the input transform as scalar additions (A/B build; profiles/r06_wino_scalar_transform_ab.txt)
 #endif
 #ifndef WN_AHEAD
 #define WN_AHEAD 3   // positions the row-operand reads run ahead of their matrix instructions (2 and 5 measure the same: profiles/r05_wino_operand_read_variants.txt)
 #endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float lds_f;
 typedef __attribute__((address_space(3))) const volatile f32x2 lds_cv2;  // an LDS read hipcc may not merge with its neighbour
 
@@ -216,11 +214,6 @@ __device__ __forceinline__ void wino_chunk(const lds_f* ul, const lds_f* pl, f32
 #undef WN_LOAD_A
 }
 
-template <int N> __device__ __forceinline__ void wn_wait_vmcnt() {
-    static_assert(N >= 0 && N < 64, "vmcnt is six bits");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // NST: stages of the LDS ring (3 where they fit: the DMA of chunk c + 2 is issued during chunk c, so the wait in front of a
 // barrier is for copies issued a whole chunk earlier)
 // (four-wave workgroups: two per CU -- without the bound hipcc spreads the kernel over 330 registers and one fits)
@@ -248,9 +241,7 @@ __global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 ? 2 : 1) void wino3x
 
     // XCD-aware (bijective) remap: the workgroups of an XCD are a contiguous run of (tile_m, tile_n), channel tiles fastest,
     // so the channel tiles that read one patch meet in one L2
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r8 = nwg & 7, xcd = b & 7;
-    const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (b >> 3);
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     // split K (p.ksplit > 1; layers with too few tiles to fill the chip): ksplit consecutive workgroups share a tile, each sums
     // its run of n_chunks channel chunks; the partial OUTPUT tiles meet in the epilogue (the output transform is linear)
     const int ksn = p.ksplit > 1 ? p.ksplit : 1;
@@ -260,12 +251,11 @@ __global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 ? 2 : 1) void wino3x
         // The 8 XCDs as a grid of xcd_gm x xcd_gn over (pixel tiles, channel tiles): an XCD's L2 then fetches 1 / xcd_gn of the
         // filters and 1 / xcd_gm of the patches (in launch order it fetches ALL filters on a layer with few pixel tiles -- 134 MB
         // per layer-4 launch of ResNet-18 at 128 crops). The splits of a tile stay neighbours inside one XCD, channel tiles fastest.
-        const int tm_per = p.tiles_m / p.xcd_gm, tn_per = p.tiles_n / p.xcd_gn, local = b >> 3;
-        const int xm = xcd / p.xcd_gn, xn = xcd - xm * p.xcd_gn;
+        const int local = blockIdx.x >> 3;
         ks = local % ksn;
-        const int r = local / ksn;
-        const int tm_l = r / tn_per;
-        wgt_ = (xm * tm_per + tm_l) * p.tiles_n + xn * tn_per + (r - tm_l * tn_per);
+        int gm_, gn_;
+        xcd_grid_tile(blockIdx.x & 7, local / ksn, p.xcd_gm, p.xcd_gn, p.tiles_m, p.tiles_n, gm_, gn_);
+        wgt_ = gm_ * p.tiles_n + gn_;
     }
     const int tile_m = wgt_ / p.tiles_n, tile_n = wgt_ - tile_m * p.tiles_n;
     const int n_chunks = (p.cin >> 3) / (p.ksplit > 1 ? p.ksplit : 1);
@@ -361,7 +351,7 @@ __global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 ? 2 : 1) void wino3x
         acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // chunk 0 landed (the copies of chunk 1, if any, stay in flight)
-    if (D == 2 && n_chunks > 1) wn_wait_vmcnt<KD>(); else wn_wait_vmcnt<0>();
+    if (D == 2 && n_chunks > 1) wait_vmcnt<KD>(); else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
 
     float* const ust[3] = {u_lds0, u_lds1, u_lds2};
@@ -400,7 +390,7 @@ __global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 ? 2 : 1) void wino3x
             if (c + 1 < n_chunks) {
                 // chunk c + 1 has landed for this thread (what was issued behind it stays in flight); behind the barrier it has
                 // for every thread, and every wave is done with the stage the next chunk's issue overwrites
-                if (D == 2 && more) wn_wait_vmcnt<KD>(); else wn_wait_vmcnt<0>();
+                if (D == 2 && more) wait_vmcnt<KD>(); else wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();
             }
         }
@@ -511,15 +501,7 @@ __global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 ? 2 : 1) void wino3x
             for (int ox = 0; ox < 2; ++ox) {
                 const long o = o00 + (long)oy * p.out_row_stride + ox * p.out_px_stride + 16 * g;
                 const f32x4 r4 = res4[g][oy][ox];
-                f32x4 v = y[g][oy][ox] + (p.res_after ? bias4 : bias4 + r4);
-                if (p.relu == 1) {
-                    v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-                    v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-                } else if (p.relu == 2) {
-                    v.x = silu_fast(v.x); v.y = silu_fast(v.y);
-                    v.z = silu_fast(v.z); v.w = silu_fast(v.w);
-                }
-                if (p.res_after) v += r4;
+                const f32x4 v = epilogue4(y[g][oy][ox], bias4, r4, p.relu, p.res_after);
                 if ((ABL & 32) && v.x != 12345.678f) continue;
                 *reinterpret_cast<f32x4*>(p.out + o) = v;
             }

@@ -245,7 +245,7 @@ def run_case(eng, sd, n, seed):
     return res
 
 
-CASES = {136: [1, 35, 136], 18: [18]}
+CASES = {136: [1, 3, 35, 136], 18: [5, 18]}   # 3 and 5 crops: layer 4 has 48 and 80 pixels -- a last tile partly out of range, tile counts that are no multiple of 8
 
 
 @pytest.mark.gpu
