@@ -932,6 +932,57 @@ int pa_eval_update(pa_eval* h, const float* logp_dev, int32_t ld, int32_t n, con
                    void* stream);
 int pa_eval_read(pa_eval* h, pa_eval_totals* totals_host, int64_t* confusion_host, void* stream);
 
+/* ---- annotation --------------------------------------------------------- */
+
+/* Draws the reference annotator's boxes and labels (playaid/annotator.py:79-145, box_label's Pillow branch -- the one
+ * Manuscript.render always takes, because set_frame's default `example` is not ASCII) on frames in HBM and pads them
+ * (maybe_pad_image's np.pad, :300-363) in the same pass: ONE launch per call copies n frames and paints what the draw
+ * lists touch. Append-only like the scoring calls above: PA_ABI_VERSION stays 15, no existing layout changes.
+ *
+ * frames_in uint8[n][H][W][3] BGR (device) -> frames_out uint8[n][H + pad_bottom][pad_left + W + pad_right][3] BGR
+ * (device, a different buffer; the padding is zeros). items[n][PA_ANNOT_MAX_ITEMS], counts[n] and text[text_bytes] are
+ * HOST arrays, checked and copied by the call (a handle keeps four calls' lists in flight and waits for the oldest
+ * before it takes a fifth, so calls may go to any streams; the handle itself is not thread-safe).
+ *
+ * An item is one box_label call. Per item, on the device (Pillow's ImageDraw, pinned against Pillow 12.2):
+ *   1. draw_box and line_width > 0: ImageDraw.rectangle(box, outline=rgb, width=line_width) -- in WHITE without has_color
+ *      (outline=None makes ImageDraw fall back to its default ink). For a box
+ *      at least 2 * line_width on a side that is line_width nested one-pixel frames; for thinner ones Pillow's
+ *      vertical strokes run between y0 + width and y1 - width + 1 whichever way round, and may leave the box
+ *      (csrc/annotate.hip states the rule). A reversed box is drawn as Pillow's C routine draws it (rows swapped);
+ *      current Pillow refuses such a box before it gets there, and so does playaid_core_amd/annotator.py.
+ *   2. text_len > 0: w = cell_w * text_len, h = cell_h, outside = box[1] - h >= 0, y = outside ? box[1] - h : box[1];
+ *      has_color: ImageDraw.rectangle((box[0], y, box[0] + w + 1, y + h + 1), fill=rgb), both corners inclusive;
+ *      then the text at (box[0], y) in WHITE (the reference's Pillow branch ignores txt_color): cell k of the string is
+ *      atlas[text[k]][text[k + 1]], the last one atlas[text[k]][n_chars] -- Pillow's bitmap font lets the next
+ *      character decide a cell's last column.
+ * Everything is clipped to the INPUT frame area; items are painted in list order, a later one over an earlier one.
+ * A colour (r, g, b) lands in the BGR frame as (b, g, r): the reference draws RGB on RGBA and converts on write.
+ *
+ * atlas: uint8[n_chars][n_chars + 1][cell_h][cell_w] (host; non-zero = ink), uploaded by pa_annot_create; text holds
+ * character codes first_char .. first_char + n_chars - 1. PA_ERR_INVALID_ARG, before any device work, for: null
+ * pointers, n < 0 or H, W < 1 or a negative pad or an output side above 32768, frames_in == frames_out, a count
+ * outside 0..max_items, line_width outside 0..32767, a text range outside text_bytes, text_bytes > max_text, a
+ * character code outside the atlas; PA_ERR_CAPACITY for n > max_frames. n == 0 is a no-op. Enqueue only. */
+#define PA_ANNOT_MAX_ITEMS 16
+typedef struct pa_annot pa_annot;
+typedef struct pa_annot_item {
+    int32_t box[4];      /* x0, y0, x1, y1 as given to box_label: any values (taken as clamped to +-2^29) */
+    int32_t draw_box;    /* 0 / 1 */
+    int32_t line_width;
+    int32_t has_color;   /* 0 = box_label(color=None): no background, white text, and a WHITE outline if draw_box */
+    int32_t text_off;    /* first character of the label in `text` */
+    int32_t text_len;    /* 0 = no label */
+    uint8_t rgb[3];
+    uint8_t reserved;
+} pa_annot_item;
+int pa_annot_create(int32_t device, const uint8_t* atlas_host, int32_t cell_w, int32_t cell_h, int32_t first_char, int32_t n_chars,
+                    int32_t max_frames, int32_t max_items, int32_t max_text, pa_annot** out);
+int pa_annotate_frames(pa_annot* h, const uint8_t* frames_in, int32_t n, int32_t height, int32_t width, const pa_annot_item* items_host,
+                       const int32_t* counts_host, const uint8_t* text_host, int32_t text_bytes, int32_t pad_left, int32_t pad_right,
+                       int32_t pad_bottom, uint8_t* frames_out, void* stream);
+void pa_annot_destroy(pa_annot* h);
+
 #ifdef __cplusplus
 }
 #endif

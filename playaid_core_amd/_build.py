@@ -42,6 +42,7 @@ SOURCES = [
     ("jpegenc.hip", ["-ffp-contract=off"]),
     ("jpegdec.hip", []),
     ("yolo.hip", ["-ffp-contract=off"]),
+    ("annotate.hip", []),
     ("pa_api.hip", []),
 ]
 

@@ -39,6 +39,7 @@ PA_ERR_NO_DEVICE = -5
 PA_ERR_NOT_READY = -6
 PA_ERR_BAD_LABELS = -7
 PA_EVAL_IGNORE = -100
+PA_ANNOT_MAX_ITEMS = 16
 
 PA_CROP_OK = 0
 PA_CROP_EMPTY = 1
@@ -106,6 +107,11 @@ class pa_net_layer(C.Structure):
 class pa_eval_totals(C.Structure):
     _fields_ = [("rows", C.c_int64), ("correct", C.c_int64), ("ignored", C.c_int64), ("bad_labels", C.c_int64),
                 ("nll_sum", C.c_double), ("conf_sum", C.c_double)]
+
+
+class pa_annot_item(C.Structure):
+    _fields_ = [("box", C.c_int32 * 4), ("draw_box", C.c_int32), ("line_width", C.c_int32), ("has_color", C.c_int32),
+                ("text_off", C.c_int32), ("text_len", C.c_int32), ("rgb", C.c_uint8 * 3), ("reserved", C.c_uint8)]
 
 
 class pa_kernel_stat(C.Structure):
@@ -242,6 +248,9 @@ SYMBOLS = [
     ("pa_eval_reset", C.c_int, [_P, _P]),
     ("pa_eval_update", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     ("pa_eval_read", C.c_int, [_P, C.POINTER(pa_eval_totals), _P, _P]),
+    ("pa_annot_create", C.c_int, [C.c_int32, _P] + [C.c_int32] * 7 + [C.POINTER(_P)]),
+    ("pa_annotate_frames", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P] + [C.c_int32] * 4 + [_P, _P]),
+    ("pa_annot_destroy", None, [_P]),
 ]
 
 _lib = None

@@ -1927,3 +1927,127 @@ int pa_eval_read(pa_eval* h, pa_eval_totals* totals_host, int64_t* confusion_hos
 }
 
 }  // extern "C"
+
+// ===============================================================================
+// Annotation (csrc/annotate.hip): a handle of its own, owned by no engine
+// ===============================================================================
+
+// A call's draw lists are staged through one of PA_ANNOT_SLOTS (pinned host + device) buffers; a slot is taken again only
+// after the event behind the launch that read it, so calls on several streams never share a list.
+constexpr int PA_ANNOT_SLOTS = 4;
+
+struct pa_annot {
+    int cell_w = 0, cell_h = 0, first_char = 0, n_chars = 0, max_frames = 0, max_items = 0, max_text = 0;
+    unsigned char* atlas = nullptr;
+    size_t items_bytes = 0, counts_bytes = 0, slot_bytes = 0;  // slot: items | counts | text
+    unsigned char* host[PA_ANNOT_SLOTS] = {};
+    unsigned char* dev[PA_ANNOT_SLOTS] = {};
+    hipEvent_t done[PA_ANNOT_SLOTS] = {};
+    bool used[PA_ANNOT_SLOTS] = {};
+    int next = 0;
+};
+
+static_assert(sizeof(pa_annot_item) == 40, "pa_annot_item is nine int32 and four bytes (playaid_core_amd/_lib.py mirrors it)");
+
+extern "C" {
+
+int pa_annot_create(int32_t device, const uint8_t* atlas_host, int32_t cell_w, int32_t cell_h, int32_t first_char, int32_t n_chars,
+                    int32_t max_frames, int32_t max_items, int32_t max_text, pa_annot** out) {
+    if (!out) return PA_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (device < 0 || !atlas_host || cell_w < 1 || cell_w > 64 || cell_h < 1 || cell_h > 64 || first_char < 0 || n_chars < 1 ||
+        first_char + n_chars > 256 || max_frames < 1 || max_frames > 65535 || max_items < 1 || max_items > PA_ANNOT_MAX_ITEMS ||
+        max_text < 1 || max_text > (1 << 20))
+        return PA_ERR_INVALID_ARG;
+    pa_annot* h = new pa_annot();
+    *out = h;
+    h->cell_w = cell_w, h->cell_h = cell_h, h->first_char = first_char, h->n_chars = n_chars;
+    h->max_frames = max_frames, h->max_items = max_items, h->max_text = max_text;
+    h->items_bytes = (size_t)max_frames * PA_ANNOT_MAX_ITEMS * sizeof(pa_annot_item);
+    h->counts_bytes = (size_t)max_frames * sizeof(int32_t);
+    h->slot_bytes = (h->items_bytes + h->counts_bytes + (size_t)max_text + 15) & ~(size_t)15;
+    if (hipSetDevice(device) != hipSuccess) return PA_ERR_NO_DEVICE;
+    const size_t atlas_bytes = (size_t)n_chars * (n_chars + 1) * cell_h * cell_w;
+    void* p = nullptr;
+    if (hipMalloc(&p, atlas_bytes) != hipSuccess) return PA_ERR_HIP;
+    h->atlas = static_cast<unsigned char*>(p);
+    if (hipMemcpy(h->atlas, atlas_host, atlas_bytes, hipMemcpyHostToDevice) != hipSuccess) return PA_ERR_HIP;
+    for (int i = 0; i < PA_ANNOT_SLOTS; ++i) {
+        if (hipHostMalloc(&p, h->slot_bytes, hipHostMallocDefault) != hipSuccess) return PA_ERR_HIP;
+        h->host[i] = static_cast<unsigned char*>(p);
+        if (hipMalloc(&p, h->slot_bytes) != hipSuccess) return PA_ERR_HIP;
+        h->dev[i] = static_cast<unsigned char*>(p);
+        if (hipEventCreateWithFlags(&h->done[i], hipEventDisableTiming) != hipSuccess) return PA_ERR_HIP;
+    }
+    return PA_OK;
+}
+
+void pa_annot_destroy(pa_annot* h) {
+    if (!h) return;
+    for (int i = 0; i < PA_ANNOT_SLOTS; ++i) {
+        if (h->used[i]) (void)hipEventSynchronize(h->done[i]);
+        if (h->done[i]) (void)hipEventDestroy(h->done[i]);
+        if (h->dev[i]) (void)hipFree(h->dev[i]);
+        if (h->host[i]) (void)hipHostFree(h->host[i]);
+    }
+    if (h->atlas) (void)hipFree(h->atlas);
+    delete h;
+}
+
+int pa_annotate_frames(pa_annot* h, const uint8_t* frames_in, int32_t n, int32_t height, int32_t width, const pa_annot_item* items_host,
+                       const int32_t* counts_host, const uint8_t* text_host, int32_t text_bytes, int32_t pad_left, int32_t pad_right,
+                       int32_t pad_bottom, uint8_t* frames_out, void* stream) {
+    if (!h || n < 0) return PA_ERR_INVALID_ARG;
+    if (n == 0) return PA_OK;
+    if (!frames_in || !frames_out || frames_in == frames_out || !counts_host || height < 1 || width < 1 || pad_left < 0 || pad_right < 0 ||
+        pad_bottom < 0 || text_bytes < 0 || text_bytes > h->max_text || (text_bytes > 0 && !text_host))
+        return PA_ERR_INVALID_ARG;
+    if ((long long)height + pad_bottom > 32768 || (long long)pad_left + width + pad_right > 32768) return PA_ERR_INVALID_ARG;
+    if (n > h->max_frames) return PA_ERR_CAPACITY;
+    for (int f = 0; f < n; ++f) {
+        if (counts_host[f] < 0 || counts_host[f] > h->max_items || (counts_host[f] > 0 && !items_host)) return PA_ERR_INVALID_ARG;
+        for (int i = 0; i < counts_host[f]; ++i) {
+            const pa_annot_item& it = items_host[(size_t)f * PA_ANNOT_MAX_ITEMS + i];
+            if (it.line_width < 0 || it.line_width > 32767 || it.text_len < 0 || it.text_off < 0 ||
+                (long long)it.text_off + it.text_len > text_bytes)
+                return PA_ERR_INVALID_ARG;
+        }
+    }
+    for (int i = 0; i < text_bytes; ++i)
+        if (text_host[i] < h->first_char || text_host[i] >= h->first_char + h->n_chars) return PA_ERR_INVALID_ARG;
+    if (!h->done[PA_ANNOT_SLOTS - 1]) return PA_ERR_NO_DEVICE;  // a create that stopped at the device
+
+    const int slot = h->next;
+    h->next = (h->next + 1) % PA_ANNOT_SLOTS;
+    if (h->used[slot] && hipEventSynchronize(h->done[slot]) != hipSuccess) return PA_ERR_HIP;
+    unsigned char* hs = h->host[slot];
+    unsigned char* ds = h->dev[slot];
+    const size_t used_items = (size_t)n * PA_ANNOT_MAX_ITEMS * sizeof(pa_annot_item);
+    if (items_host)
+        std::memcpy(hs, items_host, used_items);
+    else
+        std::memset(hs, 0, used_items);
+    std::memcpy(hs + h->items_bytes, counts_host, (size_t)n * sizeof(int32_t));
+    unsigned char* text = hs + h->items_bytes + h->counts_bytes;
+    for (int i = 0; i < text_bytes; ++i) text[i] = (unsigned char)(text_host[i] - h->first_char);  // atlas rows
+    hipStream_t s = (hipStream_t)stream;
+    // (two copies: the used head of the items, then counts and text, which lie behind the items' full capacity)
+    if (hipMemcpyAsync(ds, hs, used_items, hipMemcpyHostToDevice, s) != hipSuccess) return PA_ERR_HIP;
+    if (hipMemcpyAsync(ds + h->items_bytes, hs + h->items_bytes, h->counts_bytes + (size_t)text_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+        return PA_ERR_HIP;
+    pa::AnnotParams p;
+    p.in = frames_in;
+    p.out = frames_out;
+    p.items = ds;
+    p.counts = reinterpret_cast<const int*>(ds + h->items_bytes);
+    p.text = ds + h->items_bytes + h->counts_bytes;
+    p.atlas = h->atlas;
+    p.n = n, p.H = height, p.W = width, p.pad_left = pad_left, p.pad_right = pad_right, p.pad_bottom = pad_bottom;
+    p.cell_w = h->cell_w, p.cell_h = h->cell_h, p.n_chars = h->n_chars;
+    if (pa::launch_annotate(p, s) != hipSuccess) return PA_ERR_HIP;
+    h->used[slot] = true;
+    if (hipEventRecord(h->done[slot], s) != hipSuccess) return PA_ERR_HIP;
+    return PA_OK;
+}
+
+}  // extern "C"

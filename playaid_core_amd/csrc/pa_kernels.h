@@ -427,4 +427,20 @@ constexpr int EVAL_SLAB_PARTS = 1024;
 hipError_t launch_eval_rows(const float* logp, int ld, int n, int A, const int32_t* labels, int label_stride, unsigned long long* counts,
                             double* sums, unsigned long long* confusion, double* slab, hipStream_t s);
 
+// annotate.hip: copies n BGR frames [H][W][3] into [H + pad_bottom][pad_left + W + pad_right][3] (zero padding) and paints each
+// frame's draw list on the way (pa_annotate_frames). items: pa_annot_item[n][PA_ANNOT_MAX_ITEMS] (device), counts int32[n],
+// text: atlas ROW indices (character code - first_char), atlas uint8[n_chars][n_chars + 1][cell_h][cell_w]. Everything the
+// kernel indexes with was range-checked by the caller.
+struct AnnotParams {
+    const unsigned char* in;
+    unsigned char* out;
+    const void* items;
+    const int* counts;
+    const unsigned char* text;
+    const unsigned char* atlas;
+    int n, H, W, pad_left, pad_right, pad_bottom;
+    int cell_w, cell_h, n_chars;
+};
+hipError_t launch_annotate(const AnnotParams& p, hipStream_t s);
+
 }  // namespace pa

@@ -174,6 +174,12 @@ class LogCamera:
         return YoloCrop.from_pixel_coordinates(LOG_IMAGE_WIDTH, LOG_IMAGE_HEIGHT, *flat)
 
 
+# ``playaid/frame_data.py``'s table, {fighter name: {action: {"startup", "active_start", "active_end", ...}}}: only
+# ``Fighter.anim_state`` reads it. It ships empty -- the reference's table is a 51k-line listing this project does not
+# carry -- so ``anim_state`` is "" (the reference's answer for a fighter without frame data) until a caller fills it.
+FIGHTER_FRAME_DATA: Dict[str, Dict[str, Dict]] = {}
+
+
 class Fighter:
     """``playaid.fighter.Fighter``: constructor arguments, ``set_from_json`` and ``update`` as the
     reference (``fighter.py:394-612``). ``motion_kind`` -> ``action_string`` needs
@@ -280,6 +286,18 @@ class Fighter:
     @property
     def in_ledge_situation(self) -> bool:
         return anim_ontology.OPTION_GROUP[self.action] == "ledge"
+
+    @property
+    def anim_state(self) -> str:
+        """``fighter.py:636-660``: "startup" / "active" / "end lag" from ``FIGHTER_FRAME_DATA``, "" without an entry."""
+        move = FIGHTER_FRAME_DATA.get(self.fighter_name, {}).get(self.action)
+        if not move or not move.get("startup") or not move.get("active_start"):
+            return ""
+        if self.animation_frame_num < move["startup"]:
+            return "startup"
+        if move["active_start"] <= self.animation_frame_num <= move["active_end"]:
+            return "active"
+        return "end lag"
 
     @property
     def time_remaining(self) -> str:
