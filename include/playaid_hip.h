@@ -837,6 +837,17 @@ int pa_conv_pack_weights(const float* w_host, int32_t cin, int32_t cout, int32_t
 int pa_conv2d(const float* x, const void* w, const float* bias, const float* residual, float* out, int32_t n, int32_t height,
               int32_t width, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t in_pad, int32_t in_px_stride,
               int32_t out_px_stride, int32_t out_pad, int32_t act, int32_t res_after, int32_t compute_dtype, void* stream);
+/* The opener of a ResNet block with its downsample branch (csrc/pigemm.hip, pgemm_branch_kernel): pa_conv2d's 3x3 stride-2
+ * convolution into `out`, and from the SAME pass over x the block's 1x1 stride-2 branch out2 = x(2 y, 2 x) . w2 -- w2 float32
+ * [cout][cin] (device), out2 addressed like out, no bias, no activation -- computed on the 3x3's centre tap, which reads those
+ * pixels. Both outputs have the bits of the two pa_conv2d calls they replace. PA_DTYPE_F32 only; PA_ERR_INVALID_ARG for anything
+ * but ksize 3, stride 2, in_px_stride == cin, cout a multiple of 64, act 0 | 1, no residual. residual, ksize, stride and res_after
+ * exist so that the argument list is pa_conv2d's plus w2 and out2: they must be NULL, 3, 2 and 0. Appended: PA_ABI_VERSION stays 15,
+ * no existing layout changes. Enqueue only. */
+int pa_conv2d_branch(const float* x, const void* w, const float* bias, const float* residual, float* out, const float* w2, float* out2,
+                     int32_t n, int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t in_pad,
+                     int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad, int32_t act, int32_t res_after, int32_t compute_dtype,
+                     void* stream);
 
 /* Head of ResnetTransformerDetector (resnet_transformer_detector.py:41-93,141): Linear(in_dim, hidden_dim), the
  * enc_dim-value time encoding of the frame slot appended (d_model = hidden_dim + enc_dim, 32 per head),

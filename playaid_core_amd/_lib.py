@@ -212,6 +212,7 @@ SYMBOLS = [
     ("pa_conv_weight_bytes", C.c_size_t, [C.c_int32] * 5),
     ("pa_conv_pack_weights", C.c_int, [_P] + [C.c_int32] * 5 + [_P]),
     ("pa_conv2d", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 14 + [_P]),
+    ("pa_conv2d_branch", C.c_int, [_P, _P, _P, _P, _P, _P, _P] + [C.c_int32] * 14 + [_P]),
     ("pa_wino_conv3x3_splitk", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 11 + [_P, C.c_size_t, _P, C.c_int32, _P]),
     ("pa_crop_resize_width", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.c_int32,
                                        C.POINTER(C.c_int32), _P]),

@@ -56,3 +56,31 @@ def conv2d(x_pad: torch.Tensor, w_packed: torch.Tensor, cin: int, cout: int, ksi
     if rc:
         raise ValueError(f"pa_conv2d: status {rc}")
     return out
+
+
+def conv2d_branch(x_pad: torch.Tensor, w: torch.Tensor, w2: torch.Tensor, cin: int, cout: int, bias=None, out=None, out2=None, out_pad: int = 0,
+                  act: int = 0, in_pad: int = 1, ksize: int = 3, stride: int = 2, compute_dtype: str = "f32"):
+    """A ResNet block's 3x3 stride-2 opener and its 1x1 stride-2 downsample branch in one launch (``pa_conv2d_branch``,
+    ``csrc/pigemm.hip``): x_pad float32[n, H + 2 in_pad, W + 2 in_pad, cin] -> (out, out2), both float32[n, H / 2 + 2 out_pad,
+    W / 2 + 2 out_pad, C' >= cout]; ``out`` = act(conv3x3(x) + bias), ``out2`` = conv1x1(x) with ``w2`` float32[cout, cin] on the
+    device, no bias, no activation. ``w``: ``pack_weights(..., "f32")`` on the device. The library refuses anything but ksize 3,
+    stride 2, whole pixels (C == cin) and the exact dtype; ``ksize`` and ``stride`` are passed through as given (the C call has
+    ``pa_conv2d``'s argument list) so that a caller sees that refusal rather than a silently corrected call."""
+    lib = _lib.load()
+    if x_pad.dtype != torch.float32 or not x_pad.is_cuda or not x_pad.is_contiguous() or x_pad.dim() != 4:
+        raise ValueError("x_pad: contiguous float32[n, H + 2 pad, W + 2 pad, C] on the device")
+    n, hp, wp, cs = x_pad.shape
+    h, wd = hp - 2 * in_pad, wp - 2 * in_pad
+    oh, ow = h // stride, wd // stride
+    mk = lambda: torch.zeros((n, oh + 2 * out_pad, ow + 2 * out_pad, cout), dtype=torch.float32, device=x_pad.device)
+    out = mk() if out is None else out
+    out2 = mk() if out2 is None else out2
+    if out2.shape != out.shape:
+        raise ValueError("out2 is addressed like out: same shape")
+    ptr = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else C.c_void_p(0)
+    stream = C.c_void_p(torch.cuda.current_stream(x_pad.device).cuda_stream)
+    rc = lib.pa_conv2d_branch(ptr(x_pad), ptr(w), ptr(bias), C.c_void_p(0), ptr(out), ptr(w2), ptr(out2), n, h, wd, cin, cout, ksize, stride, in_pad, cs,
+                              out.shape[3], out_pad, int(act), 0, _lib.DTYPES[compute_dtype], stream)
+    if rc:
+        raise ValueError(f"pa_conv2d_branch: status {rc}")
+    return out, out2

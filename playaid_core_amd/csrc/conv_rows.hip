@@ -160,4 +160,31 @@ int pa_conv2d(const float* x, const void* w, const float* bias, const float* res
     return e == hipSuccess ? PA_OK : (e == hipErrorInvalidValue ? PA_ERR_INVALID_ARG : PA_ERR_HIP);
 }
 
+int pa_conv2d_branch(const float* x, const void* w, const float* bias, const float* residual, float* out, const float* w2, float* out2, int32_t n,
+                     int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t in_pad, int32_t in_px_stride,
+                     int32_t out_px_stride, int32_t out_pad, int32_t act, int32_t res_after, int32_t compute_dtype, void* stream) {
+    // the opener form alone: 3x3, stride 2, the tap the whole pixel, exact fp32, ReLU or nothing, no residual
+    if (!x || !w || !out || !w2 || !out2 || residual || res_after || n <= 0 || height <= 0 || width <= 0 || ksize != 3 || stride != 2 || height % 2 || width % 2 ||
+        in_pad < 1 || in_px_stride != cin || out_px_stride < cout || out_pad < 0 || act < 0 || act > 1 || compute_dtype != PA_DTYPE_F32 ||
+        pa_conv_weight_bytes(cin, cout, 3, compute_dtype, 0) == 0)
+        return PA_ERR_INVALID_ARG;
+    auto misaligned = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) != 0; };
+    if (in_px_stride % 4 || out_px_stride % 4 || misaligned(x) || misaligned(w) || misaligned(out) || misaligned(w2) || misaligned(out2) ||
+        (reinterpret_cast<unsigned long long>(bias) & 3ull))
+        return PA_ERR_INVALID_ARG;
+    const int oh = height / 2, ow = width / 2;
+    const int in_wb = width + 2 * in_pad, in_hb = height + 2 * in_pad, out_wb = ow + 2 * out_pad, out_hb = oh + 2 * out_pad;
+    if ((long long)n * in_hb * in_wb * in_px_stride >= (1ll << 29) || (long long)n * out_hb * out_wb * out_px_stride >= (1ll << 29)) return PA_ERR_CAPACITY;
+    pa::GemmParams p = pa::conv_row_params({/*images*/ n, /*in h, w, pad, px stride*/ height, width, in_pad, in_px_stride, /*cin, cout, ksize, stride*/ cin, cout, 3, 2,
+                                            /*out pad, px stride*/ out_pad, out_px_stride, /*act, res_after*/ act, 0});
+    p.act = x;
+    p.wgt = static_cast<const float*>(w);
+    p.bias = bias;
+    p.out = out;
+    p.wgt2 = w2;
+    p.out2 = out2;
+    const hipError_t e = pa::launch_pgemm(p, 64, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? PA_OK : (e == hipErrorInvalidValue ? PA_ERR_INVALID_ARG : PA_ERR_HIP);
+}
+
 }  // extern "C"

@@ -45,10 +45,13 @@ struct ConvLayer {
     // which the 3x3 conv then adds as its residual (patchconv_bf16.hip has no second source)
     float* ds_wgt = nullptr;  // [cout][in2_c] bf16
     float* ds_out = nullptr;
-    // ... unless the block's stride-2 opener computes it on its centre tap (igemm_bf16.hip, DS): set on the OPENER
-    // (`ds_next_*` = the next layer's ds_wgt / ds_out) and on the conv that adds the result (`ds_fused`)
+    // ... unless the block's stride-2 opener computes it on its centre tap (igemm_bf16.hip, DS; on the exact fp32 path pigemm.hip's
+    // pgemm_branch_kernel, PA_F32_DS_FUSE): set on the OPENER (`ds_next_*` = the next layer's ds_wgt / ds_out) and on the conv that
+    // adds the result (`ds_fused`). fp32: an opener launch the fused kernel does not take (split K at small batches) launches the
+    // branch GEMM itself, right behind the opener -- where it runs today
     float* ds_next_wgt = nullptr;
     float* ds_next_out = nullptr;
+    std::string ds_next_name;  // fp32: the name of the layer that owns the branch (its per-layer profile row when the opener launches the GEMM)
     bool ds_fused = false;
     bool ds_probe = false;  // PA_BF16_DS_FUSE=2: the opener takes the fused launch's tile and K split, the branch stays separate
     double k_alg = 0;  // algorithmic K (unpadded) for FLOP accounting
@@ -384,17 +387,25 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
     // the block's 1x1/2 downsample branch as a GEMM of its own: the zero-bordered block input -> ds_out, laid out like this layer's output
     // (add_conv builds the block so that this layer's output is in2_hw / in2_stride on a side with whole pixels of cout channels:
     // the branch's M, howo, wo and output strides come out equal to p's)
-    auto branch_gemm = [&]() {
-        GemmParams d = conv_row_params({/*images*/ ncrops, /*in h, w, pad, px stride*/ L.in2_hw, L.in2_hw, 1, L.in2_c,
-                                        /*cin, cout, ksize, stride*/ L.in2_c, L.cout, 1, L.in2_stride,
+    // (src, hw, c, stride: the block input; on conv2 its in2 fields, on the opener -- fp32, the fused launch refused -- its own input)
+    auto branch_gemm_of = [&](float* src, int hw, int c, int stride, float* wgt, float* out) {
+        GemmParams d = conv_row_params({/*images*/ ncrops, /*in h, w, pad, px stride*/ hw, hw, 1, c,
+                                        /*cin, cout, ksize, stride*/ c, L.cout, 1, stride,
                                         /*out pad, px stride*/ L.out_pad, L.cout, /*act, res_after*/ 0, 0});
-        d.act = at(L.in2, (size_t)crop0 * (L.in2_hw + 2) * (L.in2_hw + 2) * L.in2_c);
-        d.wgt = L.ds_wgt;
-        d.out = at(L.ds_out, crop0 * out_crop);
+        d.act = at(src, (size_t)crop0 * (hw + 2) * (hw + 2) * c);
+        d.wgt = wgt;
+        d.out = at(out, crop0 * out_crop);
         d.slab = p.slab;
         return d;
     };
-    if (bf_ds && L.ds_fused) {
+    auto branch_gemm = [&]() { return branch_gemm_of(L.in2, L.in2_hw, L.in2_c, L.in2_stride, L.ds_wgt, L.ds_out); };
+    auto launch_f32_branch = [&](const GemmParams& d) {
+        GemmTile dt;
+        int dsk;
+        choose_tile(d.M, d.N, d.chunk / 32, &dt, &dsk);
+        return launch_igemm(d, dt, s);
+    };
+    if ((bf_ds || f32_ds) && L.ds_fused) {
         p.residual = at(L.ds_out, crop0 * out_crop);  // written by the block's opener
     } else if (bf_ds) {
         const GemmParams d = branch_gemm();
@@ -410,10 +421,7 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
         } else if (e->emu && L.ds_split_wgt) {
             HIPCHK(e, launch_psgemm(d, L.ds_split_wgt, (size_t)ncrops * out_crop, 0, s));
         } else {
-            GemmTile dt;
-            int dsk;
-            choose_tile(d.M, d.N, L.in2_c / 32, &dt, &dsk);
-            HIPCHK(e, launch_igemm(d, dt, s));
+            HIPCHK(e, launch_f32_branch(d));
         }
         if (ds_only) return PA_OK;
         p.residual = d.out;
@@ -434,12 +442,14 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
     p.splitk = splitk;
     const size_t slab_avail = e->slab_floats > slab_off ? e->slab_floats - slab_off : 0;
     if ((size_t)p.splitk * p.M * p.N > slab_avail) p.splitk = 1;
-    const bool ds_here = bf && L.ds_next_wgt;  // this launch also computes the next conv's 1x1/2 branch
-    if (ds_here) {
+    const bool f32_branch = !bf && !e->emu && L.ds_next_wgt;   // the exact path's opener: the fused kernel if it takes the launch
+    const bool f32_branch_here = f32_branch && p.splitk <= 1;
+    const bool ds_here = (bf && L.ds_next_wgt) || f32_branch_here;  // this launch also computes the next conv's 1x1/2 branch
+    if (bf && L.ds_next_wgt) {
         p.wgt2 = L.ds_next_wgt;
         p.out2 = at(L.ds_next_out, crop0 * out_crop);
     }
-    if (ds_here || (bf && L.ds_probe)) {
+    if ((bf && L.ds_next_wgt) || (bf && L.ds_probe)) {
         tile = (p.N % 128 == 0 && ((p.M + 127) / 128) * (p.N / 128) >= 256) ? TILE_128x128 : TILE_128x64;
         p.splitk = 1;
     }
@@ -449,52 +459,70 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
     const double bytes = (double)es * ((double)ncrops * L.in_hw * L.in_hw * L.cin + (double)p.M * p.N * ((L.residual || bf_ds || f32_ds || ds_here) ? 2 : 1) +
                                        (double)p.N * k_main + ((L.in2 && !bf_ds && !f32_ds) ? (double)ncrops * L.in2_hw * L.in2_hw * L.in2_c : 0.0));
     const bool as_wino = !bf && L.wino_wgt && !p.act2;
-    ProfScope ps(e, s, prof_name, flops, bytes, as_wino ? flops * 4.0 / 9.0 : flops);
-    // stride-1 3x3 layers: input patch resident in LDS across the nine taps (patchconv.hip);
-    // PA_PATCH=0 keeps the generic im2col engine for A/B runs
-    static const int use_patch = getenv("PA_PATCH") ? atoi(getenv("PA_PATCH")) : 1;
-    static const int use_bf16_patch = getenv("PA_BF16_PATCH") ? atoi(getenv("PA_BF16_PATCH")) : 1;
-    if (e->emu && L.split_wgt && !p.act2 && !p.residual) {
-        HIPCHK(e, launch_psgemm(p, L.split_wgt, (size_t)ncrops * out_crop, 0, s));
-    } else if (bf) {
-        hipError_t pe = hipErrorInvalidValue;
-        if (use_bf16_patch && L.stride == 1 && !p.act2) pe = launch_conv3x3_bf16_patch(p, s);
-        if (pe == hipErrorInvalidValue) {  // stride-2 convs, fused 1x1/2 second source
-            // a 256-pixel tile halves the weight fill per pixel (this kernel is bound by its L2 -> LDS copies) where it
-            // still leaves every CU a workgroup; PA_BF16_T256=0 for A/B runs
-            static const int t256 = getenv("PA_BF16_T256") ? atoi(getenv("PA_BF16_T256")) : 1;
-            if (t256 && !p.out2 && tile == TILE_128x128 && p.splitk == 1 && ((p.M + 255) / 256) * (p.N / 128) >= 256) tile = TILE_256x128;
-            pe = launch_igemm_bf16(p, tile, s);
+    bool branch_left = f32_branch;   // the fp32 opener's branch is still to be computed
+    {   // (the opener's profile scope ends before its branch's begins)
+        ProfScope ps(e, s, prof_name, flops, bytes, as_wino ? flops * 4.0 / 9.0 : flops);
+        // stride-1 3x3 layers: input patch resident in LDS across the nine taps (patchconv.hip);
+        // PA_PATCH=0 keeps the generic im2col engine for A/B runs
+        static const int use_patch = getenv("PA_PATCH") ? atoi(getenv("PA_PATCH")) : 1;
+        static const int use_bf16_patch = getenv("PA_BF16_PATCH") ? atoi(getenv("PA_BF16_PATCH")) : 1;
+        if (e->emu && L.split_wgt && !p.act2 && !p.residual) {
+            HIPCHK(e, launch_psgemm(p, L.split_wgt, (size_t)ncrops * out_crop, 0, s));
+        } else if (bf) {
+            hipError_t pe = hipErrorInvalidValue;
+            if (use_bf16_patch && L.stride == 1 && !p.act2) pe = launch_conv3x3_bf16_patch(p, s);
+            if (pe == hipErrorInvalidValue) {  // stride-2 convs, fused 1x1/2 second source
+                // a 256-pixel tile halves the weight fill per pixel (this kernel is bound by its L2 -> LDS copies) where it
+                // still leaves every CU a workgroup; PA_BF16_T256=0 for A/B runs
+                static const int t256 = getenv("PA_BF16_T256") ? atoi(getenv("PA_BF16_T256")) : 1;
+                if (t256 && !p.out2 && tile == TILE_128x128 && p.splitk == 1 && ((p.M + 255) / 256) * (p.N / 128) >= 256) tile = TILE_256x128;
+                pe = launch_igemm_bf16(p, tile, s);
+            }
+            HIPCHK(e, pe);
+        } else if (L.wino_wgt && !p.act2) {
+            WinoParams q = wino_params(p, ncrops, L.out_hw, L.out_hw, L.cin, L.wino_wgt, L.wino_bn);
+            if (e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
+                q.slab = e->slab + slab_off;
+                q.slab_floats = e->slab_floats > slab_off ? std::min(e->slab_floats - slab_off, e->slab_floats / 2) : 0;
+                q.tickets = reinterpret_cast<int32_t*>(e->wino_tickets) + (slab_off ? WINO_TICKETS : 0);
+                q.tickets_cap = WINO_TICKETS;
+            }
+            HIPCHK(e, launch_wino3x3(q, s));
+        } else if (use_patch && L.kh == 3 && L.stride == 1) {
+            int bm = tile == TILE_64x64 || tile == TILE_64x64_K64 ? 64 : 128;
+            const int howo = L.out_hw * L.out_hw, in_w2 = L.out_hw + 2;
+            const int px128 = howo >= 128 ? (128 / L.out_hw + 2) * in_w2 : (128 / howo) * in_w2 * in_w2;
+            if (bm == 128 && px128 > 224) bm = 64;  // keep two workgroups per CU (2 patch buffers + weight ring <= 80 KB)
+            hipError_t pe = launch_conv3x3_patch(p, bm, s);
+            if (pe == hipErrorInvalidValue) pe = launch_igemm(p, tile, s);  // geometry the patch kernel does not cover
+            HIPCHK(e, pe);
+        } else {
+            // Stride-2 3x3 convolutions that need no split-K run on the persistent form of the engine (pigemm.hip) with 64-row tiles:
+            // two tiles per workgroup slot, so the second tile's first operands arrive under the first one's matrix instructions
+            // (one 128-row tile per slot, round 4's A/B, gained nothing: 48.39 k against 48.53 k frames/s). At 128 crops: 50.3 / 50.2 /
+            // 54.0 -> 48.8 / 46.6 / 52.7 us for the three openers. Same k order as igemm.hip; the bias is the value pgemm's accumulators start
+            // from and igemm's last addition: results agree to that rounding. PA_S2_PGEMM=0: igemm.hip (A/B), 1: pgemm's own choice of tile height
+            static const int use_pgemm = getenv("PA_S2_PGEMM") ? atoi(getenv("PA_S2_PGEMM")) : 2;
+            hipError_t pe = hipErrorInvalidValue;
+            const bool pg = use_pgemm && L.kh == 3 && L.stride == 2 && !p.act2 && !p.residual && p.splitk <= 1 && !p.gather;
+            if (pg && f32_branch_here) {   // the block's 1x1/2 branch on the centre tap (pgemm_branch_kernel)
+                p.wgt2 = L.ds_next_wgt;
+                p.out2 = at(L.ds_next_out, crop0 * out_crop);
+                pe = launch_pgemm(p, 64, s);
+                if (pe == hipSuccess) branch_left = false;
+                p.wgt2 = nullptr;
+                p.out2 = nullptr;
+            }
+            if (pg && pe == hipErrorInvalidValue) pe = launch_pgemm(p, use_pgemm == 2 ? 64 : 0, s);
+            if (pe == hipErrorInvalidValue) pe = launch_igemm(p, tile, s);
+            HIPCHK(e, pe);
         }
-        HIPCHK(e, pe);
-    } else if (L.wino_wgt && !p.act2) {
-        WinoParams q = wino_params(p, ncrops, L.out_hw, L.out_hw, L.cin, L.wino_wgt, L.wino_bn);
-        if (e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
-            q.slab = e->slab + slab_off;
-            q.slab_floats = e->slab_floats > slab_off ? std::min(e->slab_floats - slab_off, e->slab_floats / 2) : 0;
-            q.tickets = reinterpret_cast<int32_t*>(e->wino_tickets) + (slab_off ? WINO_TICKETS : 0);
-            q.tickets_cap = WINO_TICKETS;
-        }
-        HIPCHK(e, launch_wino3x3(q, s));
-    } else if (use_patch && L.kh == 3 && L.stride == 1) {
-        int bm = tile == TILE_64x64 || tile == TILE_64x64_K64 ? 64 : 128;
-        const int howo = L.out_hw * L.out_hw, in_w2 = L.out_hw + 2;
-        const int px128 = howo >= 128 ? (128 / L.out_hw + 2) * in_w2 : (128 / howo) * in_w2 * in_w2;
-        if (bm == 128 && px128 > 224) bm = 64;  // keep two workgroups per CU (2 patch buffers + weight ring <= 80 KB)
-        hipError_t pe = launch_conv3x3_patch(p, bm, s);
-        if (pe == hipErrorInvalidValue) pe = launch_igemm(p, tile, s);  // geometry the patch kernel does not cover
-        HIPCHK(e, pe);
-    } else {
-        // Stride-2 3x3 convolutions that need no split-K run on the persistent form of the engine (pigemm.hip) with 64-row tiles:
-        // two tiles per workgroup slot, so the second tile's first operands arrive under the first one's matrix instructions
-        // (one 128-row tile per slot, round 4's A/B, gained nothing: 48.39 k against 48.53 k frames/s). At 128 crops: 50.3 / 50.2 /
-        // 54.0 -> 48.8 / 46.6 / 52.7 us for the three openers. Same k order as igemm.hip; the bias is the value pgemm's accumulators start
-        // from and igemm's last addition: results agree to that rounding. PA_S2_PGEMM=0: igemm.hip (A/B), 1: pgemm's own choice of tile height
-        static const int use_pgemm = getenv("PA_S2_PGEMM") ? atoi(getenv("PA_S2_PGEMM")) : 2;
-        hipError_t pe = hipErrorInvalidValue;
-        if (use_pgemm && L.kh == 3 && L.stride == 2 && !p.act2 && !p.residual && p.splitk <= 1 && !p.gather) pe = launch_pgemm(p, use_pgemm == 2 ? 64 : 0, s);
-        if (pe == hipErrorInvalidValue) pe = launch_igemm(p, tile, s);
-        HIPCHK(e, pe);
+    }
+    if (branch_left) {   // the opener ran unfused (split K: small batches): the branch GEMM behind it, where it runs without PA_F32_DS_FUSE
+        const GemmParams d = branch_gemm_of(L.in, L.in_hw, L.cin, L.stride, L.ds_next_wgt, L.ds_next_out);
+        ProfScope ps(e, s, e->profile_layers ? L.ds_next_name.c_str() : prof_name, 2.0 * d.M * d.N * L.cin,   // (booked where conv2 books it: its layer's row, or the family's)
+                     4.0 * ((double)ncrops * L.in_hw * L.in_hw * L.cin / (L.stride * L.stride) + (double)d.M * d.N + (double)d.N * L.cin));
+        HIPCHK(e, launch_f32_branch(d));
     }
     return PA_OK;
 }
@@ -1000,6 +1028,23 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
                         if (rc) return rc;
                         if (e->emu && (rc = upload_split(e, &L.ds_split_wgt, wd, co, cin, false))) return rc;
                         ALLOC(L.ds_out, buf, true);
+                        // The exact path: the block's stride-2 opener computes the branch on its centre tap (pigemm.hip's pgemm_branch_kernel)
+                        // and this layer adds ds_out without a launch (headline +1.7 %, profiles/opener_branch_parent_ab.md; results are
+                        // bit-identical either way). PA_F32_DS_FUSE=0: the branch as its own GEMM (A/B); PA_DS_SIDE=1
+                        // and PA_S2_PGEMM=0 keep the separate GEMM too. Blocks 2 and 3 only: block 4's opener runs split K on igemm.hip,
+                        // which has no such form
+                        static const int f32_ds_fuse = getenv("PA_F32_DS_FUSE") ? atoi(getenv("PA_F32_DS_FUSE")) : 1;
+                        static const int ds_side_knob = getenv("PA_DS_SIDE") ? atoi(getenv("PA_DS_SIDE")) : 0;
+                        static const int s2_pgemm_knob = getenv("PA_S2_PGEMM") ? atoi(getenv("PA_S2_PGEMM")) : 2;
+                        ConvLayer& C1 = e->convs[e->convs.size() - 2];  // the block's stride-2 opener: same input, same output shape
+                        if (f32_ds_fuse && !ds_side_knob && s2_pgemm_knob && !e->emu && li < 3 && C1.in == cur && C1.kh == 3 &&
+                            C1.stride == 2 && C1.cout == co && C1.out_hw == hw_out && C1.out_pad == L.out_pad && C1.chunk == cin && C1.cin == cin &&
+                            C1.in_hw == hw_in[li] && C1.in_pad == 1 && !C1.forced) {
+                            C1.ds_next_wgt = L.ds_wgt;
+                            C1.ds_next_out = L.ds_out;
+                            C1.ds_next_name = L.name;
+                            L.ds_fused = true;
+                        }
                     }
                 }
                 rc = upload(e, &L.bias, bf);

@@ -71,7 +71,7 @@ struct GemmParams {
     int32_t blk_rows, blk_cols, blk_shift_c, blk_shift_px, blk_per_row, blk_per_img, n_blocks, src_pitch;
     // igemm_bf16.hip, stride-2 3x3 openers: a second 1x1 product off the SAME im2col rows -- the centre tap's rows are the
     // pixels the block's 1x1/2 downsample branch reads -- wgt2 = [N][chunk] bf16, out2 addressed like out (no bias, no
-    // activation); nullptr = off
+    // activation); nullptr = off. The same pair on the exact persistent GEMM (pigemm.hip's pgemm_branch_kernel): wgt2 fp32
     const float* wgt2;
     float* out2;
     unsigned long long* clk;  // ablation builds only: in-kernel clock stamps
@@ -86,6 +86,7 @@ enum GemmTile { TILE_128x128 = 0, TILE_128x64 = 1, TILE_64x64 = 2, TILE_128x64_K
 hipError_t launch_igemm(const GemmParams& p, GemmTile tile, hipStream_t s);
 // persistent form of the same engine for short tiles (pigemm.hip): conv mode, no residual / second source / split-K;
 // bm = 128 | 64, 64 output channels per tile; results equal to launch_igemm up to where the bias enters the sum
+// p.wgt2 / p.out2 set: the opener form (3x3, stride 2, whole-pixel taps, ReLU or none, 64 x 64 tiles), hipErrorInvalidValue for anything else
 hipError_t launch_pgemm(const GemmParams& p, int bm, hipStream_t s);
 // "emulated fp32" form of the persistent GEMM (psgemm.hip): fp32 activations, the weights as three bf16 slices in the kernel's
 // stage-image layout (psgemm_pack_weights, psgemm_weight_elems of them), six bf16 matrix instructions per fp32 product, fp32

@@ -53,8 +53,15 @@ template <int N> __device__ __forceinline__ void pg_wait_vm() { wait_vmcnt<(N > 
 // UP: the tile is ALSO written nearest-neighbour up-sampled by two into a second buffer (p.up_out: every output pixel to the 2 x 2
 // pixels it becomes) -- YOLOv5's nn.Upsample behind model.10 / model.14 as four more stores of the producer instead of a pass
 // of its own over HBM.
-template <int BM, int BN = 64, bool SILU = true, bool STAMP = false, bool UP = false>
-__global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
+//
+// DS (pgemm_branch_kernel: the stride-2 3x3 opener of a ResNet block, which takes the block's 1x1/2 downsample branch along): the
+// centre tap (ky == kx == 1) reads exactly the pixels the branch reads, so on its chunk / 32 k-steps the stage also receives the
+// BN x 32 block of p.wgt2 ([N][chunk]) and the wave issues its matrix instructions a second time, with the pixel operand it holds
+// already, into a second accumulator set that starts from zero -- the k order of the branch as a GEMM of its own (channel chunk,
+// eight-wide group, lane half), so p.out2 (no bias, no activation, addressed like p.out) has that GEMM's bits.
+template <int BM, int BN, bool SILU, bool STAMP, bool UP, bool DS>
+__device__ __forceinline__ void pgemm_body(const GemmParams& p) {
+    static_assert(!DS || (!UP && !STAMP && !SILU), "the branch form is the ResNet openers': ReLU, no up-sampled copy");
     // STAMP (scripts/pgemm_stamps.py): s_memtime per wave at entry [0], after the prologue [1], per tile t < 15 at 2 + 4 t:
     // tile start, first barrier passed, last matrix instruction issued, stores issued; exit [63]
     auto stamp = [&](int i) {
@@ -67,9 +74,9 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     constexpr int WM = BN == 64 ? 2 : 4;      // waves along the pixel rows
     constexpr int MI = BM / WM / 32;
     constexpr int A_ROWS = BM / 32, B_ROWS = BN / 32;
-    constexpr int NLD = A_ROWS + B_ROWS;  // LDS-DMA wave instructions per k-step
-    constexpr int NST = MI * 4 * (UP ? 5 : 1);   // store wave instructions per tile
-    constexpr int STAGE = (BM + BN) * 32;
+    constexpr int NLD = A_ROWS + B_ROWS;  // LDS-DMA wave instructions per k-step (DS: B_ROWS more on a centre-tap step, see pre())
+    constexpr int NST = MI * 4 * (UP ? 5 : (DS ? 2 : 1));   // store wave instructions per tile
+    constexpr int STAGE = (BM + BN + (DS ? BN : 0)) * 32;   // (DS: the rows of wgt2 behind those of wgt)
     __shared__ __attribute__((aligned(16))) float lds[3 * STAGE];
 
     // --- this workgroup's tiles: one channel column, every step-th pixel tile of its XCD's contiguous share -------------
@@ -84,11 +91,18 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
         const unsigned u0 = p.pg_magic_howo, u1 = p.pg_magic_wo;
         asm volatile("" ::"s"(pa_), "s"(pw_), "s"(pb_), "s"(po_), "s"(i0), "s"(i1), "s"(i2), "s"(i3), "s"(i4), "s"(i5), "s"(i6), "s"(i7), "s"(i8), "s"(i9),
                      "s"(i10), "s"(i11), "s"(i12), "s"(i13), "s"(i14), "s"(i15), "s"(i16), "s"(i17), "s"(i18), "s"(u0), "s"(u1));
+        if (DS) {
+            const float* pw2_ = p.wgt2;
+            float* po2_ = p.out2;
+            asm volatile("" ::"s"(pw2_), "s"(po2_));
+        }
     }
     if (nt == 0) return;
     stamp(60);
     const int nk = p.ktot >> 5;  // k-steps per tile
     const int total = nt * nk;
+    const int nkc = p.chunk >> 5;                 // k-steps per tap
+    const int c_lo = 4 * nkc, c_hi = 5 * nkc;     // DS: the centre tap's k-steps of a tile
 
     const int tid = threadIdx.x;
     const int wave_id = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -98,6 +112,7 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     const int wm = BN == 64 ? wave_id >> 1 : wave_id, wn = BN == 64 ? wave_id & 1 : 0;
 
     const __amdgpu_buffer_rsrc_t act_rs = glds_rsrc(p.act), wgt_rs = glds_rsrc(p.wgt);
+    const __amdgpu_buffer_rsrc_t wgt2_rs = glds_rsrc(DS ? p.wgt2 : p.wgt);
 
     const int ch0 = tile_n * BN + wn * 32 + 4 * lh;
     f32x2 nl2e = f32x2{-1.44269504088896341f, -1.44269504088896341f}, one2 = f32x2{1.f, 1.f};
@@ -106,6 +121,9 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     int b_off[B_ROWS];   // bytes
 #pragma unroll
     for (int i = 0; i < B_ROWS; ++i) b_off[i] = ((tile_n * BN + row0 + 32 * i) * p.ktot + colq * 4) * 4;
+    int b2_off[B_ROWS];   // DS: the same rows of wgt2 [N][chunk]
+#pragma unroll
+    for (int i = 0; i < B_ROWS; ++i) b2_off[i] = DS ? ((tile_n * BN + row0 + 32 * i) * p.chunk + colq * 4) * 4 : 0;
 
     // --- pixel addressing: scalar base of a 32-pixel run + the lane's distance, wraps folded in -------------------------
     // input, in bytes: A(m) = img * IS + (oy * s + off_y) * RS + (ox * s + off_x) * PS
@@ -154,6 +172,10 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
         const int koff = ((cur.ky * p.kw_taps + cur.kx) * p.chunk + cur.kc) * 4;
 #pragma unroll
         for (int i = 0; i < B_ROWS; ++i) glds16(wgt_rs, b_off[i], koff, Bs_w + i * 1024);
+        if (DS && cur.ky == 1 && cur.kx == 1) {   // a centre-tap step: B_ROWS more copies, LAST of the step's (pre() counts on that)
+#pragma unroll
+            for (int i = 0; i < B_ROWS; ++i) glds16(wgt2_rs, b2_off[i], cur.kc * 4, Bs_w + BN * 32 + i * 1024);
+        }
         cur.advance(p, nk, run, rows_of);
     };
 
@@ -189,10 +211,20 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     stamp(1);
 
     f32x16 acc[MI];
+    f32x16 acc2[MI];   // DS: the branch's sums
     // one k-step on the stage at byte offset sb: 16 matrix instructions per 32-pixel block, operands read one k group
     // ahead; the eight read addresses in one burst of vector adds before the first of them
-    auto kstep = [&](int sb, auto first_c) {
+    // branch_c (DS): 0 = not a centre-tap step, 1 = the centre tap's first step (the branch's accumulators start from zero), 2 = its others:
+    // the rows of wgt2 are read beside those of wgt and every matrix instruction is issued a second time on them
+    auto kstep = [&](int sb, auto first_c, auto branch_c) {
         constexpr bool FIRST = decltype(first_c)::value;   // a tile's first k-step: the accumulators start from the bias
+        constexpr int BR = decltype(branch_c)::value;
+        f32x16 zero16;
+        if (BR == 1) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) zero16[e] = 0.f;
+        }
+        f32x4 b2f[2];
         unsigned ra[4], rb[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
@@ -206,6 +238,7 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
         _Pragma("unroll") for (int mi = 0; mi < MI; ++mi)                                                    \
             af[SET][mi] = *(const lds_f32x4*)(size_t)(ra[KK] + mi * 4096);                                   \
         bf[SET] = *(const lds_f32x4*)(size_t)(rb[KK]);                                                       \
+        if (BR) b2f[SET] = *(const lds_f32x4*)(size_t)(rb[KK] + BN * 128);                                    \
     }
         PG_FRAGS(0, 0);
 #pragma unroll
@@ -222,6 +255,13 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
                 }
                 acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.z, a4.z, acc[mi], 0, 0, 0);
                 acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.w, a4.w, acc[mi], 0, 0, 0);
+                if (BR) {
+                    const f32x4 c4 = b2f[kk & 1];
+                    acc2[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.x, a4.x, BR == 1 && kk == 0 ? zero16 : acc2[mi], 0, 0, 0);
+                    acc2[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.y, a4.y, acc2[mi], 0, 0, 0);
+                    acc2[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.z, a4.z, acc2[mi], 0, 0, 0);
+                    acc2[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.w, a4.w, acc2[mi], 0, 0, 0);
+                }
             }
         }
 #undef PG_FRAGS
@@ -233,6 +273,9 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
         // Stage g must have landed. VMEM operations complete in order and this wave issued, after the copies of stage
         // g (during step g - 2): the stores of the tile step g - 2 closed, the copies of stage g + 1, the stores of the
         // tile step g - 1 closed -- whichever of those exist. Exactly that many may still be outstanding.
+        // DS: stage g + 1 has B_ROWS more copies when step g + 1 is a centre-tap step. The counts below take it for a plain step --
+        // the smaller count: where it is a centre-tap step the wait also covers the first B_ROWS copies of stage g + 1, issued a whole
+        // k-step ago (it over-waits, it never under-waits). The extra copies of stage g ITSELF are older than everything counted.
         const bool next = g + 1 < total;
         int closed = 0;
         if (ks == 0 && g > 0) closed = 1;
@@ -258,12 +301,14 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
         const int tile_m = run.tile(t);
         if (t < 15) stamp(2 + 4 * t);
         pre(0, t);
-        kstep(slot * (STAGE * 4), std::true_type{});
+        kstep(slot * (STAGE * 4), std::true_type{}, std::integral_constant<int, 0>{});   // (k-step 0 is tap (0, 0), never the centre)
         slot = slot == 2 ? 0 : slot + 1;
         ++g;
         for (int ks = 1; ks < nk; ++ks, ++g) {
             pre(ks, t);
-            kstep(slot * (STAGE * 4), std::false_type{});
+            if (DS && ks == c_lo) kstep(slot * (STAGE * 4), std::false_type{}, std::integral_constant<int, 1>{});
+            else if (DS && ks > c_lo && ks < c_hi) kstep(slot * (STAGE * 4), std::false_type{}, std::integral_constant<int, 2>{});
+            else kstep(slot * (STAGE * 4), std::false_type{}, std::integral_constant<int, 0>{});
             slot = slot == 2 ? 0 : slot + 1;
         }
         if (t < 15) stamp(4 + 4 * t);
@@ -271,7 +316,8 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             const int m_base = tile_m * BM + wm * (BM / WM) + mi * 32;
-            float* o_px = p.out + out_offset(m_base);
+            const int o_off = out_offset(m_base);
+            float* o_px = p.out + o_off;
             const bool live = m_base + lr < p.M;
             f32x4 out4[4];
 #pragma unroll
@@ -299,6 +345,12 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
                 if (live) *reinterpret_cast<f32x4*>(o_px + 8 * gq) = f32x4{lo.x, lo.y, hi.x, hi.y};
                 if (UP) { out4[gq] = f32x4{lo.x, lo.y, hi.x, hi.y}; }
             }
+            if (DS && live) {   // the branch: no bias, no activation, the same pixels and channels of out2 (NST counts these four too)
+                float* o2_px = p.out2 + o_off;
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq)
+                    *reinterpret_cast<f32x4*>(o2_px + 8 * gq) = f32x4{acc2[mi][4 * gq], acc2[mi][4 * gq + 1], acc2[mi][4 * gq + 2], acc2[mi][4 * gq + 3]};
+            }
             if (UP && live) {   // (a launch with an up-sampled copy has no partial tile followed by a k-step either: same invariant)
                 float* u_px = p.up_out + pixel_walk(geom, m_base, lr, p.up_img_stride, up_rs, up_ps, up_wrap_x, up_wrap_y, up_lane);
 #pragma unroll
@@ -314,10 +366,30 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
     stamp(63);
 }
 
+template <int BM, int BN = 64, bool SILU = true, bool STAMP = false, bool UP = false>
+__global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
+    pgemm_body<BM, BN, SILU, STAMP, UP, false>(p);
+}
+
+// the opener form: ReLU (p.relu) or none on out, the raw branch sums on out2; 64 x 64 tiles (three stages of 192 rows: 72 KiB, two
+// workgroups per CU)
+__global__ __launch_bounds__(256, 2) void pgemm_branch_kernel(const GemmParams p) {
+    pgemm_body<64, 64, false, false, false, true>(p);
+}
+
 // Conv mode of GemmParams (no gather, no second source, no residual, no split-K); bm = 128 | 64 | 0 (chosen here).
+// p.wgt2 / p.out2 (both or neither): the opener form -- a 3x3 stride-2 convolution whose tap is the whole pixel (chunk == in_px_stride: the
+// channels the branch reads), ReLU or no activation, no up-sampled copy, 64 x 64 tiles; anything else is refused.
 hipError_t launch_pgemm(const GemmParams& p_in, int bm, hipStream_t s) {
     GemmParams p = p_in;
     if (p.residual || p.N % 32 != 0 || (bm != 128 && bm != 64 && bm != 0) || persistent_plan(p) != hipSuccess) return hipErrorInvalidValue;
+    const bool branch = p.wgt2 || p.out2;
+    if (branch) {
+        if (!p.wgt2 || !p.out2 || p.taps != 9 || p.kw_taps != 3 || p.stride != 2 || p.in_px_stride != p.chunk || p.splitk > 1 || p.N % 64 != 0 || p.relu == 2 || p.up_out ||
+            ((reinterpret_cast<unsigned long long>(p.wgt2) | reinterpret_cast<unsigned long long>(p.out2)) & 15ull))
+            return hipErrorInvalidValue;
+        bm = 64;
+    }
     const int bn = p.N % 64 == 0 ? 64 : 32;   // 32: output channels that are not a multiple of 64 (128-row tiles only)
     if (bn == 32) bm = 128;
     p.tiles_n = p.N / bn;
@@ -352,7 +424,7 @@ hipError_t launch_pgemm(const GemmParams& p_in, int bm, hipStream_t s) {
     // diagnostic: PA_PG_STAMP_FILE=<path> PA_PG_STAMP_SHAPE=M,K,N [PA_PG_STAMP_SKIP=n]: the (n + 1)-th launch of that shape runs
     // the stamped kernel and its per-wave clock stamps are written to the file (synchronises; scripts/pgemm_stamps.py)
     static const char* stamp_file = getenv("PA_PG_STAMP_FILE");
-    if (stamp_file && bm == 128 && bn == 64 && silu) {
+    if (stamp_file && bm == 128 && bn == 64 && silu && !branch) {
         static int sm = 0, sk = 0, sn = 0, skip = getenv("PA_PG_STAMP_SKIP") ? atoi(getenv("PA_PG_STAMP_SKIP")) : 3, seen = 0;
         if (!sm && getenv("PA_PG_STAMP_SHAPE")) sscanf(getenv("PA_PG_STAMP_SHAPE"), "%d,%d,%d", &sm, &sk, &sn);
         if (p.M == sm && p.ktot == sk && p.N == sn && seen++ == skip) {
@@ -383,7 +455,8 @@ hipError_t launch_pgemm(const GemmParams& p_in, int bm, hipStream_t s) {
     } while (0)
     if (p.up_out && (!silu || p.up_px_stride % 4 || p.up_row_stride % 4 || p.up_img_stride % 4 || (reinterpret_cast<unsigned long long>(p.up_out) & 15ull)))
         return hipErrorInvalidValue;   // (the up-sampled copy exists for SiLU layers only)
-    if (bn == 32) PA_PG_LAUNCH(128, 32);
+    if (branch) hipLaunchKernelGGL(pgemm_branch_kernel, dim3(grid), dim3(256), 0, s, p);
+    else if (bn == 32) PA_PG_LAUNCH(128, 32);
     else if (bm == 128) PA_PG_LAUNCH(128, 64);
     else PA_PG_LAUNCH(64, 64);
 #undef PA_PG_LAUNCH
