@@ -212,7 +212,7 @@ struct CropPlan {
     int32_t area_mode;         // 0 copy, 1 fast 2x2, 2 fast integer, 3 general
     int32_t iscale_x, iscale_y;
     int32_t fused_rb;          // output rows per LDS sub-band of the fused kernel (8/4/2/1), 0 = multi-kernel fallback
-    int32_t pad_;
+    int32_t mfma_v;            // the fused kernel's vertical pass runs on the int8 matrix instruction (B1 transposed in LDS)
     double scale_x, scale_y;
     // Pillow coefficient tables of the two bicubic passes ([out][2 + PA_KSIZE_MAX]): the engine's cache of the
     // (2 * (d / 2) + 2 * padding -> d) pairs, or this crop's own rows of PreprocParams::coef for any other pair
@@ -261,6 +261,7 @@ struct PreprocParams {
     int32_t* fallback_list;   // [ncrops] their indices
     int32_t fused_lds;      // LDS budget of the fused kernel (set by the launcher; 0 forces the fallback)
     int32_t ablate;         // timing experiments: skip stages of the fused kernel (results wrong when != 0)
+    int32_t crop_mfma;      // PA_CROP_MFMA (default 1; set by the launcher): 0 keeps every vertical pass on the vector ALU
     uint8_t* dbg;           // debug builds only (PA_DEBUG_DUMP)
     int32_t dbg_crop, dbg_row;
 };

@@ -19,8 +19,9 @@
 // the INTER_AREA fractional path accumulates in fp32 with separate multiply
 // and add like OpenCV's generic C++ -- a fused multiply-add would change bits.
 //
-// The stage is HBM/L2 streaming work (no matrix shape): one thread per output
-// element, consecutive lanes on consecutive bytes. Five small kernels keep every
+// The stage is HBM/L2 streaming work: one thread per output
+// element, consecutive lanes on consecutive bytes (the one matrix shape in it is the fused
+// kernel's vertical bicubic pass, on the int8 matrix instruction). Five small kernels keep every
 // size general (any box, any frame): a fused LDS kernel for crops whose bands fit 48 KB,
 // a multi-pass fallback over global scratch for the rest.
 #include "tile_common.h"
@@ -202,17 +203,42 @@ __device__ __forceinline__ int align_up(int v, int a) { return (v + a - 1) / a *
 
 // LDS layout of one sub-band: B0 source rows | B1 after the horizontal pass; B2 (after the
 // vertical pass) reuses B0's space when both passes run (B0 is dead once H is done).
+// With CropPlan::mfma_v the vertical pass runs on v_mfma_i32_32x32x32_i8 and B1 is kept TRANSPOSED, [byte column][source
+// row]: byte (col, row) at off1 + col * pt + (col >> 3) * skew + row -- a lane of the pass reads the 16 consecutive rows of
+// its byte column as one operand. pt is the row count rounded up to 4 (the horizontal pass stores four rows as one dword);
+// where pt / 4 is even, one dword of skew per 8 columns spreads those stores (3 * pt / 4 dwords apart from lane to lane) and
+// the operand reads (pt / 4 apart) over the 64 banks. Columns are padded to whole 32-column blocks, 32 B of slack behind the
+// last (a lane reads rows up to 31 of its column whatever pt is: they meet zero coefficients). Behind the stage buffers,
+// at offc, the pass's coefficient operand: three base-256 digit planes [digit][resized row 0..31][source row 0..31], int8.
 struct BandLds {
     int p0, p1;          // row pitches in bytes (multiples of 4)
     int off1, off2, total;
+    int pt, skew;        // transposed B1 (mfma_v): column pitch, bytes of skew per 8 columns; pt == 0: B1 is row-major
+    int offc;            // coefficient operand (mfma_v)
 };
+
+// Sub-bands the matrix form covers: one instruction tile, N = 32 resized rows from K = 32 source rows. (A second K block
+// would never run: with both passes at <= 7 taps, more than 32 source rows of B0 and B1 do not fit the kernel's LDS budget.)
+constexpr int CF_MFMA_N = 32, CF_MFMA_K = 32;
 
 __device__ __forceinline__ BandLds band_lds(const CropPlan& pl, const BandRows& b) {
     BandLds l;
     l.p0 = align_up(pl.sw * 3, 4) + 4;
     l.p1 = align_up(pl.rw * 3, 4) + 4;
+    l.pt = l.skew = l.offc = 0;
     const int n0 = b.ty1 - b.ty0, n2 = b.ry1 - b.ry0;
-    const int s0 = align_up(n0 * l.p0, 16), s1 = align_up(n0 * l.p1, 16), s2 = align_up(n2 * l.p1, 16);
+    int s1 = align_up(n0 * l.p1, 16);
+    if (pl.mfma_v) {
+        // B2's rows hold whole 32-column blocks (the pass stores every column of its last block) and lie 2 x odd dwords
+        // apart: the pass's 64 lanes store one dword each to 32 rows x 2 neighbouring dwords, on 64 different banks
+        const int pt4 = (n0 + 3) >> 2, nblk = (pl.rw * 3 + 31) >> 5;
+        if (l.p1 < nblk * 32) l.p1 = nblk * 32;
+        while (((l.p1 >> 2) & 3) != 2) l.p1 += 4;
+        l.pt = pt4 * 4;
+        l.skew = (pt4 & 1) ? 0 : 4;
+        s1 = align_up(nblk * 32 * l.pt + nblk * 4 * l.skew + 32, 16);
+    }
+    const int s0 = align_up(n0 * l.p0, 16), s2 = align_up(n2 * l.p1, 16);
     l.off1 = s0;
     if (pl.need_h && pl.need_v) {
         // B2 reuses B0's space only when it fits there: the vertical pass reads B1 while it writes B2, so a B2
@@ -233,6 +259,10 @@ __device__ __forceinline__ BandLds band_lds(const CropPlan& pl, const BandRows& 
     } else {
         l.off2 = 0;
         l.total = s0;
+    }
+    if (pl.mfma_v) {
+        l.offc = l.total;
+        l.total += 3 * CF_MFMA_N * CF_MFMA_K;
     }
     return l;
 }
@@ -297,7 +327,7 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
     pl.area_mode = 0;
     pl.iscale_x = pl.iscale_y = 1;
     pl.fused_rb = 0;
-    pl.pad_ = 0;
+    pl.mfma_v = 0;
     pl.coef_h = pl.coef_v = nullptr;
     pl.scale_x = pl.scale_y = 1.0;
     const double* b = p.boxes + (size_t)crop * 4;
@@ -396,23 +426,33 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
     }
     if (p.ablate & 16) pl.fused_rb = 2;
     if (pl.status == PA_CROP_OK && pl.area_mode != 4 && !(p.ablate & 16)) {
-        // largest sub-band height whose LDS stages fit the fused kernel's budget
+        // largest sub-band height whose LDS stages fit the fused kernel's budget. At each height the matrix form of the
+        // vertical pass is tried first (both passes, <= 7 taps, every sub-band within one 32 x 32 operand tile); where its
+        // transposed B1 and operand space do not fit, the vector form at the same height comes before a lower height.
+        // (not under the timing ablations of either pass: a skipped pass leaves the other with the wrong layout of B1)
+        const int mfma_ok = p.crop_mfma && pl.need_h && pl.need_v && pl.ksize_v <= 7 && !(p.ablate & 6);
 #pragma unroll 1
         for (int rb = 8; rb >= 1 && pl.fused_rb == 0; rb >>= 1) {
-            int worst = 0;
 #pragma unroll 1
-            for (int r0 = lane * rb; r0 < PA_CROP; r0 += 64 * rb) {
-                const BandRows b = band_rows(pl, r0, r0 + rb);
-                const int need = band_lds(pl, b).total;
-                worst = need > worst ? need : worst;
-            }
+            for (int m = mfma_ok; m >= 0 && pl.fused_rb == 0; --m) {
+                pl.mfma_v = m;
+                int worst = 0;
+#pragma unroll 1
+                for (int r0 = lane * rb; r0 < PA_CROP; r0 += 64 * rb) {
+                    const BandRows b = band_rows(pl, r0, r0 + rb);
+                    int need = band_lds(pl, b).total;
+                    if (m && (b.ty1 - b.ty0 > CF_MFMA_K || b.ry1 - b.ry0 > CF_MFMA_N)) need = 1 << 30;
+                    worst = need > worst ? need : worst;
+                }
 #pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const int o = __shfl_xor(worst, d, 64);
-                worst = o > worst ? o : worst;
+                for (int d = 32; d >= 1; d >>= 1) {
+                    const int o = __shfl_xor(worst, d, 64);
+                    worst = o > worst ? o : worst;
+                }
+                if (worst <= p.fused_lds) pl.fused_rb = rb;
             }
-            if (worst <= p.fused_lds) pl.fused_rb = rb;
         }
+        if (pl.fused_rb == 0) pl.mfma_v = 0;
     }
     if (lane == 0) {
         if (pl.status == PA_CROP_OK && pl.fused_rb == 0) {
@@ -470,6 +510,16 @@ __global__ __launch_bounds__(256) void coef_cache_kernel(int32_t* __restrict__ c
 __device__ __forceinline__ uint32_t clip8(int v) {
     v >>= PRECISION_BITS;
     return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// Four clip8 as one dword, bytes in argument order: v_ashr_pk_u8_i32 shifts two int32 right, saturates each to 0..255 and
+// packs them into bytes 0 and 1 -- what hipcc itself selects for this pattern. Bits 16..31 of its result are not zero on
+// gfx950 (hipcc 7.2 combines its own uses as if they were: the note at the vector form of the vertical pass), so the two
+// results are joined by byte selection (v_perm_b32), which never looks at them. Used by the matrix form of the pass only.
+__device__ __forceinline__ uint32_t clip8_pk4(int a, int b, int c, int d) {
+    // (the builtin, not inline assembly: the compiler then keeps the wait states between a matrix instruction and this read)
+    const uint32_t lo = __builtin_amdgcn_ashr_pk_u8_i32(a, b, PRECISION_BITS), hi = __builtin_amdgcn_ashr_pk_u8_i32(c, d, PRECISION_BITS);
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 
 // ---------------------------------------------------------------------------
@@ -765,7 +815,9 @@ struct LdsCanvas {
 
 constexpr int CF_NT = 512;         // threads of a crop_fused_kernel workgroup
 constexpr int CF_NW = CF_NT / 64;   // its waves
-__global__ __launch_bounds__(CF_NT) void crop_fused_kernel(const PreprocParams p) {
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+__global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParams p) {
 #ifdef PA_STAMP_BUILD
     const unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -831,10 +883,34 @@ __global__ __launch_bounds__(CF_NT) void crop_fused_kernel(const PreprocParams p
                 }
             }
         }
+        // (matrix-form vertical pass, L.pt != 0: its coefficient operand starts as zeros -- the band outside the taps)
+        const bool mfma_v = L.pt != 0;
+        if (mfma_v) {
+            uint32_t* cz = reinterpret_cast<uint32_t*>(pa_smem + L.offc);
+            for (int i = tid; i < 3 * CF_MFMA_N * CF_MFMA_K / 4; i += CF_NT) cz[i] = 0u;
+        }
         __syncthreads();
         // ---- stage H: B0 -> B1 ----------------------------------------------
         int in_base = 0, in_pitch = L.p0;
         if (pl.need_h && !(p.ablate & 2)) {
+            if (mfma_v && tid < CF_MFMA_N * 8) {
+                // the vertical pass's coefficient operand, once per workgroup and sub-band: thread = (resized row, tap).
+                // k = d0 + 256 d1 + 65536 d2 with d0, d1 in [-128, 127]; digit plane j holds d_j at [row][first tap + t]
+                const int n = tid >> 3, t = tid & 7;
+                if (n < n2) {
+                    const int32_t* row = coef_v + (size_t)(b.ry0 + n) * COEF_ROW;
+                    const int rel = row[0] - b.ty0 + t;
+                    if (t < row[1] && t < 7 && rel >= 0 && rel < CF_MFMA_K) {
+                        const int k = row[2 + t];
+                        const int d0 = (int)(int8_t)(k & 0xff), k1 = (k - d0) >> 8;
+                        const int d1 = (int)(int8_t)(k1 & 0xff), d2 = (k1 - d1) >> 8;
+                        uint8_t* c = pa_smem + L.offc + n * CF_MFMA_K + rel;
+                        c[0] = (uint8_t)d0;
+                        c[CF_MFMA_N * CF_MFMA_K] = (uint8_t)d1;
+                        c[2 * CF_MFMA_N * CF_MFMA_K] = (uint8_t)d2;
+                    }
+                }
+            }
             // work item = (output column, chunk of 4 rows): the column's <= 15 coefficients are
             // fetched once per item and reused for its rows; ~6 items per thread keeps all 256
             // threads busy (one item per column would leave the second pass 3/4 empty).
@@ -869,6 +945,7 @@ __global__ __launch_bounds__(CF_NT) void crop_fused_kernel(const PreprocParams p
 #pragma unroll
                         for (int q = 0; q < 6; ++q) w[u][q] = src[q];
                     }
+                    int tr[3][4];  // transposed B1: the chunk's four rows of each channel become one dword
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         uint32_t r[6];
@@ -884,11 +961,21 @@ __global__ __launch_bounds__(CF_NT) void crop_fused_kernel(const PreprocParams p
                             a2 += __mul24((int)((r[j2 >> 2] >> (8 * (j2 & 3))) & 0xff), k[t]);
                         }
                         const int y = ck * 4 + u;
-                        if (y < n0) {
+                        if (mfma_v) {
+                            tr[0][u] = a0, tr[1][u] = a1, tr[2][u] = a2;
+                        } else if (y < n0) {
                             const int d = L.off1 + y * L.p1 + xx * 3;
                             pa_smem[d + 0] = (uint8_t)clip8(a0);
                             pa_smem[d + 1] = (uint8_t)clip8(a1);
                             pa_smem[d + 2] = (uint8_t)clip8(a2);
+                        }
+                    }
+                    if (mfma_v) {
+                        // rows past the band's end (the clamped repeats) land in the column's padding: pt >= 4 * chunks
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int col = xx * 3 + c;
+                            *reinterpret_cast<uint32_t*>(pa_smem + L.off1 + col * L.pt + (col >> 3) * L.skew + ck * 4) = clip8_pk4(tr[c][0], tr[c][1], tr[c][2], tr[c][3]);
                         }
                     }
                 } else {
@@ -901,10 +988,18 @@ __global__ __launch_bounds__(CF_NT) void crop_fused_kernel(const PreprocParams p
                             a1 += __mul24((int)pa_smem[s + 3 * t + 1], kt);
                             a2 += __mul24((int)pa_smem[s + 3 * t + 2], kt);
                         }
-                        const int d = L.off1 + y * L.p1 + xx * 3;
-                        pa_smem[d + 0] = (uint8_t)clip8(a0);
-                        pa_smem[d + 1] = (uint8_t)clip8(a1);
-                        pa_smem[d + 2] = (uint8_t)clip8(a2);
+                        if (mfma_v) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) {
+                                const int col = xx * 3 + c;
+                                pa_smem[L.off1 + col * L.pt + (col >> 3) * L.skew + y] = (uint8_t)clip8(c == 0 ? a0 : (c == 1 ? a1 : a2));
+                            }
+                        } else {
+                            const int d = L.off1 + y * L.p1 + xx * 3;
+                            pa_smem[d + 0] = (uint8_t)clip8(a0);
+                            pa_smem[d + 1] = (uint8_t)clip8(a1);
+                            pa_smem[d + 2] = (uint8_t)clip8(a2);
+                        }
                     }
                 }
             }
@@ -921,7 +1016,60 @@ __global__ __launch_bounds__(CF_NT) void crop_fused_kernel(const PreprocParams p
         // ---- stage V: (B1 | B0) -> B2 ------------------------------------------
         // wave w takes output rows w, w+4, ...: the row's coefficients are wave-uniform (loaded
         // once), each lane produces 4 bytes from one ds_read_b32 per tap row.
-        if (pl.need_v && !(p.ablate & 4)) {
+        if (mfma_v) {
+            // Matrix form: B2[resized row n][byte column] = clip8((2^21 + sum_k B1[k][column] * coef[n][k]) >> 22) as three
+            // int8 products D_j = (B1 - 128) x digit_j, one v_mfma_i32_32x32x32_i8 each: A = 32 byte
+            // columns x 32 source rows (a lane: its column's 16 consecutive rows from the transposed B1, -128 = one XOR per
+            // dword), B = the digit plane, 32 source rows x 32 resized rows (a lane: resized row lane & 31, the same 16 source
+            // rows as its A fragment, so the order of k inside the instruction does not matter). With the resized row's
+            // constant 2^21 + 128 * sum(coef), the exact int32 sum Pillow accumulates is D_0 + (D_1 << 8) + (D_2 << 16) + constant.
+            // A wave takes every eighth 32-column block; the B fragments stay in registers over its blocks.
+            const int n = lane & 31, hk = (lane >> 5) * 16;
+            const int nblk = (pl.rw * 3 + 31) >> 5;
+            const uint8_t* cop = pa_smem + L.offc + n * CF_MFMA_K + hk;  // + j * CF_MFMA_N * CF_MFMA_K: digit plane j
+            i32x4 bop[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) bop[j] = *reinterpret_cast<const i32x4*>(cop + j * CF_MFMA_N * CF_MFMA_K);
+            int cst = 0;
+            if (n < n2) {
+                const int32_t* row = coef_v + (size_t)(b.ry0 + n) * COEF_ROW;
+                const int cnt = row[1];
+                int ksum = 0;
+#pragma unroll
+                for (int t = 0; t < 7; ++t) ksum += t < cnt ? row[2 + t] : 0;
+                cst = 128 * ksum + (1 << (PRECISION_BITS - 1));
+            }
+            uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off2 + n * L.p1 + (lane >> 5) * 4);
+            for (int blk = wave; blk < nblk; blk += CF_NW) {
+                const int col = blk * 32 + n;
+                const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + L.off1 + col * L.pt + (col >> 3) * L.skew + hk);
+                i32x4 a;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) a[q] = (int)(src[q] ^ 0x80808080u);
+                // Horner over the digits, in one accumulator tile: ((D_2 << 8) + D_1 << 8) + D_0 + constant (wrapping int32
+                // arithmetic; the total itself fits)
+                i32x16 acc;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[e] = 0;
+#pragma unroll
+                for (int j = 2; j >= 0; --j) {
+                    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bop[j], acc, 0, 0, 0);
+                    if (j) {
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) acc[e] = (int)(((uint32_t)acc[e] << 8) + (j == 1 ? (uint32_t)cst : 0u));
+                    }
+                }
+                // result register 4g + e of a lane: byte column 32 blk + 8g + 4 (lane >> 5) + e of resized row lane & 31,
+                // so a register group is one dword of B2's row (whose pitch holds the whole last block)
+                if (n < n2) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) dst[blk * 8 + 2 * g] = clip8_pk4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+                }
+            }
+            in_base = L.off2;
+            in_pitch = L.p1;
+            __syncthreads();
+        } else if (pl.need_v && !(p.ablate & 4)) {
             const int row_dwords = (pl.rw * 3 + 3) >> 2;
             const uint32_t* lds32 = reinterpret_cast<const uint32_t*>(pa_smem);
             const int pitch_dw = in_pitch >> 2;
@@ -1556,6 +1704,8 @@ hipError_t launch_preprocess(const PreprocParams& p_in, hipStream_t s) {
     p.fused_lds = budget & ~15;
     static const int ablate = getenv("PA_PRE_ABLATE") ? atoi(getenv("PA_PRE_ABLATE")) : 0;  // timing experiments only
     p.ablate = ablate;
+    static const int crop_mfma = getenv("PA_CROP_MFMA") ? atoi(getenv("PA_CROP_MFMA")) : 1;  // 0: the A/B switch of the matrix-core vertical pass
+    p.crop_mfma = crop_mfma;
     const int ncrops = p.n_frames * p.fighters;
     if (ncrops <= 0) return hipSuccess;
     hipLaunchKernelGGL(crop_plan_kernel, dim3(ncrops), dim3(256), 0, s, p);

@@ -2,7 +2,8 @@
 // spread evenly between them, R LDS reads (ds_read_b128 or ds_read_b64, results feed the next iteration's operands), V full-rate
 // vector instructions (v_fma_f32) and T transcendental ones (v_exp_f32). Two waves per SIMD (workgroups of four waves, two per
 // CU), like the GEMM kernels. Prints SIMD cycles per iteration and wave -- 2048 when the extra work is free. A second section does
-// the same around v_mfma_f32_32x32x16_bf16 (1024 cycles per iteration).
+// the same around v_mfma_f32_32x32x16_bf16 (1024 cycles per iteration), a last one around v_mfma_i32_32x32x32_i8 (what the crop
+// stage's vertical bicubic pass runs on) with integer vector instructions beside it. `mfma_mix i8` runs only that last section.
 //   hipcc --offload-arch=gfx950 -O3 scripts/micro/mfma_f32_mix.hip -o /tmp/mfma_mix && /tmp/mfma_mix
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -142,6 +143,65 @@ __global__ __launch_bounds__(256, 2) void mixbf(float* out, unsigned long long* 
     if (lane == 0) clk[blockIdx.x * 4 + wave] = t1 - t0;
 }
 
+// The same loop around 32 x v_mfma_i32_32x32x32_i8 (crop_fused_kernel's vertical pass) with R ds_read_b128 and V integer vector
+// instructions (v_lshl_add_u32, what the pass's digit recombination issues) beside it.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+template <int R, int V>
+__global__ __launch_bounds__(256, 2) void mixi8(float* out, unsigned long long* clk, int iters, float a0, float b0) {
+    __shared__ __attribute__((aligned(16))) float lds[4 * 64 * 32];
+    for (int i = threadIdx.x; i < 4 * 64 * 32; i += 256) lds[i] = a0 + i * 1e-6f;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned row = (unsigned)(size_t)(__attribute__((address_space(3))) float*)(lds + (wave * 64 + lane) * 32);
+    const int swz = (lane >> 1) & 7;
+    unsigned addr[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) addr[r] = row + ((r ^ swz) * 16);
+    i32x16 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[i][e] = 0;
+    i32x4 opnd[2][8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) opnd[s][i] = i32x4{(int)a0, (int)b0, lane, wave};
+    int va[4] = {(int)a0, lane, wave, 3};
+    const int vb = (int)b0 + lane;
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (int it = 0; it < iters; it += 2) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const int cur = half, nxt = half ^ 1;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int j = 0; j < 32; ++j) {
+#pragma unroll
+                for (int r = (j * R) / 32; r < ((j + 1) * R) / 32; ++r)
+                    asm volatile("ds_read_b128 %0, %1" : "=v"(opnd[nxt][r & 7]) : "v"(addr[r & 7]) : "memory");
+#pragma unroll
+                for (int q = (j * V) / 32; q < ((j + 1) * V) / 32; ++q) asm volatile("v_lshl_add_u32 %0, %0, 8, %1" : "+v"(va[q & 3]) : "v"(vb));
+                asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, %0" : "+v"(acc[j & 3]) : "v"(opnd[cur][j & 7]), "v"(opnd[cur][(j + 1) & 7]));
+            }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+    int s = va[0] + va[1] + va[2] + va[3];
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += opnd[s2][i].x + opnd[s2][i].z;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s += acc[i][e];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (float)s;
+    if (lane == 0) clk[blockIdx.x * 4 + wave] = t1 - t0;
+}
+
 // Round 6: the Winograd kernel's own instruction, v_mfma_f32_16x16x4_f32 -- 64 per loop iteration (2048
 // issue cycles, as one chunk of wino.hip) -- with the chunk's input transform beside it either as PK packed additions
 // (v_pk_add_f32: two floats per instruction, what hipcc emits for the kernel's f32x2 arithmetic) or as V scalar ones (v_add_f32).
@@ -206,8 +266,26 @@ void run(const char* name, K kern) {
     hipFree(out); hipFree(clk);
 }
 
-int main() {
+static void i8_section() {
+    printf("--- v_mfma_i32_32x32x32_i8 (8 passes like the bf16 form: 1024 issue cycles per iteration; the rate column counts integer ops)\n");
+    base_cycles = 1024.0;
+    flop_per_mfma = 65536.0;
+    run("i8 bare", mixi8<0, 0>);
+    run("i8 + 32 ds_read_b128", mixi8<32, 0>);
+    run("i8 + 32 v_lshl_add_u32", mixi8<0, 32>);
+    run("i8 + 64 v_lshl_add_u32", mixi8<0, 64>);
+    run("i8 + 128 v_lshl_add_u32", mixi8<0, 128>);
+    run("i8 + 256 v_lshl_add_u32", mixi8<0, 256>);
+    run("i8 + 512 v_lshl_add_u32", mixi8<0, 512>);
+    run("i8 + 32 b128 + 128 v_lshl_add_u32", mixi8<32, 128>);
+}
+
+int main(int argc, char** argv) {
     run("bare", mix<0, 4, 0, 0>);
+    if (argc > 1 && argv[1][0] == 'i') {
+        i8_section();
+        return 0;
+    }
     run("4 ds_read_b128", mix<4, 4, 0, 0>);
     run("8 ds_read_b128", mix<8, 4, 0, 0>);
     run("12 ds_read_b128 (128 x 64 tile, 2 x 2 waves)", mix<12, 4, 0, 0>);
@@ -247,5 +325,6 @@ int main() {
     run("16x16x4 + 64 v_add_f32 (the same, scalar)", mix16<64, 0>);
     run("16x16x4 + 64 v_pk_add_f32", mix16<0, 64>);
     run("16x16x4 + 128 v_add_f32", mix16<128, 0>);
+    i8_section();
     return 0;
 }
