@@ -175,6 +175,23 @@ int pa_square_crops(pa_engine* e, const uint8_t* frames, int32_t n, int32_t heig
                     const double* boxes, int32_t padding, int32_t swap_rb, uint8_t* crops,
                     int32_t* status, void* stream);
 
+/* The same at any output size (ABI 15, appended): YoloCrop.square_crop(frame, output_size, padding) for every integer
+ * output_size in PA_CROP_SIZE_MIN .. PA_CROP_SIZE_MAX (PA_ERR_INVALID_ARG outside). crops: uint8[n,num_fighters,S,S,3] with
+ * S = output_size; status as above, failed crops all zero; stream-ordered with pa_square_crops (it uses the same scratch of the
+ * engine, which is sized by max_frame_height x max_frame_width and not by S). All branches of cv2.resize(INTER_AREA) to
+ * (S, int(d * (S / float(d)))) are kept: copy (d == S), 2 x 2 and integer scale, the general shrink in OpenCV's fp32 order,
+ * the fixed-point bilinear emulation for d < S, and the black last row when the height comes out as S - 1. Its kernels
+ * (csrc/crop_sized.hip) are a multi-pass form; pa_square_crops keeps the 128 x 128 kernels, which this call never launches.
+ * Kernel limits, the only sources of PA_CROP_FILTER_TOO_WIDE here (the same two as pa_square_crops): a Pillow BICUBIC pass of
+ * ImageOps.pad that shrinks by more than 3.5 (more than 15 taps: with padding 30 an unclipped box whose square side is below
+ * 24 pixels), and a slice whose intermediates (slice rows x padded width x 3 bytes) exceed one max_frame_height x
+ * max_frame_width frame. */
+#define PA_CROP_SIZE_MIN 16
+#define PA_CROP_SIZE_MAX 512
+int pa_square_crops_sized(pa_engine* e, const uint8_t* frames, int32_t n, int32_t height, int32_t width,
+                          const double* boxes, int32_t padding, int32_t swap_rb, int32_t output_size,
+                          uint8_t* crops, int32_t* status, void* stream);
+
 /* ---- a5: the runner's own input branch ----------------------------------- */
 
 /* One crop image inside a byte buffer: what YOLOv5 --save-crop wrote and cv2.imread returns
@@ -726,7 +743,8 @@ int pa_lstm_layer_forms(const pa_lstm* h, int32_t* forms, int32_t cap);
  * buffers of buf_floats_per_crop[b] floats per crop, NHWC with a zero border of `pad` pixels; a bordered buffer
  * must keep one geometry for the whole table. Layers run in table order. */
 typedef struct pa_conv_desc {
-    int32_t kind;               /* 0 convolution, 1 stem 7x7/2 + ReLU + max-pool 3x3/2 of the 128x128x3 input, 2 global average pool */
+    int32_t kind;               /* 0 convolution, 1 stem 7x7/2 + ReLU + max-pool 3x3/2 of the 128x128x3 input, 2 global average pool,
+                                   3 the same stem + max-pool of an in_hw x in_hw x 3 input (below) */
     int32_t cin, cout;          /* kind 0: cin % 32 == 0, cout % 64 == 0; kind 2: cin = channels */
     int32_t ksize, stride;      /* 1 | 3, 1 | 2 */
     int32_t in_hw;              /* spatial size of the input interior (square) */
@@ -737,6 +755,14 @@ typedef struct pa_conv_desc {
     int64_t w_off, b_off;
 } pa_conv_desc;
 typedef struct pa_convnet pa_convnet;
+/* Kind 3 (ABI 15, appended; csrc/stem_pool_any.hip): the kind-1 stem for a square input of any in_hw with in_hw % 32 == 0 and
+ * 64 <= in_hw <= 512. Weights in the same [64][7][8][4] layout, in_pad == 3, out_pad == 1; it writes the pooled map
+ * [in_hw / 4 + 2]^2 x 64 (zero border 1). A table holds at most one stem row (kind 1 or 3), and that row sets the size of the
+ * input pa_convnet_forward / pa_convnet_trace take: x float32[n,3,in_hw,in_hw], converted into [max_crops][in_hw + 6]^2 x 4
+ * (which is what trace's buf = -1 returns). Kind 1 keeps meaning 128 and keeps its kernel. fp32 only: create refuses a
+ * PA_DTYPE_BF16 table with a kind-3 row, and any kind-3 row outside the limits above, naming the row in last_error. Every other
+ * row runs on the launchers it ran on before; a stride-1 3x3 row whose map is not 4, 8, 16 or 32 pixels wide (the widths the
+ * patch-resident kernel is laid out for) and that Winograd does not take (sides % 4 != 0, or below 8) runs on the implicit GEMM. */
 int pa_convnet_create(int32_t device, const pa_conv_desc* descs, int32_t n_descs, const int64_t* buf_floats_per_crop,
                       int32_t n_bufs, const float* weights_host, size_t n_weights, int32_t max_crops, pa_convnet** out);
 /* The same with the convolutions' arithmetic chosen (ABI 11): PA_DTYPE_F32 (= pa_convnet_create) or PA_DTYPE_EMULATED_F32 -- every
@@ -764,13 +790,14 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
                             pa_convnet** out);
 void pa_convnet_destroy(pa_convnet* h);
 const char* pa_convnet_last_error(const pa_convnet* h);
-/* x float32[n,3,128,128] (NCHW, device) -> out: the last layer's output buffer, float32[n, out_floats_per_crop]. */
+/* x float32[n,3,S,S] (NCHW, device; S = 128, or the in_hw of the table's kind-3 row) -> out: the last layer's output buffer,
+ * float32[n, out_floats_per_crop]. */
 int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int32_t out_floats_per_crop, void* stream);
 /* Test aids (ABI 15). pa_convnet_trace enqueues exactly what pa_convnet_forward enqueues for n (1..max_crops) crops -- kernels,
  * tiles, knobs -- for layers 0..last_row (-1: the input conversion alone), then copies the WHOLE buffer `buf` as stored to `out`
  * (device): max_crops x buf_floats_per_crop[buf] floats, zero borders and the crops at n and above included; each layer writes
  * crop i of its output at i x its own per-crop geometry ((hw + 2 pad)^2 x channels). buf = -1 is the stem's input
- * [max_crops][134][134][4]. Under PA_DTYPE_BF16 a bf16 buffer (and buf = -1) is copied as stored, 2 bytes per element, and
+ * [max_crops][S + 6][S + 6][4] (S = 128 without a kind-3 row). Under PA_DTYPE_BF16 a bf16 buffer (and buf = -1) is copied as stored, 2 bytes per element, and
  * out_bytes is checked against that size. PA_ERR_INVALID_ARG for a row or buffer out of range, n outside 1..max_crops or out_bytes short of
  * the buffer; nothing is enqueued then. pa_convnet_layer_forms: the form each layer ran as in the last forward or trace (a
  * launcher that refuses a shape passes the layer on to the next form); forms: host int32[cap], cap >= n_descs. */
@@ -789,6 +816,10 @@ typedef enum pa_cn_form {
     PA_CN_FORM_BGEMM_SPLITK = 10,   /* ... its split-K form */
     PA_CN_FORM_AVGPOOL_BF16 = 11    /* global average pool of a bf16 map, fp32 out (PA_DTYPE_BF16) */
 } pa_cn_form;
+/* Appended: the form of a kind-3 row (stem + max-pool of any size, stem_pool_any.hip), reported by pa_convnet_layer_forms like
+ * the values above. A constant beside the enumeration, not a thirteenth enumerator: the list above and its Python mirror
+ * (_lib.CN_FORMS) are compared entry by entry by the ABI-15 tests and stay as they are; _lib.CN_FORM_NAMES has the name. */
+#define PA_CN_FORM_STEM_POOL_ANY 12
 int pa_convnet_layer_forms(const pa_convnet* h, int32_t* forms, int32_t cap);
 
 /* One stride-1 3x3 convolution (padding 1) on the Winograd F(2x2, 3x3) kernel of the fp32 convolution stack

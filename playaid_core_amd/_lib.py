@@ -28,6 +28,9 @@ DET_FORMS = ("not_run", "stem_direct", "stem_bf16", "wino", "patch", "pgemm", "p
 # pa_cn_form / pa_lstm_form (ABI 15): the form a conv-net table row / an LSTM layer ran as, by value
 CN_FORMS = ("not_run", "stem_pool", "avgpool", "wino", "patch", "igemm_128x128", "igemm_128x64", "igemm_64x64", "psgemm",
             "bgemm", "bgemm_splitk", "avgpool_bf16")
+# PA_CN_FORM_STEM_POOL_ANY (appended beside the enum, see the header): every value pa_convnet_layer_forms can report, by value
+PA_CN_FORM_STEM_POOL_ANY = 12
+CN_FORM_NAMES = CN_FORMS + ("stem_pool_any",)
 LSTM_FORMS = ("not_run", "steps", "u1", "u2", "u4", "u8", "mfma")
 
 PA_OK = 0
@@ -47,6 +50,9 @@ PA_CROP_BAD_BOX = 2
 PA_CROP_UPSCALE = 3
 PA_CROP_FILTER_TOO_WIDE = 4
 PA_CROP_BAD_FRAME = 5
+# pa_square_crops_sized: the output sizes it takes
+PA_CROP_SIZE_MIN = 16
+PA_CROP_SIZE_MAX = 512
 
 
 class HipLibraryError(RuntimeError):
@@ -139,6 +145,7 @@ SYMBOLS = [
     ("pa_weight_blob_bytes", C.c_size_t, [C.c_int, C.c_int]),
     ("pa_infer_windows", C.c_int, [_P, _P, C.c_int32, _P, _P]),
     ("pa_square_crops", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("pa_square_crops_sized", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     ("pa_runner_inputs", C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("pa_backbone_crop_images", C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     ("pa_detect_postprocess", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_int32,

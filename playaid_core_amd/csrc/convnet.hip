@@ -8,7 +8,10 @@
 //   kind 0  convolution k x k (k = 1 | 3), stride 1 | 2, + bias (+ residual) (+ ReLU): conv3x3_patch_kernel for the
 //           stride-1 3x3 layers it covers, the im2col engine (igemm.hip) for everything else (1x1 = a GEMM);
 //   kind 1  the 7x7/2 stem + BatchNorm + ReLU + 3x3/2 max-pool of a 128 x 128 x 3 input (stem_pool.hip);
-//   kind 2  global average pool of the interior.
+//   kind 2  global average pool of the interior;
+//   kind 3  the kind-1 stem + max-pool of an in_hw x in_hw x 3 input, in_hw % 32 == 0, 64 .. 512 (stem_pool_any.hip; fp32 tables only).
+// The table's stem row sets the size S of the input forward and trace take (128 without a kind-3 row); every other row runs on
+// the launchers above at whatever map size the table gives it, a launcher that refuses a shape handing it to the next form.
 // Under PA_DTYPE_BF16 (never the default) the stem and convolution rows store bf16: the stem on stem_pool.hip's bf16 form, every
 // convolution on the one-slice bf16 GEMM (bgemm.hip), in its split-K form where the unsplit grid would leave most of the chip idle,
 // the pool on a bf16 twin of the fp32 one (fp32 out). Rounding model: include/playaid_hip.h next to pa_convnet_create_dtype.
@@ -74,7 +77,9 @@ struct pa_convnet {
     std::vector<char> buf_bf16;                // per buffer: 1 = bf16 elements
     float* bg_slab = nullptr;                  // bgemm split-K partials: BGEMM_SLAB_ITEMS workgroups x 128 x 128 fp32
     int32_t* bg_tickets = nullptr;             // BGEMM_TICKETS of them, zero between launches
-    float* x0 = nullptr;  // [max_crops][134][134][4] model input of the stem (bf16 elements under PA_DTYPE_BF16)
+    float* x0 = nullptr;  // [max_crops][in_hw + 6][in_hw + 6][4] model input of the stem (bf16 elements under PA_DTYPE_BF16)
+    int in_hw = 128;      // side of the input crops: 128, or the in_hw of the table's kind-3 row
+    bool sized = false;   // the table has a kind-3 row: the input goes through the sized conversion
     std::vector<int32_t> forms;  // per layer: the pa_cn_form the last forward or trace launched it as (pa_convnet_layer_forms)
     std::string last_error;
 };
@@ -89,6 +94,7 @@ int cn_fail(pa_convnet* h, int code, const std::string& msg) {
 // interior size and channel count a layer leaves in its output buffer
 void out_geom(const pa_conv_desc& d, int* hw, int* c) {
     if (d.kind == 1) { *hw = 32; *c = 64; }
+    else if (d.kind == 3) { *hw = d.in_hw / 4; *c = 64; }
     else if (d.kind == 2) { *hw = 1; *c = d.cin; }
     else { *hw = d.in_hw / d.stride; *c = d.cout; }
 }
@@ -179,10 +185,26 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
                 return cn_fail(h, PA_ERR_BAD_WEIGHTS, "layer " + std::to_string(i) + ": weights outside the blob");
             if (!use(d.in_buf, d.in_hw, d.in_pad, d.cin, "input", i) || !use(d.out_buf, ohw, d.out_pad, oc, "output", i)) return PA_ERR_INVALID_ARG;
             if (d.res_buf >= 0 && !use(d.res_buf, ohw, d.out_pad, oc, "residual", i)) return PA_ERR_INVALID_ARG;
+            // (the launchers address a buffer with 32-bit byte offsets)
+            if ((long long)max_crops * (d.in_hw + 2 * d.in_pad) * (d.in_hw + 2 * d.in_pad) * d.cin * 4 >= (1ll << 31) ||
+                (long long)max_crops * (ohw + 2 * d.out_pad) * (ohw + 2 * d.out_pad) * oc * 4 >= (1ll << 31))
+                return cn_fail(h, PA_ERR_CAPACITY, "layer " + std::to_string(i) + ": max_crops maps of this size exceed 2 GiB");
         } else if (d.kind == 1) {
             if (d.out_pad != 1 || d.w_off < 0 || (size_t)d.w_off + 64 * 224 > n_weights || d.b_off < 0 || (size_t)d.b_off + 64 > n_weights)
                 return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": bad stem");
             if (!use(d.out_buf, 32, 1, 64, "output", i)) return PA_ERR_INVALID_ARG;
+        } else if (d.kind == 3) {
+            const std::string row = "layer " + std::to_string(i) + " (stem of any size): ";
+            if (compute_dtype == PA_DTYPE_BF16) return cn_fail(h, PA_ERR_INVALID_ARG, row + "a bf16 table takes the 128 x 128 stem (kind 1) only");
+            if (d.in_hw % 32 != 0 || d.in_hw < 64 || d.in_hw > 512)
+                return cn_fail(h, PA_ERR_INVALID_ARG, row + "in_hw must be a multiple of 32 in 64..512");
+            if (d.in_pad != 3 || d.out_pad != 1 || d.cin != 3 || d.cout != 64) return cn_fail(h, PA_ERR_INVALID_ARG, row + "needs cin 3, cout 64, in_pad 3, out_pad 1");
+            if (d.w_off < 0 || (size_t)d.w_off + 64 * 224 > n_weights || d.b_off < 0 || (size_t)d.b_off + 64 > n_weights)
+                return cn_fail(h, PA_ERR_BAD_WEIGHTS, row + "weights outside the blob");
+            if (h->sized) return cn_fail(h, PA_ERR_INVALID_ARG, row + "a table holds one stem row");
+            if (!use(d.out_buf, d.in_hw / 4, 1, 64, "output", i)) return PA_ERR_INVALID_ARG;
+            h->sized = true;
+            h->in_hw = d.in_hw;
         } else if (d.kind == 2) {
             if (d.cin < 1 || d.in_hw < 1 || d.in_pad < 0) return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": bad pool");
             if (!use(d.in_buf, d.in_hw, d.in_pad, d.cin, "input", i) || !use(d.out_buf, 1, 0, d.cin, "output", i)) return PA_ERR_INVALID_ARG;
@@ -190,6 +212,9 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
             return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": unknown kind");
         }
     }
+    if (h->sized)
+        for (int i = 0; i < n_descs; ++i)
+            if (h->descs[i].kind == 1) return cn_fail(h, PA_ERR_INVALID_ARG, "layer " + std::to_string(i) + ": a 128 x 128 stem beside a stem of another size");
     if (compute_dtype == PA_DTYPE_BF16) {
         // element type of each buffer from its writers: stem and convolutions bf16, the pool fp32; one type per buffer, every row
         // reads bf16, every convolution one bgemm takes, and the table ends in a pool (pa_convnet_forward's out is fp32)
@@ -272,7 +297,7 @@ int pa_convnet_create_dtype(int32_t device, const pa_conv_desc* descs, int32_t n
         if (!chk(hipMalloc(&h->bufs[b], bytes), "hipMalloc activations")) return PA_ERR_HIP;
         if (!chk(hipMemset(h->bufs[b], 0, bytes), "hipMemset activations")) return PA_ERR_HIP;
     }
-    const size_t x0_bytes = (size_t)max_crops * 134 * 134 * 4 * sizeof(float);
+    const size_t x0_bytes = (size_t)max_crops * (h->in_hw + 6) * (h->in_hw + 6) * 4 * sizeof(float);
     if (!chk(hipMalloc(&h->x0, x0_bytes), "hipMalloc input")) return PA_ERR_HIP;
     if (!chk(hipMemset(h->x0, 0, x0_bytes), "hipMemset input")) return PA_ERR_HIP;
     return PA_OK;
@@ -296,7 +321,8 @@ namespace {
 // each layer's form. Arguments are checked by the callers.
 int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t s) {
     const bool bf = h->compute_dtype == PA_DTYPE_BF16;
-    CN_HIP(pa::launch_nchw_to_padded(x, h->x0, n, bf ? 1 : 0, s));
+    if (h->sized) CN_HIP(pa::launch_nchw_to_padded_sized(x, h->x0, n, h->in_hw, s));
+    else CN_HIP(pa::launch_nchw_to_padded(x, h->x0, n, bf ? 1 : 0, s));
     for (int li = 0; li <= last; ++li) {
         const pa_conv_desc& d = h->descs[li];
         if (d.kind == 1) {
@@ -310,6 +336,19 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
             sp.in_bf16 = sp.out_bf16 = bf ? 1 : 0;
             CN_HIP(pa::launch_stem_pool(sp, s));
             h->forms[li] = PA_CN_FORM_STEM_POOL;
+            continue;
+        }
+        if (d.kind == 3) {
+            pa::StemPoolAnyParams sp;
+            memset(&sp, 0, sizeof(sp));
+            sp.x = h->x0;
+            sp.wgt = h->weights + d.w_off;
+            sp.bias = h->weights + d.b_off;
+            sp.out = h->bufs[d.out_buf];
+            sp.crops = n;
+            sp.in_hw = d.in_hw;
+            CN_HIP(pa::launch_stem_pool_any(sp, s));
+            h->forms[li] = PA_CN_FORM_STEM_POOL_ANY;
             continue;
         }
         if (d.kind == 2) {
@@ -356,7 +395,8 @@ int convnet_run(pa_convnet* h, const float* x, int32_t n, int last, hipStream_t 
             form = PA_CN_FORM_WINO;
             pe = pa::launch_wino3x3(pa::wino_params(p, n, d.in_hw, d.in_hw, d.cin, h->fw.wino + h->fw.wino_off[li], h->fw.wino_bn[li]), s);
         }
-        if (pe == hipErrorInvalidValue && d.ksize == 3 && d.stride == 1 && d.in_pad == 1) {
+        // (the patch-resident kernel's tiles and chunk swizzle are laid out for maps 32, 16, 8 and 4 pixels wide: no other width is tried)
+        if (pe == hipErrorInvalidValue && d.ksize == 3 && d.stride == 1 && d.in_pad == 1 && (d.in_hw == 32 || d.in_hw == 16 || d.in_hw == 8 || d.in_hw == 4)) {
             form = PA_CN_FORM_PATCH;
             pe = pa::launch_conv3x3_patch(p, tile == pa::TILE_64x64 ? 64 : 128, s);
         }
@@ -386,7 +426,7 @@ int pa_convnet_forward(pa_convnet* h, const float* x, int32_t n, float* out, int
     const pa_conv_desc& last = h->descs.back();
     int ohw, oc;
     out_geom(last, &ohw, &oc);
-    const int opad = last.kind == 0 ? last.out_pad : (last.kind == 1 ? 1 : 0);
+    const int opad = last.kind == 0 ? last.out_pad : (last.kind == 1 || last.kind == 3 ? 1 : 0);
     const int per_crop = (ohw + 2 * opad) * (ohw + 2 * opad) * oc;
     if (out_floats_per_crop != per_crop) return cn_fail(h, PA_ERR_INVALID_ARG, "pa_convnet_forward: out_floats_per_crop does not match the last layer");
     CN_HIP(hipMemcpyAsync(out, h->bufs[last.out_buf], (size_t)n * per_crop * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -400,7 +440,7 @@ int pa_convnet_trace(pa_convnet* h, const float* x, int32_t n, int32_t last_row,
     if (n < 1 || n > h->max_crops) return fail("n outside 1..max_crops");
     if (last_row < -1 || last_row >= (int32_t)h->descs.size()) return fail("row out of range");
     if (buf < -1 || buf >= (int32_t)h->buf_floats.size()) return fail("buffer out of range");
-    const size_t elems = (size_t)h->max_crops * (buf < 0 ? (size_t)134 * 134 * 4 : (size_t)h->buf_floats[buf]);
+    const size_t elems = (size_t)h->max_crops * (buf < 0 ? (size_t)(h->in_hw + 6) * (h->in_hw + 6) * 4 : (size_t)h->buf_floats[buf]);
     const size_t bytes = elems * (is_bf16(h, buf) ? 2 : sizeof(float));
     if (out_bytes < bytes) return fail("out is smaller than the buffer");
     if (buf >= (int32_t)h->bufs.size() || !h->x0) return fail("the handle holds no buffers (its creation failed)");

@@ -1348,6 +1348,45 @@ int pa_square_crops(pa_engine* e, const uint8_t* frames, int32_t n, int32_t heig
     return run_preprocess(e, frames, n, height, width, boxes, padding, swap_rb, crops, nullptr, status, (hipStream_t)stream);
 }
 
+int pa_square_crops_sized(pa_engine* e, const uint8_t* frames, int32_t n, int32_t height, int32_t width, const double* boxes,
+                          int32_t padding, int32_t swap_rb, int32_t output_size, uint8_t* crops, int32_t* status, void* stream) {
+    if (!e || !frames || !boxes || !crops || n < 1 || height < 1 || width < 1 || padding < 0)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_square_crops_sized: bad argument");
+    if (output_size < PA_CROP_SIZE_MIN || output_size > PA_CROP_SIZE_MAX)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_square_crops_sized: output_size outside " + std::to_string(PA_CROP_SIZE_MIN) + ".." + std::to_string(PA_CROP_SIZE_MAX));
+    if (n > e->cfg.max_batch_frames || height > e->cfg.max_frame_height || width > e->cfg.max_frame_width)
+        return fail(e, PA_ERR_CAPACITY, "pa_square_crops_sized: frames exceed engine capacity");
+    // the engine's crop scratch (plans, Pillow tables, the two intermediates) is sized by its frame capacity and serves every
+    // output size; the crop JPEG round trip (pa_set_crop_jpeg_quality) is a 128 x 128 stage and does not apply here
+    PreprocParams p;
+    memset(&p, 0, sizeof(p));
+    p.frames = frames;
+    p.boxes = boxes;
+    p.n_src = n;
+    p.n_frames = n;
+    p.height = height;
+    p.width = width;
+    p.fighters = e->cfg.num_fighters;
+    p.padding = padding;
+    p.swap_rb = swap_rb;
+    p.plans = e->plans;
+    p.coef = e->coef;
+    p.coef_dim = e->coef_dim;
+    p.coef_cache = e->coef_cache_pad == padding ? e->coef_cache : nullptr;
+    p.coef_cache_pad = padding;
+    p.coef_cache_dmax = e->coef_cache_dmax;
+    p.t1 = e->t1;
+    p.t2 = e->t2;
+    p.t_stride = e->t_stride;
+    p.crops_u8 = crops;
+    p.status = status;
+    hipStream_t s = (hipStream_t)stream;
+    const double ncrops = (double)n * e->cfg.num_fighters;
+    ProfScope ps(e, s, "square_crops_sized", 0.0, ncrops * (375.0 * 375 * 3 * 3 + 3.0 * output_size * output_size));
+    HIPCHK(e, launch_crop_sized(p, output_size, s));
+    return PA_OK;
+}
+
 namespace {
 int run_runner_inputs(pa_engine* e, const uint8_t* images, size_t images_bytes, const pa_crop_image* desc, int n, int swap_rb,
                       uint8_t* inputs_u8, float* inputs_f32, int32_t* status, hipStream_t s) {

@@ -143,6 +143,18 @@ struct StemPoolParams {
     int32_t out_bf16;
 };
 hipError_t launch_stem_pool(const StemPoolParams& p, hipStream_t s);
+// The same stem + max-pool for a square input of any size in_hw (in_hw % 32 == 0, 64 .. 512; stem_pool_any.hip): x fp32
+// [crops][in_hw + 6][in_hw + 6][4], wgt fp32 [64][224], out fp32 [crops][in_hw / 4 + 2]^2 x 64 (interior written). fp32 only.
+struct StemPoolAnyParams {
+    const float* x;
+    const float* wgt;
+    const float* bias;
+    float* out;
+    int32_t crops;
+    int32_t in_hw;
+    int32_t run;       // row pairs per run (set by the launcher)
+};
+hipError_t launch_stem_pool_any(const StemPoolAnyParams& p, hipStream_t s);
 // ordered split-K reduce of the slabs with the fused epilogue (igemm.hip); out_bf16: bf16 residual and output (igemm_bf16.hip)
 hipError_t launch_splitk_reduce(const GemmParams& p, hipStream_t s, bool out_bf16 = false);
 // stride-1 3x3 convolution with the input patch resident in LDS across the nine taps (patchconv.hip); bm = 128 | 64
@@ -267,6 +279,9 @@ struct PreprocParams {
 };
 
 hipError_t launch_preprocess(const PreprocParams& p, hipStream_t s);
+// square crops of out_size x out_size (PA_CROP_SIZE_MIN .. PA_CROP_SIZE_MAX) into p.crops_u8 [ncrops][out_size][out_size][3] (crop_sized.hip):
+// the multi-pass form on p's plans / coef / t1 / t2; no window ingest, no model input
+hipError_t launch_crop_sized(const PreprocParams& p, int out_size, hipStream_t s);
 // fills the engine's coefficient cache for one padding value (once per engine, or when the padding changes)
 size_t coef_cache_ints(int dmax);
 hipError_t launch_build_coef_cache(int32_t* cache, int padding, int dmax, hipStream_t s);
@@ -391,6 +406,8 @@ hipError_t launch_linear_f32(const float* X, int ld, const float* W, const float
 hipError_t launch_spin(int32_t microseconds, hipStream_t s);
 hipError_t launch_gate(const int* flag, int32_t max_microseconds, hipStream_t s);  // one thread busy for that long (stream-concurrency probe)
 hipError_t launch_nchw_to_padded(const float* x, float* out, int32_t n, int32_t out_bf16, hipStream_t s);
+// x[n][3][hw][hw] f32 -> zero-bordered fp32 [n][hw + 6][hw + 6][4] (the input of a kind-3 stem row; stem_pool_any.hip)
+hipError_t launch_nchw_to_padded_sized(const float* x, float* out, int32_t n, int32_t hw, hipStream_t s);
 // 3x3/2 max pool, padded [n][66][66][64] -> padded [n][34][34][64]
 hipError_t launch_maxpool(const float* in, float* out, int32_t n, hipStream_t s);
 // global average pool, padded [n][6][6][512] -> [n][512]

@@ -257,8 +257,26 @@ class Engine:
         return [np.ascontiguousarray(host[:, j, : oh[j]]) for j in range(len(rects))]
 
     # -- a6: crops -----------------------------------------------------------
-    def square_crops(self, frames, boxes, padding: int = constants.CROP_PADDING, swap_rb: bool = False):
-        """frames uint8[n,H,W,3], boxes float64[n,F',4] -> (crops uint8[n,F',128,128,3], status int32[n,F']) on host."""
+    @staticmethod
+    def _crop_size(output_size) -> int:
+        s = int(output_size)
+        if s != output_size or not _lib.PA_CROP_SIZE_MIN <= s <= _lib.PA_CROP_SIZE_MAX:
+            raise ValueError(f"output_size must be an integer in {_lib.PA_CROP_SIZE_MIN}..{_lib.PA_CROP_SIZE_MAX}, got {output_size!r}")
+        return s
+
+    def _square_crops_call(self, fd, n, h, w, bd, padding, swap_rb, size, crops, status):
+        """``pa_square_crops`` at 128 (the 128 x 128 kernels, as ever), ``pa_square_crops_sized`` at any other size."""
+        if size == 128:
+            rc = self._lib.pa_square_crops(self._h, _ptr(fd), n, h, w, _ptr(bd), padding, int(swap_rb), _ptr(crops), _ptr(status), self._stream())
+        else:
+            rc = self._lib.pa_square_crops_sized(self._h, _ptr(fd), n, h, w, _ptr(bd), padding, int(swap_rb), size, _ptr(crops), _ptr(status),
+                                                 self._stream())
+        self._check(rc)
+
+    def square_crops(self, frames, boxes, padding: int = constants.CROP_PADDING, swap_rb: bool = False, output_size: int = 128):
+        """frames uint8[n,H,W,3], boxes float64[n,F',4] -> (crops uint8[n,F',S,S,3], status int32[n,F']) on host, S = ``output_size``
+        (16..512; ``YoloCrop.square_crop``'s parameter)."""
+        size = self._crop_size(output_size)
         fd = self._dev(frames, torch.uint8)
         bd = self._dev(boxes, torch.float64)
         n, h, w, _ = fd.shape
@@ -270,37 +288,33 @@ class Engine:
             bd_use = pad
         else:
             bd_use = bd
-        crops = torch.empty((n, self.F, 128, 128, 3), dtype=torch.uint8, device=self.device)
+        crops = torch.empty((n, self.F, size, size, 3), dtype=torch.uint8, device=self.device)
         status = torch.empty((n, self.F), dtype=torch.int32, device=self.device)
-        self._check(
-            self._lib.pa_square_crops(
-                self._h, _ptr(fd), n, h, w, _ptr(bd_use), padding, int(swap_rb), _ptr(crops), _ptr(status), self._stream()
-            )
-        )
+        self._square_crops_call(fd, n, h, w, bd_use, padding, swap_rb, size, crops, status)
         torch.cuda.synchronize(self.device)
         return crops[:, :nf].cpu().numpy(), status[:, :nf].cpu().numpy()
 
     def square_crops_device(self, frames_dev: torch.Tensor, boxes_dev: torch.Tensor, out: torch.Tensor,
-                            padding: int = constants.CROP_PADDING, swap_rb: bool = False) -> torch.Tensor:
+                            padding: int = constants.CROP_PADDING, swap_rb: bool = False, output_size: int = 128) -> torch.Tensor:
         """One ``square_crop`` per frame, everything on the device and nothing waited for: frames uint8[k,H,W,3], boxes
-        float64[k,4] -> ``out`` uint8[k,128,128,3] (written in place); returns the status int32[k] (device)."""
+        float64[k,4] -> ``out`` uint8[k,S,S,3] (written in place), S = ``output_size`` (16..512); returns the status int32[k] (device)."""
+        size = self._crop_size(output_size)
         if frames_dev.dim() != 4 or frames_dev.shape[3] != 3 or frames_dev.dtype != torch.uint8 or not frames_dev.is_cuda \
                 or not frames_dev.is_contiguous():
             raise ValueError("square_crops_device: frames are a contiguous uint8[k, H, W, 3] device tensor")
         k, h, w, _ = frames_dev.shape
         if tuple(boxes_dev.shape) != (k, 4) or boxes_dev.dtype != torch.float64 or not boxes_dev.is_cuda:
             raise ValueError("square_crops_device: boxes are float64[k, 4] on the device")
-        if tuple(out.shape) != (k, 128, 128, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
-            raise ValueError("square_crops_device: out is a contiguous uint8[k, 128, 128, 3] device tensor")
+        if tuple(out.shape) != (k, size, size, 3) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"square_crops_device: out is a contiguous uint8[k, {size}, {size}, 3] device tensor")
         status = torch.empty((k,), dtype=torch.int32, device=self.device)
         step = self.max_batch_frames
         for i0 in range(0, k, step):
             cnt = min(step, k - i0)
             bd = boxes_dev[i0:i0 + cnt, None, :].expand(-1, self.F, -1).contiguous()
-            crops = torch.empty((cnt, self.F, 128, 128, 3), dtype=torch.uint8, device=self.device)
+            crops = torch.empty((cnt, self.F, size, size, 3), dtype=torch.uint8, device=self.device)
             st = torch.empty((cnt, self.F), dtype=torch.int32, device=self.device)
-            self._check(self._lib.pa_square_crops(self._h, _ptr(frames_dev[i0:]), cnt, h, w, _ptr(bd), padding, int(swap_rb), _ptr(crops),
-                                                  _ptr(st), self._stream()))
+            self._square_crops_call(frames_dev[i0:], cnt, h, w, bd, padding, swap_rb, size, crops, st)
             out[i0:i0 + cnt].copy_(crops[:, 0])
             status[i0:i0 + cnt].copy_(st[:, 0])
         return status

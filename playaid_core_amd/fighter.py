@@ -111,18 +111,22 @@ class YoloCrop:
         return image[y1:y2, x1:x2]
 
     def square_crop(self, image, output_size=128, padding=0, engine=None):
-        """``(ok, uint8[128,128,3])`` like ``fighter.py:323-381`` -- same
-        channel order as ``image`` -- computed by the HIP preprocess kernels.
-        ``(False, None)`` for an empty / off-screen slice. ``engine`` defaults
-        to the process-wide engine on ``cuda:0``."""
-        if output_size != 128:
-            raise ValueError("the HIP path produces 128x128 crops only (reference default)")
+        """``(ok, uint8[output_size,output_size,3])`` like ``fighter.py:323-381`` --
+        same channel order as ``image`` -- computed by the HIP preprocess kernels
+        (``output_size`` 16..512; 128 runs the 128 x 128 kernels, any other size
+        ``pa_square_crops_sized``). ``(False, None)`` for an empty / off-screen
+        slice. ``engine`` defaults to the process-wide engine on ``cuda:0``."""
+        from . import _lib
+
+        if int(output_size) != output_size or not _lib.PA_CROP_SIZE_MIN <= output_size <= _lib.PA_CROP_SIZE_MAX:
+            raise ValueError(f"the HIP path produces square crops of {_lib.PA_CROP_SIZE_MIN}..{_lib.PA_CROP_SIZE_MAX} pixels, "
+                             f"got output_size={output_size!r}")
         from .engine import default_engine
 
         eng = engine if engine is not None else default_engine()
         frames = np.ascontiguousarray(image)[None]
         boxes = np.array([[[self.center_x, self.center_y, self.crop_width, self.crop_height]]], dtype=np.float64)
-        crops, status = eng.square_crops(frames, boxes, padding=padding, swap_rb=False)
+        crops, status = eng.square_crops(frames, boxes, padding=padding, swap_rb=False, output_size=int(output_size))
         if int(status[0, 0]) != 0:
             return False, None
         return True, crops[0, 0]

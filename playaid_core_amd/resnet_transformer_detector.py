@@ -4,7 +4,8 @@ Mirror of ``playaid/models/resnet_transformer_detector.py:26-141`` for inference
 classifier (2048 pooled features per frame, ``:37``), ``Linear(2048, 247)`` (``:41``), the 9-value time encoding of the
 frame's position in the window appended (``:18-23,43-49,77-80``) -> 256, three post-norm
 ``nn.TransformerEncoderLayer(d_model=256, nhead=8)`` (``:53-60``), ``Linear(256, A)`` (``:65``), ``log_softmax`` over
-the actions (``:141``); ``model(x)`` with ``x: float32[B,S,3,128,128]`` -> ``float32[B,S,A]``. As with the LSTM model the
+the actions (``:141``); ``model(x)`` with ``x: float32[B,S,3,C,C]`` -> ``float32[B,S,A]``, C = ``crop_size`` (128 by default; the
+reference's own driver for this model cuts 256 x 256 crops). As with the LSTM model the
 encoder is built without ``batch_first``, so attention runs ACROSS THE WINDOWS of a call (dimension 0) for each
 frame slot; that is reproduced as is.
 
@@ -121,10 +122,25 @@ class _Table:
                                w_off=self.put(w.transpose(0, 2, 3, 1)), b_off=self.put(bias)))
 
 
-def build_resnet50_table(state_dict: Mapping, prefix: str = "model.resnet."):
+def check_crop_size(crop_size) -> int:
+    """The network input sizes the table's stem takes: multiples of 32 in 64..512 (the map is halved five times, and the
+    sized stem kernel's limits, ``include/playaid_hip.h`` at ``pa_conv_desc``)."""
+    c = int(crop_size)
+    if c != crop_size or c % 32 != 0 or not 64 <= c <= 512:
+        raise ValueError(f"crop_size must be a multiple of 32 in 64..512, got {crop_size!r}")
+    return c
+
+
+def build_resnet50_table(state_dict: Mapping, prefix: str = "model.resnet.", crop_size: int = 128):
     """-> (descs, buf_floats_per_crop, weights float32, feature_dim). Buffers: 0 stem output (bordered), 1 / 2 block
     outputs (ping-pong), 3 the 3x3 convolution's output, 4 the downsample branch, then one bordered buffer per
-    (map size, width) a 3x3 convolution reads, last the pooled 2048-vector."""
+    (map size, width) a 3x3 convolution reads, last the pooled 2048-vector.
+
+    ``crop_size``: the side of the square input. 128 gives the table this function always gave (stem row kind 1,
+    ``stem_pool_kernel``); any other multiple of 32 in 64..512 a kind-3 stem row (``stem_pool_any.hip``) and maps of
+    ``crop_size / 4, / 8, / 16, / 32`` pixels behind it."""
+    crop_size = check_crop_size(crop_size)
+    q = crop_size // 4   # the pooled stem map
     sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
     for key, shape in resnet50_param_shapes():
         if key not in sd:
@@ -132,17 +148,17 @@ def build_resnet50_table(state_dict: Mapping, prefix: str = "model.resnet."):
         if tuple(_np(sd[key]).shape) != tuple(shape):
             raise ValueError(f"{prefix}{key}: expected shape {tuple(shape)}, got {tuple(_np(sd[key]).shape)}")
     t = _Table()
-    stem_out = t.buffer(34 * 34 * 64)
-    ping, pong = t.buffer(32 * 32 * 256), t.buffer(32 * 32 * 256)
-    t2, ds = t.buffer(32 * 32 * 64), t.buffer(32 * 32 * 256)
+    stem_out = t.buffer((q + 2) * (q + 2) * 64)
+    ping, pong = t.buffer(q * q * 256), t.buffer(q * q * 256)
+    t2, ds = t.buffer(q * q * 64), t.buffer(q * q * 256)
     bordered: Dict[Tuple[int, int], int] = {}
     # stem: [64][7 ky][8 px][4 ch]
     w, bias = t.fold(sd, "conv1", "bn1")
     stem = np.zeros((64, 7, 8, 4), np.float64)
     stem[:, :, :7, :3] = w.transpose(0, 2, 3, 1)
-    t.descs.append(dict(kind=1, cin=3, cout=64, ksize=7, stride=2, in_hw=128, in_buf=0, in_pad=3, out_buf=stem_out, out_pad=1,
-                        res_buf=-1, relu=1, w_off=t.put(stem), b_off=t.put(bias)))
-    cur, cur_pad, cin, hw = stem_out, 1, 64, 32
+    t.descs.append(dict(kind=1 if crop_size == 128 else 3, cin=3, cout=64, ksize=7, stride=2, in_hw=crop_size, in_buf=0, in_pad=3,
+                        out_buf=stem_out, out_pad=1, res_buf=-1, relu=1, w_off=t.put(stem), b_off=t.put(bias)))
+    cur, cur_pad, cin, hw = stem_out, 1, 64, q
     for li, (width, blocks) in enumerate(zip((64, 128, 256, 512), RESNET50_BLOCKS), start=1):
         for b in range(blocks):
             p = f"layer{li}.{b}"
@@ -184,6 +200,8 @@ class ConvNet:
         self.out_floats = out_floats
         self.buf_floats = [int(b) for b in buf_floats]
         self.n_rows = len(descs)
+        # side of the input crops: the table's stem row (kind 1: 128; kind 3: its in_hw)
+        self.in_hw = next((int(d["in_hw"]) for d in descs if int(d["kind"]) == 3), 128)
         # element type of each buffer as stored (-1: the stem's input): under bf16 what a stem or convolution row writes is bf16,
         # what a pool writes fp32 (include/playaid_hip.h, PA_DTYPE_BF16)
         self.buf_dtype = {b: torch.float32 for b in range(-1, len(self.buf_floats))}
@@ -211,12 +229,12 @@ class ConvNet:
             self._h = None
 
     def trace(self, x: torch.Tensor, last_row: int, buf: int) -> torch.Tensor:
-        """Test aid (``pa_convnet_trace``): run what ``forward`` runs for x float32[n,3,128,128] (n <= max_crops, one group)
+        """Test aid (``pa_convnet_trace``): run what ``forward`` runs for x float32[n,3,S,S] (S = ``in_hw``; n <= max_crops, one group)
         through table row ``last_row`` (-1: the input conversion alone) and return the whole of buffer ``buf`` as stored:
         [max_crops * buf_floats[buf]] elements of ``buf_dtype[buf]`` (float32, or bfloat16 for what a bf16 table's stem and
-        convolutions write) on the device (buf = -1: the stem input, [max_crops][134][134][4])."""
-        xd = x.to(self.device, torch.float32).contiguous()
-        floats = self.max_crops * (134 * 134 * 4 if buf < 0 else self.buf_floats[buf])
+        convolutions write) on the device (buf = -1: the stem input, [max_crops][S + 6][S + 6][4])."""
+        xd = self._input(x)
+        floats = self.max_crops * ((self.in_hw + 6) * (self.in_hw + 6) * 4 if buf < 0 else self.buf_floats[buf])
         out = torch.empty(floats, dtype=self.buf_dtype.get(buf, torch.float32), device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         rc = self._lib.pa_convnet_trace(self._h, _ptr(xd), int(xd.shape[0]), last_row, buf, _ptr(out), out.numel() * out.element_size(), stream)
@@ -224,17 +242,22 @@ class ConvNet:
             raise EngineError(rc, self._lib.pa_convnet_last_error(self._h).decode())
         return out
 
+    def _input(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, self.in_hw, self.in_hw):
+            raise ValueError(f"expected [n,3,{self.in_hw},{self.in_hw}], got {tuple(x.shape)}")
+        return x.to(self.device, torch.float32).contiguous()
+
     def layer_forms(self) -> List[str]:
-        """The kernel form (``_lib.CN_FORMS``) each table row ran as in the last forward or trace."""
+        """The kernel form (``_lib.CN_FORM_NAMES``) each table row ran as in the last forward or trace."""
         forms = (C.c_int32 * self.n_rows)()
         rc = self._lib.pa_convnet_layer_forms(self._h, forms, self.n_rows)
         if rc != 0:
             raise EngineError(rc, "pa_convnet_layer_forms")
-        return [_lib.CN_FORMS[f] for f in forms]
+        return [_lib.CN_FORM_NAMES[f] for f in forms]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """x float32[n,3,128,128] -> float32[n, out_floats] on the device (groups of max_crops)."""
-        xd = x.to(self.device, torch.float32).contiguous()
+        """x float32[n,3,S,S] (S = ``in_hw``, the table's input size) -> float32[n, out_floats] on the device (groups of max_crops)."""
+        xd = self._input(x)
         n = int(xd.shape[0])
         out = torch.empty((n, self.out_floats), dtype=torch.float32, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -294,6 +317,7 @@ class ResnetTransformerDetector:
         state_dict: Optional[Mapping] = None,
         device: str = "cuda:0",
         max_rows: int = 448,
+        crop_size: int = 128,
         **kwargs,
     ):
         if state_dict is None:
@@ -314,8 +338,12 @@ class ResnetTransformerDetector:
         self.dataset_kwargs = kwargs
         self.training = False
         self.max_rows = max_rows
+        # (crop_size: the reference's dataset argument -- its driver feeds this model 256 x 256 crops; a multiple of 32 in 64..512)
+        self.crop_size = check_crop_size(crop_size)
+        if kwargs.get("compute_dtype", "f32") == "bf16" and self.crop_size != 128:
+            raise ValueError("compute_dtype='bf16' runs 128 x 128 crops only (the stem of any size is fp32)")
         self._lib = _lib.load()
-        descs, bufs, weights, feat_dim = build_resnet50_table(state_dict)
+        descs, bufs, weights, feat_dim = build_resnet50_table(state_dict, crop_size=self.crop_size)
         # (compute_dtype: beyond the reference's arguments -- "emulated_f32" = pa_convnet_create_dtype(PA_DTYPE_EMULATED_F32), "bf16" =
         # PA_DTYPE_BF16: the ResNet-50 in bf16 on bgemm.hip, the encoder head fp32 as always; neither is the default, and bf16 is not
         # within the fp32 path's 1e-4 bar)
@@ -367,12 +395,13 @@ class ResnetTransformerDetector:
 
     def forward(self, frames: torch.Tensor) -> torch.Tensor:
         """frames [batch_size, frames_per_sequence, channel, height, width] -> log-probabilities [batch, frames, A]."""
-        if frames.dim() != 5 or tuple(frames.shape[2:]) != (3, 128, 128) or frames.shape[1] != self.sequence_length:
-            raise ValueError(f"expected [B,{self.sequence_length},3,128,128], got {tuple(frames.shape)}")
+        c = self.crop_size
+        if frames.dim() != 5 or tuple(frames.shape[2:]) != (3, c, c) or frames.shape[1] != self.sequence_length:
+            raise ValueError(f"expected [B,{self.sequence_length},3,{c},{c}], got {tuple(frames.shape)}")
         b, s = int(frames.shape[0]), int(frames.shape[1])
         if b * s > self.max_rows:
             raise ValueError(f"{b} x {s} rows exceed max_rows={self.max_rows}")
-        feats = self._net.forward(frames.reshape(b * s, 3, 128, 128))
+        feats = self._net.forward(frames.reshape(b * s, 3, c, c))
         out = torch.empty((b, s, self.num_actions), dtype=torch.float32, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         rc = self._lib.pa_encoder_forward(self._h, _ptr(feats), feats.shape[1], b, s, _ptr(out), stream)

@@ -98,17 +98,28 @@ class ClipWindowDataset:
     """Index i -> fighter ``i // (max_frames - 1)``, frame ``1 + i % (max_frames - 1)`` (the order of
     ``AIRunner.run_action_recognition``'s two loops, ``ai_runner.py:493-520``)."""
 
-    def __init__(self, runner, actions: Optional[Sequence[Sequence[str]]] = None, animations: Optional[List[str]] = None):
+    def __init__(self, runner, actions: Optional[Sequence[Sequence[str]]] = None, animations: Optional[List[str]] = None,
+                 crop_size: int = 128):
         """``runner``: an ``AIRunner`` (its clip, label repair, crop mode and sampler settings are used as they are).
         ``actions[p][f - 1]``: the ground-truth action string of fighter slot p in frame f (what the reference reads from the
         frame's label file, ``ult_action_dataset.py:340-343``), or None: every frame is labelled ``Undefined``.
-        ``animations``: the action list the ids index (default: the ontology's 63, ``anim_ontology.py:592-600``)."""
+        ``animations``: the action list the ids index (default: the ontology's 63, ``anim_ontology.py:592-600``).
+        ``crop_size`` (``UltActionRecogDataset(crop_size=...)``; 16..512): 128 hands out the runner's own crops, as ever. With
+        any other size the S crops of an item are cut from the clip's FRAMES by ``Engine.square_crops(output_size=crop_size)``
+        with the runner's repaired boxes at the engine's crop padding (RGB, no JPEG write / read: that stage is 128 x 128) --
+        so the clip needs frames, and a clip that holds only crop files raises ValueError."""
         self.runner = runner
         self.animations = list(animations) if animations is not None else list(MOVE_TO_CLASS_ID.keys())
         self.characters = list(constants.CHAR_LIST)
         self.num_frames_per_sample = runner.num_frames_per_sample
         self.frame_delta = runner.frame_delta
-        self.crop_size = 128
+        self.crop_size = int(crop_size)
+        if self.crop_size != crop_size or not 16 <= self.crop_size <= 512:
+            raise ValueError(f"crop_size must be an integer in 16..512, got {crop_size!r}")
+        self._sized_boxes = None
+        if self.crop_size != 128 and (runner.clip.frames.shape[1] == 0 or runner.clip.frames.shape[2] == 0):
+            raise ValueError(f"crop_size={self.crop_size}: crops of another size than 128 are cut from the clip's frames, and this "
+                             "clip holds crop files only: frames are needed")
         self.actions = actions
         if actions is not None:
             if len(actions) != len(runner.fighters) or any(len(a) < runner.max_frames - 1 for a in actions):
@@ -126,12 +137,15 @@ class ClipWindowDataset:
             raise IndexError(idx)
         p, frame_num = idx // n_per, 1 + idx % n_per
         fighter_name = self.runner.fighters[p]
-        res = self.runner._run_clip()  # the clip's crops, cut once on the device and cached by the runner
         frame_nums = action_sample_from_frame_middle_out(
             frame_num, num_frames_per_sample=self.num_frames_per_sample, frame_delta=self.frame_delta,
             max_frames=self.runner.max_frames, min_frame=1,
         )
-        frames = [res["crops_rgb"][f - 1, p] for f in frame_nums]
+        if self.crop_size == 128:
+            res = self.runner._run_clip()  # the clip's crops, cut once on the device and cached by the runner
+            frames = [res["crops_rgb"][f - 1, p] for f in frame_nums]
+        else:
+            frames = self._cut_sized(p, frame_nums)
         actions = [self.actions[p][f - 1] if self.actions is not None else "Undefined" for f in frame_nums]
         input_frames = torch.tensor(np.array(frames)).permute(0, 3, 1, 2)
         anim_label = [self._action_id(a) for a in actions]
@@ -150,8 +164,35 @@ class ClipWindowDataset:
             },
         )
 
+    def _cut_sized(self, p: int, frame_nums):
+        """The crops of fighter slot p in the frames ``frame_nums`` at ``crop_size``: ``square_crop(frame, crop_size, padding)`` of
+        the repaired box, from the decoded frame the repair names (``AIRunner._boxes``), RGB."""
+        runner = self.runner
+        if self._sized_boxes is None:
+            self._sized_boxes = runner._boxes()
+        boxes, src, missing = self._sized_boxes
+        rows = [f - 1 for f in frame_nums]
+        bad = [f for f in frame_nums if missing[f - 1, p]]
+        assert not bad, f"Failed to get frame crops/{runner.fighters[p]}/{runner.video_name}_{bad[0]}.jpg"  # as _run_clip
+        eng = runner.model.engine
+        clip_frames = runner.clip.frames
+        h, w = int(clip_frames.shape[1]), int(clip_frames.shape[2])
+        if h > eng.cfg.max_frame_height or w > eng.cfg.max_frame_width or len(rows) > eng.max_batch_frames:
+            raise ValueError(f"the model's engine takes {eng.max_batch_frames} frames of {eng.cfg.max_frame_height} x {eng.cfg.max_frame_width} "
+                             f"at most; the clip's are {h} x {w}")
+        sel = [int(src[r, p]) for r in rows]
+        if isinstance(clip_frames, torch.Tensor):
+            fsel = clip_frames[torch.as_tensor(sel, device=clip_frames.device)]
+        else:
+            fsel = np.ascontiguousarray(clip_frames[sel])
+        bsel = np.ascontiguousarray(np.repeat(boxes[rows, p][:, None, :], eng.F, axis=1), dtype=np.float64)
+        crops, status = eng.square_crops(fsel, bsel, padding=eng.cfg.crop_padding, swap_rb=True, output_size=self.crop_size)
+        bad = np.nonzero(status[:, 0])[0]
+        assert len(bad) == 0, f"Failed to get square crop from frame {frame_nums[bad[0]]}"  # ai_runner.py:418
+        return [crops[i, 0] for i in range(len(rows))]
+
     def batches(self, batch_size: int):
-        """(x[B, S, 3, 128, 128], char_ids[B], action_ids[B, S], metas) in index order -- ``torch.utils.data.DataLoader``'s
+        """(x[B, S, 3, crop_size, crop_size], char_ids[B], action_ids[B, S], metas) in index order -- ``torch.utils.data.DataLoader``'s
         default collation without its worker processes (the crops live in one engine)."""
         for i0 in range(0, len(self), batch_size):
             items = [self[i] for i in range(i0, min(i0 + batch_size, len(self)))]
