@@ -880,6 +880,20 @@ int pa_conv2d_branch(const float* x, const void* w, const float* bias, const flo
                      int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad, int32_t act, int32_t res_after, int32_t compute_dtype,
                      void* stream);
 
+/* The ResNet-18 stem on integer pixels (csrc/stem_pool.hip, its third form): 7x7/2 convolution + folded BatchNorm + ReLU + 3x3/2
+ * max-pool of u8 crops, the operator the exact engines (PA_DTYPE_F32, PA_DTYPE_EMULATED_F32) run on every model input they make from
+ * u8 pixels -- exposed for parity tests and measurements of the single layer. crops_u8: uint8[n][128][128][3] (device); the pixel
+ * integers go as bf16 into the interior of `packed` = bf16[n][134][134][4] (device scratch, 16-byte aligned, ZERO before the first
+ * call: border and fourth channel are never written with anything else), are multiplied EXACTLY with the three bf16 slices of the
+ * fp32 weights on the bf16 matrix cores, summed in fp32 (slice 2, 1, 0; taps in (ky, kx, channel) order), divided by 255 once
+ * (correctly rounded), + bias, ReLU, max-pool -> out: float32[n][34][34][64] (device, interior written, the border of one pixel
+ * is the caller's zero). w_slices: bf16[3][64][224] (device), made on the host by pa_stem_int_pack_weights from the BatchNorm-folded
+ * fp32 weights [64][ky 7][kx 7][cin 3]: s0 = bf16(w), s1 = bf16(w - s0), s2 = bf16(w - s0 - s1), w = s0 + s1 + s2 exactly.
+ * bias: float32[64] (device). PA_ERR_INVALID_ARG for a NULL or misaligned pointer or n outside 1..8192, before anything is
+ * enqueued. Appended: PA_ABI_VERSION stays 15, no existing layout changes. Enqueue only. */
+int pa_stem_int_pack_weights(const float* w_host, uint16_t* out_host);
+int pa_stem_int(const uint8_t* crops_u8, const void* w_slices, const float* bias, void* packed, float* out, int32_t n, void* stream);
+
 /* Head of ResnetTransformerDetector (resnet_transformer_detector.py:41-93,141): Linear(in_dim, hidden_dim), the
  * enc_dim-value time encoding of the frame slot appended (d_model = hidden_dim + enc_dim, 32 per head),
  * num_layers post-norm nn.TransformerEncoderLayer (ReLU feed-forward of ff_dim), Linear(d_model, num_actions),

@@ -220,6 +220,8 @@ SYMBOLS = [
     ("pa_conv_pack_weights", C.c_int, [_P] + [C.c_int32] * 5 + [_P]),
     ("pa_conv2d", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 14 + [_P]),
     ("pa_conv2d_branch", C.c_int, [_P, _P, _P, _P, _P, _P, _P] + [C.c_int32] * 14 + [_P]),
+    ("pa_stem_int_pack_weights", C.c_int, [_P, _P]),
+    ("pa_stem_int", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P]),
     ("pa_wino_conv3x3_splitk", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 11 + [_P, C.c_size_t, _P, C.c_int32, _P]),
     ("pa_crop_resize_width", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.c_int32,
                                        C.POINTER(C.c_int32), _P]),

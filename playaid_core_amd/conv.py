@@ -84,3 +84,38 @@ def conv2d_branch(x_pad: torch.Tensor, w: torch.Tensor, w2: torch.Tensor, cin: i
     if rc:
         raise ValueError(f"pa_conv2d_branch: status {rc}")
     return out, out2
+
+
+def stem_int_pack_weights(w_oihw: np.ndarray) -> np.ndarray:
+    """BatchNorm-folded stem weights [64, 3, 7, 7] fp32 -> the three bf16 slices uint16[3, 64, 224] (host) ``stem_int`` reads:
+    ``w = s0 + s1 + s2`` exactly (``pa_stem_int_pack_weights``)."""
+    lib = _lib.load()
+    w = np.ascontiguousarray(np.asarray(w_oihw, dtype=np.float32).transpose(0, 2, 3, 1))   # [cout][ky][kx][cin]
+    if w.shape != (64, 7, 7, 3):
+        raise ValueError("w_oihw: [64, 3, 7, 7]")
+    out = np.empty((3, 64, 224), dtype=np.uint16)
+    rc = lib.pa_stem_int_pack_weights(w.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError(f"pa_stem_int_pack_weights: status {rc}")
+    return out
+
+
+def stem_int(crops_u8: torch.Tensor, w_slices: torch.Tensor, bias: torch.Tensor, packed: torch.Tensor = None, out: torch.Tensor = None):
+    """The ResNet-18 stem + ReLU + max-pool on integer pixels (``pa_stem_int``, ``csrc/stem_pool.hip``): crops_u8 uint8[n, 128, 128, 3]
+    (device) -> (out float32[n, 34, 34, 64] with a zero border of one pixel, packed bf16[n, 134, 134, 4]: the pixel integers the
+    stem multiplied, zero border of three pixels, zero fourth channel). ``w_slices``: ``stem_int_pack_weights`` on the device;
+    ``packed`` / ``out``: buffers of an earlier call (their borders are never written). Enqueues on the current stream."""
+    lib = _lib.load()
+    if crops_u8.dtype != torch.uint8 or not crops_u8.is_cuda or not crops_u8.is_contiguous() or crops_u8.shape[1:] != (128, 128, 3):
+        raise ValueError("crops_u8: contiguous uint8[n, 128, 128, 3] on the device")
+    n = crops_u8.shape[0]
+    if packed is None:
+        packed = torch.zeros((n, 134, 134, 4), dtype=torch.bfloat16, device=crops_u8.device)
+    if out is None:
+        out = torch.zeros((n, 34, 34, 64), dtype=torch.float32, device=crops_u8.device)
+    ptr = lambda t_: C.c_void_p(t_.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(crops_u8.device).cuda_stream)
+    rc = lib.pa_stem_int(ptr(crops_u8), ptr(w_slices), ptr(bias), ptr(packed), ptr(out), n, stream)
+    if rc:
+        raise ValueError(f"pa_stem_int: status {rc}")
+    return out, packed

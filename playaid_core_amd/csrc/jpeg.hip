@@ -128,7 +128,9 @@ __global__ __launch_bounds__(512) void jpeg_roundtrip_kernel(const JpegParams p)
             // model input: the crop's channels in memory order / 255 in the zero-bordered NHWC4 buffer (fp32 or bf16)
             const float f0 = (float)(p.bgr ? b : r) / 255.0f, f1 = (float)g / 255.0f, f2 = (float)(p.bgr ? r : b) / 255.0f;
             const size_t oo = ((size_t)crop * 134 + (y + 3)) * 134 + (x + 3);
-            if (p.x0_bf16) {
+            if (p.x0_bf16 == 2) {  // integer stem: the pixel integers as bf16
+                reinterpret_cast<uint2*>(p.x0)[oo] = make_uint2(u8_bf16x2(p.bgr ? b : r, g), u8_bf16x2(p.bgr ? r : b, 0));
+            } else if (p.x0_bf16) {
                 reinterpret_cast<uint2*>(p.x0)[oo] = make_uint2(pack_bf16x2(f0, f1), f32_to_bf16(f2));
             } else {
                 reinterpret_cast<float4*>(p.x0)[oo] = make_float4(f0, f1, f2, 0.f);

@@ -100,6 +100,13 @@ struct pa_engine {
     size_t clean_g6_cap = 0;
     float* x0 = nullptr;      // slot 0 of the model-input double buffer [max_crops][134][134][4]
     float* x0_slot[2] = {nullptr, nullptr};
+    // Integer stem (stem_pool.hip FORM 2): the producers that make the model input from u8 pixels (crop stage, runner
+    // inputs, JPEG round trip) write the pixel INTEGERS as bf16 into these dedicated, once-zeroed buffers instead of k / 255 into
+    // x0_slot; whatever comes as caller floats (pa_infer_windows, pa_backbone_windows, pa_backbone_trace) keeps x0 and the fp32 stem
+    bool stem_int = false;                        // exact engines (f32, emulated_f32) unless PA_STEM_INT=0
+    uint16_t* xi_slot[2] = {nullptr, nullptr};    // [max_crops][134][134][4] bf16, border and fourth channel zero for ever
+    int slot_form[2] = {0, 0};                    // which buffer the slot's last producer wrote: 0 = x0_slot, 2 = xi_slot
+    uint16_t* stem_wgt_int = nullptr;             // [3][64][224]: the three bf16 slices of the folded fp32 stem weights
     int32_t* pre_status[2] = {nullptr, nullptr};  // per-slot crop status written by the preprocess stage
     float* pooled = nullptr;  // [max_crops][512]
     float* feats_tmp = nullptr;  // [max_crops][1024] (b1 path)
@@ -152,6 +159,20 @@ namespace {
 int fail(pa_engine* e, int code, const std::string& msg) {
     if (e) e->last_error = msg;
     return code;
+}
+
+// model input of `slot`: where its next producer writes (recording the form), and what its last producer wrote
+float* slot_dst(pa_engine* e, int slot) {
+    e->slot_form[slot] = e->stem_int ? 2 : 0;
+    return e->stem_int ? reinterpret_cast<float*>(e->xi_slot[slot]) : e->x0_slot[slot];
+}
+const float* slot_src(const pa_engine* e, int slot) {
+    return e->slot_form[slot] == 2 ? reinterpret_cast<const float*>(e->xi_slot[slot]) : e->x0_slot[slot];
+}
+// storage of a model-input buffer as PreprocParams::crops_f32_is_bf16 counts it: 2 = one of the integer buffers
+int input_form(const pa_engine* e, const void* x) {
+    if (x && e->stem_int && (x == e->xi_slot[0] || x == e->xi_slot[1])) return 2;
+    return e->bf16 ? 1 : 0;
 }
 
 #define HIPCHK(e, call)                                                                              \
@@ -564,20 +585,24 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
     // streaming) of one half batch runs on the side stream underneath the stem (pure matrix work) of the other.
     static const int fused_pool = getenv("PA_STEM_POOL") ? atoi(getenv("PA_STEM_POOL")) : 1;
     static const int overlap_pool = getenv("PA_POOL_OVERLAP") ? atoi(getenv("PA_POOL_OVERLAP")) : 1;
+    const int x_form = input_form(e, x_in);
     if (fused_pool && !stem_igemm) {
         StemPoolParams sp;
         memset(&sp, 0, sizeof(sp));
-        const size_t es_in = e->bf16 ? 2 : 4;
+        const size_t es_in = x_form ? 2 : 4, es_out = e->bf16 ? 2 : 4;   // (integer pixels: 2-byte input, fp32 output)
         sp.x = reinterpret_cast<const char*>(x_in) + (size_t)crop0 * 134 * 134 * 4 * es_in;
-        sp.wgt = e->bf16 ? e->stem_wgt_bf16 : stem.wgt;
+        sp.wgt = x_form == 2 ? (const void*)e->stem_wgt_int : e->bf16 ? (const void*)e->stem_wgt_bf16 : (const void*)stem.wgt;
         sp.bias = stem.bias;
-        sp.out = reinterpret_cast<char*>(e->p1) + (size_t)crop0 * 34 * 34 * 64 * es_in;
+        sp.out = reinterpret_cast<char*>(e->p1) + (size_t)crop0 * 34 * 34 * 64 * es_out;
         sp.crops = ncrops;
-        sp.in_bf16 = sp.out_bf16 = e->bf16 ? 1 : 0;
+        sp.in_bf16 = x_form;
+        sp.out_bf16 = e->bf16 ? 1 : 0;
         const double px = (double)ncrops * 64 * 64;
         ProfScope ps(e, s, "stem_conv7x7_pool", 2.0 * px * 64 * 147,
-                     (double)es_in * ((double)ncrops * 128 * 128 * 4 + (double)ncrops * 32 * 32 * 64 + 64.0 * 147));
+                     (double)es_in * ((double)ncrops * 128 * 128 * 4 + 64.0 * 147 * (x_form == 2 ? 3 : 1)) + (double)es_out * ncrops * 32 * 32 * 64);
         HIPCHK(e, launch_stem_pool(sp, s));
+    } else if (x_form == 2) {
+        return fail(e, PA_ERR_INVALID_ARG, "integer pixels reached an unfused stem (PA_STEM_POOL=0 / PA_STEM_IGEMM=1 switch the integer stem off)");
     } else if (e->bf16) {
         return fail(e, PA_ERR_INVALID_ARG, "the bf16 path has no unfused stem (PA_STEM_POOL=0 / PA_STEM_IGEMM=1 are fp32 A/B knobs)");
     } else if (overlap_pool && !e->profiling && !e->interleave && e->side && s != e->side && ncrops >= 64) {
@@ -746,7 +771,7 @@ int run_preprocess(pa_engine* e, const uint8_t* frames, int n, int height, int w
     p.t_stride = e->t_stride;
     p.crops_u8 = crops_u8;
     p.crops_f32 = crops_f32;
-    p.crops_f32_is_bf16 = e->bf16 ? 1 : 0;
+    p.crops_f32_is_bf16 = input_form(e, crops_f32);
     p.status = status;
     p.fallback_count = e->fallback;
     p.fallback_list = e->fallback + 4;
@@ -760,7 +785,7 @@ int run_preprocess(pa_engine* e, const uint8_t* frames, int n, int height, int w
         j.crops_u8 = p.crops_u8;
         j.qtab = e->jpeg_qtab;
         j.x0 = crops_f32;
-        j.x0_bf16 = e->bf16 ? 1 : 0;
+        j.x0_bf16 = input_form(e, crops_f32);
         j.bgr = swap_rb ? 0 : 1;   // frames are B, G, R; swap_rb turns the crops into R, G, B
         ProfScope pj(e, s, "jpeg_roundtrip", 0.0, ncrops * 49152.0 * 2);
         HIPCHK(e, launch_jpeg_roundtrip(j, (int)ncrops, s));
@@ -847,6 +872,18 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     ALLOC(e->x0_slot[0], (size_t)NC * 134 * 134 * 4, true);
     ALLOC(e->x0_slot[1], (size_t)NC * 134 * 134 * 4, true);
     e->x0 = e->x0_slot[0];
+    {
+        // PA_STEM_INT=0: every producer writes k / 255 and the fp32 stem runs, as before the integer form (A/B runs). The unfused stems
+        // of PA_STEM_POOL=0 / PA_STEM_IGEMM=1 have no integer form and switch it off too.
+        static const int stem_int_knob = getenv("PA_STEM_INT") ? atoi(getenv("PA_STEM_INT")) : 1;
+        static const int fused_pool = getenv("PA_STEM_POOL") ? atoi(getenv("PA_STEM_POOL")) : 1;
+        static const int stem_igemm = getenv("PA_STEM_IGEMM") ? atoi(getenv("PA_STEM_IGEMM")) : 0;
+        e->stem_int = !e->bf16 && stem_int_knob && fused_pool && !stem_igemm;
+    }
+    if (e->stem_int) {
+        ALLOC(e->xi_slot[0], (size_t)NC * 134 * 134 * 4, true);
+        ALLOC(e->xi_slot[1], (size_t)NC * 134 * 134 * 4, true);
+    }
     ALLOC(e->savebox_rects, (size_t)NC * 4, true);
     ALLOC(e->pre_status[0], (size_t)NC, true);
     ALLOC(e->pre_status[1], (size_t)NC, true);
@@ -1133,6 +1170,28 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
         HIPCHK(e, hipMemcpy(e->arena, e->arena_stage.data(), e->arena_used, hipMemcpyHostToDevice));
         std::vector<uint8_t>().swap(e->arena_stage);
     }
+    if (e->stem_int) {
+        // the integer stem's three bf16 slices, from the folded fp32 stem weights as they lie in the arena (so a folded and an adopted
+        // arena give the same slices and the arena keeps its size and layout): s0 = bf16(w), s1 = bf16(w - s0), s2 = bf16(w - s0 - s1),
+        // round to nearest even each, the splitting of pack_stage_weights
+        const size_t nw = (size_t)64 * 224;
+        std::vector<float> w(nw);
+        HIPCHK(e, hipMemcpy(w.data(), e->convs[0].wgt, nw * sizeof(float), hipMemcpyDeviceToHost));
+        std::vector<uint16_t> sl(3 * nw);
+        for (size_t i = 0; i < nw; ++i) {
+            float x = w[i];
+            for (int k = 0; k < 3; ++k) {
+                const uint16_t hq = bf16_rne(x);
+                sl[k * nw + i] = hq;
+                const uint32_t u = (uint32_t)hq << 16;
+                float f;
+                memcpy(&f, &u, 4);
+                x -= f;
+            }
+        }
+        ALLOC(e->stem_wgt_int, 3 * nw, false);
+        HIPCHK(e, hipMemcpy(e->stem_wgt_int, sl.data(), sl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
     // split-K slabs: the largest splitk*M*N over all layers
     {
         size_t need = 0;
@@ -1404,7 +1463,7 @@ int run_runner_inputs(pa_engine* e, const uint8_t* images, size_t images_bytes, 
     q.t_stride = e->t_stride;
     q.inputs_u8 = inputs_u8;
     q.inputs_f32 = inputs_f32;
-    q.inputs_f32_is_bf16 = e->bf16 ? 1 : 0;
+    q.inputs_f32_is_bf16 = input_form(e, inputs_f32);
     q.status = status;
     ProfScope ps(e, s, "runner_inputs", 0.0, (double)images_bytes + (double)n * 49152.0 * 5);
     HIPCHK(e, launch_runner_inputs(q, s));
@@ -1428,7 +1487,7 @@ int pa_backbone_crop_images(pa_engine* e, const uint8_t* images, size_t images_b
         return fail(e, PA_ERR_CAPACITY, "pa_backbone_crop_images: frames exceed engine / clip capacity");
     hipStream_t s = (hipStream_t)stream;
     const int F = e->cfg.num_fighters;
-    int rc = run_runner_inputs(e, images, images_bytes, desc, n * F, 1, crops_rgb, e->x0_slot[0], e->pre_status[0], s);
+    int rc = run_runner_inputs(e, images, images_bytes, desc, n * F, 1, crops_rgb, slot_dst(e, 0), e->pre_status[0], s);
     if (rc) return rc;
     if (status) HIPCHK(e, hipMemcpyAsync(status, e->pre_status[0], sizeof(int32_t) * n * F, hipMemcpyDeviceToDevice, s));
     return pa_backbone_slot(e, 0, n, frame0, stream);
@@ -1517,7 +1576,7 @@ int pa_preprocess_windows(pa_engine* e, const uint8_t* windows_dev, const pa_cro
         return fail(e, PA_ERR_CAPACITY, "pa_preprocess_windows: frames exceed engine capacity");
     hipStream_t s = (hipStream_t)stream;
     const int F = e->cfg.num_fighters;
-    int rc = run_preprocess(e, windows_dev, n, height, width, boxes, e->cfg.crop_padding, 1, crops_rgb, e->x0_slot[slot],
+    int rc = run_preprocess(e, windows_dev, n, height, width, boxes, e->cfg.crop_padding, 1, crops_rgb, slot_dst(e, slot),
                             e->pre_status[slot], s, nullptr, 0, desc_dev);
     if (rc) return rc;
     if (status) HIPCHK(e, hipMemcpyAsync(status, e->pre_status[slot], sizeof(int32_t) * n * F, hipMemcpyDeviceToDevice, s));
@@ -1604,7 +1663,7 @@ int pa_preprocess_frames(pa_engine* e, const uint8_t* frames, int32_t n, int32_t
         return fail(e, PA_ERR_CAPACITY, "pa_preprocess_frames: frames exceed engine capacity");
     hipStream_t s = (hipStream_t)stream;
     const int F = e->cfg.num_fighters;
-    int rc = run_preprocess(e, frames, n, height, width, boxes, e->cfg.crop_padding, 1, crops_rgb, e->x0_slot[slot],
+    int rc = run_preprocess(e, frames, n, height, width, boxes, e->cfg.crop_padding, 1, crops_rgb, slot_dst(e, slot),
                             e->pre_status[slot], s);
     if (rc) return rc;
     if (status) HIPCHK(e, hipMemcpyAsync(status, e->pre_status[slot], sizeof(int32_t) * n * F, hipMemcpyDeviceToDevice, s));
@@ -1620,7 +1679,7 @@ int pa_backbone_slot(pa_engine* e, int32_t slot, int32_t n, int32_t frame0, void
     const int F = e->cfg.num_fighters;
     HIPCHK(e, hipMemcpyAsync(e->cache_status + (size_t)frame0 * F, e->pre_status[slot], sizeof(int32_t) * n * F,
                              hipMemcpyDeviceToDevice, s));
-    int rc = run_backbone(e, n * F, e->x0_slot[slot], e->cache + (size_t)frame0 * F * PA_FEATURE_STRIDE, s);
+    int rc = run_backbone(e, n * F, slot_src(e, slot), e->cache + (size_t)frame0 * F * PA_FEATURE_STRIDE, s);
     if (rc) return rc;
     for (int i = 0; i < n; ++i) e->ready[frame0 + i] = 1;
     return PA_OK;
@@ -1644,7 +1703,7 @@ int pa_backbone_frames_indexed(pa_engine* e, const uint8_t* frames, int32_t n, i
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int F = e->cfg.num_fighters;
-    rc = run_backbone(e, n * F, e->x0_slot[0], e->feats_tmp, s);
+    rc = run_backbone(e, n * F, slot_src(e, 0), e->feats_tmp, s);
     if (rc) return rc;
     ProfScope ps(e, s, "scatter_features", 0.0, 2.0 * n * F * PA_FEATURE_STRIDE * 4.0);
     HIPCHK(e, launch_scatter_rows(e->feats_tmp, e->pre_status[0], frame_ids, e->cache, e->cache_status, n, F, e->clip_frames,
@@ -1773,7 +1832,7 @@ int pa_backbone_frames_src(pa_engine* e, const uint8_t* frames, int32_t n_src, i
         return fail(e, PA_ERR_CAPACITY, "pa_backbone_frames_src: frames exceed engine / clip capacity");
     hipStream_t s = (hipStream_t)stream;
     const int F = e->cfg.num_fighters;
-    int rc = run_preprocess(e, frames, n, height, width, boxes, e->cfg.crop_padding, 1, crops_rgb, e->x0_slot[0],
+    int rc = run_preprocess(e, frames, n, height, width, boxes, e->cfg.crop_padding, 1, crops_rgb, slot_dst(e, 0),
                             e->pre_status[0], s, src_frame, n_src);
     if (rc) return rc;
     if (status) HIPCHK(e, hipMemcpyAsync(status, e->pre_status[0], sizeof(int32_t) * n * F, hipMemcpyDeviceToDevice, s));

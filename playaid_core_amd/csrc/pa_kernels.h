@@ -131,7 +131,8 @@ struct StemParams {
 };
 hipError_t launch_stem7x7(const StemParams& p, hipStream_t s);
 // Stem + BatchNorm + ReLU + 3x3/2 max-pool in one persistent kernel (stem_pool.hip): x as above (fp32) or bf16
-// [crops][134][134][4]; wgt fp32 or bf16 [64][224]; out = pooled map [crops][34][34][64], fp32 or bf16.
+// [crops][134][134][4]; wgt fp32 or bf16 [64][224]; out = pooled map [crops][34][34][64], fp32 or bf16. in_bf16 == 2: x holds
+// the pixel integers 0 .. 255 as bf16, wgt three bf16 slices [3][64][224] of the fp32 weights, out fp32 (exact products).
 struct StemPoolParams {
     const void* x;
     const void* wgt;
@@ -139,7 +140,7 @@ struct StemPoolParams {
     void* out;
     int32_t crops;
     int32_t run;       // row pairs per run (set by the launcher)
-    int32_t in_bf16;   // x and wgt are bf16: multiply on the bf16 matrix cores
+    int32_t in_bf16;   // 1: x and wgt are bf16: multiply on the bf16 matrix cores; 2: integer pixels and three weight slices
     int32_t out_bf16;
 };
 hipError_t launch_stem_pool(const StemPoolParams& p, hipStream_t s);
@@ -267,7 +268,7 @@ struct PreprocParams {
     size_t t_stride;
     uint8_t* crops_u8;      // [ncrops][128][128][3] or nullptr
     float* crops_f32;       // [ncrops][134][134][4] zero-bordered, or nullptr
-    int32_t crops_f32_is_bf16;  // the model input is stored as bf16 [ncrops][134][134][4] instead (bf16 conv path)
+    int32_t crops_f32_is_bf16;  // 1: the model input is stored as bf16 [ncrops][134][134][4] instead (bf16 conv path); 2: as the pixel integers in bf16 (integer stem)
     int32_t* status;        // [ncrops] or nullptr
     int32_t* fallback_count;  // [1] number of crops routed to the multi-kernel fallback (zeroed per call)
     int32_t* fallback_list;   // [ncrops] their indices
@@ -301,7 +302,7 @@ struct RunnerInParams {
     size_t t_stride;
     uint8_t* inputs_u8;         // [n][128][128][3] or nullptr
     float* inputs_f32;          // [n][134][134][4] zero-bordered model input (fp32, or bf16 storage) or nullptr
-    int32_t inputs_f32_is_bf16;
+    int32_t inputs_f32_is_bf16;  // 0 / 1 / 2 as PreprocParams::crops_f32_is_bf16
     int32_t* status;            // [n] PA_CROP_* or nullptr
 };
 hipError_t launch_runner_inputs(const RunnerInParams& q, hipStream_t s);
@@ -311,7 +312,7 @@ struct JpegParams {
     uint8_t* crops_u8;   // [ncrops][128][128][3]
     const int32_t* qtab; // [2][64] quantisation tables (luminance, chrominance) in natural order, device
     void* x0;            // model input [ncrops][134][134][4] (fp32 or bf16) rewritten from the new pixels, or nullptr
-    int32_t x0_bf16;
+    int32_t x0_bf16;     // 0 / 1 / 2 as PreprocParams::crops_f32_is_bf16
     int32_t bgr;         // memory order of the crops: 1 = B, G, R (cv2), 0 = R, G, B
 };
 hipError_t launch_jpeg_roundtrip(const JpegParams& p, int ncrops, hipStream_t s);

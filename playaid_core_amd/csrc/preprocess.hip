@@ -425,7 +425,7 @@ __device__ void fallback_v(const PreprocParams& p, int crop, const CropPlan& pl)
     }
 }
 
-// channel swap + u8 crop + /255 fp32 zero-bordered NHWC4 model input for pixel i of `crop`
+// channel swap + u8 crop + zero-bordered NHWC4 model input for pixel i of `crop`: k / 255 as fp32 or bf16, or the integers k as bf16
 __device__ __forceinline__ void write_crop_pixel(const PreprocParams& p, int crop, int i, int o0, int o1, int o2) {
     if (p.swap_rb) {
         const int t = o0;
@@ -439,13 +439,17 @@ __device__ __forceinline__ void write_crop_pixel(const PreprocParams& p, int cro
         o[2] = (uint8_t)o2;
     }
     if (p.crops_f32) {
+        const int dy = i >> 7, dx = i & 127;
+        const size_t o = ((size_t)crop * 134 + (dy + 3)) * 134 + (dx + 3);
+        if (p.crops_f32_is_bf16 == 2) {  // integer stem: the pixel integers themselves, each exactly one bf16 (the stem divides its sums)
+            reinterpret_cast<uint2*>(p.crops_f32)[o] = make_uint2(u8_bf16x2(o0, o1), u8_bf16x2(o2, 0));
+            return;
+        }
         float4 v;
         v.x = (float)o0 / 255.0f;
         v.y = (float)o1 / 255.0f;
         v.z = (float)o2 / 255.0f;
         v.w = 0.f;
-        const int dy = i >> 7, dx = i & 127;
-        const size_t o = ((size_t)crop * 134 + (dy + 3)) * 134 + (dx + 3);
         if (p.crops_f32_is_bf16) {  // bf16 conv path: the /255 quotient rounded to bf16 (nearest even)
             reinterpret_cast<uint2*>(p.crops_f32)[o] = make_uint2(pack_bf16x2(v.x, v.y), f32_to_bf16(v.z));
         } else {

@@ -15,7 +15,19 @@
 // maxpool_kernel. BF16 = true (the bf16 conv path, BASELINE.json configs[2]) takes the crop as bf16
 // NHWC4 pixels and multiplies on v_mfma_f32_32x32x16_bf16: 28 matrix instructions per tile and wave
 // instead of 168 fp32 ones (consecutive lanes then read consecutive 16-byte chunks: no swizzle needed).
+//
+// FORM 2 (integer pixels, the exact engines' default: DESIGN.md 5.1a) reads the same bf16 NHWC4 layout, but the values are the
+// pixel INTEGERS 0 .. 255 -- each exactly one bf16 -- and the fp32 weights come as three bf16 slices w = w0 + w1 + w2 (round to
+// nearest even of the running remainder, exact for every weight whose third slice is not a denormal). Every product k * w_i is
+// an 8-bit by 8-bit significand product, exact in fp32, so the accumulator holds an fp32 sum of EXACT products -- no term is
+// dropped -- and the epilogue divides ONCE, correctly rounded: relu(acc / 255 + bias). The summation order is fixed: slice 2
+// (the lowest), then 1, then 0, each over g = ky * 2 + half = 0 .. 13 with 16 k per matrix instruction: 3 x 28 = 84 bf16 matrix
+// instructions per tile and wave instead of 150 fp32 ones, all three slice sets resident in 168 VGPRs. The order does not depend
+// on the grid, the run length or the crop's position.
 #include "tile_common.h"
+#include "conv_rows.h"
+#include "../../include/playaid_hip.h"
+#include <cstring>
 
 namespace pa {
 
@@ -26,7 +38,8 @@ constexpr int POOL_W = 34;  // padded pooled width (border 1 for the first 3x3 c
 constexpr int COUT = 64;
 constexpr int KTOT = 224;   // weight row stride (7 ky x 8 px x 4 ch)
 
-template <bool BF16> struct StemGeom {
+template <int FORM> struct StemGeom {
+    static constexpr bool BF16 = FORM != 0;
     static constexpr int ROW_CH = BF16 ? IN_W / 2 : IN_W;        // 16-byte chunks per padded input row
     static constexpr int PATCH_CH = 9 * ROW_CH;                  // 2 output rows x stride 2 + 7 taps - 2 = 9 input rows
     static constexpr int PASSES = (PATCH_CH + 255) / 256;
@@ -39,9 +52,13 @@ __device__ __forceinline__ f32x4 max4(f32x4 a, f32x4 b) {
 
 }  // namespace
 
-template <bool BF16>
+// FORM 0: fp32 pixels and weights; 1: bf16 pixels (k / 255 rounded) and one bf16 weight plane; 2: integer pixels as bf16 and three
+// bf16 weight slices [3][64][224], fp32 output
+template <int FORM>
 __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams p) {
-    using G = StemGeom<BF16>;
+    using G = StemGeom<FORM>;
+    constexpr bool BF16 = FORM != 0;
+    constexpr int NSL = FORM == 2 ? 3 : 1;  // resident bf16 weight planes
     constexpr int TS = 64;  // row (floats) of the transposed stem tile
     __shared__ __attribute__((aligned(16))) float lds[2 * G::STAGE_CH * 4 + 128 * TS];
     float* const tbuf = lds + 2 * G::STAGE_CH * 4;
@@ -86,11 +103,11 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
     // weights of this lane's output channel, resident for the whole kernel
     const int n = wn * 32 + lr;
     float bw[25][3];     // fp32: step s multiplies taps (2 s, 2 s + 1) of the 49 (ky, kx): this lane (half lh) holds tap 2 s + lh, channels 0-2
-    u32x4 bwh[14];       // bf16: 16-wide k groups, this lane's 8 k = group*16 + 8*lh
+    u32x4 bwh[NSL * 14]; // bf16: 16-wide k groups, this lane's 8 k = group*16 + 8*lh (FORM 2: slice sl at [sl * 14 ..])
     if constexpr (BF16) {
         const uint16_t* w = reinterpret_cast<const uint16_t*>(p.wgt) + (size_t)n * KTOT + 8 * lh;
 #pragma unroll
-        for (int g = 0; g < 14; ++g) bwh[g] = *reinterpret_cast<const u32x4*>(w + g * 16);
+        for (int g = 0; g < NSL * 14; ++g) bwh[g] = *reinterpret_cast<const u32x4*>(w + (size_t)(g / 14) * COUT * KTOT + (g % 14) * 16);
     } else {
         // K = 7 x 7 x 3 = 147 exactly (round 4): the k pair of a matrix instruction is two consecutive TAPS of the 49, one per
         // lane half, instead of two of the eight pixels of a kernel row (whose eighth met zero weights: 168 executed).
@@ -150,16 +167,19 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
             af[SET][mi] = *reinterpret_cast<const u32x4*>(patch + c * 4);                          \
         }                                                                                          \
     }
+            if (FORM == 1 || !(warm && wm == 0)) {  // (FORM 2, like the fp32 form: a warm-up tile's first row is never read)
             SP_FRAGS_H(0, 0);
 #pragma unroll
-            for (int g = 0; g < 14; ++g) {  // g = ky*2 + half: pixels 4*half .. 4*half+3 of tap row ky
-                if (g + 1 < 14) SP_FRAGS_H((g + 1) & 1, g + 1);
+            for (int t = 0; t < NSL * 14; ++t) {  // slice NSL-1 .. 0 (lowest first); g = ky*2 + half: pixels 4*half .. 4*half+3 of tap row ky
+                const int g = t % 14, sl = NSL - 1 - t / 14;
+                if (t + 1 < NSL * 14) SP_FRAGS_H((t + 1) & 1, (t + 1) % 14);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int mi = 0; mi < 2; ++mi)
-                    acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[g & 1][mi]),
-                                                                      __builtin_bit_cast(bf16x8, bwh[g]), acc[mi], 0, 0, 0);
+                    acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[t & 1][mi]),
+                                                                      __builtin_bit_cast(bf16x8, bwh[sl * 14 + g]), acc[mi], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
+            }
             }
 #undef SP_FRAGS_H
         } else {
@@ -203,7 +223,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const StemPoolParams 
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int ox = mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                const float v = acc[mi][e] + bias;
+                // FORM 2: the accumulator is 255 x the convolution; one correctly rounded division per output
+                const float v = (FORM == 2 ? __fdiv_rn(acc[mi][e], 255.0f) : acc[mi][e]) + bias;
                 tbuf[(wm * 64 + ox) * TS + n] = v > 0.f ? v : 0.f;
             }
         __syncthreads();
@@ -254,11 +275,74 @@ hipError_t launch_stem_pool(const StemPoolParams& p_in, hipStream_t s) {
     p.run = 32 / per_crop;
     const int runs = p.crops * per_crop;
     const int grid = runs < 512 ? runs : 512;
-    if (p.in_bf16)
-        hipLaunchKernelGGL(stem_pool_kernel<true>, dim3(grid), dim3(256), 0, s, p);
+    if (p.in_bf16 == 2) {
+        if (p.out_bf16) return hipErrorInvalidValue;  // the integer form belongs to the exact engines
+        hipLaunchKernelGGL(stem_pool_kernel<2>, dim3(grid), dim3(256), 0, s, p);
+    } else if (p.in_bf16)
+        hipLaunchKernelGGL(stem_pool_kernel<1>, dim3(grid), dim3(256), 0, s, p);
     else
-        hipLaunchKernelGGL(stem_pool_kernel<false>, dim3(grid), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(stem_pool_kernel<0>, dim3(grid), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
+// u8 crops [n][128][128][3] -> the integer form's input: the pixel integers as bf16 in the interior of [n][134][134][4] (border
+// untouched: it is zero once and for ever; the fourth channel is written as zero)
+__global__ __launch_bounds__(256) void stem_int_pack_kernel(const uint8_t* __restrict__ crops, uint2* __restrict__ out, int n) {
+    const size_t total = (size_t)n * 128 * 128;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int img = (int)(i >> 14), pix = (int)(i & 16383);
+        const int y = pix >> 7, x = pix & 127;
+        const uint8_t* c = crops + i * 3;
+        out[((size_t)img * IN_W + (y + 3)) * IN_W + (x + 3)] = make_uint2(u8_bf16x2(c[0], c[1]), u8_bf16x2(c[2], 0));
+    }
+}
+
 }  // namespace pa
+
+extern "C" {
+
+int pa_stem_int_pack_weights(const float* w_host, uint16_t* out_host) {
+    if (!w_host || !out_host) return PA_ERR_INVALID_ARG;
+    const size_t plane = (size_t)pa::COUT * pa::KTOT;
+    memset(out_host, 0, 3 * plane * sizeof(uint16_t));
+    for (int co = 0; co < pa::COUT; ++co)
+        for (int t = 0; t < 49; ++t)
+            for (int c = 0; c < 3; ++c) {
+                float x = w_host[((size_t)co * 49 + t) * 3 + c];
+                const size_t o = (size_t)co * pa::KTOT + (t / 7) * 32 + (t % 7) * 4 + c;
+                for (int k = 0; k < 3; ++k) {   // s0 = bf16(x), s1 = bf16(x - s0), s2 = bf16(x - s0 - s1): pack_stage_weights' splitting
+                    const uint16_t hq = pa::bf16_rne(x);
+                    out_host[k * plane + o] = hq;
+                    const uint32_t u = (uint32_t)hq << 16;
+                    float f;
+                    memcpy(&f, &u, 4);
+                    x -= f;
+                }
+            }
+    return PA_OK;
+}
+
+int pa_stem_int(const uint8_t* crops_u8, const void* w_slices, const float* bias, void* packed, float* out, int32_t n, void* stream) {
+    // (8192 crops: the kernel's 32-bit byte offsets into `packed`, 143 648 per crop, stay below 2^31)
+    if (!crops_u8 || !w_slices || !bias || !packed || !out || n < 1 || n > 8192) return PA_ERR_INVALID_ARG;
+    auto misaligned = [](const void* q, unsigned long long m) { return (reinterpret_cast<unsigned long long>(q) & m) != 0; };
+    if (misaligned(w_slices, 15) || misaligned(packed, 15) || misaligned(out, 15) || misaligned(bias, 3)) return PA_ERR_INVALID_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int grid = (n * 16384 + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(pa::stem_int_pack_kernel, dim3(grid), dim3(256), 0, s, crops_u8, static_cast<uint2*>(packed), n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return PA_ERR_HIP;
+    pa::StemPoolParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = packed;
+    p.wgt = w_slices;
+    p.bias = bias;
+    p.out = out;
+    p.crops = n;
+    p.in_bf16 = 2;
+    e = pa::launch_stem_pool(p, s);
+    return e == hipSuccess ? PA_OK : (e == hipErrorInvalidValue ? PA_ERR_INVALID_ARG : PA_ERR_HIP);
+}
+
+}  // extern "C"

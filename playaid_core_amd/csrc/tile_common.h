@@ -84,6 +84,11 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {  // (lo = a,
     return (bf16_round_bits(a) >> 16) | (bf16_round_bits(b) & 0xffff0000u);
 }
 
+// two integers 0 .. 255 as two bf16 (lo = a, hi = b): the upper halves of their fp32 patterns, exact (8 significant bits at most)
+__device__ __forceinline__ uint32_t u8_bf16x2(int a, int b) {
+    return (__float_as_uint((float)a) >> 16) | (__float_as_uint((float)b) & 0xffff0000u);
+}
+
 // activation of a conv epilogue on four floats: GemmParams::relu = 0 none, 1 ReLU, 2 SiLU
 __device__ __forceinline__ f32x4 act4(f32x4 v, int relu) {
     if (relu == 1) {
