@@ -1039,6 +1039,61 @@ int pa_annotate_frames(pa_annot* h, const uint8_t* frames_in, int32_t n, int32_t
                        int32_t pad_bottom, uint8_t* frames_out, void* stream);
 void pa_annot_destroy(pa_annot* h);
 
+/* ---- training the temporal head ------------------------------------------ */
+
+/* Trains CNNActionDetector's temporal head -- cnn1d.0, classifier.0, classifier.2; the ResNet-18 encoder and its fc stay
+ * frozen -- on feature rows the engine has already computed (pa_backbone_windows, pa_features_export), with the reference's
+ * loss and optimiser (cnn_action_detector.py:94-116, 165-167: F.nll_loss on the window's centre label, torch.optim.Adam with
+ * its default betas and eps). Append-only: PA_ABI_VERSION stays 15.
+ *
+ * The weights are updated IN PLACE in the engine's arena, in the layouts the inference kernels read, so the next
+ * pa_infer_windows / pa_head_frames / captured graph / pa_weights_export sees the step without a re-pack. The trainer owns
+ * the two Adam moments (same layouts) and the step's scratch. It borrows the engine: destroy the trainer first, and do not
+ * run a step concurrently with inference on another stream.
+ *
+ * pa_head_train_step, all pointers on the device: feats float32[n_rows][PA_FEATURE_STRIDE] (16-byte aligned, 1000 used),
+ * gather int32[batch][S] row indices into feats (the kernels clamp them into [0, n_rows)), labels int32[batch] in
+ * [0, num_actions) or PA_EVAL_IGNORE (any other value is treated as PA_EVAL_IGNORE). With n = the number of labelled
+ * windows, loss = -(1/n) sum logp[b][labels[b]]; n == 0 divides by 1 (loss 0, all gradients 0) where torch gives NaN.
+ *   apply = 1: one optimiser step (step count k += 1):  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
+ *              w -= (lr / (1 - beta1^k)) * m / (sqrt(v) / sqrt(1 - beta2^k) + eps). grads_out may be NULL.
+ *   apply = 0: nothing changes; grads_out receives the six gradients, concatenated, in PyTorch layouts and blob order:
+ *              cnn1d.0.weight [512][1000][S], cnn1d.0.bias [512], classifier.0.weight [128][512], classifier.0.bias [128],
+ *              classifier.2.weight [A][128], classifier.2.bias [A]  (512000 S + 66176 + 129 A floats).
+ * stats_dev (may be NULL) receives the step's pa_train_stats: the loss BEFORE the update, the number of labelled windows and
+ * how many of them the model got right (first maximum). Enqueue only: stream-ordered, nothing is read back, every sum has
+ * a fixed order (no floating-point atomics), so the same calls give the same bits.
+ *
+ * pa_head_trainer_read copies one set of six tensors (weights, first or second moments) to out_dev in the PyTorch layouts
+ * above; floats must be that total. With PA_TRAIN_RAW or-ed into `which` the set is copied as it lies on the device instead:
+ * [512][S][1024] (columns 1000..1023 are padding), [512], k-major [512][128], [128], k-major [128][64] (columns A..63 are
+ * padding), [A] -- 524288 S + 74368 + A floats; padding has gradient 0 and stays bitwise zero. Enqueue only.
+ *
+ * PA_ERR_INVALID_ARG before any device call: null handle or pointers, batch < 1, batch > max_batch, max_batch outside 1..256,
+ * lr or eps not finite or <= 0, a beta outside [0, 1), apply outside {0, 1}, apply = 0 without grads_out, n_rows < 1. A create
+ * that stops at the device (PA_ERR_NO_DEVICE / PA_ERR_HIP) still hands the handle back, to be destroyed by the caller. */
+typedef struct pa_head_trainer pa_head_trainer;
+typedef struct pa_adam_config {
+    float lr, beta1, beta2, eps;
+} pa_adam_config;
+typedef struct pa_train_stats {
+    float loss;
+    int32_t valid;
+    int32_t correct;
+    int32_t pad;
+} pa_train_stats;
+#define PA_TRAIN_WEIGHTS 0
+#define PA_TRAIN_M 1
+#define PA_TRAIN_V 2
+#define PA_TRAIN_RAW 16 /* or-ed in: the set as it lies on the device, padding included (see pa_head_trainer_read) */
+int pa_head_trainer_create(pa_engine* e, const pa_adam_config* cfg, int32_t max_batch, pa_head_trainer** out);
+void pa_head_trainer_destroy(pa_head_trainer* t);
+const char* pa_head_trainer_last_error(const pa_head_trainer* t);
+int64_t pa_head_trainer_steps(const pa_head_trainer* t);
+int pa_head_train_step(pa_head_trainer* t, const float* feats, int32_t n_rows, const int32_t* gather, const int32_t* labels, int32_t batch,
+                       int32_t apply, float* grads_out, pa_train_stats* stats_dev, void* stream);
+int pa_head_trainer_read(pa_head_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ SOURCES = [
     ("jpegdec.hip", []),
     ("yolo.hip", ["-ffp-contract=off"]),
     ("annotate.hip", []),
+    ("head_train.hip", []),
     ("pa_api.hip", []),
 ]
 

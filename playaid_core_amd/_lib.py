@@ -43,6 +43,11 @@ PA_ERR_NOT_READY = -6
 PA_ERR_BAD_LABELS = -7
 PA_EVAL_IGNORE = -100
 PA_ANNOT_MAX_ITEMS = 16
+# pa_head_trainer_read: which set of six tensors
+PA_TRAIN_WEIGHTS = 0
+PA_TRAIN_M = 1
+PA_TRAIN_V = 2
+PA_TRAIN_RAW = 16
 
 PA_CROP_OK = 0
 PA_CROP_EMPTY = 1
@@ -118,6 +123,14 @@ class pa_eval_totals(C.Structure):
 class pa_annot_item(C.Structure):
     _fields_ = [("box", C.c_int32 * 4), ("draw_box", C.c_int32), ("line_width", C.c_int32), ("has_color", C.c_int32),
                 ("text_off", C.c_int32), ("text_len", C.c_int32), ("rgb", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class pa_adam_config(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
+
+
+class pa_train_stats(C.Structure):
+    _fields_ = [("loss", C.c_float), ("valid", C.c_int32), ("correct", C.c_int32), ("pad", C.c_int32)]
 
 
 class pa_kernel_stat(C.Structure):
@@ -261,6 +274,12 @@ SYMBOLS = [
     ("pa_annot_create", C.c_int, [C.c_int32, _P] + [C.c_int32] * 7 + [C.POINTER(_P)]),
     ("pa_annotate_frames", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P] + [C.c_int32] * 4 + [_P, _P]),
     ("pa_annot_destroy", None, [_P]),
+    ("pa_head_trainer_create", C.c_int, [_P, C.POINTER(pa_adam_config), C.c_int32, C.POINTER(_P)]),
+    ("pa_head_trainer_destroy", None, [_P]),
+    ("pa_head_trainer_last_error", C.c_char_p, [_P]),
+    ("pa_head_trainer_steps", C.c_int64, [_P]),
+    ("pa_head_train_step", C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("pa_head_trainer_read", C.c_int, [_P, C.c_int32, _P, C.c_size_t, _P]),
 ]
 
 _lib = None

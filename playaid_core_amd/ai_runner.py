@@ -386,6 +386,7 @@ class AIRunner:
                 ws.append(int((hd[..., 1] >> 32).max()))
             eng = eng.reconfigured(frame_delta=self.frame_delta, fighter_class_ids=tuple(self._class_ids),
                                    max_clip_frames=max(self.max_frames, 64), max_frame_height=max(hs), max_frame_width=max(ws))
+        self._clip_engine = eng   # (fit_head exports the clip's features from its cache)
         boxes, src, missing = self._boxes()
         n = self.max_frames
         if self.clip.crop_images is not None or self.clip.packed_crops is not None:
@@ -599,6 +600,61 @@ class AIRunner:
             out = st.compute()
         out["labels"] = table
         return out
+
+    def fit_head(self, actions=None, ground_truth_csv: str = None, epochs: int = 1, batch_size: int = 64, seed: int = 0, lines=None,
+                 first_frame: int = 0):
+        """Fine-tunes the model's temporal head on the open clip (``head_trainer.HeadTrainer``; the model is built with
+        ``freeze_encoder=True``): the clip runs ONCE as ``run_action_recognition`` runs it, its per-crop features are taken from
+        the engine's cache (``pa_features_export``), and every epoch is a seeded permutation of the labelled (frame, fighter)
+        windows in minibatches of ``batch_size`` -- windows from the runner's own sampler and ``frame_delta``, centre labels from
+        ``label_table`` (ground truth as in ``evaluate``; unlabelled frames are left out). The head's weights change in place in
+        the model's engine; the clip's cached results are dropped, so the next ``run_action_recognition`` / ``evaluate`` runs
+        the trained model. One read per epoch. -> ``[{"epoch", "loss", "accuracy", "windows"}, ...]`` (each step's loss is taken
+        before its update)."""
+        from .ult_action_dataset import label_table, load_ground_truth_labels
+
+        if actions is not None and ground_truth_csv is not None:
+            raise ValueError("fit_head: actions= or ground_truth_csv=, not both")
+        if ground_truth_csv is not None:
+            actions, first = load_ground_truth_labels(ground_truth_csv, lines)[0], first_frame
+        elif actions is None:
+            actions, first = getattr(self.clip, "ground_truth", None), 0
+            if actions is None:
+                raise ValueError("fit_head: no ground truth (actions=, ground_truth_csv= or a ClipSource.from_ground_truth clip)")
+        else:
+            first = 0
+        if epochs < 1 or batch_size < 1:
+            raise ValueError("fit_head: epochs and batch_size are at least 1")
+        table = label_table(self, actions, self.model.actions, first_frame=first)   # int32[max_frames - 1, F]
+        self.model.train()                      # (NotImplementedError unless freeze_encoder=True)
+        trainer = self.model.configure_optimizers()
+        if batch_size > trainer.max_batch:
+            raise ValueError(f"fit_head: batch_size above {trainer.max_batch}")
+        try:
+            self._run_clip()
+            ceng = self._clip_engine
+            n, F = self.max_frames, ceng.F
+            feats = ceng.features_export(0, n)                                       # [n, F, 1024], rows (frame - 1) * F + slot
+            idx = np.argwhere(table != -100)                                         # (frame - 1, slot) of every labelled window
+            if len(idx) == 0:
+                raise ValueError("fit_head: the ground truth labels no frame of this clip")
+            wins = np.array([[(f - 1) * F + p for f in action_sample_from_frame_middle_out(
+                int(i) + 1, num_frames_per_sample=self.num_frames_per_sample, frame_delta=self.frame_delta, max_frames=n, min_frame=1)]
+                for i, p in idx], dtype=np.int32)
+            labels = table[idx[:, 0], idx[:, 1]].astype(np.int32)
+            rng = np.random.default_rng(seed)
+            history = []
+            trainer.epoch_stats()   # a fresh epoch
+            for epoch in range(epochs):
+                order = rng.permutation(len(idx))
+                for b0 in range(0, len(order), batch_size):
+                    sel = order[b0:b0 + batch_size]
+                    trainer.step(feats, wins[sel], labels[sel])
+                history.append(dict(epoch=epoch, **trainer.epoch_stats()))
+        finally:
+            self.model.eval()
+        self._results = None   # predictions of the untrained head
+        return history
 
     def load_ai_output(self):
         if not os.path.exists(self.ai_output_file):

@@ -14,9 +14,14 @@ without reading anything back per step; ``metrics("val" | "test")`` is the one
 read and returns the figures under the reference's log names
 (``val_action_loss``, ``val_action_acc``, ...) plus the confusion matrix and
 mean confidence of ``visualizations/cnn_action_detector_vis.py:89-153``;
-``reset_metrics(split)`` starts a new epoch. Not mirrored: ``training_step``,
-``training_epoch_end``, ``configure_optimizers`` and the data hooks
-(``:94-129,165-207``).
+``reset_metrics(split)`` starts a new epoch.
+
+Training is mirrored for the temporal head with the encoder frozen (``freeze_encoder=True``; ``head_trainer.HeadTrainer``,
+csrc/head_train.hip): ``train()``, ``configure_optimizers()`` (the reference's ``torch.optim.Adam(lr=self.learning_rate)``,
+``:165-167``, as a device trainer), ``training_step`` (``:94-116``: centre label, NLL loss; the ResNet-18 features come from the
+existing inference kernels, eval-mode BatchNorm), ``state_dict()`` and ``save_checkpoint()``. The head's weights are updated
+in place where inference reads them. Not mirrored: training the encoder (``train()`` with ``freeze_encoder=False`` raises
+``NotImplementedError``), ``training_epoch_end`` and the data hooks (``:118-129,169-207``).
 """
 from __future__ import annotations
 
@@ -57,7 +62,10 @@ class CNNActionDetector:
         self.learning_rate = learning_rate
         self.num_samples = num_samples
         self.dataset_kwargs = kwargs
+        self.freeze_encoder = bool(freeze_encoder)
         self.training = False
+        self._state_dict = state_dict
+        self._trainer = None
         # (beyond the reference's arguments: the engine's capacities and, never by default, the arithmetic of the fp32 path --
         # compute_dtype="emulated_f32", PA_DTYPE_EMULATED_F32)
         self._engine = Engine(state_dict, device=device, **{k: v for k, v in kwargs.items() if k.startswith("max_") or k == "compute_dtype"})
@@ -83,9 +91,59 @@ class CNNActionDetector:
         return self
 
     def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("training is out of scope for the MI355X inference path")
+        if mode and not self.freeze_encoder:
+            raise NotImplementedError("training is out of scope for the MI355X inference path "
+                                      "(only the temporal head trains: build the model with freeze_encoder=True)")
+        self.training = bool(mode)
         return self
+
+    # -- training of the head (cnn_action_detector.py:94-116, 165-167; encoder frozen) ------------
+    def configure_optimizers(self):
+        """The reference's ``torch.optim.Adam(self.parameters(), lr=self.learning_rate)`` for the head's six tensors, as a
+        ``HeadTrainer`` on this model's engine (made once; it owns the Adam moments and the running epoch statistics)."""
+        if not self.freeze_encoder:
+            raise NotImplementedError("only the temporal head trains: build the model with freeze_encoder=True")
+        if self._trainer is None:
+            from .head_trainer import MAX_BATCH, HeadTrainer
+
+            self._trainer = HeadTrainer(self._engine, lr=self.learning_rate, max_batch=MAX_BATCH)
+        return self._trainer
+
+    def training_step(self, batch, batch_idx):
+        """One optimiser step on ``batch = (input[B,S,3,128,128], char_label, action_label[B,S], meta)``: the centre label of
+        every window (``-100`` = none), the ResNet-18 features of its crops (``pa_backbone_windows``), one ``pa_head_train_step``.
+        -> the loss before the update as a 0-dim device tensor; nothing is read back."""
+        if not self.training:
+            raise RuntimeError("training_step needs train() (and freeze_encoder=True)")
+        input, char_label, action_label, _ = batch
+        eng = self._engine
+        if input.dim() != 5 or input.shape[1] != eng.S or tuple(input.shape[2:]) != (3, 128, 128):
+            raise ValueError(f"expected [B,{eng.S},3,128,128], got {tuple(input.shape)}")
+        trainer = self.configure_optimizers()
+        b, s = int(input.shape[0]), int(input.shape[1])
+        labels = torch.as_tensor(action_label)[:, s // 2].to(torch.int32)
+        xd = eng._dev(input, torch.float32)
+        feats = torch.empty((b * s, 1024), dtype=torch.float32, device=eng.device)
+        eng._check(eng._lib.pa_backbone_windows(eng._h, xd.data_ptr(), b * s, feats.data_ptr(), eng._stream()))
+        gather = torch.arange(b * s, dtype=torch.int32, device=eng.device).view(b, s)
+        stats = trainer.step(feats, gather, labels)
+        return trainer.loss_of(stats)
+
+    def state_dict(self):
+        """The state dict the model was built from with the six head tensors as they are now (numpy; waits for the device)."""
+        out = dict(self._state_dict)
+        if self._trainer is not None:
+            for k, v in self._trainer.read("weights").items():
+                out[k] = v.cpu().numpy()
+        return out
+
+    def save_checkpoint(self, path: str):
+        """Writes the Lightning-shaped ``.ckpt`` that ``load_from_checkpoint`` reads: ``state_dict`` + ``hyper_parameters``."""
+        sd = {k: torch.as_tensor(v).detach().cpu().clone() for k, v in self.state_dict().items()}
+        hparams = {"batch_size": self.batch_size, "sequence_length": self.sequence_length, "learning_rate": self.learning_rate,
+                   "num_samples": self.num_samples, "freeze_encoder": self.freeze_encoder}
+        torch.save({"state_dict": sd, "hyper_parameters": hparams, "pytorch-lightning_version": "1.6.5", "epoch": 0,
+                    "global_step": int(self._trainer.steps) if self._trainer is not None else 0}, path)
 
     @property
     def engine(self) -> Engine:

@@ -2072,6 +2072,171 @@ int pa_eval_read(pa_eval* h, pa_eval_totals* totals_host, int64_t* confusion_hos
 }  // extern "C"
 
 // ===============================================================================
+// Training of the temporal head (csrc/head_train.hip): a handle beside its engine
+// ===============================================================================
+
+struct pa_head_trainer {
+    pa_engine* eng = nullptr;
+    pa_adam_config cfg;
+    int max_batch = 0, S = 0, A = 0;
+    int64_t steps = 0;
+    std::string last_error;
+    float* state = nullptr;    // one allocation: m | v (six tensors each, in the weights' layouts) | the step's scratch
+    float *m[6] = {}, *v[6] = {};
+    float *h1 = nullptr, *h2 = nullptr, *dz3 = nullptr, *dz2 = nullptr, *dz1 = nullptr, *loss_b = nullptr, *gs = nullptr, *stats = nullptr;
+    int32_t* hit_b = nullptr;
+};
+
+static_assert(sizeof(pa_train_stats) == 16 && sizeof(pa_adam_config) == 16, "pa_train_stats / pa_adam_config are four 32-bit words");
+
+namespace {
+
+int tfail(pa_head_trainer* t, int code, const std::string& msg) {
+    t->last_error = msg;
+    return code;
+}
+
+// floats of tensor i (blob order) in the layout the inference kernels read
+size_t head_layout_floats(int i, int S, int A) {
+    const size_t n[6] = {(size_t)512 * S * PA_FEATURE_STRIDE, 512, 512 * 128, 128, 128 * 64, (size_t)A};
+    return (n[i] + 63) & ~(size_t)63;   // every tensor starts 256-byte aligned
+}
+
+}  // namespace
+
+extern "C" {
+
+int pa_head_trainer_create(pa_engine* e, const pa_adam_config* cfg, int32_t max_batch, pa_head_trainer** out) {
+    if (!out) return PA_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!e || !cfg || max_batch < 1 || max_batch > 256) return PA_ERR_INVALID_ARG;
+    if (!std::isfinite(cfg->lr) || cfg->lr <= 0.f || !std::isfinite(cfg->eps) || cfg->eps <= 0.f || !(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) ||
+        !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f))
+        return PA_ERR_INVALID_ARG;
+    pa_head_trainer* t = new pa_head_trainer();
+    *out = t;   // handed back even when the device stops the creation, for the error text (and destroyed by the caller)
+    t->eng = e;
+    t->cfg = *cfg;
+    t->max_batch = max_batch;
+    t->S = e->cfg.sequence_length;
+    t->A = e->cfg.num_actions;
+    if (!e->w1d || !e->b1d || !e->w2 || !e->b2 || !e->w3 || !e->b3)
+        return tfail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_create: the engine has no weights on a device");
+    if (hipSetDevice(e->cfg.device_id) != hipSuccess) return tfail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_create: hipSetDevice failed");
+    size_t moments = 0;
+    for (int i = 0; i < 6; ++i) moments += head_layout_floats(i, t->S, t->A);
+    const size_t B = (size_t)max_batch;
+    const size_t scratch = B * 512 * 2 + B * 128 * 2 + B * 64 + B * 2 + (512 * 128 + 128 * 64 + 512 + 128 + 64) + 64;
+    void* p = nullptr;
+    if (hipMalloc(&p, (2 * moments + scratch) * sizeof(float)) != hipSuccess) return tfail(t, PA_ERR_HIP, "pa_head_trainer_create: hipMalloc failed");
+    t->state = static_cast<float*>(p);
+    if (hipMemset(p, 0, (2 * moments + scratch) * sizeof(float)) != hipSuccess) return tfail(t, PA_ERR_HIP, "pa_head_trainer_create: hipMemset failed");
+    float* q = t->state;
+    for (int i = 0; i < 6; ++i) {
+        t->m[i] = q;
+        q += head_layout_floats(i, t->S, t->A);
+    }
+    for (int i = 0; i < 6; ++i) {
+        t->v[i] = q;
+        q += head_layout_floats(i, t->S, t->A);
+    }
+    t->h1 = q, q += B * 512;
+    t->dz1 = q, q += B * 512;
+    t->h2 = q, q += B * 128;
+    t->dz2 = q, q += B * 128;
+    t->dz3 = q, q += B * 64;
+    t->loss_b = q, q += B;
+    t->hit_b = reinterpret_cast<int32_t*>(q), q += B;
+    t->gs = q, q += 512 * 128 + 128 * 64 + 512 + 128 + 64;
+    t->stats = q;
+    return PA_OK;
+}
+
+void pa_head_trainer_destroy(pa_head_trainer* t) {
+    if (!t) return;
+    (void)hipFree(t->state);
+    delete t;
+}
+
+const char* pa_head_trainer_last_error(const pa_head_trainer* t) { return t ? t->last_error.c_str() : "null trainer"; }
+
+int64_t pa_head_trainer_steps(const pa_head_trainer* t) { return t ? t->steps : -1; }
+
+int pa_head_train_step(pa_head_trainer* t, const float* feats, int32_t n_rows, const int32_t* gather, const int32_t* labels, int32_t batch,
+                       int32_t apply, float* grads_out, pa_train_stats* stats_dev, void* stream) {
+    if (!t) return PA_ERR_INVALID_ARG;
+    if (!feats || !gather || !labels || n_rows < 1) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: null input or n_rows < 1");
+    if (batch < 1 || batch > t->max_batch) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: batch outside 1..max_batch");
+    if ((apply != 0 && apply != 1) || (!apply && !grads_out)) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: apply is 0 (with grads_out) or 1");
+    if ((reinterpret_cast<uintptr_t>(feats) & 15) != 0) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: feats must be 16-byte aligned");
+    if (!t->state) return tfail(t, PA_ERR_NO_DEVICE, "pa_head_train_step: the trainer has no device state");
+    pa_engine* e = t->eng;
+    HeadTrainParams p;
+    memset(&p, 0, sizeof(p));
+    p.feats = feats;
+    p.gather = gather;
+    p.labels = labels;
+    p.n_rows = n_rows;
+    p.B = batch;
+    p.S = t->S;
+    p.A = t->A;
+    p.apply = apply;
+    float* w[6] = {e->w1d, e->b1d, e->w2, e->b2, e->w3, e->b3};
+    for (int i = 0; i < 6; ++i) {
+        p.w[i] = w[i];
+        p.m[i] = t->m[i];
+        p.v[i] = t->v[i];
+    }
+    p.h1 = t->h1, p.h2 = t->h2, p.dz3 = t->dz3, p.dz2 = t->dz2, p.dz1 = t->dz1, p.loss_b = t->loss_b, p.gs = t->gs, p.stats = t->stats;
+    p.hit_b = t->hit_b;
+    p.stats_out = reinterpret_cast<float*>(stats_dev);
+    p.grads_out = grads_out;
+    AdamScalars ak;
+    memset(&ak, 0, sizeof(ak));
+    if (apply) {
+        const double k = (double)(t->steps + 1), b1 = (double)t->cfg.beta1, b2 = (double)t->cfg.beta2;
+        ak.one_minus_b1 = 1.0 - b1;
+        ak.b2 = b2;
+        ak.one_minus_b2 = 1.0 - b2;
+        ak.step_size = (float)((double)t->cfg.lr / (1.0 - std::pow(b1, k)));
+        ak.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, k));
+        ak.eps = t->cfg.eps;
+    }
+    const hipError_t err = launch_head_train_step(p, ak, (hipStream_t)stream);
+    if (err != hipSuccess) return tfail(t, PA_ERR_HIP, std::string("pa_head_train_step: ") + hipGetErrorString(err));
+    if (apply) t->steps += 1;
+    return PA_OK;
+}
+
+int pa_head_trainer_read(pa_head_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream) {
+    if (!t) return PA_ERR_INVALID_ARG;
+    const int set = which & ~PA_TRAIN_RAW;
+    if (!out_dev || which < 0 || set > PA_TRAIN_V) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_trainer_read: null output or unknown tensor set");
+    const bool raw = (which & PA_TRAIN_RAW) != 0;
+    const size_t raw_n[6] = {(size_t)512 * t->S * PA_FEATURE_STRIDE, 512, 512 * 128, 128, 128 * 64, (size_t)t->A};
+    const size_t want = raw ? raw_n[0] + raw_n[1] + raw_n[2] + raw_n[3] + raw_n[4] + raw_n[5] : head_tensor_floats(t->S, t->A);
+    if (floats != want) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_trainer_read: wrong output size");
+    if (!t->state) return tfail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_read: the trainer has no device state");
+    pa_engine* e = t->eng;
+    HeadTensors src;
+    const float* w[6] = {e->w1d, e->b1d, e->w2, e->b2, e->w3, e->b3};
+    for (int i = 0; i < 6; ++i) src.p[i] = set == PA_TRAIN_WEIGHTS ? w[i] : set == PA_TRAIN_M ? t->m[i] : t->v[i];
+    if (raw) {
+        for (int i = 0; i < 6; ++i) {
+            if (hipMemcpyAsync(out_dev, src.p[i], raw_n[i] * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+                return tfail(t, PA_ERR_HIP, "pa_head_trainer_read: hipMemcpyAsync failed");
+            out_dev += raw_n[i];
+        }
+        return PA_OK;
+    }
+    const hipError_t err = launch_head_export(src, t->S, t->A, out_dev, (hipStream_t)stream);
+    if (err != hipSuccess) return tfail(t, PA_ERR_HIP, std::string("pa_head_trainer_read: ") + hipGetErrorString(err));
+    return PA_OK;
+}
+
+}  // extern "C"
+
+// ===============================================================================
 // Annotation (csrc/annotate.hip): a handle of its own, owned by no engine
 // ===============================================================================
 

@@ -463,4 +463,33 @@ struct AnnotParams {
 };
 hipError_t launch_annotate(const AnnotParams& p, hipStream_t s);
 
+// head_train.hip: one training step of the temporal head (pa_head_train_step). The six tensors are always in blob order --
+// 0 cnn1d.0.weight, 1 cnn1d.0.bias, 2 classifier.0.weight, 3 classifier.0.bias, 4 classifier.2.weight, 5 classifier.2.bias --
+// and in the layouts the inference kernels read: [512][S][1024], [512], k-major [512][128], [128], k-major [128][64], [A].
+struct AdamScalars {
+    double one_minus_b1, b2, one_minus_b2;   // the moments are formed in double (adam_apply)
+    float step_size, bc2_sqrt, eps;          // lr / (1 - beta1^k), sqrt(1 - beta2^k): double on the host, rounded once
+};
+struct HeadTensors {
+    const float* p[6];
+};
+struct HeadTrainParams {
+    const float* feats;      // [n_rows][1024]
+    const int32_t* gather;   // [B][S] rows of feats (clamped into [0, n_rows) by every kernel)
+    const int32_t* labels;   // [B], -100 = ignore
+    int32_t n_rows, B, S, A, apply;
+    float* w[6];             // the engine's weights, updated in place when apply
+    float* m[6];
+    float* v[6];
+    // the trainer's scratch: h1 [B][512], h2 [B][128], dz3 [B][64], dz2 [B][128], dz1 [B][512], loss_b [B], hit_b [B],
+    // gs = the five small gradients (65536 + 8192 + 512 + 128 + 64 floats), stats = pa_train_stats
+    float *h1, *h2, *dz3, *dz2, *dz1, *loss_b, *gs, *stats;
+    int32_t* hit_b;
+    float* stats_out;        // caller's pa_train_stats or nullptr
+    float* grads_out;        // apply == 0: the six gradients in PyTorch layouts, concatenated
+};
+size_t head_tensor_floats(int S, int A);
+hipError_t launch_head_train_step(const HeadTrainParams& p, const AdamScalars& ak, hipStream_t s);
+hipError_t launch_head_export(const HeadTensors& src, int S, int A, float* out, hipStream_t s);
+
 }  // namespace pa

@@ -127,9 +127,15 @@ class Engine:
         return Engine(self.weights_arena(), **kw)
 
     def reconfigured(self, **overrides) -> "Engine":
-        """A new engine on the same device and weights with some geometry changed."""
+        """A new engine on the same device and weights with some geometry changed. Once a ``HeadTrainer`` has stepped this
+        engine's head the weights it was built from are stale: the new engine then adopts this one's arena (``clone``), which
+        the arithmetic type must match."""
         kw = dict(self._ctor_kwargs)
         kw.update(overrides)
+        if getattr(self, "_head_trained", False):
+            if kw["compute_dtype"] != self.compute_dtype:
+                raise ValueError("reconfigured: a trained engine cannot change compute_dtype (build one from model.state_dict())")
+            return Engine(self.weights_arena(), **kw)
         return Engine(self._weights, **kw)
 
     # -- plumbing ---------------------------------------------------------
