@@ -657,7 +657,9 @@ int pa_infer_clip(pa_engine* e, const uint8_t* frames, int32_t n, int32_t height
 
 /* Feature-cache access for frame-parallel sharding: copy
  * the cached rows of frames frame0..frame0+n-1 out of / into the engine.
- * feats: float32[n,num_fighters,PA_FEATURE_STRIDE]. */
+ * feats: float32[n,num_fighters,PA_FEATURE_STRIDE]. pa_features_import also sets the crop status of the rows it
+ * writes to PA_CROP_OK (on the same stream): an imported row has no crop of this engine, so the pa_record.status of a
+ * window whose middle frame was imported is 0, not what an earlier clip left in that row. */
 int pa_features_export(pa_engine* e, int32_t frame0, int32_t n, float* feats, void* stream);
 int pa_features_import(pa_engine* e, int32_t frame0, int32_t n, const float* feats, void* stream);
 

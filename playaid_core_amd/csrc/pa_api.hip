@@ -1915,6 +1915,10 @@ int pa_features_import(pa_engine* e, int32_t frame0, int32_t n, const float* fea
     const size_t row = (size_t)e->cfg.num_fighters * PA_FEATURE_STRIDE;
     HIPCHK(e, hipMemcpyAsync(e->cache + (size_t)frame0 * row, feats, sizeof(float) * n * row, hipMemcpyDeviceToDevice,
                              (hipStream_t)stream));
+    // imported rows carry no crop of this engine: their status is PA_CROP_OK (== 0), not what an earlier clip left in the row
+    static_assert(PA_CROP_OK == 0, "the memset below writes PA_CROP_OK");
+    HIPCHK(e, hipMemsetAsync(e->cache_status + (size_t)frame0 * e->cfg.num_fighters, 0,
+                             sizeof(int32_t) * (size_t)n * e->cfg.num_fighters, (hipStream_t)stream));
     for (int i = 0; i < n; ++i) e->ready[frame0 + i] = 1;
     return PA_OK;
 }
