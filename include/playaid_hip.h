@@ -1096,6 +1096,47 @@ int pa_head_train_step(pa_head_trainer* t, const float* feats, int32_t n_rows, c
                        int32_t apply, float* grads_out, pa_train_stats* stats_dev, void* stream);
 int pa_head_trainer_read(pa_head_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream);
 
+/* ---- training the LSTM head ----------------------------------------------- */
+
+/* Trains RNNActionDetector's recurrent head -- every lstm.weight_ih / weight_hh / bias_ih / bias_hh, action_decoder.0 and
+ * action_decoder.2; resnet.* (resnet.fc.0 included) stays frozen -- on feature rows already computed (pa_backbone_windows), with
+ * the reference's loss and optimiser (rnn_action_detector.py:97-117, 162-164: F.nll_loss over every (window, frame) row,
+ * torch.optim.Adam with its default betas and eps). Append-only: PA_ABI_VERSION stays 15.
+ *
+ * The trainer borrows the pa_lstm handle's weights and updates them IN PLACE, where pa_lstm_forward reads them (PyTorch
+ * layouts: there is no other form, PA_TRAIN_RAW is refused). It owns the two Adam moments and the saved activations, sized for
+ * the handle's max_rows. Destroy the trainer before the handle, and do not run a step concurrently with pa_lstm_forward on
+ * another stream. The hidden size must be a multiple of 32 (the served 512 is); other handles stay inference-only.
+ *
+ * pa_lstm_train_step, all pointers on the device: x float32[seq_len * batch][ld] (input_dim used), as pa_lstm_forward takes it:
+ * seq_len time steps (the windows) of batch <= 16 rows (a window's frames), zero initial state; labels int32[seq_len * batch]
+ * in [0, num_actions) or PA_EVAL_IGNORE (any other value is treated as PA_EVAL_IGNORE). With n = the number of labelled rows,
+ * loss = -(1/n) sum logp[r][labels[r]]; n == 0 divides by 1 (loss 0, all gradients 0) where torch gives NaN.
+ *   apply = 1: one optimiser step, as pa_head_train_step's; one step counter serves all tensors. grads_out may be NULL.
+ *   apply = 0: nothing changes; grads_out receives the gradients, concatenated, in the blob's tensor order and PyTorch layouts:
+ *              per layer w_ih [4H][in], w_hh [4H][H], b_ih [4H], b_hh [4H], then action_decoder.0.weight [128][H], .bias [128],
+ *              action_decoder.2.weight [A][128], .bias [A]  (pa_lstm_trainer_floats floats).
+ * stats_dev (may be NULL) receives the step's pa_train_stats: the loss BEFORE the update, the labelled rows and how many of
+ * them the model got right (first maximum). Enqueue only: stream-ordered, nothing is read back, one launch per time step and
+ * layer in each direction (no kernel waits for another workgroup), every sum in a fixed order: the same calls give the same bits.
+ *
+ * pa_lstm_trainer_read copies one set (PA_TRAIN_WEIGHTS, PA_TRAIN_M, PA_TRAIN_V) to out_dev in that order; floats must be
+ * pa_lstm_trainer_floats(handle). Enqueue only.
+ *
+ * PA_ERR_INVALID_ARG before any device call: null handle or pointers, seq_len < 1, batch outside 1..16, seq_len * batch >
+ * max_rows, ld < input_dim, apply outside {0, 1}, apply = 0 without grads_out, lr or eps not finite or <= 0, a beta outside
+ * [0, 1), a hidden size that is no multiple of 32, PA_TRAIN_RAW. A create that stops at the device (PA_ERR_NO_DEVICE /
+ * PA_ERR_HIP) still hands the trainer back, to be destroyed by the caller. */
+typedef struct pa_lstm_trainer pa_lstm_trainer;
+int pa_lstm_trainer_create(pa_lstm* h, const pa_adam_config* cfg, pa_lstm_trainer** out);
+void pa_lstm_trainer_destroy(pa_lstm_trainer* t);
+const char* pa_lstm_trainer_last_error(const pa_lstm_trainer* t);
+int64_t pa_lstm_trainer_steps(const pa_lstm_trainer* t);
+int pa_lstm_train_step(pa_lstm_trainer* t, const float* x, int32_t ld, int32_t seq_len, int32_t batch, const int32_t* labels, int32_t apply,
+                       float* grads_out, pa_train_stats* stats_dev, void* stream);
+int pa_lstm_trainer_read(pa_lstm_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream);
+size_t pa_lstm_trainer_floats(const pa_lstm* h);
+
 #ifdef __cplusplus
 }
 #endif

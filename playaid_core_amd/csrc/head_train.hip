@@ -16,6 +16,7 @@
 // Gather indices are device data: every kernel clamps them into [0, n_rows). Labels outside [0, A) count as ignored
 // (the host wrapper refuses them; -100 is the only such value a checked caller passes).
 #include "pa_kernels.h"
+#include "adam.h"   // adam_apply
 
 namespace pa {
 
@@ -27,18 +28,6 @@ constexpr int FS = 1024;   // feature row stride (PA_FEATURE_STRIDE)
 constexpr int FC = 1000;   // features used
 
 __device__ __forceinline__ int clamp_row(int g, int n_rows) { return min(max(g, 0), n_rows - 1); }
-
-// One Adam update (torch.optim.Adam, no weight decay, no amsgrad). The two moments are formed in double and rounded
-// once -- m' = m + (g - m)(1 - beta1) cancels when g and m disagree in sign, and three fp32 roundings there are many
-// ulp of a small m' --; the weight update is fp32: w -= step_size * (m / (sqrt(v) / bc2_sqrt + eps)), step_size =
-// lr / (1 - beta1^k) and bc2_sqrt = sqrt(1 - beta2^k) computed in double on the host and rounded to fp32 once.
-__device__ __forceinline__ void adam_apply(float& w, float& m, float& v, float g, const AdamScalars& k) {
-    const double gd = (double)g;
-    m = (float)((double)m + (gd - (double)m) * k.one_minus_b1);
-    v = (float)(k.b2 * (double)v + k.one_minus_b2 * gd * gd);
-    const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-    w = w - k.step_size * (m / denom);
-}
 
 // ---- 1. Conv1d over the gathered rows ------------------------------------------------------------------------------
 // grid (ceil(B / 32), 16), 256 threads: a 32 (b) x 32 (o) tile of h1 per workgroup. Wave w takes the 8-float chunks

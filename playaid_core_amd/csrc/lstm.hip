@@ -14,6 +14,7 @@
 // the hot loop: no MFMA tiling here on purpose.
 #include "conv_rows.h"
 #include "../../include/playaid_hip.h"
+#include "lstm_handle.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -379,32 +380,7 @@ hipError_t launch_linear_f32(const float* X, int ld, const float* W, const float
 
 }  // namespace pa
 
-struct pa_lstm {
-    int in_dim = 0, hid = 0, layers = 0, actions = 0, max_rows = 0, device = 0;
-    std::vector<float*> w_ih, w_hh, b_ih, b_hh;
-    float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
-    float *weights = nullptr;            // one allocation behind all of the above
-    float *pre = nullptr, *hseq[2] = {nullptr, nullptr}, *c = nullptr;
-    int* sync_words = nullptr;            // [2 * layers]: per layer an unused word and the error word of its launch
-    unsigned long long* gran = nullptr;   // [2][LSTM_NMAX][512] h granules {value, tag} of the layer in flight
-    unsigned long long* dbg = nullptr;    // PA_LSTM_STAMP=1: in-kernel clock sums of the last layer launch
-    int* sync_host = nullptr;             // pinned copy of the error words
-    hipEvent_t sync_ev = nullptr;         // behind the last forward's copies into sync_host: the host reads the words only once it is done
-    bool sync_pending = false;            // a forward has been enqueued since the words were last read
-    int occ_blocks = -1, occ_key = -1;    // co-resident lstm_layer_kernel workgroups the device holds for batch * 16 + U == occ_key
-    bool persistent = true;               // one launch per layer (lstm_layer_kernel); false after a barrier timeout
-    std::vector<int32_t> forms;           // per layer: the pa_lstm_form the last forward launched it as (pa_lstm_layer_forms)
-    std::string last_error;
-};
-
-namespace {
-size_t lstm_float_count(int in_dim, int hid, int layers, int actions) {
-    size_t n = 0;
-    for (int l = 0; l < layers; ++l) n += (size_t)4 * hid * (l == 0 ? in_dim : hid) + (size_t)4 * hid * hid + 8 * (size_t)hid;
-    n += (size_t)128 * hid + 128 + (size_t)actions * 128 + actions;
-    return n;
-}
-}  // namespace
+using pa::lstm_float_count;   // (struct pa_lstm and the blob's float count: lstm_handle.h, shared with lstm_train.hip)
 
 extern "C" {
 

@@ -4,6 +4,7 @@
 // in the enqueue calls.
 #include "../../include/playaid_hip.h"
 #include "conv_rows.h"
+#include "adam.h"   // adam_scalars, adam_config_ok
 
 #include <algorithm>
 #include <cmath>
@@ -2114,9 +2115,7 @@ int pa_head_trainer_create(pa_engine* e, const pa_adam_config* cfg, int32_t max_
     if (!out) return PA_ERR_INVALID_ARG;
     *out = nullptr;
     if (!e || !cfg || max_batch < 1 || max_batch > 256) return PA_ERR_INVALID_ARG;
-    if (!std::isfinite(cfg->lr) || cfg->lr <= 0.f || !std::isfinite(cfg->eps) || cfg->eps <= 0.f || !(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) ||
-        !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f))
-        return PA_ERR_INVALID_ARG;
+    if (!adam_config_ok(cfg->lr, cfg->beta1, cfg->beta2, cfg->eps)) return PA_ERR_INVALID_ARG;
     pa_head_trainer* t = new pa_head_trainer();
     *out = t;   // handed back even when the device stops the creation, for the error text (and destroyed by the caller)
     t->eng = e;
@@ -2195,17 +2194,7 @@ int pa_head_train_step(pa_head_trainer* t, const float* feats, int32_t n_rows, c
     p.hit_b = t->hit_b;
     p.stats_out = reinterpret_cast<float*>(stats_dev);
     p.grads_out = grads_out;
-    AdamScalars ak;
-    memset(&ak, 0, sizeof(ak));
-    if (apply) {
-        const double k = (double)(t->steps + 1), b1 = (double)t->cfg.beta1, b2 = (double)t->cfg.beta2;
-        ak.one_minus_b1 = 1.0 - b1;
-        ak.b2 = b2;
-        ak.one_minus_b2 = 1.0 - b2;
-        ak.step_size = (float)((double)t->cfg.lr / (1.0 - std::pow(b1, k)));
-        ak.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, k));
-        ak.eps = t->cfg.eps;
-    }
+    const AdamScalars ak = adam_scalars(t->cfg.lr, t->cfg.beta1, t->cfg.beta2, t->cfg.eps, t->steps + 1, apply != 0);
     const hipError_t err = launch_head_train_step(p, ak, (hipStream_t)stream);
     if (err != hipSuccess) return tfail(t, PA_ERR_HIP, std::string("pa_head_train_step: ") + hipGetErrorString(err));
     if (apply) t->steps += 1;

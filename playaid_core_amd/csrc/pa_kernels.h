@@ -466,6 +466,8 @@ hipError_t launch_annotate(const AnnotParams& p, hipStream_t s);
 // head_train.hip: one training step of the temporal head (pa_head_train_step). The six tensors are always in blob order --
 // 0 cnn1d.0.weight, 1 cnn1d.0.bias, 2 classifier.0.weight, 3 classifier.0.bias, 4 classifier.2.weight, 5 classifier.2.bias --
 // and in the layouts the inference kernels read: [512][S][1024], [512], k-major [512][128], [128], k-major [128][64], [A].
+// AdamScalars is shared with lstm_train.hip (pa_lstm_train_step, whose kernels and handle are that file's own); adam_apply
+// and the host side of the scalars are in adam.h.
 struct AdamScalars {
     double one_minus_b1, b2, one_minus_b2;   // the moments are formed in double (adam_apply)
     float step_size, bc2_sqrt, eps;          // lr / (1 - beta1^k), sqrt(1 - beta2^k): double on the host, rounded once

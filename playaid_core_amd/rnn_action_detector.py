@@ -14,7 +14,14 @@ Scoring is mirrored (``validation_step`` / ``test_step``, ``:132-160``): this mo
 ``[B*S, A]`` output against ``action_label.view(B * S)`` (not the centre label the CNN model scores) -- NLL loss and multiclass
 top-1 accuracy, accumulated on the device (``metrics.EvalState``) with nothing read back per step; ``metrics(split)`` is the
 one read (``val_action_loss``, ``val_action_acc``, ... plus confusion matrix and mean confidence), ``reset_metrics(split)``
-clears a split. Not mirrored: ``training_step``, the optimiser and the data hooks (``:97-130,162-260``).
+clears a split.
+
+Training is mirrored for the recurrent head with the encoder frozen (``freeze_encoder=True``; ``lstm_trainer.LSTMTrainer``,
+csrc/lstm_train.hip): ``train()``, ``configure_optimizers()`` (the reference's ``torch.optim.Adam(lr=self.learning_rate)``,
+``:162-164``), ``training_step`` (``:97-117``: NLL over every row against ``action_label.view(B * S)``), ``state_dict()`` and
+``save_checkpoint()``. ``resnet.*`` -- ``resnet.fc.0`` included -- stays as loaded and runs on the inference kernels with
+eval-mode BatchNorm. Not mirrored: training the encoder and its BatchNorm statistics, ``training_epoch_end`` and the data hooks
+(``:119-130, 166-260``).
 """
 from __future__ import annotations
 
@@ -117,7 +124,10 @@ class RNNActionDetector:
         self.learning_rate = learning_rate
         self.num_samples = num_samples
         self.dataset_kwargs = kwargs
+        self.freeze_encoder = bool(freeze_encoder)
         self.training = False
+        self._trainer = None
+        self._state_dict = {k: v for k, v in state_dict.items()}   # (resnet.* as loaded: state_dict() hands it back)
         self.max_rows = max_rows
         # (compute_dtype: beyond the reference's arguments -- "emulated_f32" puts the backbone's stride-2 openers and branch GEMMs on the
         # emulated-fp32 kernels, PA_DTYPE_EMULATED_F32; never the default)
@@ -152,11 +162,63 @@ class RNNActionDetector:
         return self
 
     def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("training is out of scope for the MI355X inference path")
+        if mode and not self.freeze_encoder:
+            raise NotImplementedError("only the LSTM head trains: build the model with freeze_encoder=True")
+        self.training = bool(mode)
         return self
 
+    # -- training (rnn_action_detector.py:97-117, 162-164; the encoder frozen) -------------
+    def configure_optimizers(self):
+        """The reference's ``torch.optim.Adam(self.parameters(), lr=self.learning_rate)`` for what trains here: the one
+        ``LSTMTrainer`` on this model's handle (made once; it owns the Adam moments and the running epoch statistics)."""
+        if not self.freeze_encoder:
+            raise NotImplementedError("only the LSTM head trains: build the model with freeze_encoder=True")
+        if self._trainer is None:
+            from .lstm_trainer import LSTMTrainer
+
+            self._trainer = LSTMTrainer(self, lr=self.learning_rate)
+        return self._trainer
+
+    def training_step(self, batch, batch_idx):
+        """``batch = (input [B,S,3,128,128], char_label, action_label [B,S], ...)``: the ResNet-18 features of every frame
+        (``pa_backbone_windows``), then one ``pa_lstm_train_step`` with ``action_label.view(B * S)`` (``-100`` = no ground
+        truth). -> the loss before the update, a 0-dim float32 device tensor; nothing waits."""
+        if not self.training:
+            raise RuntimeError("training_step in eval mode: call train() first")
+        input, action_label = batch[0], batch[2]
+        if input.dim() != 5 or tuple(input.shape[2:]) != (3, 128, 128):
+            raise ValueError(f"expected [B,S,3,128,128], got {tuple(input.shape)}")
+        b, s = int(input.shape[0]), int(input.shape[1])
+        if b * s > self.max_rows:
+            raise ValueError(f"{b} x {s} rows exceed max_rows={self.max_rows}")
+        trainer = self.configure_optimizers()
+        eng = self._engine
+        xd = eng._dev(input, torch.float32)
+        eng._check(self._lib.pa_backbone_windows(eng._h, _ptr(xd), b * s, _ptr(self._feats), eng._stream()))
+        labels = action_label.reshape(b * s) if isinstance(action_label, torch.Tensor) else np.asarray(action_label).reshape(b * s)
+        stats = trainer.step(self._feats[:b * s], b, s, labels)
+        return trainer.loss_of(stats)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The key set the model was built from: ``resnet.*`` (and anything else it carried) as loaded, the trained tensors as
+        they are on the device now (CPU tensors; waits for the read when a trainer exists)."""
+        out = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v))) for k, v in self._state_dict.items()}
+        if self._trainer is not None:
+            for k, v in self._trainer.read("weights").items():
+                out[k] = v.cpu()
+        return out
+
+    def save_checkpoint(self, path: str):
+        """A Lightning-shaped ``.ckpt`` (``state_dict`` + ``hyper_parameters``) that ``load_from_checkpoint`` reads back."""
+        hparams = dict(fighter_name=self.fighter_name, actions=list(self.actions), batch_size=self.batch_size,
+                       learning_rate=self.learning_rate, num_samples=self.num_samples, freeze_encoder=self.freeze_encoder)
+        hparams.update(self.dataset_kwargs)
+        torch.save({"state_dict": self.state_dict(), "hyper_parameters": hparams}, path)
+
     def close(self):
+        if getattr(self, "_trainer", None) is not None:
+            self._trainer.close()   # (before the handle whose weights it borrows)
+            self._trainer = None
         if getattr(self, "_h", None):
             self._lib.pa_lstm_destroy(self._h)
             self._h = None
