@@ -43,7 +43,7 @@ PA_ERR_NOT_READY = -6
 PA_ERR_BAD_LABELS = -7
 PA_EVAL_IGNORE = -100
 PA_ANNOT_MAX_ITEMS = 16
-# pa_head_trainer_read: which set of six tensors
+# pa_head_trainer_read / pa_lstm_trainer_read: which set of the trained tensors (PA_TRAIN_RAW, or-ed in: the head's alone)
 PA_TRAIN_WEIGHTS = 0
 PA_TRAIN_M = 1
 PA_TRAIN_V = 2

@@ -16,13 +16,11 @@
 // Gather indices are device data: every kernel clamps them into [0, n_rows). Labels outside [0, A) count as ignored
 // (the host wrapper refuses them; -100 is the only such value a checked caller passes).
 #include "pa_kernels.h"
-#include "adam.h"   // adam_apply
+#include "train_common.h"   // the loss, the statistics, adam_apply*
 
 namespace pa {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int FS = 1024;   // feature row stride (PA_FEATURE_STRIDE)
 constexpr int FC = 1000;   // features used
@@ -78,6 +76,8 @@ __global__ __launch_bounds__(256) void ht_sample_kernel(HeadTrainParams p) {
     const float *w2 = p.w[2], *b2 = p.w[3], *w3 = p.w[4], *b3 = p.w[5];
     if (tid == 0) nvalid = 0;
     __syncthreads();
+    // Not count_labelled: its per-thread sums make 64 LDS atomics of a wave where the compiler folds this form's constant 1
+    // into one, and the step at B = 64 measured 1.9 us (1 %) slower with it. (B <= 256 == blockDim: pa_head_trainer_create.)
     if (tid < p.B) {
         const int l = p.labels[tid];
         if (l >= 0 && l < A) atomicAdd(&nvalid, 1);   // (an integer count in LDS: exact in any order)
@@ -102,27 +102,12 @@ __global__ __launch_bounds__(256) void ht_sample_kernel(HeadTrainParams p) {
             z3 = b3[tid];
             for (int k = 0; k < 128; ++k) z3 = fmaf(w3[k * 64 + tid], h2s[k], z3);
         }
-        float mx = z3;
-        int arg = tid;
-        for (int d = 32; d >= 1; d >>= 1) {   // maximum and its first index
-            const float om = __shfl_xor(mx, d);
-            const int oa = __shfl_xor(arg, d);
-            if (om > mx || (om == mx && oa < arg)) {
-                mx = om;
-                arg = oa;
-            }
-        }
-        float se = tid < A ? expf(z3 - mx) : 0.f;
-        for (int d = 32; d >= 1; d >>= 1) se += __shfl_xor(se, d);
-        const float logp = z3 - mx - logf(se);
-        const float lp_label = __shfl(logp, valid ? label : 0);
-        float d3 = 0.f;
-        if (valid && tid < A) d3 = (expf(logp) - (tid == label ? 1.f : 0.f)) / n;
-        dz3s[tid] = d3;
-        p.dz3[b * 64 + tid] = d3;
+        const RowLoss r = softmax_nll_wave0(z3, tid, A, label, valid, n);
+        dz3s[tid] = r.d;
+        p.dz3[b * 64 + tid] = r.d;
         if (tid == 0) {
-            p.loss_b[b] = valid ? -lp_label : 0.f;
-            p.hit_b[b] = valid && arg == label ? 1 : 0;
+            p.loss_b[b] = r.loss;
+            p.hit_b[b] = r.hit;
         }
     }
     __syncthreads();
@@ -169,24 +154,7 @@ __global__ __launch_bounds__(256) void ht_param_kernel(HeadTrainParams p) {
     } else if (i < GS_END) {
         for (int b = 0; b < B; ++b) s += p.dz3[b * 64 + (i - GS_B3)];
     } else if (i == GS_END) {
-        int nv = 0, hits = 0;
-        for (int b = 0; b < B; ++b) {
-            const int l = p.labels[b];
-            nv += l >= 0 && l < p.A;
-            hits += p.hit_b[b];
-            s += p.loss_b[b];
-        }
-        const float loss = s / (float)max(nv, 1);
-        p.stats[0] = loss;
-        p.stats[1] = __int_as_float(nv);
-        p.stats[2] = __int_as_float(hits);
-        p.stats[3] = 0.f;
-        if (p.stats_out) {
-            p.stats_out[0] = loss;
-            p.stats_out[1] = __int_as_float(nv);
-            p.stats_out[2] = __int_as_float(hits);
-            p.stats_out[3] = 0.f;
-        }
+        write_train_stats(p.stats, p.stats_out, p.labels, p.hit_b, p.loss_b, B, p.A);
         return;
     } else {
         return;
@@ -266,17 +234,7 @@ __global__ __launch_bounds__(256) void ht_dw1_kernel(const float* __restrict__ f
 #pragma unroll
                     for (int j = 0; j < 4; ++j) gout[((size_t)o * FC + c + j) * S + t] = gr[j];   // cnn1d.0.weight [512][1000][S]
                 } else {
-                    const size_t idx = ((size_t)o * S + t) * FS + c;
-                    float4 w4 = *reinterpret_cast<float4*>(w + idx);
-                    float4 m4 = *reinterpret_cast<float4*>(m + idx);
-                    float4 v4 = *reinterpret_cast<float4*>(v + idx);
-                    adam_apply(w4.x, m4.x, v4.x, gr[0], ak);
-                    adam_apply(w4.y, m4.y, v4.y, gr[1], ak);
-                    adam_apply(w4.z, m4.z, v4.z, gr[2], ak);
-                    adam_apply(w4.w, m4.w, v4.w, gr[3], ak);
-                    *reinterpret_cast<float4*>(w + idx) = w4;
-                    *reinterpret_cast<float4*>(m + idx) = m4;
-                    *reinterpret_cast<float4*>(v + idx) = v4;
+                    adam_apply4_at(w, m, v, ((size_t)o * S + t) * FS + c, gr, ak);
                 }
             }
         }
@@ -293,11 +251,7 @@ __global__ __launch_bounds__(256) void ht_adam_kernel(HeadTrainParams p, AdamSca
     else if (i < GS_B3) t = 3, j = i - GS_B2;
     else if (i < GS_B3 + p.A) t = 5, j = i - GS_B3;
     else return;
-    float w = p.w[t][j], m = p.m[t][j], v = p.v[t][j];
-    adam_apply(w, m, v, p.gs[i], ak);
-    p.w[t][j] = w;
-    p.m[t][j] = m;
-    p.v[t][j] = v;
+    adam_apply_at(p.w[t], p.m[t], p.v[t], j, p.gs[i], ak);
 }
 
 // ---- read-out: six tensors in the layouts above -> PyTorch layouts, concatenated in blob order ---------------------

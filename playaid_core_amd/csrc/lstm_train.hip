@@ -19,15 +19,11 @@
 //
 // Labels outside [0, A) count as ignored (the Python wrapper refuses them; -100 is the only such value a checked caller passes).
 #include "pa_kernels.h"
-#include "adam.h"
+#include "train_common.h"
 #include "lstm_handle.h"
-#include "../../include/playaid_hip.h"
-#include <string>
 
 namespace pa {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int LT_NMAX = 16;   // batch rows of a time step (pa_lstm_forward's limit)
 
@@ -160,12 +156,7 @@ __global__ __launch_bounds__(128) void lt_decode_kernel(LstmTrainParams p) {
     const int tid = threadIdx.x, row = blockIdx.x, H = p.H, A = p.A;
     if (tid == 0) nvalid = 0;
     __syncthreads();
-    int cnt = 0;
-    for (int i = tid; i < p.M; i += 128) {
-        const int l = p.labels[i];
-        cnt += l >= 0 && l < A;
-    }
-    if (cnt) atomicAdd(&nvalid, cnt);   // (an integer count in LDS: exact in any order)
+    count_labelled(p.labels, p.M, A, tid, 128, &nvalid);
     for (int k = tid; k < H; k += 128) hr[k] = p.htop[(size_t)row * H + k];
     __syncthreads();
     const float n = (float)max(nvalid, 1);   // no labelled row: divide by 1, every gradient is then 0
@@ -196,27 +187,12 @@ __global__ __launch_bounds__(128) void lt_decode_kernel(LstmTrainParams p) {
             for (int k = 0; k < 128; ++k) a = fmaf(w[k], h1s[k], a);
             z2 = a + p.b2[tid];
         }
-        float mx = z2;
-        int arg = tid;
-        for (int d = 32; d >= 1; d >>= 1) {   // maximum and its first index
-            const float om = __shfl_xor(mx, d);
-            const int oa = __shfl_xor(arg, d);
-            if (om > mx || (om == mx && oa < arg)) {
-                mx = om;
-                arg = oa;
-            }
-        }
-        float se = tid < A ? expf(z2 - mx) : 0.f;
-        for (int d = 32; d >= 1; d >>= 1) se += __shfl_xor(se, d);
-        const float logp = z2 - mx - logf(se);
-        const float lp_label = __shfl(logp, valid ? label : 0);
-        float d2 = 0.f;
-        if (valid && tid < A) d2 = (expf(logp) - (tid == label ? 1.f : 0.f)) / n;
-        dz2s[tid] = d2;
-        p.dz2[(size_t)row * 64 + tid] = d2;
+        const RowLoss r = softmax_nll_wave0(z2, tid, A, label, valid, n);
+        dz2s[tid] = r.d;
+        p.dz2[(size_t)row * 64 + tid] = r.d;
         if (tid == 0) {
-            p.loss_r[row] = valid ? -lp_label : 0.f;
-            p.hit_r[row] = valid && arg == label ? 1 : 0;
+            p.loss_r[row] = r.loss;
+            p.hit_r[row] = r.hit;
         }
     }
     __syncthreads();
@@ -249,24 +225,7 @@ __global__ __launch_bounds__(256) void lt_param_kernel(LstmTrainParams p) {
     } else if (i < n_end) {
         for (int r = 0; r < M; ++r) s += p.dz2[(size_t)r * 64 + (i - n_w2)];
     } else if (i == n_end) {
-        int nv = 0, hits = 0;
-        for (int r = 0; r < M; ++r) {
-            const int l = p.labels[r];
-            nv += l >= 0 && l < A;
-            hits += p.hit_r[r];
-            s += p.loss_r[r];
-        }
-        const float loss = s / (float)max(nv, 1);
-        p.stats[0] = loss;
-        p.stats[1] = __int_as_float(nv);
-        p.stats[2] = __int_as_float(hits);
-        p.stats[3] = 0.f;
-        if (p.stats_out) {
-            p.stats_out[0] = loss;
-            p.stats_out[1] = __int_as_float(nv);
-            p.stats_out[2] = __int_as_float(hits);
-            p.stats_out[3] = 0.f;
-        }
+        write_train_stats(p.stats, p.stats_out, p.labels, p.hit_r, p.loss_r, M, A);
         return;
     } else {
         return;
@@ -279,6 +238,8 @@ __global__ __launch_bounds__(256) void lt_small_adam_kernel(float* __restrict__ 
                                                             const float* __restrict__ g, int n, AdamScalars ak) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    // Not adam_apply_at: with the gradient read before w, m and v the compiler fuses the other product of v's sum into the
+    // double-precision FMA here (fma((1 - b2) g, g, b2 v) for fma(b2, v, (1 - b2) g g)), which rounds differently.
     float wi = w[i], mi = m[i], vi = v[i];
     adam_apply(wi, mi, vi, g[i], ak);
     w[i] = wi;
@@ -466,26 +427,11 @@ __global__ __launch_bounds__(256) void lt_dw_kernel(const float* __restrict__ X,
             for (int j = 0; j < 4; ++j)
                 if (c + j < C) gout[idx + j] = gr[j];
         } else if (vec) {   // (c is a multiple of 4 and so is C: c + 3 < C, idx is 16-byte aligned)
-            float4 w4 = *reinterpret_cast<float4*>(w + idx);
-            float4 m4 = *reinterpret_cast<float4*>(m + idx);
-            float4 v4 = *reinterpret_cast<float4*>(v + idx);
-            adam_apply(w4.x, m4.x, v4.x, gr[0], ak);
-            adam_apply(w4.y, m4.y, v4.y, gr[1], ak);
-            adam_apply(w4.z, m4.z, v4.z, gr[2], ak);
-            adam_apply(w4.w, m4.w, v4.w, gr[3], ak);
-            *reinterpret_cast<float4*>(w + idx) = w4;
-            *reinterpret_cast<float4*>(m + idx) = m4;
-            *reinterpret_cast<float4*>(v + idx) = v4;
+            adam_apply4_at(w, m, v, idx, gr, ak);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (c + j < C) {
-                    float wi = w[idx + j], mi = m[idx + j], vi = v[idx + j];
-                    adam_apply(wi, mi, vi, gr[j], ak);
-                    w[idx + j] = wi;
-                    m[idx + j] = mi;
-                    v[idx + j] = vi;
-                }
+                if (c + j < C) adam_apply_at(w, m, v, idx + j, gr[j], ak);
         }
     }
 }
@@ -502,15 +448,10 @@ __global__ __launch_bounds__(256) void lt_bias_kernel(const float* __restrict__ 
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const int i = b * H4 + k;
-        if (STORE_G) {
+        if (STORE_G)
             gout[i] = s;
-        } else {
-            float wi = w[i], mi = m[i], vi = v[i];
-            adam_apply(wi, mi, vi, s, ak);
-            w[i] = wi;
-            m[i] = mi;
-            v[i] = vi;
-        }
+        else
+            adam_apply_at(w, m, v, i, s, ak);
     }
 }
 
@@ -532,13 +473,9 @@ hipError_t launch_dw(bool apply, const float* X, int ldx, const float* D, int ld
 // The trainer: a handle beside its pa_lstm
 // =====================================================================================
 
-struct pa_lstm_trainer {
+struct pa_lstm_trainer : pa::TrainerCore {   // state: m | v (blob order, PyTorch layouts) | the saved activations and scratch
     pa_lstm* h = nullptr;
-    pa_adam_config cfg;
-    int64_t steps = 0;
-    std::string last_error;
     size_t nw = 0;             // floats of one tensor set (the blob's)
-    float* state = nullptr;    // one allocation: m | v (blob order, PyTorch layouts) | the saved activations and scratch
     float *m = nullptr, *v = nullptr;
     float *pre = nullptr, *dA = nullptr, *dh = nullptr, *carry = nullptr;
     float *gates = nullptr, *cs = nullptr, *hs = nullptr;   // per layer: [max_rows][4H], [max_rows][H], [max_rows][H]
@@ -546,14 +483,7 @@ struct pa_lstm_trainer {
     int32_t* hit_r = nullptr;
 };
 
-namespace {
-
-int ltfail(pa_lstm_trainer* t, int code, const std::string& msg) {
-    t->last_error = msg;
-    return code;
-}
-
-}  // namespace
+using pa::trainer_fail;
 
 extern "C" {
 
@@ -569,20 +499,17 @@ int pa_lstm_trainer_create(pa_lstm* h, const pa_adam_config* cfg, pa_lstm_traine
         return PA_ERR_INVALID_ARG;
     }
     pa_lstm_trainer* t = new pa_lstm_trainer();
-    *out = t;   // handed back even when the device stops the creation, for the error text (and destroyed by the caller)
+    *out = t;   // (handed back whatever follows: TrainerCore)
     t->h = h;
     t->cfg = *cfg;
     t->nw = pa::lstm_float_count(h->in_dim, h->hid, h->layers, h->actions);
-    if (!h->weights) return ltfail(t, PA_ERR_NO_DEVICE, "pa_lstm_trainer_create: the handle has no weights on a device");
-    if (hipSetDevice(h->device) != hipSuccess) return ltfail(t, PA_ERR_NO_DEVICE, "pa_lstm_trainer_create: hipSetDevice failed");
+    if (!h->weights) return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_lstm_trainer_create: the handle has no weights on a device");
+    if (hipSetDevice(h->device) != hipSuccess) return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_lstm_trainer_create: hipSetDevice failed");
     const size_t R = (size_t)h->max_rows, H = (size_t)h->hid, L = (size_t)h->layers, A = (size_t)h->actions;
     const size_t nw = (t->nw + 63) & ~(size_t)63;
     const size_t n_small = (128 + 129 * A + 63) & ~(size_t)63;
     const size_t scratch = R * 4 * H * 2 + R * H + pa::LT_NMAX * H + L * R * 6 * H + R * (128 + 128 + 64 + 2) + n_small + 64;
-    void* p = nullptr;
-    if (hipMalloc(&p, (2 * nw + scratch) * sizeof(float)) != hipSuccess) return ltfail(t, PA_ERR_HIP, "pa_lstm_trainer_create: hipMalloc failed");
-    t->state = static_cast<float*>(p);
-    if (hipMemset(p, 0, (2 * nw + scratch) * sizeof(float)) != hipSuccess) return ltfail(t, PA_ERR_HIP, "pa_lstm_trainer_create: hipMemset failed");
+    if (const int rc = pa::trainer_alloc_zeroed(t, 2 * nw + scratch, "pa_lstm_trainer_create")) return rc;
     float* q = t->state;
     t->m = q, q += nw;
     t->v = q, q += nw;
@@ -603,33 +530,29 @@ int pa_lstm_trainer_create(pa_lstm* h, const pa_adam_config* cfg, pa_lstm_traine
     return PA_OK;
 }
 
-void pa_lstm_trainer_destroy(pa_lstm_trainer* t) {
-    if (!t) return;
-    (void)hipFree(t->state);
-    delete t;
-}
+void pa_lstm_trainer_destroy(pa_lstm_trainer* t) { pa::trainer_destroy(t); }
 
-const char* pa_lstm_trainer_last_error(const pa_lstm_trainer* t) { return t ? t->last_error.c_str() : "null trainer"; }
+const char* pa_lstm_trainer_last_error(const pa_lstm_trainer* t) { return pa::trainer_last_error(t); }
 
-int64_t pa_lstm_trainer_steps(const pa_lstm_trainer* t) { return t ? t->steps : -1; }
+int64_t pa_lstm_trainer_steps(const pa_lstm_trainer* t) { return pa::trainer_steps(t); }
 
 int pa_lstm_train_step(pa_lstm_trainer* t, const float* x, int32_t ld, int32_t seq_len, int32_t batch, const int32_t* labels, int32_t apply,
                        float* grads_out, pa_train_stats* stats_dev, void* stream) {
     using namespace pa;
     if (!t) return PA_ERR_INVALID_ARG;
     pa_lstm* h = t->h;
-    if (!x || !labels) return ltfail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: null input");
-    if (seq_len < 1 || batch < 1 || batch > LT_NMAX) return ltfail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: seq_len < 1 or batch outside 1..16");
-    if ((long long)seq_len * batch > h->max_rows) return ltfail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: seq_len * batch exceeds max_rows");
-    if (ld < h->in_dim) return ltfail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: ld < input_dim");
-    if ((apply != 0 && apply != 1) || (!apply && !grads_out)) return ltfail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: apply is 0 (with grads_out) or 1");
-    if (!t->state) return ltfail(t, PA_ERR_NO_DEVICE, "pa_lstm_train_step: the trainer has no device state");
+    if (!x || !labels) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: null input");
+    if (seq_len < 1 || batch < 1 || batch > LT_NMAX) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: seq_len < 1 or batch outside 1..16");
+    if ((long long)seq_len * batch > h->max_rows) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: seq_len * batch exceeds max_rows");
+    if (ld < h->in_dim) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_lstm_train_step: ld < input_dim");
+    if (const int rc = trainer_check_apply(t, apply, grads_out, "pa_lstm_train_step")) return rc;
+    if (!t->state) return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_lstm_train_step: the trainer has no device state");
     hipStream_t s = (hipStream_t)stream;
     const int H = h->hid, L = h->layers, A = h->actions, T = seq_len, N = batch, M = T * N;
     const size_t R = (size_t)h->max_rows;
     const AdamScalars ak = adam_scalars(t->cfg.lr, t->cfg.beta1, t->cfg.beta2, t->cfg.eps, t->steps + 1, apply != 0);
     hipError_t err = hipSuccess;
-    auto fail = [&](hipError_t e) { return ltfail(t, PA_ERR_HIP, std::string("pa_lstm_train_step: ") + hipGetErrorString(e)); };
+    auto fail = [&](hipError_t e) { return trainer_fail(t, PA_ERR_HIP, std::string("pa_lstm_train_step: ") + hipGetErrorString(e)); };
     // a tensor of the handle -> the same tensor of m, v or grads_out (all in blob order)
     auto off = [&](const float* wp) { return (size_t)(wp - h->weights); };
 
@@ -718,13 +641,13 @@ int pa_lstm_train_step(pa_lstm_trainer* t, const float* x, int32_t ld, int32_t s
 
 int pa_lstm_trainer_read(pa_lstm_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream) {
     if (!t) return PA_ERR_INVALID_ARG;
-    if (!out_dev || which < 0 || which > PA_TRAIN_V)   // (PA_TRAIN_RAW too: the tensors lie in PyTorch layouts, there is no other form)
-        return ltfail(t, PA_ERR_INVALID_ARG, "pa_lstm_trainer_read: null output or unknown tensor set");
-    if (floats != t->nw) return ltfail(t, PA_ERR_INVALID_ARG, "pa_lstm_trainer_read: wrong output size");
-    if (!t->state) return ltfail(t, PA_ERR_NO_DEVICE, "pa_lstm_trainer_read: the trainer has no device state");
+    // (PA_TRAIN_RAW is refused too: the tensors lie in PyTorch layouts, there is no other form)
+    if (const int rc = pa::trainer_check_which(t, which, out_dev, "pa_lstm_trainer_read")) return rc;
+    if (floats != t->nw) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_lstm_trainer_read: wrong output size");
+    if (!t->state) return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_lstm_trainer_read: the trainer has no device state");
     const float* src = which == PA_TRAIN_WEIGHTS ? t->h->weights : which == PA_TRAIN_M ? t->m : t->v;
     if (hipMemcpyAsync(out_dev, src, t->nw * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-        return ltfail(t, PA_ERR_HIP, "pa_lstm_trainer_read: hipMemcpyAsync failed");
+        return trainer_fail(t, PA_ERR_HIP, "pa_lstm_trainer_read: hipMemcpyAsync failed");
     return PA_OK;
 }
 

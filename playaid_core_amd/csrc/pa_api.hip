@@ -4,7 +4,7 @@
 // in the enqueue calls.
 #include "../../include/playaid_hip.h"
 #include "conv_rows.h"
-#include "adam.h"   // adam_scalars, adam_config_ok
+#include "train_common.h"   // adam_scalars, adam_config_ok, TrainerCore
 
 #include <algorithm>
 #include <cmath>
@@ -2080,13 +2080,9 @@ int pa_eval_read(pa_eval* h, pa_eval_totals* totals_host, int64_t* confusion_hos
 // Training of the temporal head (csrc/head_train.hip): a handle beside its engine
 // ===============================================================================
 
-struct pa_head_trainer {
+struct pa_head_trainer : pa::TrainerCore {   // state: m | v (six tensors each, in the weights' layouts) | the step's scratch
     pa_engine* eng = nullptr;
-    pa_adam_config cfg;
     int max_batch = 0, S = 0, A = 0;
-    int64_t steps = 0;
-    std::string last_error;
-    float* state = nullptr;    // one allocation: m | v (six tensors each, in the weights' layouts) | the step's scratch
     float *m[6] = {}, *v[6] = {};
     float *h1 = nullptr, *h2 = nullptr, *dz3 = nullptr, *dz2 = nullptr, *dz1 = nullptr, *loss_b = nullptr, *gs = nullptr, *stats = nullptr;
     int32_t* hit_b = nullptr;
@@ -2095,11 +2091,6 @@ struct pa_head_trainer {
 static_assert(sizeof(pa_train_stats) == 16 && sizeof(pa_adam_config) == 16, "pa_train_stats / pa_adam_config are four 32-bit words");
 
 namespace {
-
-int tfail(pa_head_trainer* t, int code, const std::string& msg) {
-    t->last_error = msg;
-    return code;
-}
 
 // floats of tensor i (blob order) in the layout the inference kernels read
 size_t head_layout_floats(int i, int S, int A) {
@@ -2117,23 +2108,20 @@ int pa_head_trainer_create(pa_engine* e, const pa_adam_config* cfg, int32_t max_
     if (!e || !cfg || max_batch < 1 || max_batch > 256) return PA_ERR_INVALID_ARG;
     if (!adam_config_ok(cfg->lr, cfg->beta1, cfg->beta2, cfg->eps)) return PA_ERR_INVALID_ARG;
     pa_head_trainer* t = new pa_head_trainer();
-    *out = t;   // handed back even when the device stops the creation, for the error text (and destroyed by the caller)
+    *out = t;   // (handed back whatever follows: TrainerCore)
     t->eng = e;
     t->cfg = *cfg;
     t->max_batch = max_batch;
     t->S = e->cfg.sequence_length;
     t->A = e->cfg.num_actions;
     if (!e->w1d || !e->b1d || !e->w2 || !e->b2 || !e->w3 || !e->b3)
-        return tfail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_create: the engine has no weights on a device");
-    if (hipSetDevice(e->cfg.device_id) != hipSuccess) return tfail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_create: hipSetDevice failed");
+        return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_create: the engine has no weights on a device");
+    if (hipSetDevice(e->cfg.device_id) != hipSuccess) return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_create: hipSetDevice failed");
     size_t moments = 0;
     for (int i = 0; i < 6; ++i) moments += head_layout_floats(i, t->S, t->A);
     const size_t B = (size_t)max_batch;
     const size_t scratch = B * 512 * 2 + B * 128 * 2 + B * 64 + B * 2 + (512 * 128 + 128 * 64 + 512 + 128 + 64) + 64;
-    void* p = nullptr;
-    if (hipMalloc(&p, (2 * moments + scratch) * sizeof(float)) != hipSuccess) return tfail(t, PA_ERR_HIP, "pa_head_trainer_create: hipMalloc failed");
-    t->state = static_cast<float*>(p);
-    if (hipMemset(p, 0, (2 * moments + scratch) * sizeof(float)) != hipSuccess) return tfail(t, PA_ERR_HIP, "pa_head_trainer_create: hipMemset failed");
+    if (const int rc = trainer_alloc_zeroed(t, 2 * moments + scratch, "pa_head_trainer_create")) return rc;
     float* q = t->state;
     for (int i = 0; i < 6; ++i) {
         t->m[i] = q;
@@ -2155,24 +2143,20 @@ int pa_head_trainer_create(pa_engine* e, const pa_adam_config* cfg, int32_t max_
     return PA_OK;
 }
 
-void pa_head_trainer_destroy(pa_head_trainer* t) {
-    if (!t) return;
-    (void)hipFree(t->state);
-    delete t;
-}
+void pa_head_trainer_destroy(pa_head_trainer* t) { trainer_destroy(t); }
 
-const char* pa_head_trainer_last_error(const pa_head_trainer* t) { return t ? t->last_error.c_str() : "null trainer"; }
+const char* pa_head_trainer_last_error(const pa_head_trainer* t) { return trainer_last_error(t); }
 
-int64_t pa_head_trainer_steps(const pa_head_trainer* t) { return t ? t->steps : -1; }
+int64_t pa_head_trainer_steps(const pa_head_trainer* t) { return trainer_steps(t); }
 
 int pa_head_train_step(pa_head_trainer* t, const float* feats, int32_t n_rows, const int32_t* gather, const int32_t* labels, int32_t batch,
                        int32_t apply, float* grads_out, pa_train_stats* stats_dev, void* stream) {
     if (!t) return PA_ERR_INVALID_ARG;
-    if (!feats || !gather || !labels || n_rows < 1) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: null input or n_rows < 1");
-    if (batch < 1 || batch > t->max_batch) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: batch outside 1..max_batch");
-    if ((apply != 0 && apply != 1) || (!apply && !grads_out)) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: apply is 0 (with grads_out) or 1");
-    if ((reinterpret_cast<uintptr_t>(feats) & 15) != 0) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: feats must be 16-byte aligned");
-    if (!t->state) return tfail(t, PA_ERR_NO_DEVICE, "pa_head_train_step: the trainer has no device state");
+    if (!feats || !gather || !labels || n_rows < 1) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: null input or n_rows < 1");
+    if (batch < 1 || batch > t->max_batch) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: batch outside 1..max_batch");
+    if (const int rc = trainer_check_apply(t, apply, grads_out, "pa_head_train_step")) return rc;
+    if ((reinterpret_cast<uintptr_t>(feats) & 15) != 0) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_head_train_step: feats must be 16-byte aligned");
+    if (!t->state) return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_head_train_step: the trainer has no device state");
     pa_engine* e = t->eng;
     HeadTrainParams p;
     memset(&p, 0, sizeof(p));
@@ -2196,7 +2180,7 @@ int pa_head_train_step(pa_head_trainer* t, const float* feats, int32_t n_rows, c
     p.grads_out = grads_out;
     const AdamScalars ak = adam_scalars(t->cfg.lr, t->cfg.beta1, t->cfg.beta2, t->cfg.eps, t->steps + 1, apply != 0);
     const hipError_t err = launch_head_train_step(p, ak, (hipStream_t)stream);
-    if (err != hipSuccess) return tfail(t, PA_ERR_HIP, std::string("pa_head_train_step: ") + hipGetErrorString(err));
+    if (err != hipSuccess) return trainer_fail(t, PA_ERR_HIP, std::string("pa_head_train_step: ") + hipGetErrorString(err));
     if (apply) t->steps += 1;
     return PA_OK;
 }
@@ -2204,12 +2188,12 @@ int pa_head_train_step(pa_head_trainer* t, const float* feats, int32_t n_rows, c
 int pa_head_trainer_read(pa_head_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream) {
     if (!t) return PA_ERR_INVALID_ARG;
     const int set = which & ~PA_TRAIN_RAW;
-    if (!out_dev || which < 0 || set > PA_TRAIN_V) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_trainer_read: null output or unknown tensor set");
+    if (const int rc = trainer_check_which(t, set, out_dev, "pa_head_trainer_read")) return rc;
     const bool raw = (which & PA_TRAIN_RAW) != 0;
     const size_t raw_n[6] = {(size_t)512 * t->S * PA_FEATURE_STRIDE, 512, 512 * 128, 128, 128 * 64, (size_t)t->A};
     const size_t want = raw ? raw_n[0] + raw_n[1] + raw_n[2] + raw_n[3] + raw_n[4] + raw_n[5] : head_tensor_floats(t->S, t->A);
-    if (floats != want) return tfail(t, PA_ERR_INVALID_ARG, "pa_head_trainer_read: wrong output size");
-    if (!t->state) return tfail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_read: the trainer has no device state");
+    if (floats != want) return trainer_fail(t, PA_ERR_INVALID_ARG, "pa_head_trainer_read: wrong output size");
+    if (!t->state) return trainer_fail(t, PA_ERR_NO_DEVICE, "pa_head_trainer_read: the trainer has no device state");
     pa_engine* e = t->eng;
     HeadTensors src;
     const float* w[6] = {e->w1d, e->b1d, e->w2, e->b2, e->w3, e->b3};
@@ -2217,13 +2201,13 @@ int pa_head_trainer_read(pa_head_trainer* t, int32_t which, float* out_dev, size
     if (raw) {
         for (int i = 0; i < 6; ++i) {
             if (hipMemcpyAsync(out_dev, src.p[i], raw_n[i] * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-                return tfail(t, PA_ERR_HIP, "pa_head_trainer_read: hipMemcpyAsync failed");
+                return trainer_fail(t, PA_ERR_HIP, "pa_head_trainer_read: hipMemcpyAsync failed");
             out_dev += raw_n[i];
         }
         return PA_OK;
     }
     const hipError_t err = launch_head_export(src, t->S, t->A, out_dev, (hipStream_t)stream);
-    if (err != hipSuccess) return tfail(t, PA_ERR_HIP, std::string("pa_head_trainer_read: ") + hipGetErrorString(err));
+    if (err != hipSuccess) return trainer_fail(t, PA_ERR_HIP, std::string("pa_head_trainer_read: ") + hipGetErrorString(err));
     return PA_OK;
 }
 

@@ -13,19 +13,17 @@ handed. Like the rest of the product path there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, trainer_base
+from .trainer_base import _WHICH, IGNORE, AdamTrainer, check_labels  # noqa: F401  (IGNORE: part of this module's interface)
 
-IGNORE = _lib.PA_EVAL_IGNORE
 MAX_BATCH = 256
 TENSOR_KEYS = ("model.cnn1d.0.weight", "model.cnn1d.0.bias", "model.classifier.0.weight", "model.classifier.0.bias",
                "model.classifier.2.weight", "model.classifier.2.bias")
-_WHICH = {"weights": _lib.PA_TRAIN_WEIGHTS, "m": _lib.PA_TRAIN_M, "v": _lib.PA_TRAIN_V}
 
 
 def tensor_shapes(sequence_length: int, num_actions: int) -> Tuple[Tuple[int, ...], ...]:
@@ -39,25 +37,15 @@ def tensor_floats(sequence_length: int, num_actions: int) -> int:
 
 def check_adam(lr: float, betas: Sequence[float], eps: float, max_batch: int):
     """What ``pa_head_trainer_create`` refuses, refused with a message first."""
-    if not (math.isfinite(lr) and lr > 0):
-        raise ValueError(f"lr must be finite and positive, got {lr!r}")
-    if not (math.isfinite(eps) and eps > 0):
-        raise ValueError(f"eps must be finite and positive, got {eps!r}")
-    if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
-        raise ValueError(f"betas must be two values in [0, 1), got {betas!r}")
+    trainer_base.check_adam(lr, betas, eps)
     if not 1 <= int(max_batch) <= MAX_BATCH or int(max_batch) != max_batch:
         raise ValueError(f"max_batch must be an integer in 1..{MAX_BATCH}, got {max_batch!r}")
 
 
 def check_batch(gather, labels, n_rows: int, sequence_length: int, num_actions: int, max_batch: int) -> int:
     """Shapes of ``gather`` [B, S] and ``labels`` [B] and, where they are host data (numpy arrays, lists, CPU tensors), their
-    values: row indices in ``[0, n_rows)``, labels in ``{-100} | [0, A)``. Device tensors are checked for shape only -- reading
-    them would wait for the device; the kernels clamp indices and ignore labels outside the range. -> B."""
-    def host(a):
-        if isinstance(a, torch.Tensor):
-            return None if a.is_cuda else a.numpy()
-        return np.asarray(a)
-
+    values: row indices in ``[0, n_rows)``, labels as ``check_labels`` has them. Device tensors are not read -- that would wait
+    for the device; the kernels clamp indices and ignore labels outside the range. -> B."""
     gs = tuple(gather.shape) if hasattr(gather, "shape") else np.asarray(gather).shape
     ls = tuple(labels.shape) if hasattr(labels, "shape") else np.asarray(labels).shape
     if len(gs) != 2 or gs[1] != sequence_length:
@@ -69,72 +57,32 @@ def check_batch(gather, labels, n_rows: int, sequence_length: int, num_actions: 
         raise ValueError(f"labels are int32[{b}], got shape {tuple(ls)}")
     if n_rows < 1:
         raise ValueError("feats has no rows")
-    g, l = host(gather), host(labels)
-    for name, a in (("gather", g), ("labels", l)):
-        if a is not None and not np.issubdtype(a.dtype, np.integer):
-            raise ValueError(f"{name} must be integers, got {a.dtype}")
+    if isinstance(gather, torch.Tensor):
+        g = None if gather.is_cuda else gather.numpy()
+    else:
+        g = np.asarray(gather)
+    if g is not None and not np.issubdtype(g.dtype, np.integer):
+        raise ValueError(f"gather must be integers, got {g.dtype}")
     if g is not None and g.size and (g.min() < 0 or g.max() >= n_rows):
         raise ValueError(f"gather indices outside [0, {n_rows})")
-    if l is not None and not np.all((l == IGNORE) | ((l >= 0) & (l < num_actions))):
-        raise ValueError(f"labels must be {IGNORE} or in [0, {num_actions})")
+    check_labels(labels, b, num_actions)
     return b
 
 
-class HeadTrainer:
+class HeadTrainer(AdamTrainer):
     """Adam on the head of ``engine`` (``pa_head_trainer_create`` / ``pa_head_trainer_destroy``)."""
 
+    PREFIX = "pa_head_trainer"
+
     def __init__(self, engine, lr: float = 2e-4, betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8, max_batch: int = 64):
-        self._h = C.c_void_p(0)
         check_adam(lr, betas, eps, max_batch)
-        self._lib = _lib.load()
+        cfg = self._begin(lr, betas, eps)
         self.engine = engine   # (kept alive: the trainer borrows its weights)
         self.device = engine.device
         self.S, self.A = engine.S, engine.A
         self.max_batch = int(max_batch)
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        cfg = _lib.pa_adam_config(self.lr, self.betas[0], self.betas[1], self.eps)
-        rc = self._lib.pa_head_trainer_create(engine._h, C.byref(cfg), self.max_batch, C.byref(self._h))
-        if rc != _lib.PA_OK:
-            msg = self._lib.pa_head_trainer_last_error(self._h).decode() if self._h else self._lib.pa_status_string(rc).decode()
-            self.close()
-            self._raise(rc, msg)
-        self._floats = tensor_floats(self.S, self.A)
-        # running epoch statistics on the device: sum of loss * valid, valid, correct (float64, exact for the counts)
-        self._epoch = torch.zeros(3, dtype=torch.float64, device=self.device)
-
-    @staticmethod
-    def _raise(rc: int, msg: str):
-        from .engine import EngineError
-
-        raise EngineError(rc, msg)
-
-    def _check(self, rc: int):
-        if rc != _lib.PA_OK:
-            self._raise(rc, self._lib.pa_head_trainer_last_error(self._h).decode())
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.pa_head_trainer_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def steps(self) -> int:
-        return int(self._lib.pa_head_trainer_steps(self._h))
+        self.keys, self.shapes = TENSOR_KEYS, tensor_shapes(self.S, self.A)
+        self._created(self._lib.pa_head_trainer_create(engine._h, C.byref(cfg), self.max_batch, C.byref(self._h)))
 
     # -- one step ---------------------------------------------------------------
     def _inputs(self, feats, gather, labels):
@@ -163,14 +111,8 @@ class HeadTrainer:
         update (float32 bits: ``stats[:1].view(torch.float32)``), ``[1]`` labelled windows, ``[2]`` of them predicted right."""
         stats = self._run(feats, gather, labels, True, None)
         self.engine._head_trained = True   # (Engine.reconfigured: the state dict the engine was built from is stale now)
-        valid = stats[1].to(torch.float64)
-        self._epoch += torch.stack((stats[:1].view(torch.float32)[0].to(torch.float64) * valid, valid, stats[2].to(torch.float64)))
+        self._count(stats)
         return stats
-
-    @staticmethod
-    def loss_of(stats: torch.Tensor) -> torch.Tensor:
-        """The loss of a ``step`` / ``grads`` result as a 0-dim float32 device tensor (no read)."""
-        return stats[:1].view(torch.float32)[0]
 
     def grads(self, feats, gather, labels) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
         """The six gradients of the batch's loss in PyTorch layouts (device tensors under ``TENSOR_KEYS``) and the stats;
@@ -178,22 +120,6 @@ class HeadTrainer:
         flat = torch.empty(self._floats, dtype=torch.float32, device=self.device)
         stats = self._run(feats, gather, labels, False, flat)
         return self._split(flat), stats
-
-    def _split(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        out, off = {}, 0
-        for key, shape in zip(TENSOR_KEYS, tensor_shapes(self.S, self.A)):
-            n = int(np.prod(shape))
-            out[key] = flat[off:off + n].view(shape)
-            off += n
-        return out
-
-    def read(self, which: str = "weights") -> Dict[str, torch.Tensor]:
-        """``"weights"`` | ``"m"`` | ``"v"`` -> the six tensors in PyTorch layouts (device tensors under ``TENSOR_KEYS``)."""
-        if which not in _WHICH:
-            raise ValueError(f"which must be one of {sorted(_WHICH)}")
-        flat = torch.empty(self._floats, dtype=torch.float32, device=self.device)
-        self._check(self._lib.pa_head_trainer_read(self._h, _WHICH[which], C.c_void_p(flat.data_ptr()), self._floats, self._stream()))
-        return self._split(flat)
 
     def read_raw(self, which: str = "weights") -> Tuple[torch.Tensor, ...]:
         """The set as it lies on the device, padding included (``PA_TRAIN_RAW``): float32 device tensors [512, S, 1024], [512],
@@ -211,13 +137,3 @@ class HeadTrainer:
             out.append(flat[off:off + n].view(s))
             off += n
         return tuple(out)
-
-    # -- running statistics -------------------------------------------------------
-    def epoch_stats(self, reset: bool = True) -> Dict[str, float]:
-        """Loss (mean over the labelled windows of the steps since the last reset, each step's loss taken before its update)
-        and accuracy of the epoch so far: ONE read."""
-        s = self._epoch.cpu().numpy()
-        if reset:
-            self._epoch.zero_()
-        n = float(s[1])
-        return {"loss": float(s[0]) / n if n else float("nan"), "accuracy": float(s[2]) / n if n else float("nan"), "windows": int(n)}

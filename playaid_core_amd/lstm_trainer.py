@@ -19,11 +19,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .head_trainer import check_adam
+from .trainer_base import IGNORE, AdamTrainer, check_adam, check_labels  # noqa: F401  (IGNORE: part of this module's interface)
 
-IGNORE = _lib.PA_EVAL_IGNORE
 MAX_BATCH = 16   # rows of a time step (``pa_lstm_forward``'s limit)
-_WHICH = {"weights": _lib.PA_TRAIN_WEIGHTS, "m": _lib.PA_TRAIN_M, "v": _lib.PA_TRAIN_V}
 _DECODER_KEYS = ("action_decoder.0.weight", "action_decoder.0.bias", "action_decoder.2.weight", "action_decoder.2.bias")
 
 
@@ -51,9 +49,8 @@ def tensor_floats(input_dim: int, hidden: int, layers: int, actions: int) -> int
 
 
 def check_step(x_shape, seq_len: int, batch: int, labels, input_dim: int, actions: int, max_rows: int) -> int:
-    """What ``pa_lstm_train_step`` refuses, refused with a message first, and the values of host-side labels (numpy arrays,
-    lists, CPU tensors): ``{-100} | [0, A)``. Device labels are checked for their size only -- reading them would wait for the
-    device; the kernels ignore labels outside the range. -> the number of rows."""
+    """What ``pa_lstm_train_step`` refuses, refused with a message first, and the labels as ``check_labels`` has them. -> the
+    number of rows."""
     if int(seq_len) != seq_len or seq_len < 1:
         raise ValueError(f"seq_len must be a positive integer, got {seq_len!r}")
     if int(batch) != batch or not 1 <= batch <= MAX_BATCH:
@@ -64,31 +61,21 @@ def check_step(x_shape, seq_len: int, batch: int, labels, input_dim: int, action
     x_shape = tuple(x_shape)
     if len(x_shape) < 2 or x_shape[-1] < input_dim or int(np.prod(x_shape[:-1])) != rows:
         raise ValueError(f"x is float32[{rows} rows, >= {input_dim}], got shape {x_shape}")
-    if isinstance(labels, torch.Tensor):
-        host = None if labels.is_cuda else labels.numpy()
-        n, integral = labels.numel(), not (labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool)
-    else:
-        host = np.asarray(labels)
-        n, integral = host.size, np.issubdtype(host.dtype, np.integer)
-    if n != rows:
-        raise ValueError(f"labels are int32[{rows}], got {n} values")
-    if not integral:
-        raise ValueError("labels must be integers")
-    if host is not None and not np.all((host == IGNORE) | ((host >= 0) & (host < actions))):
-        raise ValueError(f"labels must be {IGNORE} or in [0, {actions})")
+    check_labels(labels, rows, actions)
     return rows
 
 
-class LSTMTrainer:
+class LSTMTrainer(AdamTrainer):
     """Adam on the LSTM head of an ``RNNActionDetector`` -- or of a bare ``pa_lstm`` handle (a ``ctypes.c_void_p``), then with
     ``dims=(input_dim, hidden, layers, actions)``, ``max_rows=`` and optionally ``device=`` -- (``pa_lstm_trainer_create`` /
     ``pa_lstm_trainer_destroy``). Close the trainer before the model or handle it borrows."""
 
+    PREFIX = "pa_lstm_trainer"
+
     def __init__(self, model_or_handle, lr: float = 2e-4, betas: Sequence[float] = (0.9, 0.999), eps: float = 1e-8, *,
                  dims: Optional[Tuple[int, int, int, int]] = None, max_rows: Optional[int] = None, device=None):
-        self._h = C.c_void_p(0)
-        check_adam(lr, betas, eps, 1)
-        self._lib = _lib.load()
+        check_adam(lr, betas, eps)
+        cfg = self._begin(lr, betas, eps)
         if isinstance(model_or_handle, (C.c_void_p, int)):
             if dims is None or max_rows is None:
                 raise ValueError("a bare pa_lstm handle needs dims=(input_dim, hidden, layers, actions) and max_rows=")
@@ -107,56 +94,12 @@ class LSTMTrainer:
         self.max_rows = int(max_rows)
         self.keys = tensor_keys(self.layers)
         self.shapes = tensor_shapes(*dims)
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        cfg = _lib.pa_adam_config(self.lr, self.betas[0], self.betas[1], self.eps)
-        rc = self._lib.pa_lstm_trainer_create(handle, C.byref(cfg), C.byref(self._h))
-        if rc != _lib.PA_OK:
-            if self._h:
-                msg = self._lib.pa_lstm_trainer_last_error(self._h).decode()
-            else:
-                msg = self._lib.pa_lstm_last_error(handle).decode() or self._lib.pa_status_string(rc).decode()
-            self.close()
-            self._raise(rc, msg)
-        self._floats = tensor_floats(*dims)
+        # (no trainer handle came back: the refusal's text is on the pa_lstm handle)
+        self._created(self._lib.pa_lstm_trainer_create(handle, C.byref(cfg), C.byref(self._h)),
+                      lambda: self._lib.pa_lstm_last_error(handle).decode())
         if self._floats != int(self._lib.pa_lstm_trainer_floats(handle)):
             self.close()
             raise ValueError(f"dims {tuple(dims)} are not the handle's")
-        # running epoch statistics on the device: sum of loss * valid, valid, correct (float64, exact for the counts)
-        self._epoch = torch.zeros(3, dtype=torch.float64, device=self.device)
-
-    @staticmethod
-    def _raise(rc: int, msg: str):
-        from .engine import EngineError
-
-        raise EngineError(rc, msg)
-
-    def _check(self, rc: int):
-        if rc != _lib.PA_OK:
-            self._raise(rc, self._lib.pa_lstm_trainer_last_error(self._h).decode())
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.pa_lstm_trainer_destroy(self._h)
-            self._h = C.c_void_p(0)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    @property
-    def steps(self) -> int:
-        return int(self._lib.pa_lstm_trainer_steps(self._h))
 
     # -- one step ---------------------------------------------------------------
     def _run(self, x, seq_len, batch, labels, apply: bool, grads):
@@ -179,14 +122,8 @@ class LSTMTrainer:
         (``-100`` = no ground truth). -> the step's ``pa_train_stats`` as a device tensor int32[4]: ``[0]`` the loss before the
         update (float32 bits: ``loss_of(stats)``), ``[1]`` labelled rows, ``[2]`` of them predicted right."""
         stats = self._run(x, seq_len, batch, labels, True, None)
-        valid = stats[1].to(torch.float64)
-        self._epoch += torch.stack((stats[:1].view(torch.float32)[0].to(torch.float64) * valid, valid, stats[2].to(torch.float64)))
+        self._count(stats)
         return stats
-
-    @staticmethod
-    def loss_of(stats: torch.Tensor) -> torch.Tensor:
-        """The loss of a ``step`` / ``grads`` result as a 0-dim float32 device tensor (no read)."""
-        return stats[:1].view(torch.float32)[0]
 
     def grads(self, x, seq_len: int, batch: int, labels) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
         """The gradients of the batch's loss in PyTorch layouts (device tensors under the PyTorch keys) and the stats; weights,
@@ -194,30 +131,3 @@ class LSTMTrainer:
         flat = torch.empty(self._floats, dtype=torch.float32, device=self.device)
         stats = self._run(x, seq_len, batch, labels, False, flat)
         return self._split(flat), stats
-
-    def _split(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        out, off = {}, 0
-        for key, shape in zip(self.keys, self.shapes):
-            n = int(np.prod(shape))
-            out[key] = flat[off:off + n].view(shape)
-            off += n
-        return out
-
-    def read(self, which: str = "weights") -> Dict[str, torch.Tensor]:
-        """``"weights"`` | ``"m"`` | ``"v"`` -> the tensors in PyTorch layouts (device tensors under ``lstm.weight_ih_l0`` ...
-        ``action_decoder.2.bias``)."""
-        if which not in _WHICH:
-            raise ValueError(f"which must be one of {sorted(_WHICH)}")
-        flat = torch.empty(self._floats, dtype=torch.float32, device=self.device)
-        self._check(self._lib.pa_lstm_trainer_read(self._h, _WHICH[which], C.c_void_p(flat.data_ptr()), self._floats, self._stream()))
-        return self._split(flat)
-
-    # -- running statistics -------------------------------------------------------
-    def epoch_stats(self, reset: bool = True) -> Dict[str, float]:
-        """Loss (mean over the labelled rows of the steps since the last reset, each step's loss taken before its update) and
-        accuracy of the epoch so far: ONE read. ``"windows"`` counts the labelled rows."""
-        s = self._epoch.cpu().numpy()
-        if reset:
-            self._epoch.zero_()
-        n = float(s[1])
-        return {"loss": float(s[0]) / n if n else float("nan"), "accuracy": float(s[2]) / n if n else float("nan"), "windows": int(n)}

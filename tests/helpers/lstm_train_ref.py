@@ -11,6 +11,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import lstm_head as LH
+from .adam_ref import adam_step_f64  # noqa: F401  (the tests reach it through this module)
 
 IGNORE = -100
 ROW_TOL = 2e-5    # fp32 rows against float64, relative to the tensor's largest entry (tests/test_head_train.py)
@@ -130,15 +131,6 @@ def train(dims, w, batches, lr, dtype=torch.float64, betas=(0.9, 0.999), eps=1e-
         losses.append(float(loss.detach()))
         traj.append([p.detach().numpy().copy() for p in net.ordered()])
     return losses, traj
-
-
-def adam_step_f64(w, m, v, g, k, lr, beta1, beta2, eps):
-    """One Adam step in float64 numpy on arrays of any shape (step number k = 1, 2, ...) -> (w, m, v)."""
-    w, m, v, g = (np.asarray(a, dtype=np.float64) for a in (w, m, v, g))
-    m = m + (g - m) * (1.0 - beta1)
-    v = beta2 * v + (1.0 - beta2) * g * g
-    w = w - (lr / (1.0 - beta1 ** k)) * m / (np.sqrt(v) / np.sqrt(1.0 - beta2 ** k) + eps)
-    return w, m, v
 
 
 TOY_LR = 1e-2

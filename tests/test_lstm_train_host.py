@@ -141,6 +141,46 @@ def test_lstm_trainer_host_validation():
             lt.check_step(shape, t, n, ll, 21, A, rows)
 
 
+def test_both_trainers_take_their_scaffolding_and_label_check_from_trainer_base():
+    """``HeadTrainer`` and ``LSTMTrainer`` define none of the shared scaffolding themselves -- it is ``AdamTrainer``'s --, their
+    modules hold no constants or label check of their own, and ``check_labels`` refuses through both entry points what the two
+    separate checks refused: a float array, a label of A, a label of -1; -100 passes."""
+    from playaid_core_amd import head_trainer as ht
+    from playaid_core_amd import lstm_trainer as lt
+    from playaid_core_amd import trainer_base as tb
+
+    shared = ("_raise", "_check", "_stream", "close", "__del__", "__enter__", "__exit__", "steps", "loss_of", "_split", "read", "epoch_stats",
+              "_count", "_begin", "_created")
+    for cls in (ht.HeadTrainer, lt.LSTMTrainer):
+        assert issubclass(cls, tb.AdamTrainer) and cls.PREFIX == f"pa_{'head' if cls is ht.HeadTrainer else 'lstm'}_trainer"
+        for name in shared:
+            assert name in vars(tb.AdamTrainer) and name not in vars(cls), (cls.__name__, name)
+        for name in ("__init__", "_run", "step", "grads"):
+            assert name in vars(cls), (cls.__name__, name)
+    assert "_inputs" in vars(ht.HeadTrainer) and "read_raw" in vars(ht.HeadTrainer)
+    assert ht.IGNORE is tb.IGNORE is lt.IGNORE and tb.IGNORE == -100 and ht._WHICH is tb._WHICH
+    assert ht.check_labels is tb.check_labels is lt.check_labels and lt.check_adam is tb.check_adam
+    assert "head_trainer" not in open(lt.__file__).read()
+    tb.check_adam(2e-4, (0.9, 0.999), 1e-8)
+    ht.check_adam(2e-4, (0.9, 0.999), 1e-8, 1)
+    for bad in ((0.0, (0.9, 0.999), 1e-8), (2e-4, (0.9, 1.0), 1e-8), (2e-4, (0.9, 0.999), float("inf"))):
+        for check in (tb.check_adam, lambda *a: ht.check_adam(*a, 64)):
+            with pytest.raises(ValueError):
+                check(*bad)
+
+    A, n = 5, 4
+    good = np.array([0, 4, tb.IGNORE, 2], np.int32)
+    g = np.arange(n * 3, dtype=np.int32).reshape(n, 3) % 10
+    entries = (lambda l: tb.check_labels(l, n, A), lambda l: ht.check_batch(g, l, 10, 3, A, 8), lambda l: lt.check_step((n, 1, 32), n, 1, l, 21, A, n))
+    for entry in entries:
+        for ok in (good, good.tolist(), torch.from_numpy(good), good.astype(np.int64), np.full(n, tb.IGNORE, np.int32)):
+            entry(ok)
+        for bad in (good.astype(np.float32), torch.from_numpy(good).double(), good.astype(bool), np.where(good == 4, A, good),
+                    np.where(good == 4, -1, good), np.where(good == 4, -99, good), good[:3]):
+            with pytest.raises(ValueError):
+                entry(bad)
+
+
 def test_reference_gradient_against_central_differences():
     """The helper's float64 autograd gradient, 20 entries per tensor, against (L(w + h) - L(w - h)) / 2h."""
     case = (R.SMALL, (8, 4))
