@@ -1137,6 +1137,75 @@ int pa_lstm_train_step(pa_lstm_trainer* t, const float* x, int32_t ld, int32_t s
 int pa_lstm_trainer_read(pa_lstm_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream);
 size_t pa_lstm_trainer_floats(const pa_lstm* h);
 
+/* ---- training the transformer-encoder head ------------------------------------ */
+
+/* Trains ResnetTransformerDetector's head -- resnet_ffn, every transformer layer's self_attn.in_proj / out_proj, linear1,
+ * linear2, norm1, norm2, and the classifier; the ResNet-50, freq_encoding and resnet_classifier stay as loaded -- on feature
+ * rows already computed (pa_convnet_forward), with the reference's loss and optimiser (resnet_transformer_detector.py:143-164,
+ * 207-209: F.nll_loss over every (window, frame) row in train mode, i.e. with the encoder layers' dropout; torch.optim.Adam with
+ * its default betas and eps). Append-only: PA_ABI_VERSION stays 15.
+ *
+ * The trainer borrows the pa_encoder handle's weights and updates them IN PLACE, where pa_encoder_forward reads them (PyTorch
+ * layouts: there is no other form, PA_TRAIN_RAW is refused); after an applied step the handle's zero-padded copy of the front
+ * projection is refreshed on the stream. It owns the two Adam moments and the saved activations, sized for the handle's
+ * max_rows; the handle's inference buffers are not touched. Destroy the trainer before the handle, and do not run a step
+ * concurrently with pa_encoder_forward on another stream.
+ *
+ * A handle is trainable when num_actions <= 64, ff_dim % 32 == 0 and max_rows >= slots (the 32-wide heads of every pa_encoder make
+ * hidden_dim + enc_dim a multiple of 32); anything else is refused at create with PA_ERR_INVALID_ARG and a message on the
+ * pa_encoder handle. pa_encoder_trainer_max_windows = min(64, max_rows / slots): the seq_len one step takes (the attention
+ * kernels hold one (slot, head)'s seq_len x seq_len block in a workgroup); more returns PA_ERR_CAPACITY with a message.
+ *
+ * pa_encoder_train_step, all pointers on the device: feats float32[seq_len * batch][ld] (in_dim used) as pa_encoder_forward
+ * takes them: seq_len windows (the attention's sequence) of batch = slots rows, row r = l * batch + n; labels int32[seq_len *
+ * batch] in [0, num_actions) or PA_EVAL_IGNORE (any other value is treated as PA_EVAL_IGNORE). With n = the number of labelled
+ * rows, loss = -(1/n) sum logp[r][labels[r]]; n == 0 divides by 1 (loss 0, all gradients 0) where torch gives NaN.
+ *   apply = 1: one optimiser step, as pa_head_train_step's; one step counter serves all tensors. grads_out may be NULL.
+ *   apply = 0: nothing changes; grads_out receives the gradients, concatenated, in the blob's order without freq_encoding and in
+ *              PyTorch layouts: resnet_ffn.weight [hidden][in], .bias [hidden]; per layer in_proj_weight [3D][D], in_proj_bias
+ *              [3D], out_proj.weight [D][D], .bias [D], linear1.weight [ff][D], .bias [ff], linear2.weight [D][ff], .bias [D],
+ *              norm1.weight, .bias, norm2.weight, .bias [D]; classifier.weight [A][D], .bias [A]
+ *              (pa_encoder_trainer_floats floats). pa_encoder_trainer_read uses the same order.
+ * stats_dev (may be NULL) receives the step's pa_train_stats: the loss BEFORE the update, the labelled rows and how many of
+ * them the model got right (first maximum). Enqueue only: stream-ordered, nothing is read back, no kernel waits for another
+ * workgroup, every sum has a fixed order and there are no floating-point atomics: the same calls give the same bits.
+ *
+ * Dropout (`dropout` = p in [0, 1), `seed`): four sites per layer, each element kept with probability 1 - p and scaled by
+ * 1 / (1 - p) (fp32: 1.f / (1.f - p)), the same mask in the forward and the backward pass:
+ *   site 0  the attention probabilities, element index i in torch's layout [batch * heads][seq_len][seq_len]
+ *   site 1  the attention block's output before the residual, [rows][D]
+ *   site 2  the feed-forward activation after the ReLU, [rows][ff]
+ *   site 3  the feed-forward output before the residual, [rows][D]
+ * keep(seed, step, layer, site, i), all arithmetic on uint32 (wrapping), step = pa_encoder_trainer_steps before the call (so
+ * an apply = 0 call and the apply = 1 call behind it see the same masks):
+ *   mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16;  return x
+ *   key = mix((uint32)seed + 0x9e3779b9)
+ *   key = mix(key ^ (uint32)(seed >> 32))
+ *   key = mix(key ^ (uint32)step)
+ *   key = mix(key ^ (uint32)((uint64)step >> 32))
+ *   key = mix(key ^ ((uint32)(layer * 4 + site + 1) * 0x85ebca6b))
+ *   r   = mix(mix((uint32)i ^ key) + key)
+ *   keep = r >= thr,  thr = (uint32)(uint64)((double)p * 4294967296.0)   (p the float handed to create)
+ * It does not depend on the launch geometry; encoder_trainer.dropout_keep is its numpy twin. With p = 0 nothing is generated.
+ *
+ * pa_encoder_trainer_read copies one set (PA_TRAIN_WEIGHTS, PA_TRAIN_M, PA_TRAIN_V) to out_dev in the order above; floats must
+ * be pa_encoder_trainer_floats(handle). Enqueue only.
+ *
+ * PA_ERR_INVALID_ARG before any device call: null handle or pointers, seq_len < 1, batch != slots, ld < in_dim, apply outside
+ * {0, 1}, apply = 0 without grads_out, lr or eps not finite or <= 0, a beta outside [0, 1), dropout outside [0, 1), a handle that
+ * is not trainable, PA_TRAIN_RAW. A create that stops at the device (PA_ERR_NO_DEVICE / PA_ERR_HIP) still hands the trainer
+ * back, to be destroyed by the caller. */
+typedef struct pa_encoder_trainer pa_encoder_trainer;
+int pa_encoder_trainer_create(pa_encoder* h, const pa_adam_config* cfg, float dropout, uint64_t seed, pa_encoder_trainer** out);
+void pa_encoder_trainer_destroy(pa_encoder_trainer* t);
+const char* pa_encoder_trainer_last_error(const pa_encoder_trainer* t);
+int64_t pa_encoder_trainer_steps(const pa_encoder_trainer* t);
+int pa_encoder_train_step(pa_encoder_trainer* t, const float* feats, int32_t ld, int32_t seq_len, int32_t batch, const int32_t* labels,
+                          int32_t apply, float* grads_out, pa_train_stats* stats_dev, void* stream);
+int pa_encoder_trainer_read(pa_encoder_trainer* t, int32_t which, float* out_dev, size_t floats, void* stream);
+size_t pa_encoder_trainer_floats(const pa_encoder* h);
+int32_t pa_encoder_trainer_max_windows(const pa_encoder* h);
+
 #ifdef __cplusplus
 }
 #endif

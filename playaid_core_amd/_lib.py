@@ -287,6 +287,14 @@ SYMBOLS = [
     ("pa_lstm_train_step", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("pa_lstm_trainer_read", C.c_int, [_P, C.c_int32, _P, C.c_size_t, _P]),
     ("pa_lstm_trainer_floats", C.c_size_t, [_P]),
+    ("pa_encoder_trainer_create", C.c_int, [_P, C.POINTER(pa_adam_config), C.c_float, C.c_uint64, C.POINTER(_P)]),
+    ("pa_encoder_trainer_destroy", None, [_P]),
+    ("pa_encoder_trainer_last_error", C.c_char_p, [_P]),
+    ("pa_encoder_trainer_steps", C.c_int64, [_P]),
+    ("pa_encoder_train_step", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    ("pa_encoder_trainer_read", C.c_int, [_P, C.c_int32, _P, C.c_size_t, _P]),
+    ("pa_encoder_trainer_floats", C.c_size_t, [_P]),
+    ("pa_encoder_trainer_max_windows", C.c_int32, [_P]),
 ]
 
 _lib = None

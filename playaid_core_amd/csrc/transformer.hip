@@ -11,6 +11,7 @@
 // Side path (tens of rows): dense layers on the shared vector-unit linear kernel (lstm.hip), one wave per
 // (slot, head) for the attention with an online softmax, one wave per row for LayerNorm. All fp32.
 #include "pa_kernels.h"
+#include "encoder_handle.h"
 #include "../../include/playaid_hip.h"
 #include <cmath>
 #include <cstring>
@@ -104,27 +105,7 @@ __global__ __launch_bounds__(64) void log_softmax_rows_kernel(float* __restrict_
 }  // namespace
 }  // namespace pa
 
-struct pa_encoder {
-    int in_dim = 0, hidden = 0, slots = 0, enc_dim = 0, heads = 0, layers = 0, ff = 0, actions = 0, max_rows = 0, D = 0;
-    float* weights = nullptr;
-    float *ffn_w = nullptr, *ffn_b = nullptr, *enc = nullptr, *cls_w = nullptr, *cls_b = nullptr;
-    float* ffn_pad = nullptr;  // [D][in_dim] + [D]: the front projection with zero rows for the encoding's columns, so that its
-                               // N is whole matrix tiles (247 -> 256) and it runs on the MFMA kernel; append_encoding overwrites them
-    struct Layer { float *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_g, *n1_b, *n2_g, *n2_b; };
-    std::vector<Layer> layer;
-    float *x = nullptr, *qkv = nullptr, *att = nullptr, *y = nullptr, *f1 = nullptr;
-    std::string last_error;
-};
-
-namespace {
-size_t encoder_float_count(int in_dim, int hidden, int slots, int enc_dim, int layers, int ff, int actions) {
-    const size_t D = (size_t)hidden + enc_dim;
-    size_t n = (size_t)hidden * in_dim + hidden + (size_t)slots * enc_dim;
-    n += (size_t)layers * (3 * D * D + 3 * D + D * D + D + (size_t)ff * D + ff + D * ff + D + 4 * D);
-    n += (size_t)actions * D + actions;
-    return n;
-}
-}  // namespace
+using pa::encoder_float_count;
 
 extern "C" {
 
@@ -152,7 +133,7 @@ int pa_encoder_create(int32_t device, int32_t in_dim, int32_t hidden_dim, int32_
     pa_encoder* h = new pa_encoder();
     *out = h;
     h->in_dim = in_dim; h->hidden = hidden_dim; h->slots = slots; h->enc_dim = enc_dim; h->heads = num_heads; h->layers = num_layers;
-    h->ff = ff_dim; h->actions = num_actions; h->max_rows = max_rows; h->D = D;
+    h->ff = ff_dim; h->actions = num_actions; h->max_rows = max_rows; h->D = D; h->device = device;
     auto chk = [&](hipError_t e, const char* what) -> bool {
         if (e == hipSuccess) return true;
         h->last_error = std::string(what) + ": " + hipGetErrorString(e);

@@ -18,7 +18,17 @@ Scoring is mirrored (``validation_step`` / ``test_step``, ``:179-205``): this mo
 and ``action_label`` to ``B * S`` rows and scores every one of them (not the centre label the CNN model scores) -- NLL loss and
 multiclass top-1 accuracy, accumulated on the device (``metrics.EvalState``) with nothing read back per step;
 ``metrics(split)`` is the one read (``val_action_loss``, ``val_action_acc``, ... plus confusion matrix and mean confidence),
-``reset_metrics(split)`` clears a split. Not mirrored: ``training_step``, the optimiser and the data hooks (``:143-177,207-260``).
+``reset_metrics(split)`` clears a split.
+
+Training is mirrored for the encoder head with the ResNet-50 frozen (``freeze_encoder=True``; ``encoder_trainer.EncoderTrainer``,
+csrc/encoder_train.hip): ``train()``, ``configure_optimizers()`` (the reference's ``torch.optim.Adam(lr=self.learning_rate)``,
+``:207-209``), ``training_step`` (``:143-164``: NLL over every row against ``action_label`` flattened to ``B * S``, with the encoder
+layers' dropout), ``state_dict()`` and ``save_checkpoint()``. ``model.resnet.*`` stays as loaded and runs on the inference kernels
+with eval-mode BatchNorm; ``model.freq_encoding`` is a buffer and ``model.resnet_classifier.*`` (never used by the reference's
+forward) passes through. The reference ignores ``freeze_encoder`` for this model and trains the ResNet-50 too: here it is the
+explicit opt-in and the only form that trains. ``model(x)`` stays the inference path, without dropout, also while
+``model.training`` is set. Not mirrored: training the ResNet-50 and its BatchNorm statistics, and the data hooks
+(``:166-177, 211-260``).
 
 ``compute_dtype="bf16"`` (never the default) runs the ResNet-50 with bf16 storage and bf16 products: the stem on
 ``stem_pool_kernel``'s bf16 form, every convolution on the one-slice bf16 GEMM (``csrc/bgemm.hip``, split-K on the small maps),
@@ -336,7 +346,10 @@ class ResnetTransformerDetector:
         self.learning_rate = learning_rate
         self.num_samples = num_samples
         self.dataset_kwargs = kwargs
+        self.freeze_encoder = bool(freeze_encoder)
         self.training = False
+        self._trainer = None
+        self._state_dict = {k: v for k, v in state_dict.items()}   # (model.resnet.* as loaded: state_dict() hands it back)
         self.max_rows = max_rows
         # (crop_size: the reference's dataset argument -- its driver feeds this model 256 x 256 crops; a multiple of 32 in 64..512)
         self.crop_size = check_crop_size(crop_size)
@@ -378,11 +391,66 @@ class ResnetTransformerDetector:
         return self
 
     def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("training is out of scope for the MI355X inference path")
+        if mode and not self.freeze_encoder:
+            raise NotImplementedError("only the encoder head trains: build the model with freeze_encoder=True")
+        self.training = bool(mode)
         return self
 
+    # -- training (resnet_transformer_detector.py:143-164, 207-209; the ResNet-50 frozen) -------------
+    def configure_optimizers(self):
+        """The reference's ``torch.optim.Adam(self.parameters(), lr=self.learning_rate)`` for what trains here: the one
+        ``EncoderTrainer`` on this model's handle (made once; it owns the Adam moments and the running epoch statistics).
+        ``dropout=`` and ``seed=`` among the model's keyword arguments are the trainer's (0.1 and 0 by default)."""
+        if not self.freeze_encoder:
+            raise NotImplementedError("only the encoder head trains: build the model with freeze_encoder=True")
+        if self._trainer is None:
+            from .encoder_trainer import EncoderTrainer
+
+            self._trainer = EncoderTrainer(self, lr=self.learning_rate, dropout=self.dataset_kwargs.get("dropout", 0.1),
+                                           seed=self.dataset_kwargs.get("seed", 0))
+        return self._trainer
+
+    def training_step(self, batch, batch_idx):
+        """``batch = (input [B,S,3,C,C], char_label, action_label [B,S], ...)``: the ResNet-50 features of every frame, then one
+        ``pa_encoder_train_step`` with ``seq_len = B`` windows of ``batch = S`` slots and ``action_label.view(B * S)`` (``-100`` =
+        no ground truth). -> the loss before the update, a 0-dim float32 device tensor; nothing waits."""
+        if not self.training:
+            raise RuntimeError("training_step in eval mode: call train() first")
+        input, action_label = batch[0], batch[2]
+        c = self.crop_size
+        if input.dim() != 5 or tuple(input.shape[2:]) != (3, c, c) or input.shape[1] != self.sequence_length:
+            raise ValueError(f"expected [B,{self.sequence_length},3,{c},{c}], got {tuple(input.shape)}")
+        b, s = int(input.shape[0]), int(input.shape[1])
+        if b * s > self.max_rows:
+            raise ValueError(f"{b} x {s} rows exceed max_rows={self.max_rows}")
+        trainer = self.configure_optimizers()
+        feats = self._net.forward(input.reshape(b * s, 3, c, c))
+        labels = action_label.reshape(b * s) if isinstance(action_label, torch.Tensor) else np.asarray(action_label).reshape(b * s)
+        stats = trainer.step(feats, b, s, labels)
+        return trainer.loss_of(stats)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The key set the model was built from: ``model.resnet.*``, ``model.freq_encoding`` (and anything else it carried, such
+        as ``model.resnet_classifier.*``) as loaded, the trained tensors as they are on the device now (CPU tensors; waits for
+        the read when a trainer exists)."""
+        out = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v))) for k, v in self._state_dict.items()}
+        if self._trainer is not None:
+            for k, v in self._trainer.read("weights").items():
+                out[k] = v.cpu()
+        return out
+
+    def save_checkpoint(self, path: str):
+        """A Lightning-shaped ``.ckpt`` (``state_dict`` + ``hyper_parameters``) that ``load_from_checkpoint`` reads back."""
+        hparams = dict(actions=list(self.actions), batch_size=self.batch_size, sequence_length=self.sequence_length,
+                       learning_rate=self.learning_rate, num_samples=self.num_samples, freeze_encoder=self.freeze_encoder,
+                       crop_size=self.crop_size)
+        hparams.update(self.dataset_kwargs)
+        torch.save({"state_dict": self.state_dict(), "hyper_parameters": hparams}, path)
+
     def close(self):
+        if getattr(self, "_trainer", None) is not None:
+            self._trainer.close()   # (before the handle whose weights it borrows)
+            self._trainer = None
         if getattr(self, "_h", None):
             self._lib.pa_encoder_destroy(self._h)
             self._h = None
