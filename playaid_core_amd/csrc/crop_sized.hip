@@ -40,6 +40,7 @@ __global__ __launch_bounds__(256) void crop_sized_plan_kernel(const PreprocParam
         pl.iscale_x = pl.iscale_y = 1;
         pl.fused_rb = 0;
         pl.mfma_v = 0;
+        pl.mfma_h = pl.h_mis = 0;
         pl.coef_h = pl.coef_v = nullptr;
         pl.scale_x = pl.scale_y = 1.0;
         const double* b = p.boxes + (size_t)crop * 4;

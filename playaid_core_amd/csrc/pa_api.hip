@@ -138,6 +138,7 @@ struct pa_engine {
     int32_t* coef_cache = nullptr;  // Pillow tables of the passes (2 * (d / 2) + 2 * padding -> d), built for one padding at a time
     int coef_cache_pad = -1, coef_cache_dmax = 0;
     AreaTabPacked* area_tabs = nullptr;
+    uint8_t* hop = nullptr;  // the horizontal matrix form's operands: [max crops][PA_HOP_BLOCKS_MAX][PA_HOP_BLOCK_BYTES]
     uint8_t *t1 = nullptr, *t2 = nullptr;
     size_t t_stride = 0;
     int32_t* status_tmp = nullptr;
@@ -767,6 +768,7 @@ int run_preprocess(pa_engine* e, const uint8_t* frames, int n, int height, int w
     p.coef_cache_pad = padding;
     p.coef_cache_dmax = e->coef_cache_dmax;
     p.area_tabs = e->area_tabs;
+    p.hop = e->hop;
     p.t1 = e->t1;
     p.t2 = e->t2;
     p.t_stride = e->t_stride;
@@ -1227,6 +1229,7 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     e->coef_cache_pad = 30;  // the one padding the reference's runner passes (ai_runner.py:418)
     HIPCHK(e, launch_build_coef_cache(e->coef_cache, e->coef_cache_pad, e->coef_cache_dmax, nullptr));
     ALLOC(e->area_tabs, (size_t)NC * 2 * PA_CROP, true);
+    ALLOC(e->hop, (size_t)NC * PA_HOP_BLOCKS_MAX * PA_HOP_BLOCK_BYTES, true);  // 302 KB a crop
     ALLOC(e->t1, (size_t)NC * e->t_stride, false);
     ALLOC(e->t2, (size_t)NC * e->t_stride, false);
 #undef ALLOC

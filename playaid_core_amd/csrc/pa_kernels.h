@@ -226,6 +226,10 @@ struct CropPlan {
     int32_t iscale_x, iscale_y;
     int32_t fused_rb;          // output rows per LDS sub-band of the fused kernel (8/4/2/1), 0 = multi-kernel fallback
     int32_t mfma_v;            // the fused kernel's vertical pass runs on the int8 matrix instruction (B1 transposed in LDS)
+    // the horizontal pass runs on it as well (only with mfma_v), from the crop's operand in PreprocParams::hop. 1: B0 is
+    // staged as the frame's aligned dwords and the operand's tap positions carry the slice's byte misalignment h_mis;
+    // 2 (PA_CROP_MFMA_H=2, the A/B row of the staging alone): B0 is staged re-aligned as for the vector form, h_mis = 0
+    int32_t mfma_h, h_mis;
     double scale_x, scale_y;
     // Pillow coefficient tables of the two bicubic passes ([out][2 + PA_KSIZE_MAX]): the engine's cache of the
     // (2 * (d / 2) + 2 * padding -> d) pairs, or this crop's own rows of PreprocParams::coef for any other pair
@@ -238,6 +242,16 @@ struct AreaTabPacked {
     uint32_t bits;  // s_first | n_mid << 16 | has_first << 24 | has_last << 25
     float a_first, a_mid, a_last;
 };
+
+// The horizontal matrix form's operand (crop_hop_kernel -> crop_fused_kernel): per crop PA_HOP_BLOCKS_MAX blocks of 10
+// output pixels (30 byte columns of the 32 the instruction has), PA_HOP_BLOCK_BYTES each: six 1 KB fragments -- digit
+// plane 2, 1, 0 x the two 32-byte halves of the block's 64-byte input window, lane l's 16 bytes at 16 l -- then the 32
+// columns' constants 2^21 + 128 sum(k), then the window's first byte inside the staged row (a multiple of 4).
+#define PA_HOP_BLOCKS_MAX 48
+#define PA_HOP_PIXELS 10
+#define PA_HOP_WINDOW 64
+#define PA_HOP_BLOCK_BYTES (6 * 1024 + 32 * 4 + 16)
+#define PA_CROP_MFMA_H_DEFAULT 1  // PA_CROP_MFMA_H when the environment does not set it
 
 struct CropWindow {  // == pa_crop_window of the public header
     int64_t offset;      // first byte of the crop's slice inside the window buffer
@@ -274,7 +288,10 @@ struct PreprocParams {
     int32_t* fallback_list;   // [ncrops] their indices
     int32_t fused_lds;      // LDS budget of the fused kernel (set by the launcher; 0 forces the fallback)
     int32_t ablate;         // timing experiments: skip stages of the fused kernel (results wrong when != 0)
-    int32_t crop_mfma;      // PA_CROP_MFMA (default 1; set by the launcher): 0 keeps every vertical pass on the vector ALU
+    int32_t crop_mfma;      // PA_CROP_MFMA (default 1; set by the launcher): 0 keeps both bicubic passes on the vector ALU
+    int32_t crop_mfma_h;    // PA_CROP_MFMA_H (set by the launcher): 0 keeps the horizontal pass and today's staging; 1; 2 (CropPlan::mfma_h)
+    int32_t crop_xcd;       // PA_CROP_XCD (default 1; set by the launcher): a crop's 16 workgroups run on one XCD
+    uint8_t* hop;           // [ncrops][PA_HOP_BLOCKS_MAX][PA_HOP_BLOCK_BYTES] or nullptr (no horizontal matrix form)
     uint8_t* dbg;           // debug builds only (PA_DEBUG_DUMP)
     int32_t dbg_crop, dbg_row;
 };

@@ -20,8 +20,8 @@
 // and add like OpenCV's generic C++ -- a fused multiply-add would change bits.
 //
 // The stage is HBM/L2 streaming work: one thread per output
-// element, consecutive lanes on consecutive bytes (the one matrix shape in it is the fused
-// kernel's vertical bicubic pass, on the int8 matrix instruction). Five small kernels keep every
+// element, consecutive lanes on consecutive bytes (the matrix shapes in it are the fused
+// kernel's two bicubic passes, on the int8 matrix instruction). Five small kernels keep every
 // size general (any box, any frame): a fused LDS kernel for crops whose bands fit 48 KB,
 // a multi-pass fallback over global scratch for the rest.
 #include "crop_common.h"
@@ -108,6 +108,9 @@ constexpr int CF_MFMA_N = 32, CF_MFMA_K = 32;
 __device__ __forceinline__ BandLds band_lds(const CropPlan& pl, const BandRows& b) {
     BandLds l;
     l.p0 = align_up(pl.sw * 3, 4) + 4;
+    // matrix-form horizontal pass: a row holds the slice's bytes behind their misalignment (aligned staging), and the
+    // pitch is an odd number of dwords -- the pass's 32 lanes of a half read the same dwords of 32 rows, on 32 banks
+    if (pl.mfma_h) l.p0 = align_up(pl.h_mis + pl.sw * 3, 4) | 4;
     l.p1 = align_up(pl.rw * 3, 4) + 4;
     l.pt = l.skew = l.offc = 0;
     const int n0 = b.ty1 - b.ty0, n2 = b.ry1 - b.ry0;
@@ -170,6 +173,7 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
     pl.iscale_x = pl.iscale_y = 1;
     pl.fused_rb = 0;
     pl.mfma_v = 0;
+    pl.mfma_h = pl.h_mis = 0;
     pl.coef_h = pl.coef_v = nullptr;
     pl.scale_x = pl.scale_y = 1.0;
     const double* b = p.boxes + (size_t)crop * 4;
@@ -273,11 +277,36 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
         // transposed B1 and operand space do not fit, the vector form at the same height comes before a lower height.
         // (not under the timing ablations of either pass: a skipped pass leaves the other with the wrong layout of B1)
         const int mfma_ok = p.crop_mfma && pl.need_h && pl.need_v && pl.ksize_v <= 7 && !(p.ablate & 6);
+        // The horizontal pass takes the matrix form too (tried first, m == 2) where its filter has <= 7 taps, the slice's rows
+        // share one byte misalignment (row pitch a multiple of 4), the crop's blocks of PA_HOP_PIXELS output pixels fit the
+        // operand scratch, and the taps of every block -- THIS pass's own bounds, clipped slices included -- lie within the
+        // PA_HOP_WINDOW bytes behind the aligned dword that holds the block's first tap (lane = block).
+        int h_mode = 0, h_mis = 0;
+        if (mfma_ok && p.crop_mfma_h && p.hop && pl.ksize_h <= 7) {
+            size_t pitch;
+            const uint8_t* sp = slice_ptr(p, crop, pl, &pitch);
+            const int nb = (pl.rw + PA_HOP_PIXELS - 1) / PA_HOP_PIXELS;
+            if ((pitch & 3) == 0 && nb <= PA_HOP_BLOCKS_MAX) {
+                h_mode = p.crop_mfma_h == 2 ? 2 : 1;
+                h_mis = h_mode == 2 ? 0 : (int)((uintptr_t)sp & 3);
+                int fit = 1;
+                if (lane < nb) {
+                    const int x0 = lane * PA_HOP_PIXELS, x1 = x0 + PA_HOP_PIXELS - 1 < pl.rw - 1 ? x0 + PA_HOP_PIXELS - 1 : pl.rw - 1;
+                    int lo, cnt, lo1, cnt1;
+                    bicubic_bounds(pl.sw, pl.rw, x0, &lo, &cnt);
+                    bicubic_bounds(pl.sw, pl.rw, x1, &lo1, &cnt1);  // (first tap and end are monotone in the output coordinate)
+                    fit = ((h_mis + 3 * lo) & 3) + 3 * (lo1 + cnt1 - lo) <= PA_HOP_WINDOW;
+                }
+                if (__ballot(!fit) != 0ull) h_mode = 0;
+            }
+        }
 #pragma unroll 1
         for (int rb = 8; rb >= 1 && pl.fused_rb == 0; rb >>= 1) {
 #pragma unroll 1
-            for (int m = mfma_ok; m >= 0 && pl.fused_rb == 0; --m) {
-                pl.mfma_v = m;
+            for (int m = mfma_ok ? (h_mode ? 2 : 1) : 0; m >= 0 && pl.fused_rb == 0; --m) {
+                pl.mfma_v = m >= 1;
+                pl.mfma_h = m == 2 ? h_mode : 0;
+                pl.h_mis = m == 2 ? h_mis : 0;
                 int worst = 0;
 #pragma unroll 1
                 for (int r0 = lane * rb; r0 < PA_CROP; r0 += 64 * rb) {
@@ -294,7 +323,7 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
                 if (worst <= p.fused_lds) pl.fused_rb = rb;
             }
         }
-        if (pl.fused_rb == 0) pl.mfma_v = 0;
+        if (pl.fused_rb == 0) pl.mfma_v = pl.mfma_h = pl.h_mis = 0;
     }
     if (lane == 0) {
         if (pl.status == PA_CROP_OK && pl.fused_rb == 0) {
@@ -344,6 +373,75 @@ __global__ __launch_bounds__(256) void coef_cache_kernel(int32_t* __restrict__ c
     const int d = blockIdx.y + 1, xx = blockIdx.x * 256 + threadIdx.x;
     if (d > dmax || xx >= d) return;
     bicubic_coef_row(2 * (d / 2) + 2 * padding, d, xx, cache + ((size_t)d * (d - 1) / 2 + xx) * COEF_ROW);
+}
+
+// The horizontal matrix form's operand, once per crop (CropPlan::mfma_h) and call, block by block of PA_HOP_PIXELS
+// output pixels. The pass computes B1[source row][output byte column] from the block's PA_HOP_WINDOW-byte window of the
+// staged row as int8 products with this [window byte][column] matrix of coefficient digits -- non-zero only at the
+// <= 7 taps x 3 channels of a column, at window byte s + 3 * (tap pixel - first pixel of the block) + channel, where s is
+// the first tap's byte offset inside its aligned dword (slice misalignment included). Zero-fill, then scatter the digits
+// in fragment order (pa_kernels.h: PA_HOP_BLOCK_BYTES), so that a wave of the pass loads a fragment as one 1 KB read.
+// A workgroup builds PA_HOP_WG_BLOCKS neighbouring blocks, so that the loads of their taps are in flight together and the
+// crops of a clip take one round of workgroups.
+constexpr int PA_HOP_WG_BLOCKS = 4;
+__global__ __launch_bounds__(256) void crop_hop_kernel(const PreprocParams p) {
+    const int crop = blockIdx.y, blk0 = blockIdx.x * PA_HOP_WG_BLOCKS, tid = threadIdx.x;
+    const CropPlan* plp = p.plans + crop;
+    if (plp->status != PA_CROP_OK || !plp->mfma_h) return;
+    const int rw = plp->rw, h_mis = plp->h_mis;
+    int nblk = (rw + PA_HOP_PIXELS - 1) / PA_HOP_PIXELS;
+    nblk = nblk < PA_HOP_BLOCKS_MAX ? nblk : PA_HOP_BLOCKS_MAX;  // (the plan's own condition: never write outside the crop's operand)
+    const int here = nblk - blk0 < PA_HOP_WG_BLOCKS ? nblk - blk0 : PA_HOP_WG_BLOCKS;
+    if (here <= 0) return;
+    const int32_t* coef = plp->coef_h;
+    uint8_t* ob0 = p.hop + ((size_t)crop * PA_HOP_BLOCKS_MAX + blk0) * PA_HOP_BLOCK_BYTES;
+    for (int i = tid; i < here * (6 * 1024 / 16); i += 256) {
+        const int u = i / (6 * 1024 / 16), j = i - u * (6 * 1024 / 16);
+        reinterpret_cast<uint4*>(ob0 + (size_t)u * PA_HOP_BLOCK_BYTES)[j] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (tid < here * 33) {  // the blocks' tails: 32 constants and the window base each
+        const int u = tid / 33, e = tid - u * 33, x0 = (blk0 + u) * PA_HOP_PIXELS;
+        int v = 0;
+        if (e == 32) {
+            v = (h_mis + 3 * coef[(size_t)x0 * COEF_ROW]) & ~3;
+        } else if (e < 3 * PA_HOP_PIXELS && x0 + e / 3 < rw) {
+            const int32_t* row = coef + (size_t)(x0 + e / 3) * COEF_ROW;
+            const int cnt = row[1];
+            int ksum = 0;
+            for (int t = 0; t < 7; ++t) ksum += t < cnt ? row[2 + t] : 0;
+            v = 128 * ksum + (1 << (PRECISION_BITS - 1));
+        }
+        reinterpret_cast<int32_t*>(ob0 + (size_t)u * PA_HOP_BLOCK_BYTES + 6 * 1024)[e] = v;
+    }
+    // thread = (output byte column, tap) of every block of the workgroup: all loads first
+    const int n = tid >> 3, t = tid & 7;
+    const int px = n / 3, c = n - 3 * px;
+    int xmin0[PA_HOP_WG_BLOCKS], xmin[PA_HOP_WG_BLOCKS], cnt[PA_HOP_WG_BLOCKS], k[PA_HOP_WG_BLOCKS];
+#pragma unroll
+    for (int u = 0; u < PA_HOP_WG_BLOCKS; ++u) {
+        const int x0 = (blk0 + u) * PA_HOP_PIXELS, xx = x0 + px;
+        const bool on = u < here && n < 3 * PA_HOP_PIXELS && xx < rw && t < 7;
+        const int32_t* row = coef + (size_t)(on ? xx : 0) * COEF_ROW;
+        xmin0[u] = coef[(size_t)(on ? x0 : 0) * COEF_ROW];
+        xmin[u] = row[0];
+        cnt[u] = on ? row[1] : 0;
+        k[u] = row[2 + (t < 7 ? t : 0)];
+    }
+    __syncthreads();  // the zeros are in place before the digits
+#pragma unroll
+    for (int u = 0; u < PA_HOP_WG_BLOCKS; ++u) {
+        const int first = h_mis + 3 * xmin0[u];
+        const int kidx = (first & 3) + 3 * (xmin[u] + t - xmin0[u]) + c;
+        if (t < cnt[u] && kidx >= 0 && kidx < PA_HOP_WINDOW) {  // (the plan checked the window; never write outside the block)
+            const int d0 = (int)(int8_t)(k[u] & 0xff), k1 = (k[u] - d0) >> 8;
+            const int d1 = (int)(int8_t)(k1 & 0xff), d2 = (k1 - d1) >> 8;
+            // fragment (digit, half window): lane = (window byte's 16-byte quarter & 1) * 32 + column, its byte kidx & 15
+            uint8_t* o = ob0 + (size_t)u * PA_HOP_BLOCK_BYTES + (kidx >> 5) * 1024 + (((kidx >> 4) & 1) * 32 + n) * 16 + (kidx & 15);
+            o[0 * 2048] = (uint8_t)d2;
+            o[1 * 2048] = (uint8_t)d1;
+            o[2 * 2048] = (uint8_t)d0;
+        }
+    }
 }
 
 // Four clip8 as one dword, bytes in argument order: v_ashr_pk_u8_i32 shifts two int32 right, saturates each to 0..255 and
@@ -480,9 +578,9 @@ __device__ void fallback_area(const PreprocParams& p, int crop, const CropPlan& 
 }
 
 // Runs as the LAST row of crop_fused_kernel's grid (blockIdx.y == number of crops): no launch of its own.
-__device__ void crop_fallback_body(const PreprocParams& p) {
+__device__ void crop_fallback_body(const PreprocParams& p, int band) {
     const int count = *p.fallback_count;
-    for (int fb = blockIdx.x; fb < count; fb += gridDim.x) {
+    for (int fb = band; fb < count; fb += gridDim.x) {
         const int crop = p.fallback_list[fb];
         const CropPlan pl = p.plans[crop];
         fallback_h(p, crop, pl);
@@ -515,6 +613,8 @@ __device__ void crop_fallback_body(const PreprocParams& p) {
 //   stage V  Pillow vertical pass B1 -> B2 (thread = 4 output bytes: one
 //            ds_read_b32 per tap row feeds four accumulators)
 //   stage A  INTER_AREA from B2 (black outside the paste) -> u8 crop + fp32 input
+// With CropPlan::mfma_v / mfma_h stages V / H run on the int8 matrix instruction instead; with mfma_h
+// stage 0 copies the frame's aligned dwords as they are.
 // The frame is read from HBM exactly once (about 0.42 MB per crop at 1080p).
 extern __shared__ __attribute__((aligned(16))) uint8_t pa_smem[];
 
@@ -535,6 +635,12 @@ struct LdsCanvas {
     }
 };
 
+__device__ __forceinline__ const int32_t* uniform_ptr(const int32_t* q) {
+    const uintptr_t v = (uintptr_t)q;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return reinterpret_cast<const int32_t*>(((uintptr_t)hi << 32) | lo);
+}
+
 constexpr int CF_NT = 512;         // threads of a crop_fused_kernel workgroup
 constexpr int CF_NW = CF_NT / 64;   // its waves
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -543,12 +649,21 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
 #ifdef PA_STAMP_BUILD
     const unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    const int crop = blockIdx.y;
+    // Workgroups are handed to the 8 XCDs round robin in launch order. PreprocParams::crop_xcd: of every 128 consecutive
+    // workgroups (8 rows of the grid), the 16 that one XCD gets are the 16 bands of ONE row, so a crop's operand of the
+    // horizontal matrix form is fetched into one XCD's L2, not into all eight. The rows behind the last whole group of 8
+    // (the fallback row among them) keep the grid's own order.
+    int crop = blockIdx.y, band = blockIdx.x;
+    if (p.crop_xcd && (int)blockIdx.y < (int)(gridDim.y & ~7u)) {
+        const int l = (blockIdx.y & 7) * 16 + blockIdx.x;  // gridDim.x == 16
+        crop = (blockIdx.y & ~7) + (l & 7);
+        band = l >> 3;
+    }
     if (crop == p.n_frames * p.fighters) {  // the grid's extra row: crops whose bands do not fit the LDS budget
-        crop_fallback_body(p);
+        crop_fallback_body(p, band);
         return;
     }
-    const int band0 = blockIdx.x * 8;  // first of this workgroup's 8 output rows
+    const int band0 = band * 8;  // first of this workgroup's 8 output rows
     const int tid = threadIdx.x;
     const CropPlan pl = p.plans[crop];
     if (pl.status != PA_CROP_OK) {
@@ -559,8 +674,10 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
     if (!pl.fused_rb) return;
     size_t frame_pitch;
     const uint8_t* slice = slice_ptr(p, crop, pl, &frame_pitch);
-    const int32_t* coef_h = pl.coef_h;
-    const int32_t* coef_v = pl.coef_v;
+    // (the plan arrives through vector loads; the two table addresses are the same in every lane and are used in every
+    // stage, so they are moved to scalar registers -- as a lane's pair of vector registers one of them went to scratch)
+    const int32_t* coef_h = uniform_ptr(pl.coef_h);
+    const int32_t* coef_v = uniform_ptr(pl.coef_v);
     const int rb = pl.fused_rb;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -580,7 +697,30 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
         // ---- stage 0: slice rows -> B0 (aligned dwords) ----------------------
         // wave w takes rows w, w+4, ...; its lanes take consecutive dwords of the row, four
         // independent 256-byte segments in flight per iteration (the loop is latency-bound).
-        if (!(p.ablate & 1)) {
+        if (pl.mfma_h == 1 && !(p.ablate & 1)) {
+            // matrix-form horizontal pass: the frame's own aligned dwords, one load each -- the rows share the
+            // misalignment h_mis (row pitch a multiple of 4) and the pass's operand places its taps behind it. The first
+            // and last dword of a row are whole dwords that hold a byte of the slice, so they lie inside the frame buffer.
+            const int row_dwords = (pl.h_mis + pl.sw * 3 + 3) >> 2;
+            for (int y = wave; y < n0; y += CF_NW) {
+                const uintptr_t ga = (uintptr_t)(slice + (size_t)(b.ty0 + y) * frame_pitch);
+                const uint32_t* g4 = reinterpret_cast<const uint32_t*>(ga & ~(uintptr_t)3);
+                uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + y * L.p0);
+                for (int j0 = 0; j0 < row_dwords; j0 += 256) {
+                    uint32_t v[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int j = j0 + lane + 64 * u;
+                        v[u] = j < row_dwords ? g4[j] : 0u;
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int j = j0 + lane + 64 * u;
+                        if (j < row_dwords) dst[j] = v[u];
+                    }
+                }
+            }
+        } else if (!(p.ablate & 1)) {
             const int row_dwords = (pl.sw * 3 + 3) >> 2;
             const int row_bytes = pl.sw * 3;
             for (int y = wave; y < n0; y += CF_NW) {
@@ -620,7 +760,7 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
                 // k = d0 + 256 d1 + 65536 d2 with d0, d1 in [-128, 127]; digit plane j holds d_j at [row][first tap + t]
                 const int n = tid >> 3, t = tid & 7;
                 if (n < n2) {
-                    const int32_t* row = coef_v + (size_t)(b.ry0 + n) * COEF_ROW;
+                    const int32_t* row = coef_v + (uint32_t)(b.ry0 + n) * (uint32_t)COEF_ROW;  // (scalar base + 32-bit lane offset)
                     const int rel = row[0] - b.ty0 + t;
                     if (t < row[1] && t < 7 && rel >= 0 && rel < CF_MFMA_K) {
                         const int k = row[2 + t];
@@ -633,11 +773,68 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
                     }
                 }
             }
-            // work item = (output column, chunk of 4 rows): the column's <= 15 coefficients are
+            if (pl.mfma_h && n0 > 0) {
+                // Matrix form: B1[source row m][output byte column] of a block of PA_HOP_PIXELS output pixels = the block's
+                // 64-byte window of row m x the crop's operand (crop_hop_kernel), digit by digit as in the vertical pass
+                // below. A = 32 source rows x 64 window bytes: a lane (row lane & 31, half lane >> 5) reads bytes
+                // 16 half .. + 15 of each 32-byte step of its row from B0, - 128 = one XOR per dword; rows past the band's
+                // end repeat its last row, window bytes past the row's end meet zero digits. B = the operand's fragments,
+                // straight from global memory (L2: the crop's 16 workgroups share them), column lane & 31, the same bytes.
+                // Result register 4g + e of a lane is source row 8g + 4 (lane >> 5) + e of column lane & 31: a register
+                // group is one dword of the transposed B1 the vertical pass reads. A wave takes every eighth block.
+                const int n = lane & 31, half = lane >> 5;
+                const int nb = (pl.rw + PA_HOP_PIXELS - 1) / PA_HOP_PIXELS, rw3 = pl.rw * 3;
+                const uint8_t* hop = p.hop + (size_t)crop * PA_HOP_BLOCKS_MAX * PA_HOP_BLOCK_BYTES;
+                const int arow = (n < n0 ? n : n0 - 1) * L.p0 + half * 16;
+                // The window bases of all of this wave's blocks come in one load before the loop (lane i: its i-th block), and
+                // a block's six fragments and constants are requested together ahead of the reads of B0 -- a tile would
+                // otherwise wait for L2 four times in a row (base -> B0 address, then fragment pair by fragment pair).
+                int wb_all = 0;
+                if (wave + CF_NW * lane < nb)
+                    wb_all = reinterpret_cast<const int32_t*>(hop + (size_t)(wave + CF_NW * lane) * PA_HOP_BLOCK_BYTES + 6 * 1024)[32];
+                int it = 0;
+                for (int blk = wave; blk < nb; blk += CF_NW, ++it) {
+                    const uint8_t* ob = hop + (size_t)blk * PA_HOP_BLOCK_BYTES;
+                    i32x4 bf[6];
+#pragma unroll
+                    for (int f = 0; f < 6; ++f) bf[f] = (reinterpret_cast<const i32x4*>(ob) + lane)[f * 64];
+                    const int cst = reinterpret_cast<const int32_t*>(ob + 6 * 1024)[n];
+                    int wbase = __builtin_amdgcn_readlane(wb_all, it);
+                    // (the builder wrote a dword offset inside the row; clamped all the same, so that a read never leaves LDS)
+                    wbase = wbase < 0 ? 0 : (wbase > L.p0 ? L.p0 : wbase) & ~3;
+                    const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + arow + wbase);
+                    i32x4 a0, a1;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        a0[q] = (int)(src[q] ^ 0x80808080u);
+                        a1[q] = (int)(src[8 + q] ^ 0x80808080u);
+                    }
+                    i32x16 acc;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[e] = 0;
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {  // digit 2, 1, 0
+                        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, bf[2 * j], acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, bf[2 * j + 1], acc, 0, 0, 0);
+                        if (j < 2) {
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) acc[e] = (int)(((uint32_t)acc[e] << 8) + (j == 1 ? (uint32_t)cst : 0u));
+                        }
+                    }
+                    const int col = blk * (3 * PA_HOP_PIXELS) + n;
+                    if (n < 3 * PA_HOP_PIXELS && col < rw3) {
+                        uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off1 + col * L.pt + (col >> 3) * L.skew + half * 4);
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+                            if (8 * g + 4 * half < L.pt) dst[2 * g] = clip8_pk4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+                    }
+                }
+            }
+            // vector form: work item = (output column, chunk of 4 rows): the column's <= 15 coefficients are
             // fetched once per item and reused for its rows; ~6 items per thread keeps all 256
             // threads busy (one item per column would leave the second pass 3/4 empty).
             const int chunks = (n0 + 3) >> 2;
-            const int items = chunks * pl.rw;
+            const int items = pl.mfma_h ? 0 : chunks * pl.rw;
             for (int it = tid; it < items; it += CF_NT) {
                 const int ck = it / pl.rw, xx = it - ck * pl.rw;
                 const int32_t* row = coef_h + (size_t)xx * COEF_ROW;
@@ -754,7 +951,7 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
             for (int j = 0; j < 3; ++j) bop[j] = *reinterpret_cast<const i32x4*>(cop + j * CF_MFMA_N * CF_MFMA_K);
             int cst = 0;
             if (n < n2) {
-                const int32_t* row = coef_v + (size_t)(b.ry0 + n) * COEF_ROW;
+                const int32_t* row = coef_v + (uint32_t)(b.ry0 + n) * (uint32_t)COEF_ROW;
                 const int cnt = row[1];
                 int ksum = 0;
 #pragma unroll
@@ -1428,9 +1625,15 @@ hipError_t launch_preprocess(const PreprocParams& p_in, hipStream_t s) {
     p.ablate = ablate;
     static const int crop_mfma = getenv("PA_CROP_MFMA") ? atoi(getenv("PA_CROP_MFMA")) : 1;  // 0: the A/B switch of the matrix-core vertical pass
     p.crop_mfma = crop_mfma;
+    // 0: the vector horizontal pass and re-aligning staging; 1: the matrix form; 2: the matrix form behind re-aligning staging
+    static const int crop_mfma_h = getenv("PA_CROP_MFMA_H") ? atoi(getenv("PA_CROP_MFMA_H")) : PA_CROP_MFMA_H_DEFAULT;
+    p.crop_mfma_h = crop_mfma && p.hop ? crop_mfma_h : 0;
+    static const int crop_xcd = getenv("PA_CROP_XCD") ? atoi(getenv("PA_CROP_XCD")) : 1;  // 0: a crop's workgroups in launch order
+    p.crop_xcd = crop_xcd;
     const int ncrops = p.n_frames * p.fighters;
     if (ncrops <= 0) return hipSuccess;
     hipLaunchKernelGGL(crop_plan_kernel, dim3(ncrops), dim3(256), 0, s, p);
+    if (p.crop_mfma_h) hipLaunchKernelGGL(crop_hop_kernel, dim3(PA_HOP_BLOCKS_MAX / PA_HOP_WG_BLOCKS, ncrops), dim3(256), 0, s, p);
 #ifdef PA_STAMP_BUILD
     static int calls = 0;
     static unsigned long long* sd = nullptr;
