@@ -2,6 +2,7 @@
 // the host code the three executors (pa_api.hip's ResNet-18 engine, convnet.hip, yolo.hip) share. No kernel here. Which form a row
 // takes, and in what order the forms are tried, stays with each executor.
 #pragma once
+#include "gemm_tile.h"   // im2col_tile: the im2col engine's choice of tile shape
 #include "pa_kernels.h"
 #include <cstring>
 #include <vector>
@@ -29,9 +30,6 @@ GemmParams conv_row_params(const ConvRow& r);
 
 // the Winograd launch of a stride-1 3x3 row from its filled GemmParams: pointers, strides and epilogue as there; no split-K scratch
 WinoParams wino_params(const GemmParams& p, int n_img, int height, int width, int cin, const float* filters, int bn);
-
-// im2col engine (igemm.hip): the largest tile shape that still gives the chip ~two workgroups per CU (512 tiles)
-GemmTile im2col_tile(long long M, int N);
 
 // The per-form copies of a table's convolution weights: up to three device planes and each row's offset into them.
 enum { FORM_WINO = 1, FORM_PSGEMM = 2, FORM_BGEMM = 4 };

@@ -45,11 +45,6 @@ WinoParams wino_params(const GemmParams& p, int n_img, int height, int width, in
     return q;
 }
 
-GemmTile im2col_tile(long long M, int N) {
-    const long long t128 = (M + 127) / 128 * (N / 64);   // 128 x 64 tiles; half as many 128 x 128 ones
-    return (N % 128 == 0 && t128 / 2 >= 512) ? TILE_128x128 : (t128 >= 512 ? TILE_128x64 : TILE_64x64);
-}
-
 FormWeights::~FormWeights() {
     (void)hipFree(wino);
     (void)hipFree(psgemm);

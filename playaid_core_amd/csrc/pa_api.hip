@@ -4,6 +4,7 @@
 // in the enqueue calls.
 #include "../../include/playaid_hip.h"
 #include "conv_rows.h"
+#include "engine_plan.h"
 #include "train_common.h"   // adam_scalars, adam_config_ok, TrainerCore
 
 #include <algorithm>
@@ -20,46 +21,25 @@ namespace {
 
 constexpr int WINO_TICKETS = 4096;   // tiles of one Winograd launch that may use split K (more: no split)
 
-struct ConvLayer {
+// A row of the layer table: what engine_plan.h plans from, plus its buffers and weights
+struct ConvLayer : LayerDesc {
     std::string name;
-    int cin, cout, kh, kw, stride;  // logical conv
-    int in_hw, out_hw;              // spatial size (square) of input / output interior
-    int in_pad, out_pad;            // zero-border widths of the buffers
-    int off;                        // tap origin inside the padded input
-    int taps, kw_taps, chunk;       // igemm K geometry
-    int in_px_stride;               // floats per input pixel
     float* in = nullptr;
     float* out = nullptr;
     float* residual = nullptr;
-    float* wgt = nullptr;   // device [cout][taps*chunk]
-    float* wino_wgt = nullptr;  // fp32 stride-1 3x3 layers run as Winograd F(2x2, 3x3): the filters in wino.hip's layout, else nullptr
+    float* wgt = nullptr;   // device [cout][taps*chunk]; block-0 conv2 of layers 2-4, fp32: [W2 | Wd], the branch as extra K read from `ds.src`
+    float* wino_wgt = nullptr;  // LayerDesc::wino: the filters in wino.hip's layout
     int wino_bn = 0;            // ... laid out for workgroups of this many output channels (wino_pick_bn at the full batch)
     float* bias = nullptr;  // device [cout]
-    int relu = 1;
-    GemmTile tile = TILE_128x64;
-    int splitk = 1;
-    bool forced = false;  // tile/split-K pinned by PA_FORCE_* (tuning), else chosen per launch
-    // fused 1x1 stride-2 downsample branch (block 0 of layers 2-4): extra K read from `in2`
-    float* in2 = nullptr;
-    int in2_c = 0, in2_hw = 0, in2_stride = 1;
-    // bf16 path: the downsample branch is its own small GEMM into `ds_out` (bf16, same padded layout as `out`),
-    // which the 3x3 conv then adds as its residual (patchconv_bf16.hip has no second source)
-    float* ds_wgt = nullptr;  // [cout][in2_c] bf16
-    float* ds_out = nullptr;
-    // ... unless the block's stride-2 opener computes it on its centre tap (igemm_bf16.hip, DS; on the exact fp32 path pigemm.hip's
-    // pgemm_branch_kernel, PA_F32_DS_FUSE): set on the OPENER (`ds_next_*` = the next layer's ds_wgt / ds_out) and on the conv that
-    // adds the result (`ds_fused`). fp32: an opener launch the fused kernel does not take (split K at small batches) launches the
-    // branch GEMM itself, right behind the opener -- where it runs today
-    float* ds_next_wgt = nullptr;
-    float* ds_next_out = nullptr;
-    std::string ds_next_name;  // fp32: the name of the layer that owns the branch (its per-layer profile row when the opener launches the GEMM)
-    bool ds_fused = false;
-    bool ds_probe = false;  // PA_BF16_DS_FUSE=2: the opener takes the fused launch's tile and K split, the branch stays separate
-    double k_alg = 0;  // algorithmic K (unpadded) for FLOP accounting
-    // compute_dtype PA_DTYPE_EMULATED_F32: the layer's weights as three bf16 slices in psgemm.hip's stage-image order (the layer then
-    // runs on that kernel), and the same for the 1x1/2 branch GEMM of a Winograd-form block opener's conv2
-    unsigned short* split_wgt = nullptr;
-    unsigned short* ds_split_wgt = nullptr;
+    unsigned short* split_wgt = nullptr;  // LayerDesc::split: three bf16 slices per weight in psgemm.hip's stage-image order
+    // conv2 of block 0 of layers 2-4: its 1x1/2 downsample branch (LayerDesc::branch says where it is computed)
+    struct {
+        float* src = nullptr;   // the zero-bordered block input
+        float* wgt = nullptr;   // [cout][branch.c], bf16 on the bf16 path; nullptr: BRANCH_SECOND_K
+        float* out = nullptr;   // the stored branch, laid out like `out` (no bias, no activation): conv2 adds it as its residual
+        unsigned short* split_wgt = nullptr;  // LayerDesc::branch.split
+    } ds;
+    int carries_of = -1;  // the block's opener (LayerDesc::carries): index in pa_engine::convs of the conv2 whose branch it carries
 };
 
 struct ProfEntry {
@@ -75,7 +55,9 @@ struct pa_engine {
     pa_config cfg;
     std::string last_error;
     int max_crops = 0;   // crops per backbone call
-    bool emu = false;    // cfg.compute_dtype == PA_DTYPE_EMULATED_F32: fp32 buffers and interfaces, the layers that have ConvLayer::split_wgt on psgemm.hip
+    EngineKnobs knobs;   // the environment's knobs as pa_create found them (engine_plan.h)
+    ComputeDtype dtype = DT_F32;  // cfg.compute_dtype, as engine_plan.h counts it
+    bool emu = false;   // cfg.compute_dtype == PA_DTYPE_EMULATED_F32: fp32 buffers and interfaces, the layers that have ConvLayer::split_wgt on psgemm.hip
     bool bf16 = false;   // cfg.compute_dtype == PA_DTYPE_BF16: the 3x3 conv stack stores bf16 (buffers keep their fp32 size)
     int cache_rows = 0;  // feature-cache rows
     // clip state
@@ -143,14 +125,13 @@ struct pa_engine {
     size_t t_stride = 0;
     int32_t* status_tmp = nullptr;
     int32_t* fallback = nullptr;  // [1 + max_crops]: count, then crop indices
-    // two-way interleave of the backbone (two half batches on two streams)
+    // two-way interleave of the backbone (two half batches on two streams; knobs.interleave: measured +0.5 % only -- kernels of two
+    // streams do not overlap usefully -- and kept as a knob)
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_ds_fork = nullptr, ev_ds_join = nullptr;   // PA_DS_SIDE: a block's 1x1/2 branch GEMM on the side stream, under its opener
-    int interleave = 0;  // measured +0.5 % only (kernels of two streams do not overlap usefully); kept as a knob
     // profiling
     bool profiling = false;
-    bool profile_layers = false;  // PA_PROFILE_LAYERS=1: one row per conv layer instead of per kernel family
     std::vector<std::string> prof_names;
     std::vector<ProfEntry> prof_log;
     std::vector<hipEvent_t> event_pool;
@@ -305,18 +286,6 @@ bool fold_conv(BlobReader& br, const ConvLayer& L, std::vector<float>& w_out, st
     return true;
 }
 
-void choose_tile(int M, int N, int nk, GemmTile* tile, int* splitk) {
-    // Aim for >= 2 workgroups per CU (512) so that the un-pipelined K loop of
-    // one workgroup hides behind another's; fall back to split-K when even the
-    // smallest tile cannot fill the chip.
-    *tile = im2col_tile(M, N);
-    const int tm = (M + 127) / 128;
-    const int tiles = *tile == TILE_128x128 ? tm * (N / 128) : *tile == TILE_128x64 ? tm * (N / 64) : ((M + 63) / 64) * (N / 64);
-    int sk = 1;
-    while (tiles * sk < 512 && nk / (sk * 2) >= 8) sk *= 2;
-    *splitk = sk;
-}
-
 // --- profiling ------------------------------------------------------------------
 int prof_name_id(pa_engine* e, const char* name) {
     for (size_t i = 0; i < e->prof_names.size(); ++i)
@@ -363,36 +332,59 @@ struct ProfScope {
     }
 };
 
-// crop0: first crop of this launch inside the layer's buffers (the two interleaved half
-// batches address disjoint crop ranges of the same buffers); slab_off: its split-K slab region.
-// ds_stream: where the 1x1/2 branch GEMM of a Winograd-form block opener's conv2 goes (nullptr: `s`, right in front of the convolution);
-// ds_only: launch just that GEMM and return; ds_done: it has been launched already (by a ds_only call), only its result is added
-int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t slab_off, hipStream_t s, const char* prof_name,
-             bool ds_only = false, bool ds_done = false) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
+// element `elems` of a layer buffer: 2-byte elements on the bf16 conv path (bf), else floats
+float* buf_at(float* base, size_t elems, bool bf) { return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * (bf ? 2 : 4)); }
+
+// PA_DS_SIDE=1 (A/B): the 1x1/2 branch GEMM of a block (layers 2-4: ~10 us each, a few dozen tiles) is
+// launched on the side stream BEFORE the block's stride-2 opener instead of between the opener and conv2 -- both read the block
+// input, so the small GEMM runs under the opener and conv2 only waits for an event. Whether the launches on `s` do so
+bool branch_on_side(const pa_engine* e, hipStream_t s) { return e->knobs.ds_side && !e->profiling && !e->bf16 && e->side && s != e->side; }
+
+// The 1x1/2 downsample branch of conv2 `L` as a GEMM of its own: the zero-bordered block input -> ds.out, laid out like L's output
+// (add_conv builds the block so that L's output is branch.hw / branch.stride on a side with whole pixels of cout channels:
+// the branch's M, howo, wo and output strides come out equal to the convolution's)
+int run_branch_gemm(pa_engine* e, const ConvLayer& L, const BranchPlan& b, int crop0, int ncrops, size_t slab_off, hipStream_t s, const char* prof_name) {
+    const int hw = L.branch.hw, c = L.branch.c, out_w = L.out_hw + 2 * L.out_pad;
+    const size_t out_crop = (size_t)out_w * out_w * L.cout;
+    GemmParams d = conv_row_params({/*images*/ ncrops, /*in h, w, pad, px stride*/ hw, hw, 1, c,
+                                    /*cin, cout, ksize, stride*/ c, L.cout, 1, L.branch.stride,
+                                    /*out pad, px stride*/ L.out_pad, L.cout, /*act, res_after*/ 0, 0});
+    d.act = buf_at(L.ds.src, (size_t)crop0 * (hw + 2) * (hw + 2) * c, e->bf16);
+    d.wgt = L.ds.wgt;
+    d.out = buf_at(L.ds.out, crop0 * out_crop, e->bf16);
+    d.slab = e->slab + slab_off;
+    ProfScope ps(e, s, prof_name, b.acct.flops, b.acct.bytes);
+    if (e->bf16) HIPCHK(e, launch_igemm_bf16(d, b.tile, s));
+    else if (b.psgemm) HIPCHK(e, launch_psgemm(d, L.ds.split_wgt, (size_t)ncrops * out_crop, 0, s));
+    else HIPCHK(e, launch_igemm(d, b.tile, s));
+    return PA_OK;
+}
+
+// One layer: what plan_conv (engine_plan.h) decides, launched. crop0: first crop of this launch inside the layer's buffers (the two
+// interleaved half batches address disjoint crop ranges of the same buffers); slab_off: its split-K slab region.
+int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t slab_off, hipStream_t s, const char* prof_name) {
+    const size_t slab_avail = e->slab_floats > slab_off ? e->slab_floats - slab_off : 0;
+    const ConvPlan P = plan_conv(e->knobs, e->dtype, L, ncrops, slab_avail, branch_on_side(e, s));
+    const bool bf = e->bf16 && L.kh == 3;  // bf16 conv path: the 3x3 stack (buffers addressed in 2-byte elements)
     const int in_w = L.in_hw + 2 * L.in_pad;
     const int out_w = L.out_hw + 2 * L.out_pad;
     const size_t in_crop = (size_t)in_w * in_w * L.in_px_stride;
     const size_t out_crop = (size_t)out_w * out_w * L.cout;
-    const bool bf = e->bf16 && L.kh == 3;  // bf16 conv path: the 3x3 stack (buffers addressed in 2-byte elements)
-    const bool bf_ds = bf && L.in2 && L.ds_wgt;  // downsample branch as its own GEMM, added as the residual
-    const bool f32_ds = !bf && L.in2 && L.ds_wgt && L.wino_wgt;  // the same for the fp32 Winograd form of the layer
-    const size_t es = bf ? 2 : 4;
-    auto at = [es](float* base, size_t elems) { return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + elems * es); };
-    p.act = at(L.in, crop0 * in_crop);
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.act = buf_at(L.in, crop0 * in_crop, bf);
     p.wgt = L.wgt;
     p.bias = L.bias;
-    p.residual = L.residual ? at(L.residual, crop0 * out_crop) : nullptr;
-    p.out = at(L.out, crop0 * out_crop);
+    p.residual = L.residual ? buf_at(L.residual, crop0 * out_crop, bf) : nullptr;
+    p.out = buf_at(L.out, crop0 * out_crop, bf);
     p.slab = e->slab + slab_off;
     p.gather = nullptr;
-    p.M = ncrops * L.out_hw * L.out_hw;
-    p.N = L.cout;
+    p.M = P.M;
+    p.N = P.N;
     p.taps = L.taps;
     p.kw_taps = L.kw_taps;
     p.chunk = L.chunk;
-    p.ktot = L.taps * L.chunk;
+    p.ktot = P.ktot;
     p.skip_w = L.kh == 7;  // stem: 3 channels in 4-float pixels
     p.howo = L.out_hw * L.out_hw;
     p.wo = L.out_hw;
@@ -407,102 +399,35 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
     p.out_img_stride = (int)out_crop;
     p.out_pad = L.out_pad;
     p.relu = L.relu;
-    // the block's 1x1/2 downsample branch as a GEMM of its own: the zero-bordered block input -> ds_out, laid out like this layer's output
-    // (add_conv builds the block so that this layer's output is in2_hw / in2_stride on a side with whole pixels of cout channels:
-    // the branch's M, howo, wo and output strides come out equal to p's)
-    // (src, hw, c, stride: the block input; on conv2 its in2 fields, on the opener -- fp32, the fused launch refused -- its own input)
-    auto branch_gemm_of = [&](float* src, int hw, int c, int stride, float* wgt, float* out) {
-        GemmParams d = conv_row_params({/*images*/ ncrops, /*in h, w, pad, px stride*/ hw, hw, 1, c,
-                                        /*cin, cout, ksize, stride*/ c, L.cout, 1, stride,
-                                        /*out pad, px stride*/ L.out_pad, L.cout, /*act, res_after*/ 0, 0});
-        d.act = at(src, (size_t)crop0 * (hw + 2) * (hw + 2) * c);
-        d.wgt = wgt;
-        d.out = at(out, crop0 * out_crop);
-        d.slab = p.slab;
-        return d;
-    };
-    auto branch_gemm = [&]() { return branch_gemm_of(L.in2, L.in2_hw, L.in2_c, L.in2_stride, L.ds_wgt, L.ds_out); };
-    auto launch_f32_branch = [&](const GemmParams& d) {
-        GemmTile dt;
-        int dsk;
-        choose_tile(d.M, d.N, d.chunk / 32, &dt, &dsk);
-        return launch_igemm(d, dt, s);
-    };
-    if ((bf_ds || f32_ds) && L.ds_fused) {
-        p.residual = at(L.ds_out, crop0 * out_crop);  // written by the block's opener
-    } else if (bf_ds) {
-        const GemmParams d = branch_gemm();
-        ProfScope ps(e, s, prof_name, 2.0 * d.M * d.N * L.in2_c,
-                     2.0 * ((double)ncrops * L.in2_hw * L.in2_hw * L.in2_c / (L.in2_stride * L.in2_stride) + (double)d.M * d.N + (double)d.N * L.in2_c));
-        HIPCHK(e, launch_igemm_bf16(d, TILE_128x64, s));  // (128x128 / 256x128 tiles measured 2-7 us slower here)
-        p.residual = d.out;
-    } else if (f32_ds) {
-        const GemmParams d = branch_gemm();
-        ProfScope ps(e, s, prof_name, ds_done ? 0.0 : 2.0 * d.M * d.N * L.in2_c,
-                     ds_done ? 0.0 : 4.0 * ((double)ncrops * L.in2_hw * L.in2_hw * L.in2_c / (L.in2_stride * L.in2_stride) + (double)d.M * d.N + (double)d.N * L.in2_c));
-        if (ds_done) {
-        } else if (e->emu && L.ds_split_wgt) {
-            HIPCHK(e, launch_psgemm(d, L.ds_split_wgt, (size_t)ncrops * out_crop, 0, s));
-        } else {
-            HIPCHK(e, launch_f32_branch(d));
-        }
-        if (ds_only) return PA_OK;
-        p.residual = d.out;
-    } else if (L.in2) {
-        const int w2 = L.in2_hw + 2;  // zero-bordered block input
-        p.act2 = at(L.in2, (size_t)crop0 * w2 * w2 * L.in2_c);
-        p.k2_steps = L.in2_c / (bf ? 64 : 32);
-        p.in2_px_stride = L.in2_c;
-        p.in2_row_stride = w2 * L.in2_c;
-        p.in2_img_stride = w2 * w2 * L.in2_c;
-        p.stride2 = L.in2_stride;
+    p.splitk = P.splitk;
+    if (P.branch == BL_GEMM_BEFORE) {
+        const int rc = run_branch_gemm(e, L, P.branch_gemm, crop0, ncrops, slab_off, s, prof_name);
+        if (rc) return rc;
+    }
+    if (P.branch == BL_GEMM_BEFORE || P.branch == BL_STORED) {
+        p.residual = buf_at(L.ds.out, crop0 * out_crop, bf);
+    } else if (P.branch == BL_SECOND_K) {
+        const int w2 = L.branch.hw + 2;  // zero-bordered block input
+        p.act2 = buf_at(L.ds.src, (size_t)crop0 * w2 * w2 * L.branch.c, bf);
+        p.k2_steps = L.branch.c / (bf ? 64 : 32);
+        p.in2_px_stride = L.branch.c;
+        p.in2_row_stride = w2 * L.branch.c;
+        p.in2_img_stride = w2 * w2 * L.branch.c;
+        p.stride2 = L.branch.stride;
         p.off2 = 1;
-        p.ktot += L.in2_c;
     }
-    GemmTile tile = L.tile;
-    int splitk = L.splitk;
-    if (!L.forced) choose_tile(p.M, p.N, p.ktot / (bf ? 64 : 32), &tile, &splitk);  // per launch: M depends on the batch
-    p.splitk = splitk;
-    const size_t slab_avail = e->slab_floats > slab_off ? e->slab_floats - slab_off : 0;
-    if ((size_t)p.splitk * p.M * p.N > slab_avail) p.splitk = 1;
-    const bool f32_branch = !bf && !e->emu && L.ds_next_wgt;   // the exact path's opener: the fused kernel if it takes the launch
-    const bool f32_branch_here = f32_branch && p.splitk <= 1;
-    const bool ds_here = (bf && L.ds_next_wgt) || f32_branch_here;  // this launch also computes the next conv's 1x1/2 branch
-    if (bf && L.ds_next_wgt) {
-        p.wgt2 = L.ds_next_wgt;
-        p.out2 = at(L.ds_next_out, crop0 * out_crop);
+    const ConvLayer* C2 = L.carries_of >= 0 ? &e->convs[L.carries_of] : nullptr;  // the conv2 whose branch this opener carries
+    if (bf && P.branch == BL_ON_OPENER) {
+        p.wgt2 = C2->ds.wgt;
+        p.out2 = buf_at(C2->ds.out, crop0 * out_crop, bf);
     }
-    if ((bf && L.ds_next_wgt) || (bf && L.ds_probe)) {
-        tile = (p.N % 128 == 0 && ((p.M + 127) / 128) * (p.N / 128) >= 256) ? TILE_128x128 : TILE_128x64;
-        p.splitk = 1;
-    }
-    // (the branch's FLOPs and bytes are booked where it runs: its own launch, or the opener's)
-    const double k_main = ((bf_ds || f32_ds) ? L.k_alg - L.in2_c : L.k_alg) + (ds_here ? L.cin : 0);
-    const double flops = 2.0 * p.M * p.N * k_main;
-    const double bytes = (double)es * ((double)ncrops * L.in_hw * L.in_hw * L.cin + (double)p.M * p.N * ((L.residual || bf_ds || f32_ds || ds_here) ? 2 : 1) +
-                                       (double)p.N * k_main + ((L.in2 && !bf_ds && !f32_ds) ? (double)ncrops * L.in2_hw * L.in2_hw * L.in2_c : 0.0));
-    const bool as_wino = !bf && L.wino_wgt && !p.act2;
-    bool branch_left = f32_branch;   // the fp32 opener's branch is still to be computed
+    bool branch_left = P.branch == BL_GEMM_BEHIND;   // the fp32 opener's branch is still to be computed
     {   // (the opener's profile scope ends before its branch's begins)
-        ProfScope ps(e, s, prof_name, flops, bytes, as_wino ? flops * 4.0 / 9.0 : flops);
-        // stride-1 3x3 layers: input patch resident in LDS across the nine taps (patchconv.hip);
-        // PA_PATCH=0 keeps the generic im2col engine for A/B runs
-        static const int use_patch = getenv("PA_PATCH") ? atoi(getenv("PA_PATCH")) : 1;
-        static const int use_bf16_patch = getenv("PA_BF16_PATCH") ? atoi(getenv("PA_BF16_PATCH")) : 1;
-        if (e->emu && L.split_wgt && !p.act2 && !p.residual) {
-            HIPCHK(e, launch_psgemm(p, L.split_wgt, (size_t)ncrops * out_crop, 0, s));
-        } else if (bf) {
-            hipError_t pe = hipErrorInvalidValue;
-            if (use_bf16_patch && L.stride == 1 && !p.act2) pe = launch_conv3x3_bf16_patch(p, s);
-            if (pe == hipErrorInvalidValue) {  // stride-2 convs, fused 1x1/2 second source
-                // a 256-pixel tile halves the weight fill per pixel (this kernel is bound by its L2 -> LDS copies) where it
-                // still leaves every CU a workgroup; PA_BF16_T256=0 for A/B runs
-                static const int t256 = getenv("PA_BF16_T256") ? atoi(getenv("PA_BF16_T256")) : 1;
-                if (t256 && !p.out2 && tile == TILE_128x128 && p.splitk == 1 && ((p.M + 255) / 256) * (p.N / 128) >= 256) tile = TILE_256x128;
-                pe = launch_igemm_bf16(p, tile, s);
-            }
-            HIPCHK(e, pe);
-        } else if (L.wino_wgt && !p.act2) {
+        ProfScope ps(e, s, prof_name, P.acct.flops, P.acct.bytes, P.acct.flops_executed);
+        hipError_t pe = hipErrorInvalidValue;   // a launcher's refusal: the next form takes the launch
+        if (P.form == CONV_PSGEMM) {
+            pe = launch_psgemm(p, L.split_wgt, (size_t)ncrops * out_crop, 0, s);
+        } else if (P.form == CONV_WINO) {
             WinoParams q = wino_params(p, ncrops, L.out_hw, L.out_hw, L.cin, L.wino_wgt, L.wino_bn);
             if (e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
                 q.slab = e->slab + slab_off;
@@ -510,43 +435,27 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
                 q.tickets = reinterpret_cast<int32_t*>(e->wino_tickets) + (slab_off ? WINO_TICKETS : 0);
                 q.tickets_cap = WINO_TICKETS;
             }
-            HIPCHK(e, launch_wino3x3(q, s));
-        } else if (use_patch && L.kh == 3 && L.stride == 1) {
-            int bm = tile == TILE_64x64 || tile == TILE_64x64_K64 ? 64 : 128;
-            const int howo = L.out_hw * L.out_hw, in_w2 = L.out_hw + 2;
-            const int px128 = howo >= 128 ? (128 / L.out_hw + 2) * in_w2 : (128 / howo) * in_w2 * in_w2;
-            if (bm == 128 && px128 > 224) bm = 64;  // keep two workgroups per CU (2 patch buffers + weight ring <= 80 KB)
-            hipError_t pe = launch_conv3x3_patch(p, bm, s);
-            if (pe == hipErrorInvalidValue) pe = launch_igemm(p, tile, s);  // geometry the patch kernel does not cover
-            HIPCHK(e, pe);
+            pe = launch_wino3x3(q, s);
+        } else if (bf) {
+            if (P.form == CONV_BF16_PATCH) pe = launch_conv3x3_bf16_patch(p, s);
+            if (pe == hipErrorInvalidValue) pe = launch_igemm_bf16(p, P.tile_256 ? TILE_256x128 : P.tile, s);
         } else {
-            // Stride-2 3x3 convolutions that need no split-K run on the persistent form of the engine (pigemm.hip) with 64-row tiles:
-            // two tiles per workgroup slot, so the second tile's first operands arrive under the first one's matrix instructions
-            // (one 128-row tile per slot, round 4's A/B, gained nothing: 48.39 k against 48.53 k frames/s). At 128 crops: 50.3 / 50.2 /
-            // 54.0 -> 48.8 / 46.6 / 52.7 us for the three openers. Same k order as igemm.hip; the bias is the value pgemm's accumulators start
-            // from and igemm's last addition: results agree to that rounding. PA_S2_PGEMM=0: igemm.hip (A/B), 1: pgemm's own choice of tile height
-            static const int use_pgemm = getenv("PA_S2_PGEMM") ? atoi(getenv("PA_S2_PGEMM")) : 2;
-            hipError_t pe = hipErrorInvalidValue;
-            const bool pg = use_pgemm && L.kh == 3 && L.stride == 2 && !p.act2 && !p.residual && p.splitk <= 1 && !p.gather;
-            if (pg && f32_branch_here) {   // the block's 1x1/2 branch on the centre tap (pgemm_branch_kernel)
-                p.wgt2 = L.ds_next_wgt;
-                p.out2 = at(L.ds_next_out, crop0 * out_crop);
+            if (P.form == CONV_PATCH) pe = launch_conv3x3_patch(p, P.patch_bm, s);
+            if (P.form == CONV_PGEMM && P.branch == BL_ON_OPENER) {   // the block's 1x1/2 branch on the centre tap (pgemm_branch_kernel)
+                p.wgt2 = C2->ds.wgt;
+                p.out2 = buf_at(C2->ds.out, crop0 * out_crop, bf);
                 pe = launch_pgemm(p, 64, s);
-                if (pe == hipSuccess) branch_left = false;
+                branch_left = pe != hipSuccess;
                 p.wgt2 = nullptr;
                 p.out2 = nullptr;
             }
-            if (pg && pe == hipErrorInvalidValue) pe = launch_pgemm(p, use_pgemm == 2 ? 64 : 0, s);
-            if (pe == hipErrorInvalidValue) pe = launch_igemm(p, tile, s);
-            HIPCHK(e, pe);
+            if (P.form == CONV_PGEMM && pe == hipErrorInvalidValue) pe = launch_pgemm(p, P.pgemm_bm, s);
+            if (pe == hipErrorInvalidValue) pe = launch_igemm(p, P.tile, s);  // geometry the patch kernel / the persistent GEMM does not cover
         }
+        HIPCHK(e, pe);
     }
-    if (branch_left) {   // the opener ran unfused (split K: small batches): the branch GEMM behind it, where it runs without PA_F32_DS_FUSE
-        const GemmParams d = branch_gemm_of(L.in, L.in_hw, L.cin, L.stride, L.ds_next_wgt, L.ds_next_out);
-        ProfScope ps(e, s, e->profile_layers ? L.ds_next_name.c_str() : prof_name, 2.0 * d.M * d.N * L.cin,   // (booked where conv2 books it: its layer's row, or the family's)
-                     4.0 * ((double)ncrops * L.in_hw * L.in_hw * L.cin / (L.stride * L.stride) + (double)d.M * d.N + (double)d.N * L.cin));
-        HIPCHK(e, launch_f32_branch(d));
-    }
+    // the opener ran unfused: the branch GEMM behind it, booked where conv2 books it (its layer's row, or the family's)
+    if (branch_left) return run_branch_gemm(e, *C2, P.branch_gemm, crop0, ncrops, slab_off, s, e->knobs.profile_layers ? C2->name.c_str() : prof_name);
     return PA_OK;
 }
 
@@ -557,9 +466,9 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
     int rc;
     ConvLayer stem = e->convs[0];
     stem.in = const_cast<float*>(x_in);  // x_in / feats_out are the caller's bases: crop0 is applied by run_conv
-    static const bool stem_igemm = getenv("PA_STEM_IGEMM") && atoi(getenv("PA_STEM_IGEMM"));  // A/B knob: generic engine
+    const EngineKnobs& K = e->knobs;
     auto stem_part = [&](int c0, int n, hipStream_t st) -> int {
-        if (stem_igemm && !e->bf16) return run_conv(e, stem, c0, n, slab_off, st, "igemm_conv7x7_stem");
+        if (K.stem_igemm && !e->bf16) return run_conv(e, stem, c0, n, slab_off, st, "igemm_conv7x7_stem");
         StemParams sp;
         memset(&sp, 0, sizeof(sp));
         sp.x = x_in + (size_t)c0 * 134 * 134 * 4;
@@ -585,10 +494,8 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
     // Default: stem + BatchNorm + ReLU + max-pool in one persistent kernel (stem_pool.hip), the 64 x 64 stem map never
     // reaches memory. PA_STEM_POOL=0 keeps the two-kernel form for A/B runs: there the max-pool (pure HBM/L2
     // streaming) of one half batch runs on the side stream underneath the stem (pure matrix work) of the other.
-    static const int fused_pool = getenv("PA_STEM_POOL") ? atoi(getenv("PA_STEM_POOL")) : 1;
-    static const int overlap_pool = getenv("PA_POOL_OVERLAP") ? atoi(getenv("PA_POOL_OVERLAP")) : 1;
     const int x_form = input_form(e, x_in);
-    if (fused_pool && !stem_igemm) {
+    if (engine_forms(K, e->dtype).stem_fused) {
         StemPoolParams sp;
         memset(&sp, 0, sizeof(sp));
         const size_t es_in = x_form ? 2 : 4, es_out = e->bf16 ? 2 : 4;   // (integer pixels: 2-byte input, fp32 output)
@@ -607,7 +514,7 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
         return fail(e, PA_ERR_INVALID_ARG, "integer pixels reached an unfused stem (PA_STEM_POOL=0 / PA_STEM_IGEMM=1 switch the integer stem off)");
     } else if (e->bf16) {
         return fail(e, PA_ERR_INVALID_ARG, "the bf16 path has no unfused stem (PA_STEM_POOL=0 / PA_STEM_IGEMM=1 are fp32 A/B knobs)");
-    } else if (overlap_pool && !e->profiling && !e->interleave && e->side && s != e->side && ncrops >= 64) {
+    } else if (K.pool_overlap && !e->profiling && !K.interleave && e->side && s != e->side && ncrops >= 64) {
         const int half = (ncrops / 2 + 7) & ~7;
         if ((rc = stem_part(crop0, half, s))) return rc;
         HIPCHK(e, hipEventRecord(e->ev_fork, s));
@@ -622,31 +529,22 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
         if ((rc = pool_part(crop0, ncrops, s))) return rc;
     }
     if (stop <= 1) return PA_OK;
-    // PA_DS_SIDE=1 (A/B): the 1x1/2 branch GEMM of a block (layers 2-4: ~10 us each, a few dozen tiles) is
-    // launched on the side stream BEFORE the block's stride-2 opener instead of between the opener and conv2 -- both read the block
-    // input, so the small GEMM runs under the opener and conv2 only waits for an event
-    static const int ds_side = getenv("PA_DS_SIDE") ? atoi(getenv("PA_DS_SIDE")) : 0;
-    bool ds_pending = false;
+    const bool on_side = branch_on_side(e, s);  // a branch GEMM of its own goes to the side stream, in front of its block's opener
     for (size_t i = 1; i < e->convs.size(); ++i) {
         const ConvLayer& L = e->convs[i];
-        const char* pn = e->profile_layers ? L.name.c_str() : (L.kh == 3 ? "igemm_conv3x3" : "igemm_conv1x1_ds");
-        if (ds_side && !e->profiling && !e->bf16 && e->side && s != e->side && i + 1 < e->convs.size()) {
+        const char* pn = K.profile_layers ? L.name.c_str() : (L.kh == 3 ? "igemm_conv3x3" : "igemm_conv1x1_ds");
+        const bool side_next = on_side && i + 1 < e->convs.size() && e->convs[i + 1].branch.place == BRANCH_OWN_GEMM;  // L is such an opener
+        if (side_next) {
             const ConvLayer& Nx = e->convs[i + 1];
-            if (Nx.in2 && Nx.ds_wgt && Nx.wino_wgt && Nx.in2 == L.in && L.stride == 2) {
-                HIPCHK(e, hipEventRecord(e->ev_ds_fork, s));
-                HIPCHK(e, hipStreamWaitEvent(e->side, e->ev_ds_fork, 0));
-                if ((rc = run_conv(e, Nx, crop0, ncrops, slab_off, e->side, "igemm_conv1x1_ds", /*ds_only=*/true))) return rc;
-                HIPCHK(e, hipEventRecord(e->ev_ds_join, e->side));
-                ds_pending = true;
-            }
+            HIPCHK(e, hipEventRecord(e->ev_ds_fork, s));
+            HIPCHK(e, hipStreamWaitEvent(e->side, e->ev_ds_fork, 0));
+            if ((rc = run_branch_gemm(e, Nx, plan_branch(e->dtype, Nx, ncrops), crop0, ncrops, slab_off, e->side, "igemm_conv1x1_ds"))) return rc;
+            HIPCHK(e, hipEventRecord(e->ev_ds_join, e->side));
         }
-        const bool use_pending = ds_pending && L.in2 && L.ds_wgt && L.wino_wgt;
-        if (use_pending) HIPCHK(e, hipStreamWaitEvent(s, e->ev_ds_join, 0));
-        rc = run_conv(e, L, crop0, ncrops, slab_off, s, pn, false, use_pending);
-        if (use_pending) ds_pending = false;
-        if (rc) return rc;
+        if (on_side && L.branch.place == BRANCH_OWN_GEMM) HIPCHK(e, hipStreamWaitEvent(s, e->ev_ds_join, 0));  // (plan_conv: the branch is stored)
+        if ((rc = run_conv(e, L, crop0, ncrops, slab_off, s, pn))) return rc;
         if (stop <= (int)i + 1) {
-            if (ds_pending) HIPCHK(e, hipStreamWaitEvent(s, e->ev_ds_join, 0));  // no side-stream work outlives the call
+            if (side_next) HIPCHK(e, hipStreamWaitEvent(s, e->ev_ds_join, 0));  // no side-stream work outlives the call
             return PA_OK;
         }
     }
@@ -670,7 +568,7 @@ int run_backbone_part(pa_engine* e, int crop0, int ncrops, const float* x_in, fl
 // phase, so the launch gaps, prologues, epilogues and split-K reduces of one half are covered
 // by the steady-state MFMA loop of the other (the layers' outside-the-loop time was ~14 %).
 int run_backbone(pa_engine* e, int ncrops, const float* x_in, float* feats_out, hipStream_t s, int stop = PA_TRACE_STAGES) {
-    if (!e->interleave || ncrops < 64 || !e->side) return run_backbone_part(e, 0, ncrops, x_in, feats_out, 0, s, stop);
+    if (!e->knobs.interleave || ncrops < 64 || !e->side) return run_backbone_part(e, 0, ncrops, x_in, feats_out, 0, s, stop);
     const int half = (ncrops / 2 + 7) & ~7;
     HIPCHK(e, hipEventRecord(e->ev_fork, s));
     HIPCHK(e, hipStreamWaitEvent(e->side, e->ev_fork, 0));
@@ -846,11 +744,10 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     e->cfg = *cfg;
     e->bf16 = cfg->compute_dtype == PA_DTYPE_BF16;
     e->emu = cfg->compute_dtype == PA_DTYPE_EMULATED_F32;
+    e->dtype = e->bf16 ? DT_BF16 : e->emu ? DT_EMULATED_F32 : DT_F32;
     e->adopt = blob == nullptr;
-    {
-        const char* pl = getenv("PA_PROFILE_LAYERS");
-        e->profile_layers = pl && pl[0] == '1';
-    }
+    e->knobs = engine_knobs();  // the per-create knobs as the environment has them now
+    const EngineKnobs& K = e->knobs;
     *out = e;  // handed back even on failure so the caller can read pa_last_error, then pa_destroy
     {
         int ndev = 0;
@@ -875,14 +772,9 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     ALLOC(e->x0_slot[0], (size_t)NC * 134 * 134 * 4, true);
     ALLOC(e->x0_slot[1], (size_t)NC * 134 * 134 * 4, true);
     e->x0 = e->x0_slot[0];
-    {
-        // PA_STEM_INT=0: every producer writes k / 255 and the fp32 stem runs, as before the integer form (A/B runs). The unfused stems
-        // of PA_STEM_POOL=0 / PA_STEM_IGEMM=1 have no integer form and switch it off too.
-        static const int stem_int_knob = getenv("PA_STEM_INT") ? atoi(getenv("PA_STEM_INT")) : 1;
-        static const int fused_pool = getenv("PA_STEM_POOL") ? atoi(getenv("PA_STEM_POOL")) : 1;
-        static const int stem_igemm = getenv("PA_STEM_IGEMM") ? atoi(getenv("PA_STEM_IGEMM")) : 0;
-        e->stem_int = !e->bf16 && stem_int_knob && fused_pool && !stem_igemm;
-    }
+    // PA_STEM_INT=0: every producer writes k / 255 and the fp32 stem runs, as before the integer form (A/B runs). The unfused stems
+    // of PA_STEM_POOL=0 / PA_STEM_IGEMM=1 have no integer form and switch it off too.
+    e->stem_int = engine_forms(K, e->dtype).stem_int;
     if (e->stem_int) {
         ALLOC(e->xi_slot[0], (size_t)NC * 134 * 134 * 4, true);
         ALLOC(e->xi_slot[1], (size_t)NC * 134 * 134 * 4, true);
@@ -926,28 +818,12 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     auto add_conv = [&](const std::string& name, int cin, int cout, int k, int stride, int in_hw, float* in, float* outb,
                         float* residual, int relu, bool keep = false) -> int {
         ConvLayer L;
+        static_cast<LayerDesc&>(L) = conv_desc(K, e->dtype, NC, cin, cout, k, stride, in_hw, residual != nullptr);
         L.name = name;
-        L.cin = cin;
-        L.cout = cout;
-        L.kh = L.kw = k;
-        L.stride = stride;
-        L.in_hw = in_hw;
-        L.out_hw = in_hw / stride;
         L.in = in;
         L.out = outb;
         L.residual = residual;
         L.relu = relu;
-        if (k == 7) {
-            L.in_pad = 3; L.out_pad = 1; L.off = 0;
-            L.taps = 7; L.kw_taps = 1; L.chunk = 32; L.in_px_stride = 4;
-        } else if (k == 3) {
-            L.in_pad = 1; L.out_pad = 1; L.off = 0;
-            L.taps = 9; L.kw_taps = 3; L.chunk = cin; L.in_px_stride = cin;
-        } else {
-            L.in_pad = 1; L.out_pad = 1; L.off = 1;
-            L.taps = 1; L.kw_taps = 1; L.chunk = cin; L.in_px_stride = cin;
-        }
-        L.k_alg = (double)cin * k * k;
         std::vector<float> w, b;
         if (!fold_conv(br, L, w, b)) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at " + name);
         int r2 = PA_OK;
@@ -957,13 +833,8 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
         } else {
             r2 = (e->bf16 && k == 3) ? upload_bf16(e, &L.wgt, w) : upload(e, &L.wgt, w);
             if (r2) return r2;
-            // Winograd F(2x2, 3x3) for the fp32 stride-1 3x3 layers (wino.hip; measured per layer at 128 crops,
-            // profiles/r05_resnet_layer_times_wino_options.txt). Layer 4's 4 x 4 maps -- 64 tiles at 128 crops -- were slower there
-            // than on the direct kernel (117-160 against 84 us) until the kernel learnt to split K. PA_WINO=0: none (A/B);
-            // PA_WINO_MIN_HW=8: layers 1-3 only (A/B)
-            static const int wino_mode = getenv("PA_WINO") ? atoi(getenv("PA_WINO")) : 1;
-            static const int wino_min_hw = getenv("PA_WINO_MIN_HW") ? atoi(getenv("PA_WINO_MIN_HW")) : 4;
-            if (!e->bf16 && k == 3 && stride == 1 && wino_mode && L.out_hw >= wino_min_hw && L.out_hw % 4 == 0) {
+            if (wino_layer(K, e->dtype, L)) {
+                L.wino = true;
                 L.wino_bn = wino_pick_bn(cout, (long long)NC * (L.out_hw / 4) * (L.out_hw / 4), cin);
                 std::vector<float> ug(wino_weight_floats(cin, cout), 0.f);
                 if (!br.dry) wino_transform_weights(w.data(), cin, cout, L.wino_bn, ug.data());
@@ -972,18 +843,12 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
             }
             // PA_DTYPE_EMULATED_F32: the stride-2 3x3 openers of layers 2-4 on psgemm.hip (the stride-1 3x3 layers keep their exact
             // Winograd kernel: per layer the two measure the same, profiles/r06_pgemm_split_layers.txt)
-            if (e->emu && k == 3 && stride == 2 && cin % 32 == 0 && (r2 = upload_split(e, &L.split_wgt, w, cout, 9 * cin, false))) return r2;
+            L.split = e->emu && k == 3 && stride == 2 && cin % 32 == 0;
+            if (L.split && (r2 = upload_split(e, &L.split_wgt, w, cout, 9 * cin, false))) return r2;
             if (e->bf16 && k == 7 && (r2 = upload_bf16(e, &e->stem_wgt_bf16, w))) return r2;
             r2 = upload(e, &L.bias, b);
             if (r2) return r2;
         }
-        choose_tile(NC * L.out_hw * L.out_hw, cout, L.taps * L.chunk / ((e->bf16 && k == 3) ? 64 : 32), &L.tile, &L.splitk);
-        // tuning knobs (scripts/tune_tiles.py): PA_FORCE_TILE=0|1|2, PA_FORCE_SPLITK=n
-        if (const char* ft = getenv("PA_FORCE_TILE")) {
-            const int t = atoi(ft);
-            if (t >= 0 && t <= 4 && !(t == 0 && cout % 128 != 0)) { L.tile = (GemmTile)t; L.forced = true; }
-        }
-        if (const char* fs = getenv("PA_FORCE_SPLITK")) { L.splitk = std::max(1, atoi(fs)); L.forced = true; }
         e->convs.push_back(L);
         return PA_OK;
     };
@@ -1030,69 +895,48 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
                     memcpy(&wf[(size_t)o * k_all + k_main], &wd[(size_t)o * cin], sizeof(float) * cin);
                     bf[o] = (float)((double)keep_b[o] + (double)bd[o]);
                 }
+                L.ds.src = cur;
+                L.branch.c = cin;
+                L.branch.hw = hw_in[li];
+                L.branch.stride = stride;
                 if (e->bf16) {
                     rc = upload_bf16(e, &L.wgt, keep_w);  // [co][9 co]: the 3x3 alone
                     if (rc) return rc;
-                    rc = upload_bf16(e, &L.ds_wgt, wd);   // [co][cin]
+                    rc = upload_bf16(e, &L.ds.wgt, wd);   // [co][cin]
                     if (rc) return rc;
-                    ALLOC(L.ds_out, buf, true);
-                    // PA_BF16_DS_FUSE=0: the branch as its own GEMM (round 2-3), for A/B runs
-                    static const int ds_fuse = getenv("PA_BF16_DS_FUSE") ? atoi(getenv("PA_BF16_DS_FUSE")) : 1;
-                    ConvLayer& C1 = e->convs[e->convs.size() - 2];  // the block's stride-2 opener: same input, same output shape
-                    if (ds_fuse && C1.in == cur && C1.stride == 2 && C1.cout == co && C1.out_hw == hw_out && C1.out_pad == L.out_pad &&
-                        C1.chunk == cin && C1.chunk % 64 == 0 && !C1.forced) {
-                        if (ds_fuse == 2) {
-                            C1.ds_probe = true;  // (A/B: same opener launch, branch as its own GEMM -> bit-identical results)
-                        } else {
-                            C1.ds_next_wgt = L.ds_wgt;
-                            C1.ds_next_out = L.ds_out;
-                            L.ds_fused = true;
-                        }
-                    }
+                    ALLOC(L.ds.out, buf, true);
                 } else {
                     rc = upload(e, &L.wgt, wf);
                     if (rc) return rc;
                     // the same layer in Winograd form: the 3x3 alone on wino.hip, the 1x1/2 branch as a small GEMM of its own whose
                     // result the 3x3 adds as its residual (PA_WINO >= 1 and the map sizes the kernel is faster on; else the fused
                     // implicit GEMM above)
-                    static const int wino_mode = getenv("PA_WINO") ? atoi(getenv("PA_WINO")) : 1;
-                    static const int wino_ds = getenv("PA_WINO_DS") ? atoi(getenv("PA_WINO_DS")) : 1;
-                    static const int wino_min_hw = getenv("PA_WINO_MIN_HW") ? atoi(getenv("PA_WINO_MIN_HW")) : 4;
-                    if (wino_mode && wino_ds && hw_out >= wino_min_hw && hw_out % 4 == 0) {
+                    if (K.wino_ds && wino_layer(K, e->dtype, L)) {
+                        L.wino = true;
                         L.wino_bn = wino_pick_bn(co, (long long)NC * (hw_out / 4) * (hw_out / 4), co);
                         std::vector<float> ug(wino_weight_floats(co, co), 0.f);
                         if (!br.dry) wino_transform_weights(keep_w.data(), co, co, L.wino_bn, ug.data());
                         rc = upload(e, &L.wino_wgt, ug);
                         if (rc) return rc;
-                        rc = upload(e, &L.ds_wgt, wd);   // [co][cin] fp32
+                        rc = upload(e, &L.ds.wgt, wd);   // [co][cin] fp32
                         if (rc) return rc;
-                        if (e->emu && (rc = upload_split(e, &L.ds_split_wgt, wd, co, cin, false))) return rc;
-                        ALLOC(L.ds_out, buf, true);
-                        // The exact path: the block's stride-2 opener computes the branch on its centre tap (pigemm.hip's pgemm_branch_kernel)
-                        // and this layer adds ds_out without a launch (headline +1.7 %, profiles/opener_branch_parent_ab.md; results are
-                        // bit-identical either way). PA_F32_DS_FUSE=0: the branch as its own GEMM (A/B); PA_DS_SIDE=1
-                        // and PA_S2_PGEMM=0 keep the separate GEMM too. Blocks 2 and 3 only: block 4's opener runs split K on igemm.hip,
-                        // which has no such form
-                        static const int f32_ds_fuse = getenv("PA_F32_DS_FUSE") ? atoi(getenv("PA_F32_DS_FUSE")) : 1;
-                        static const int ds_side_knob = getenv("PA_DS_SIDE") ? atoi(getenv("PA_DS_SIDE")) : 0;
-                        static const int s2_pgemm_knob = getenv("PA_S2_PGEMM") ? atoi(getenv("PA_S2_PGEMM")) : 2;
-                        ConvLayer& C1 = e->convs[e->convs.size() - 2];  // the block's stride-2 opener: same input, same output shape
-                        if (f32_ds_fuse && !ds_side_knob && s2_pgemm_knob && !e->emu && li < 3 && C1.in == cur && C1.kh == 3 &&
-                            C1.stride == 2 && C1.cout == co && C1.out_hw == hw_out && C1.out_pad == L.out_pad && C1.chunk == cin && C1.cin == cin &&
-                            C1.in_hw == hw_in[li] && C1.in_pad == 1 && !C1.forced) {
-                            C1.ds_next_wgt = L.ds_wgt;
-                            C1.ds_next_out = L.ds_out;
-                            C1.ds_next_name = L.name;
-                            L.ds_fused = true;
-                        }
+                        L.branch.split = e->emu;
+                        if (e->emu && (rc = upload_split(e, &L.ds.split_wgt, wd, co, cin, false))) return rc;
+                        ALLOC(L.ds.out, buf, true);
                     }
+                }
+                // Where the branch is computed (engine_plan.h). bf16, PA_BF16_DS_FUSE=0: its own GEMM (round 2-3), for A/B runs. The exact
+                // path: the block's stride-2 opener computes it on its centre tap (pigemm.hip's pgemm_branch_kernel) and this layer adds
+                // ds.out without a launch (headline +1.7 %, profiles/opener_branch_parent_ab.md; results are bit-identical either way).
+                // PA_F32_DS_FUSE=0: the branch as its own GEMM (A/B); PA_DS_SIDE=1 and PA_S2_PGEMM=0 keep the separate GEMM too
+                ConvLayer& C1 = e->convs[e->convs.size() - 2];  // the block's stride-2 opener
+                L.branch.place = place_branch(K, e->dtype, C1, L, C1.in == cur, li);
+                if (L.branch.place == BRANCH_OPENER || L.branch.place == BRANCH_OPENER_PROBE) {
+                    C1.carries = L.branch.place;
+                    C1.carries_of = (int)e->convs.size() - 1;
                 }
                 rc = upload(e, &L.bias, bf);
                 if (rc) return rc;
-                L.in2 = cur;
-                L.in2_c = cin;
-                L.in2_hw = hw_in[li];
-                L.in2_stride = stride;
                 L.k_alg += cin;
             }
             rc = add_conv(pre + ".1.conv1", co, co, 3, 1, hw_out, outA, mid, nullptr, 1);
@@ -1114,21 +958,13 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
             memcpy(bp.data(), b, sizeof(float) * 1000);
         }
         ConvLayer& L = e->fc;
+        static_cast<LayerDesc&>(L) = fc_desc(K, PA_FEATURE_STRIDE);
         L.name = "fc";
-        L.cin = 512; L.cout = PA_FEATURE_STRIDE; L.kh = L.kw = 1; L.stride = 1;
-        L.in_hw = 1; L.out_hw = 1; L.in_pad = 0; L.out_pad = 0; L.off = 0;
-        L.taps = 1; L.kw_taps = 1; L.chunk = 512; L.in_px_stride = 512;
-        L.in = e->pooled; L.out = nullptr; L.residual = nullptr; L.relu = 0;
-        L.k_alg = 512.0 * 1000.0 / 1024.0;
+        L.in = e->pooled; L.out = nullptr; L.residual = nullptr;
         rc = upload(e, &L.wgt, wp);
         if (rc) return rc;
         rc = upload(e, &L.bias, bp);
         if (rc) return rc;
-        // 32 tiles of 64x64 only: split the 16 k-steps four ways (measured 16.9 / 14.5 / 12.3 us for 1 / 2 / 4)
-        L.tile = TILE_64x64;
-        L.splitk = 4;
-        L.forced = true;
-        if (const char* fs = getenv("PA_FC_SPLITK")) L.splitk = std::max(1, atoi(fs));
     }
     {  // Conv1d(1000 -> 512, k=S): [512][1000][S] -> [512][S][1024]
         const float* w = br.take((size_t)512 * 1000 * S);
@@ -1146,7 +982,7 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
         choose_tile(NC, 512, S * 32, &e->head_tile, &e->head_splitk);
         // 16 tiles x 224 k-steps: 16 splits of 14 steps beat 32 of 7 (26.2 vs 28.6 us incl. the reduce)
         if (e->head_splitk > 16) e->head_splitk = 16;
-        if (const char* hs = getenv("PA_HEAD_SPLITK")) e->head_splitk = std::max(1, atoi(hs));
+        if (K.head_splitk) e->head_splitk = K.head_splitk;
     }
     {
         const float* w2 = br.take(128 * 512);
@@ -1233,7 +1069,6 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     ALLOC(e->t1, (size_t)NC * e->t_stride, false);
     ALLOC(e->t2, (size_t)NC * e->t_stride, false);
 #undef ALLOC
-    if (const char* il = getenv("PA_INTERLEAVE")) e->interleave = atoi(il);
     HIPCHK(e, hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
@@ -1345,8 +1180,8 @@ int pa_backbone_trace(pa_engine* e, const float* x, int32_t n_crops, int32_t sta
         const size_t w = (size_t)L.out_hw + 2 * L.out_pad;
         src = L.out;
         bytes = n * w * w * L.cout * es;
-        has_branch = L.in2 != nullptr;
-        aux_src = L.ds_out;
+        has_branch = L.branch.place != BRANCH_NONE;
+        aux_src = L.ds.out;
     } else if (stage == 18) {
         src = e->pooled;
         bytes = n * 512 * sizeof(float);

@@ -1,6 +1,7 @@
 // Internal declarations shared by the HIP translation units and the C-ABI host
 // code. Not part of the public ABI (include/playaid_hip.h is).
 #pragma once
+#include "gemm_tile.h"   // GemmTile
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -78,10 +79,6 @@ struct GemmParams {
     // split-K form of the one-slice bf16 GEMM (bgemm.hip, splitk > 1): 4 zeroed tickets per output tile, left zeroed behind a launch
     int32_t* tickets;
 };
-
-// BM x BN (x BK; 32 unless named)
-enum GemmTile { TILE_128x128 = 0, TILE_128x64 = 1, TILE_64x64 = 2, TILE_128x64_K64 = 3, TILE_64x64_K64 = 4,
-                TILE_256x128 = 5 /* igemm_bf16.hip only */ };
 
 hipError_t launch_igemm(const GemmParams& p, GemmTile tile, hipStream_t s);
 // persistent form of the same engine for short tiles (pigemm.hip): conv mode, no residual / second source / split-K;

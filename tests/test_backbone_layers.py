@@ -20,7 +20,7 @@ Bars:
   * every stage: the border is exactly zero, and so is channel 3 of the model input.
 
 Cases (one engine per dtype and capacity, created and closed one after another). What each reaches, from
-``choose_tile`` and the launchers at the default knobs:
+``choose_tile`` and the launchers at the default knobs (the plan's side of it is pinned by tests/test_engine_plan.py):
   * 1 of 136 crops: every tile is partial; at M = 16..1024 rows choose_tile takes 64x64 tiles and the deepest split K,
     the Winograd layers their split-K tickets.
   * 35 of 136 (5 windows x 7): the bf16 patch kernel's 8-image tiles (8x8 maps) and 16-image tiles (4x4 maps) both end

@@ -160,9 +160,11 @@ def test_capacity_and_argument_errors(state_dict):
 
 
 def test_im2col_engine_still_agrees(engine, tmp_path):
-    """The thirteen stride-1 3x3 convs run on conv3x3_patch_kernel; PA_PATCH=0 (read once per process)
-    sends them back through the im2col engine, which stays the fallback for geometries the patch
-    kernel rejects. Both kernels must agree to fp32 rounding (different summation order)."""
+    """PA_PATCH=0 (read once per process) sends the fp32 stride-1 3x3 convs that would run on conv3x3_patch_kernel
+    back through the im2col engine, which stays the fallback for geometries the patch kernel rejects. At the
+    default PA_WINO=1 all thirteen of them run as Winograd and PA_PATCH changes no launch of this engine
+    (tests/test_engine_plan.py): the two processes must then agree like two runs of one build, and to fp32
+    rounding (different summation order) wherever the patch kernel does run."""
     import subprocess
     import sys
 
