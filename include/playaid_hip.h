@@ -1206,6 +1206,21 @@ int pa_encoder_trainer_read(pa_encoder_trainer* t, int32_t which, float* out_dev
 size_t pa_encoder_trainer_floats(const pa_encoder* h);
 int32_t pa_encoder_trainer_max_windows(const pa_encoder* h);
 
+/* Appended (the version stays 15): one stride-1 3x3 convolution (padding 1) on a 4 x 4 map as Winograd F(4x4, 3x3) taken apart
+ * (csrc/wino4.hip) -- an input transform, 36 grouped GEMMs on the exact persistent GEMM, an output transform with the epilogue:
+ * three launches on `stream`. The form the fp32 engine runs ResNet-18's layer 4 on from PA_WINO_F4_MIN crops; exposed for parity
+ * tests and measurements of single layers. Arguments as pa_wino_conv3x3 (x: float32[n][6][6][in_px_stride] with a zero ring, out:
+ * float32[n][4 + 2 out_pad][4 + 2 out_pad][out_px_stride], interior written) without `bn`; height and width must be 4, cin and cout
+ * multiples of 64. Filters: pa_wino4_transform_weights turns BatchNorm-folded [cout][ky][kx][cin] (host) into U[36][cout][cin]
+ * (host, pa_wino4_weight_floats floats; 0 for channel counts the form does not take), which the caller uploads. scratch: device,
+ * 16-byte aligned, scratch_floats >= 36 * ceil(n / 64) * 64 * (cin + cout). No K split: a crop's result does not depend on the
+ * batch it is in. PA_ERR_INVALID_ARG for anything else. Enqueue only. */
+size_t pa_wino4_weight_floats(int32_t cin, int32_t cout);
+int pa_wino4_transform_weights(const float* w_host, int32_t cin, int32_t cout, float* u_host);
+int pa_wino4_conv3x3(const float* x, const float* u, const float* bias, const float* residual, float* out, int32_t n, int32_t height,
+                     int32_t width, int32_t cin, int32_t cout, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad, int32_t act,
+                     int32_t res_after, float* scratch, size_t scratch_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ SOURCES = [
     ("patchconv.hip", []),
     ("patchconv_bf16.hip", []),
     ("wino.hip", []),
+    ("wino4.hip", []),
     ("stem.hip", []),
     ("stem_pool.hip", []),
     ("stem_pool_any.hip", []),

@@ -295,6 +295,9 @@ SYMBOLS = [
     ("pa_encoder_trainer_read", C.c_int, [_P, C.c_int32, _P, C.c_size_t, _P]),
     ("pa_encoder_trainer_floats", C.c_size_t, [_P]),
     ("pa_encoder_trainer_max_windows", C.c_int32, [_P]),
+    ("pa_wino4_weight_floats", C.c_size_t, [C.c_int32, C.c_int32]),
+    ("pa_wino4_transform_weights", C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    ("pa_wino4_conv3x3", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 10 + [_P, C.c_size_t, _P]),
 ]
 
 _lib = None

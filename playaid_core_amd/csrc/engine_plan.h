@@ -10,6 +10,10 @@
 
 namespace pa {
 
+// Crops per launch from which F(4x4, 3x3) taken apart (wino4.hip) replaces the fused F(2x2) kernel on 4 x 4 maps: measured per layer
+// in profiles/wino_f4_parent_ab.md. Clips of 40 and of 64 frames (80 and 128 crops) are on the same side of it.
+constexpr int WINO_F4_MIN_CROPS = 64;
+
 // One field per knob pa_api.hip obeys, with its default. (The launchers' own knobs stay private to their kernels.)
 struct EngineKnobs {
     // -- read once per process: every engine of a process sees the same values --
@@ -25,6 +29,8 @@ struct EngineKnobs {
     int wino = 1;           // PA_WINO=0: no Winograd form
     int wino_min_hw = 4;    // PA_WINO_MIN_HW: ... for maps at least this wide
     int wino_ds = 1;        // PA_WINO_DS=0: block-0 conv2 of layers 2-4 stays one implicit GEMM with the branch as its second K source
+    int wino_f4 = 1;        // PA_WINO_F4=0: the Winograd layers on 4 x 4 maps stay on the fused F(2x2) kernel at every batch
+    int wino_f4_min = WINO_F4_MIN_CROPS;  // PA_WINO_F4_MIN: ... below this many crops per launch
     int bf16_ds_fuse = 1;   // PA_BF16_DS_FUSE: the bf16 openers carry their block's branch; 0: its own GEMM, 2: own GEMM, the opener's tile as if fused
     int f32_ds_fuse = 1;    // PA_F32_DS_FUSE=0: the exact openers do not carry their block's branch
     // -- read at every pa_create / pa_create_from_arena --
@@ -61,6 +67,8 @@ inline EngineKnobs engine_knobs() {
         k.wino = env_int("PA_WINO", k.wino);
         k.wino_min_hw = env_int("PA_WINO_MIN_HW", k.wino_min_hw);
         k.wino_ds = env_int("PA_WINO_DS", k.wino_ds);
+        k.wino_f4 = env_int("PA_WINO_F4", k.wino_f4);
+        k.wino_f4_min = env_int("PA_WINO_F4_MIN", k.wino_f4_min);
         k.bf16_ds_fuse = env_int("PA_BF16_DS_FUSE", k.bf16_ds_fuse);
         k.f32_ds_fuse = env_int("PA_F32_DS_FUSE", k.f32_ds_fuse);
         return k;
@@ -126,6 +134,7 @@ struct LayerDesc {
     bool forced = false;            // ... pinned by PA_FORCE_* / the fc's own choice, else chosen per launch
     bool adds_residual = false;     // adds a residual tensor of its own (not the stored branch)
     bool wino = false;              // has its filters in wino.hip's layout: fp32 stride-1 3x3 layers run as Winograd F(2x2, 3x3)
+    bool wino4 = false;             // ... and in wino4.hip's too: a 4 x 4 map runs as F(4x4, 3x3) taken apart from wino_f4_min crops on
     bool split = false;             // emulated_f32: has its weights as three bf16 slices and runs on psgemm.hip
     struct {
         BranchPlace place = BRANCH_NONE;
@@ -194,6 +203,12 @@ inline bool wino_layer(const EngineKnobs& k, ComputeDtype dt, const LayerDesc& L
     return dt != DT_BF16 && L.kh == 3 && L.stride == 1 && k.wino && L.out_hw >= k.wino_min_hw && L.out_hw % 4 == 0;
 }
 
+// ... of which the 4 x 4 maps (layer 4) also get their filters as 36 GEMM images: F(4x4, 3x3) taken apart (wino4.hip, DESIGN.md
+// 5.1d), if the engine's full batch reaches the threshold at all. PA_WINO_F4=0: never (A/B)
+inline bool wino4_layer(const EngineKnobs& k, ComputeDtype dt, const LayerDesc& L, int max_crops) {
+    return wino_layer(k, dt, L) && k.wino_f4 && L.out_hw == 4 && L.in_hw == 4 && L.cin % 64 == 0 && L.cout % 64 == 0 && max_crops >= k.wino_f4_min;
+}
+
 // Can `opener` compute the branch that `conv2` adds? Same input, same output shape, padding and chunk, tile not pinned;
 // `extras`: what the dtype's fused kernel asks beyond that
 inline bool opener_can_carry(const LayerDesc& opener, const LayerDesc& conv2, bool same_input, bool extras) {
@@ -252,6 +267,7 @@ struct ConvPlan {
     bool tile_256 = false;        // bf16 im2col (also behind a refusing patch kernel): promote `tile` to 256x128
     int patch_bm = 0;             // CONV_PATCH: rows per tile
     int pgemm_bm = 0;             // CONV_PGEMM: 64, or 0 = the launcher's own choice of tile height
+    bool wino_f4 = false;         // CONV_WINO: as F(4x4, 3x3) taken apart -- three launches (wino4.hip) instead of the fused F(2x2) kernel
     BranchLaunch branch = BL_NONE;
     LaunchAccount acct;           // of the main launch, a branch it carries included
     BranchPlan branch_gemm;       // BL_GEMM_BEFORE, BL_GEMM_BEHIND, and fp32 BL_ON_OPENER's fallback
@@ -306,6 +322,10 @@ inline ConvPlan plan_conv(const EngineKnobs& k, ComputeDtype dt, const LayerDesc
     } else if (L.wino && !second_k) {
         P.form = CONV_WINO;
         P.acct.flops_executed = P.acct.flops * 4.0 / 9.0;
+        if (L.wino4 && k.wino_f4 && ncrops >= k.wino_f4_min) {   // 36 products per 4 x 4 map where the direct form has 144
+            P.wino_f4 = true;
+            P.acct.flops_executed = P.acct.flops / 4.0;
+        }
     } else if (k.patch && L.kh == 3 && L.stride == 1) {
         // stride-1 3x3 layers without the Winograd form: input patch resident in LDS across the nine taps (patchconv.hip);
         // PA_PATCH=0 keeps the generic im2col engine for A/B runs

@@ -30,6 +30,7 @@ struct ConvLayer : LayerDesc {
     float* wgt = nullptr;   // device [cout][taps*chunk]; block-0 conv2 of layers 2-4, fp32: [W2 | Wd], the branch as extra K read from `ds.src`
     float* wino_wgt = nullptr;  // LayerDesc::wino: the filters in wino.hip's layout
     int wino_bn = 0;            // ... laid out for workgroups of this many output channels (wino_pick_bn at the full batch)
+    float* wino4_wgt = nullptr; // LayerDesc::wino4: the filters as wino4.hip's 36 GEMM images
     float* bias = nullptr;  // device [cout]
     unsigned short* split_wgt = nullptr;  // LayerDesc::split: three bf16 slices per weight in psgemm.hip's stage-image order
     // conv2 of block 0 of layers 2-4: its 1x1/2 downsample branch (LayerDesc::branch says where it is computed)
@@ -101,6 +102,8 @@ struct pa_engine {
     float* slab = nullptr;
     size_t slab_floats = 0;
     float* wino_tickets = nullptr;  // int32[2][WINO_TICKETS], zero between launches: split-K tickets of the Winograd kernel, one set per half batch
+    float* wino4_scratch = nullptr;  // V and M of wino4.hip, one region of wino4_region floats per interleaved half batch
+    size_t wino4_region = 0;
     std::vector<ConvLayer> convs;  // stem + the sixteen 3x3 convs (a block-0 downsample belongs to its conv2's entry)
     ConvLayer fc;
     float* stem_wgt_bf16 = nullptr;  // bf16 path: the folded stem weights [64][224] as bf16
@@ -427,6 +430,16 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
         hipError_t pe = hipErrorInvalidValue;   // a launcher's refusal: the next form takes the launch
         if (P.form == CONV_PSGEMM) {
             pe = launch_psgemm(p, L.split_wgt, (size_t)ncrops * out_crop, 0, s);
+        } else if (P.form == CONV_WINO && P.wino_f4) {   // F(4x4, 3x3) taken apart: three launches in this one profile row
+            Wino4Params q{};
+            q.act = p.act; q.wgt = L.wino4_wgt; q.bias = p.bias; q.residual = p.residual; q.out = p.out;
+            q.v = e->wino4_scratch + (slab_off ? e->wino4_region : 0);
+            q.m = q.v + (size_t)36 * wino4_rows(ncrops) * L.cin;
+            q.n_img = ncrops; q.cin = L.cin; q.cout = L.cout;
+            q.in_px_stride = p.in_px_stride; q.in_row_stride = p.in_row_stride; q.in_img_stride = p.in_img_stride;
+            q.out_px_stride = p.out_px_stride; q.out_row_stride = p.out_row_stride; q.out_img_stride = p.out_img_stride; q.out_pad = p.out_pad;
+            q.relu = p.relu; q.res_after = p.res_after;
+            pe = launch_wino4_conv3x3(q, s);
         } else if (P.form == CONV_WINO) {
             WinoParams q = wino_params(p, ncrops, L.out_hw, L.out_hw, L.cin, L.wino_wgt, L.wino_bn);
             if (e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
@@ -803,7 +816,9 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     // arena capacity: the folded tensors are the blob's plus zero padding (stem K 147 -> 224, fc and
     // Conv1d 1000 -> 1024) and 256-byte alignment per tensor; 1.25x + 1 MiB covers every (S, A)
     // (+ 16 / 9 of the 3x3 filters once more: the Winograd layout of the fp32 stride-1 3x3 layers, kept beside the direct one)
+    // (+ 36 / 9 of layer 4's three stride-1 filters where F(4x4, 3x3) taken apart can engage: engine_plan.h's wino4_layer)
     e->arena_cap = pa_weight_blob_bytes(S, A) / 4 * 13 + (1u << 20);
+    if (e->dtype != DT_BF16 && K.wino && K.wino_f4 && NC >= K.wino_f4_min) e->arena_cap += 3 * (wino4_weight_floats(512, 512) * sizeof(float) + 256);
     {
         void* ar = nullptr;
         HIPCHK(e, hipMalloc(&ar, e->arena_cap));
@@ -815,6 +830,15 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     const float* blob_f = e->adopt ? dry_source : reinterpret_cast<const float*>(hdr + 8);
     BlobReader br{blob_f, 0, blob_float_count(S, A), e->adopt};
     std::vector<float> keep_w, keep_b;  // host copy of the last conv added with keep=true (not uploaded yet)
+    // a Winograd layer on a 4 x 4 map: its filters once more as the 36 GEMM images of F(4x4, 3x3) taken apart (wino4.hip), beside the
+    // F(2x2) image, which serves the batches below the threshold and PA_WINO_F4=0 at run time
+    auto add_wino4 = [&](ConvLayer& L, const std::vector<float>& w) -> int {
+        if (!wino4_layer(K, e->dtype, L, NC)) return PA_OK;
+        L.wino4 = true;
+        std::vector<float> u4(wino4_weight_floats(L.cin, L.cout), 0.f);
+        if (!br.dry) wino4_transform_weights(w.data(), L.cin, L.cout, u4.data());
+        return upload(e, &L.wino4_wgt, u4);
+    };
     auto add_conv = [&](const std::string& name, int cin, int cout, int k, int stride, int in_hw, float* in, float* outb,
                         float* residual, int relu, bool keep = false) -> int {
         ConvLayer L;
@@ -840,6 +864,7 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
                 if (!br.dry) wino_transform_weights(w.data(), cin, cout, L.wino_bn, ug.data());
                 r2 = upload(e, &L.wino_wgt, ug);
                 if (r2) return r2;
+                if ((r2 = add_wino4(L, w))) return r2;
             }
             // PA_DTYPE_EMULATED_F32: the stride-2 3x3 openers of layers 2-4 on psgemm.hip (the stride-1 3x3 layers keep their exact
             // Winograd kernel: per layer the two measure the same, profiles/r06_pgemm_split_layers.txt)
@@ -918,6 +943,7 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
                         if (!br.dry) wino_transform_weights(keep_w.data(), co, co, L.wino_bn, ug.data());
                         rc = upload(e, &L.wino_wgt, ug);
                         if (rc) return rc;
+                        if ((rc = add_wino4(L, keep_w))) return rc;
                         rc = upload(e, &L.ds.wgt, wd);   // [co][cin] fp32
                         if (rc) return rc;
                         L.branch.split = e->emu;
@@ -1046,6 +1072,10 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
             need = std::max(need, (size_t)256 * 512 * 32);
             ALLOC(e->wino_tickets, (size_t)2 * WINO_TICKETS, true);
         }
+        // V and M of F(4x4, 3x3) taken apart (wino4.hip)
+        for (const ConvLayer& L : e->convs)
+            if (L.wino4_wgt) e->wino4_region = std::max(e->wino4_region, (size_t)36 * wino4_rows(NC) * (L.cin + L.cout));
+        if (e->wino4_region) ALLOC(e->wino4_scratch, e->wino4_region * (K.interleave ? 2 : 1), false);
         need *= 2;  // one region per interleaved half batch
         e->slab_floats = need;
         ALLOC(e->slab, need, false);

@@ -78,6 +78,10 @@ struct GemmParams {
     unsigned long long* clk;  // ablation builds only: in-kernel clock stamps
     // split-K form of the one-slice bf16 GEMM (bgemm.hip, splitk > 1): 4 zeroed tickets per output tile, left zeroed behind a launch
     int32_t* tickets;
+    // grouped form of the exact persistent GEMM (pigemm.hip's pgemm_group_kernel, set by launch_pgemm_grouped): `grp_tiles` consecutive
+    // pixel tiles share one [N][ktot] weight image, the next ones read the image grp_wgt_bytes further on; grp_magic = ceil(2^32 / grp_tiles)
+    int32_t grp_tiles, grp_wgt_bytes;
+    uint32_t grp_magic;
 };
 
 hipError_t launch_igemm(const GemmParams& p, GemmTile tile, hipStream_t s);
@@ -85,6 +89,12 @@ hipError_t launch_igemm(const GemmParams& p, GemmTile tile, hipStream_t s);
 // bm = 128 | 64, 64 output channels per tile; results equal to launch_igemm up to where the bias enters the sum
 // p.wgt2 / p.out2 set: the opener form (3x3, stride 2, whole-pixel taps, ReLU or none, 64 x 64 tiles), hipErrorInvalidValue for anything else
 hipError_t launch_pgemm(const GemmParams& p, int bm, hipStream_t s);
+// `groups` independent products out[g] = a[g] . w[g]^T in ONE launch of the same kernel (no bias, no activation, no K split): a =
+// [groups][rows][K], w = [groups][N][K], out = [groups][rows][N], all fp32, 16-byte aligned; rows a multiple of 64, K of 32, N of 64.
+// A pixel tile's first row gives its group, and the group moves the weight base by one scalar offset (rows are whole tiles, so the
+// activation and output rows of all groups are one contiguous matrix). tile: 1 = 64 x 64, 2 = 128 x 64 (rows % 128 == 0), 3 = 128 x 32
+// (the same), 0 = the default. A row's bits depend on neither the tile nor the other rows.
+hipError_t launch_pgemm_grouped(const float* a, const float* w, float* out, int groups, int rows, int K, int N, int tile, hipStream_t s);
 // "emulated fp32" form of the persistent GEMM (psgemm.hip): fp32 activations, the weights as three bf16 slices in the kernel's
 // stage-image layout (psgemm_pack_weights, psgemm_weight_elems of them), six bf16 matrix instructions per fp32 product, fp32
 // accumulate. Conv mode; bias, ReLU / SiLU; out_floats = floats from p.out to the end of its buffer (the store descriptor's bounds).
@@ -193,6 +203,30 @@ int wino_pick_bn(int cout, long long n_sb, int cin_split = 0);
 // w [cout][ky][kx][cin] (host) -> ug [wino_weight_floats] (host)
 void wino_transform_weights(const float* w, int cin, int cout, int bn, float* ug);
 hipError_t launch_wino3x3(const WinoParams& p, hipStream_t s);
+
+// stride-1 3x3 convolution on a 4 x 4 map as Winograd F(4x4, 3x3) taken apart (wino4.hip): input transform, 36 grouped GEMMs on
+// pigemm.hip, output transform + epilogue -- three launches on the stream. Zero-bordered NHWC input (border 1), cin and cout
+// multiples of 64; epilogue as WinoParams. v, m: scratch of 36 * wino4_rows(n_img) * cin and ... * cout floats.
+struct Wino4Params {
+    const float* act;       // first channel of padded pixel (0, 0) of image 0
+    const float* wgt;       // wino4_transform_weights' image of the filters: U[36][cout][cin]
+    const float* bias;      // [cout] or nullptr
+    const float* residual;  // addressed like out, or nullptr
+    float* out;             // first channel of padded pixel (0, 0) of image 0
+    float* v;               // scratch: the transformed input V[36][rows][cin]
+    float* m;               // scratch: the products M[36][rows][cout]
+    int32_t n_img, cin, cout;
+    int32_t in_px_stride, in_row_stride, in_img_stride;      // floats
+    int32_t out_px_stride, out_row_stride, out_img_stride, out_pad;
+    int32_t relu, res_after;  // as GemmParams
+    int32_t tile;             // the GEMM's tile (launch_pgemm_grouped), 0 = the default
+    int32_t rows;             // set by the launcher: wino4_rows(n_img)
+};
+size_t wino4_weight_floats(int cin, int cout);
+int wino4_rows(int n_img);   // crops padded to the GEMM's row tile
+// w [cout][ky][kx][cin] (host) -> u [wino4_weight_floats] (host)
+void wino4_transform_weights(const float* w, int cin, int cout, float* u);
+hipError_t launch_wino4_conv3x3(const Wino4Params& p, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // crop preprocessing (preprocess.hip)

@@ -59,9 +59,18 @@ template <int N> __device__ __forceinline__ void pg_wait_vm() { wait_vmcnt<(N > 
 // BN x 32 block of p.wgt2 ([N][chunk]) and the wave issues its matrix instructions a second time, with the pixel operand it holds
 // already, into a second accumulator set that starts from zero -- the k order of the branch as a GEMM of its own (channel chunk,
 // eight-wide group, lane half), so p.out2 (no bias, no activation, addressed like p.out) has that GEMM's bits.
-template <int BM, int BN, bool SILU, bool STAMP, bool UP, bool DS>
+//
+// GRP (pgemm_group_kernel: the 36 products of Winograd F(4x4, 3x3) taken apart, wino4.hip): p.grp_tiles consecutive pixel tiles are
+// one group with a weight image [N][ktot] of its own, p.grp_wgt_bytes behind the previous group's. The group of a tile is one scalar
+// division where the tile's row offsets are computed (rows_of) and enters the weight copies as part of their scalar offset; a
+// workgroup's run of tiles may cross groups. The sums run in FOUR accumulator chains, one per eight-wide k group of a k-step (chain
+// c: k with (k % 32) / 8 == c, ascending), added as (c0 + c1) + (c2 + c3) in front of the stores: the Winograd output transform
+// multiplies the rounding of these sums by up to 64, and one chain of K = 512 fp32 additions put the layer at 1e-5 of its largest
+// output where four chains of 128 stay near 4e-6. A row's bits depend on neither the tile shape nor the other rows.
+template <int BM, int BN, bool SILU, bool STAMP, bool UP, bool DS, bool GRP = false>
 __device__ __forceinline__ void pgemm_body(const GemmParams& p) {
     static_assert(!DS || (!UP && !STAMP && !SILU), "the branch form is the ResNet openers': ReLU, no up-sampled copy");
+    static_assert(!GRP || (!UP && !STAMP && !SILU && !DS), "the grouped form is a plain product");
     // STAMP (scripts/pgemm_stamps.py): s_memtime per wave at entry [0], after the prologue [1], per tile t < 15 at 2 + 4 t:
     // tile start, first barrier passed, last matrix instruction issued, stores issued; exit [63]
     auto stamp = [&](int i) {
@@ -95,6 +104,11 @@ __device__ __forceinline__ void pgemm_body(const GemmParams& p) {
             const float* pw2_ = p.wgt2;
             float* po2_ = p.out2;
             asm volatile("" ::"s"(pw2_), "s"(po2_));
+        }
+        if (GRP) {
+            const int g0 = p.grp_tiles, g1 = p.grp_wgt_bytes;
+            const unsigned g2 = p.grp_magic;
+            asm volatile("" ::"s"(g0), "s"(g1), "s"(g2));
         }
     }
     if (nt == 0) return;
@@ -157,9 +171,14 @@ __device__ __forceinline__ void pgemm_body(const GemmParams& p) {
     // issue cursor: tile, (ky, kx, kc) of its next k-step; the tile's row offsets
     IssueCursor cur{run.first, 0, 0, 0, 0};
     int a_off[A_ROWS];   // bytes
+    int w_grp = 0;       // GRP: byte offset of the tile's weight image
     auto rows_of = [&](int tile_m) {
 #pragma unroll
         for (int i = 0; i < A_ROWS; ++i) a_off[i] = in_offset(tile_m * BM + 32 * i);
+        if (GRP) {
+            int rem;
+            w_grp = pgemm_sdiv(tile_m, p.grp_tiles, p.grp_magic, rem) * p.grp_wgt_bytes;
+        }
     };
     rows_of(cur.tile);
     stamp(61);
@@ -169,7 +188,7 @@ __device__ __forceinline__ void pgemm_body(const GemmParams& p) {
         const int tapoff = cur.tap_offset(p) * 4;
 #pragma unroll
         for (int i = 0; i < A_ROWS; ++i) glds16(act_rs, a_off[i], tapoff, As_w + i * 1024);
-        const int koff = ((cur.ky * p.kw_taps + cur.kx) * p.chunk + cur.kc) * 4;
+        const int koff = ((cur.ky * p.kw_taps + cur.kx) * p.chunk + cur.kc) * 4 + (GRP ? w_grp : 0);
 #pragma unroll
         for (int i = 0; i < B_ROWS; ++i) glds16(wgt_rs, b_off[i], koff, Bs_w + i * 1024);
         if (DS && cur.ky == 1 && cur.kx == 1) {   // a centre-tap step: B_ROWS more copies, LAST of the step's (pre() counts on that)
@@ -212,6 +231,7 @@ __device__ __forceinline__ void pgemm_body(const GemmParams& p) {
 
     f32x16 acc[MI];
     f32x16 acc2[MI];   // DS: the branch's sums
+    f32x16 accg[GRP ? 3 : 1][MI];   // GRP: chains 1..3 (chain 0 is acc)
     // one k-step on the stage at byte offset sb: 16 matrix instructions per 32-pixel block, operands read one k group
     // ahead; the eight read addresses in one burst of vector adds before the first of them
     // branch_c (DS): 0 = not a centre-tap step, 1 = the centre tap's first step (the branch's accumulators start from zero), 2 = its others:
@@ -246,15 +266,16 @@ __device__ __forceinline__ void pgemm_body(const GemmParams& p) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
                 const f32x4 a4 = af[kk & 1][mi], b4 = bf[kk & 1];
-                acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.x, a4.x, FIRST && kk == 0 ? biasv : acc[mi], 0, 0, 0);
-                acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.y, a4.y, acc[mi], 0, 0, 0);
+                f32x16& acc_k = GRP && kk > 0 ? accg[GRP ? kk - 1 : 0][mi] : acc[mi];   // (GRP: the k group's own chain; its bias is zero)
+                acc_k = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.x, a4.x, FIRST && (GRP || kk == 0) ? biasv : acc_k, 0, 0, 0);
+                acc_k = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.y, a4.y, acc_k, 0, 0, 0);
                 if (mi == 0 && kk + 1 < 4) {
                     __builtin_amdgcn_sched_barrier(0);
                     if (kk == 0) { PG_FRAGS(1, 1); } else if (kk == 1) { PG_FRAGS(0, 2); } else { PG_FRAGS(1, 3); }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.z, a4.z, acc[mi], 0, 0, 0);
-                acc[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.w, a4.w, acc[mi], 0, 0, 0);
+                acc_k = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.z, a4.z, acc_k, 0, 0, 0);
+                acc_k = __builtin_amdgcn_mfma_f32_32x32x2f32(b4.w, a4.w, acc_k, 0, 0, 0);
                 if (BR) {
                     const f32x4 c4 = b2f[kk & 1];
                     acc2[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(c4.x, a4.x, BR == 1 && kk == 0 ? zero16 : acc2[mi], 0, 0, 0);
@@ -315,6 +336,7 @@ __device__ __forceinline__ void pgemm_body(const GemmParams& p) {
         // epilogue of the tile, straight from the accumulators: lane = pixel lr of its 32-pixel block, channels ch0 + 8 g + 0..3
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
+            if (GRP) acc[mi] = (acc[mi] + accg[0][mi]) + (accg[GRP ? 1 : 0][mi] + accg[GRP ? 2 : 0][mi]);
             const int m_base = tile_m * BM + wm * (BM / WM) + mi * 32;
             const int o_off = out_offset(m_base);
             float* o_px = p.out + o_off;
@@ -375,6 +397,12 @@ __global__ __launch_bounds__(256, 2) void pgemm_kernel(const GemmParams p) {
 // workgroups per CU)
 __global__ __launch_bounds__(256, 2) void pgemm_branch_kernel(const GemmParams p) {
     pgemm_body<64, 64, false, false, false, true>(p);
+}
+
+// the grouped form: no bias, no activation (launch_pgemm_grouped)
+template <int BM, int BN>
+__global__ __launch_bounds__(256, 2) void pgemm_group_kernel(const GemmParams p) {
+    pgemm_body<BM, BN, false, false, false, false, true>(p);
 }
 
 // Conv mode of GemmParams (no gather, no second source, no residual, no split-K); bm = 128 | 64 | 0 (chosen here).
@@ -460,6 +488,53 @@ hipError_t launch_pgemm(const GemmParams& p_in, int bm, hipStream_t s) {
     else if (bm == 128) PA_PG_LAUNCH(128, 64);
     else PA_PG_LAUNCH(64, 64);
 #undef PA_PG_LAUNCH
+    return hipGetLastError();
+}
+
+// The groups as "images" of a 1x1 convolution over a rows x 1 map: pixel m = (group, row), whole tiles per group, so activations and
+// outputs are one contiguous [groups * rows][K] / [..][N] matrix and only the weight image moves with the group. Grid as launch_pgemm.
+hipError_t launch_pgemm_grouped(const float* a, const float* w, float* out, int groups, int rows, int K, int N, int tile, hipStream_t s) {
+    auto mis = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) != 0; };
+    if (!a || !w || !out || mis(a) || mis(w) || mis(out) || groups < 1 || rows < 64 || rows % 64 || rows >= (1 << 16) || K < 32 || K % 32 || N < 64 || N % 64 ||
+        tile < 0 || tile > 3)
+        return hipErrorInvalidValue;
+    // byte offsets inside the buffer descriptors are 32-bit
+    if ((long long)groups * rows * K * 4 >= (1ll << 31) || (long long)groups * N * K * 4 >= (1ll << 31) || (long long)groups * rows * N >= (1ll << 31))
+        return hipErrorInvalidValue;
+    // 64 x 64 tiles: the fastest of the three at ResNet-18's layer 4 and 128 crops (profiles/wino_f4_parent_ab.md); the 128-row tiles
+    // need groups of whole 128-row tiles
+    if (tile == 0) tile = 1;
+    if (tile != 1 && rows % 128) tile = 1;
+    const int bm = tile == 1 ? 64 : 128, bn = tile == 3 ? 32 : 64;
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.act = a; p.wgt = w; p.out = out;
+    p.M = groups * rows; p.N = N; p.ktot = K;
+    p.taps = 1; p.kw_taps = 1; p.chunk = K;
+    p.howo = rows; p.wo = rows;
+    p.in_px_stride = K; p.in_row_stride = rows * K; p.in_img_stride = rows * K; p.stride = 1;
+    p.out_px_stride = N; p.out_row_stride = rows * N; p.out_img_stride = rows * N;
+    p.splitk = 1;
+    if (persistent_plan(p) != hipSuccess) return hipErrorInvalidValue;
+    p.tiles_n = N / bn;
+    p.tiles_m = p.M / bm;
+    if (p.tiles_n > 64) return hipErrorInvalidValue;
+    p.grp_tiles = rows / bm;
+    p.grp_wgt_bytes = N * K * 4;
+    p.grp_magic = (unsigned)std::min<unsigned long long>(((1ull << 32) + p.grp_tiles - 1) / p.grp_tiles, 0xffffffffull);
+    // Workgroups per channel column and XCD: up to 96 per XCD -- the 64 x 64 kernel's registers and 48 KiB of LDS let three share a CU --
+    // so that at ResNet-18's layer 4 and 128 crops (9 pixel tiles x 8 columns per XCD) every workgroup has ONE tile: 576 workgroups took
+    // 43.9 us where 512, an eighth of them with two tiles, took 46.1 (the whole layer, profiles/wino_f4_parent_ab.md)
+    const int share = (p.tiles_m + 7) / 8;
+    int lm = 96 / p.tiles_n;
+    static const int lm_force = getenv("PA_PGEMM_GROUP_LM") ? atoi(getenv("PA_PGEMM_GROUP_LM")) : 0;   // A/B: workgroups per channel column and XCD
+    if (lm_force > 0) lm = lm_force;
+    lm = lm < 1 ? 1 : (lm > share ? share : lm);
+    p.pg_per = lm * p.tiles_n;
+    const int grid = p.pg_per * 8;
+    if (tile == 1) hipLaunchKernelGGL((pgemm_group_kernel<64, 64>), dim3(grid), dim3(256), 0, s, p);
+    else if (tile == 2) hipLaunchKernelGGL((pgemm_group_kernel<128, 64>), dim3(grid), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((pgemm_group_kernel<128, 32>), dim3(grid), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

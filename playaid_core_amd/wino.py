@@ -73,3 +73,49 @@ def conv3x3(x_pad: torch.Tensor, ug: torch.Tensor, cin: int, cout: int, bias=Non
     if rc:
         raise ValueError(f"pa_wino_conv3x3: status {rc}")
     return out
+
+
+# ---- F(4x4, 3x3) taken apart (``csrc/wino4.hip``, ``pa_wino4_*``): 4 x 4 maps, cin and cout multiples of 64 ----
+
+
+def transform_weights_f4(w_oihw: np.ndarray) -> np.ndarray:
+    """[cout, cin, 3, 3] (BatchNorm already folded) -> U[36, cout, cin] (float32, host): the 36 GEMM weight images."""
+    lib = _lib.load()
+    w = np.ascontiguousarray(np.asarray(w_oihw, dtype=np.float32).transpose(0, 2, 3, 1))  # [cout][ky][kx][cin]
+    cout, cin = w.shape[0], w.shape[3]
+    n = lib.pa_wino4_weight_floats(cin, cout)
+    if n == 0:
+        raise ValueError("cin and cout must be multiples of 64")
+    u = np.empty(n, dtype=np.float32)
+    rc = lib.pa_wino4_transform_weights(w.ctypes.data_as(C.c_void_p), cin, cout, u.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise ValueError(f"pa_wino4_transform_weights: {rc}")
+    return u.reshape(36, cout, cin)
+
+
+def scratch_floats_f4(n: int, cin: int, cout: int) -> int:
+    """Floats of device scratch one ``conv3x3_f4`` launch over ``n`` images needs (V and M, rows padded to 64)."""
+    return 36 * ((n + 63) // 64 * 64) * (cin + cout)
+
+
+def conv3x3_f4(x_pad: torch.Tensor, u: torch.Tensor, cin: int, cout: int, bias=None, residual=None, out=None, out_pad: int = 1,
+               act: int = 0, res_after: bool = False, out_px_stride: int = None, scratch: torch.Tensor = None) -> torch.Tensor:
+    """x_pad float32[n, 6, 6, C >= cin] (device, zero ring) -> out float32[n, 4 + 2 out_pad, 4 + 2 out_pad, C'] (interior written).
+    Three launches on the current stream; ``scratch``: float32 device tensor of at least ``scratch_floats_f4`` elements."""
+    lib = _lib.load()
+    if x_pad.dtype != torch.float32 or not x_pad.is_cuda or not x_pad.is_contiguous() or x_pad.dim() != 4:
+        raise ValueError("x_pad: contiguous float32[n, 6, 6, C] on the device")
+    n, hp, wp, cs = x_pad.shape
+    h, w = hp - 2, wp - 2
+    ops = out_px_stride or cout
+    if out is None:
+        out = torch.zeros((n, h + 2 * out_pad, w + 2 * out_pad, ops), dtype=torch.float32, device=x_pad.device)
+    if scratch is None:
+        scratch = torch.empty(scratch_floats_f4(n, cin, cout), dtype=torch.float32, device=x_pad.device)
+    ptr = lambda t_: C.c_void_p(t_.data_ptr()) if t_ is not None else C.c_void_p(0)
+    stream = C.c_void_p(torch.cuda.current_stream(x_pad.device).cuda_stream)
+    rc = lib.pa_wino4_conv3x3(ptr(x_pad), ptr(u), ptr(bias), ptr(residual), ptr(out), n, h, w, cin, cout, cs, out.shape[3], out_pad, int(act),
+                              int(bool(res_after)), ptr(scratch), scratch.numel(), stream)
+    if rc:
+        raise ValueError(f"pa_wino4_conv3x3: status {rc}")
+    return out
