@@ -1221,6 +1221,64 @@ int pa_wino4_conv3x3(const float* x, const float* u, const float* bias, const fl
                      int32_t width, int32_t cin, int32_t cout, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad, int32_t act,
                      int32_t res_after, float* scratch, size_t scratch_floats, void* stream);
 
+/* Appended (the version stays 15): the reference's training augmentation of 128 x 128 crops, augment_char_crop
+ * (dataset_utils.py:141-252), as ONE launch over crops that are already on the device (csrc/augment.hip).
+ * Output crop i reads source crop params[i].src of src uint8[n_src][128][128][3] (RGB) and applies, in A.Compose's order:
+ *   1 HorizontalFlip        flip != 0: source column 127 - u
+ *   2 BrightnessContrast    table trunc(clip((float)k * alpha + beta * 255.f, 0, 255)), fp32, no fused multiply-add
+ *   3 Blur                  blur_k 2 or 3 (0: none): box filter over step 2's values, window u - 1 .. u - 1 + (k - 1) (OpenCV's
+ *                           anchor k / 2), reflect-101 border, sum / k^2 rounded to nearest, ties to even
+ *   4 HueSaturationValue    skipped when the three shifts are all exactly 0; else OpenCV's 8-bit integer RGB -> HSV (H 0..179),
+ *                           tables trunc((k + hue_shift) mod 180) and trunc(clip(k + shift, 0, 255)) in fp64, then HSV -> RGB in
+ *                           fp32: h * (6.f / 180.f), s and v * (1.f / 255.f), OpenCV's sector form, rint(x * 255.f) clipped
+ *   5 GaussNoise            noise_sigma > 0: per channel trunc(clip((float)byte + sigma * z, 0, 255)); z from the counter hash below
+ *   6 PixelDropout          pixel_drop_thr != 0: all three bytes 0 where hash(stream 1, v * 128 + u) < thr
+ *   7 CoarseDropout         n_holes holes of 4 x 4 at (holes[2 j], holes[2 j + 1]) = (x, y), zeroed
+ *   8 ChannelDropout        channel c zeroed where channel_mask bit c is set (bit 0 = R)
+ *   9 Downscale + RandomSizedCrop, both nearest neighbour, composed by the host: output pixel (x, y) is the chain's value at
+ *                           (u, v) = (xmap[x], ymap[y])
+ * Counter hash (mix as in the encoder trainer's dropout): k = mix((uint32)key + 0x9e3779b9); k = mix(k ^ (uint32)(key >> 32));
+ * ks = mix(k ^ ((uint32)(stream + 1) * 0x85ebca6b)); r(i) = mix(mix((uint32)i ^ ks) + ks). Stream 0 is the noise with
+ * i = (v * 128 + u) * 3 + c, stream 1 the pixel dropout with i = v * 128 + u: neither depends on the launch geometry.
+ * z = q[r >> 22] + (float)(r & 0x3fffff) * 2^-22 * (q[(r >> 22) + 1] - q[r >> 22]) with q the handle's table of 1025 normal
+ * quantiles (pa_augment_quantiles; adds and multiplies only on the device). augment.augment_reference is the numpy twin.
+ *
+ * The kernel is defined for ANY parameter bytes: src is clamped to [0, n_src), map entries are taken & 127, holes are clipped to
+ * the image, n_holes is clamped to 0..8, channel_mask is taken & 7, a blur_k other than 2 or 3 is 0, a float that is not finite
+ * counts as its identity value (alpha 1, the others 0) and finite ones are clamped to alpha 0..4, beta -2..2, hue -1024..1024,
+ * sat / val -512..512, sigma 0..256. pa_augment_params_check (host only, no device call) returns PA_ERR_INVALID_ARG for
+ * anything of that kind and for values outside the reference's limits: alpha outside [0.8, 1.2], beta outside [-0.2, 0.4], hue
+ * outside [-256, 256], sat outside [-67, 67], val outside [-5, 5], sigma outside [0, sqrt(200)], a hole beyond 124, flip
+ * outside {0, 1}, channel_mask outside 0..6.
+ *
+ * pa_augment_crops: src and params on the device (src and out 16-byte aligned), n >= 1, n_src >= 1; out_format PA_AUGMENT_U8 ->
+ * out uint8[n][128][128][3], PA_AUGMENT_MODEL -> out float32[n][3][128][128] with value (float)byte / 255.f (the input of
+ * pa_backbone_windows / pa_infer_windows). Enqueue only; nothing is read back. PA_ERR_INVALID_ARG otherwise. */
+typedef struct pa_augment_params {
+    int32_t src;
+    int32_t flip;
+    float alpha, beta;
+    int32_t blur_k;
+    float hue_shift, sat_shift, val_shift;
+    float noise_sigma;
+    uint32_t pixel_drop_thr;
+    int32_t n_holes;
+    uint8_t holes[16];
+    int32_t channel_mask;
+    uint8_t xmap[128];
+    uint8_t ymap[128];
+    uint64_t key;
+} pa_augment_params;
+#define PA_AUGMENT_U8 0
+#define PA_AUGMENT_MODEL 1
+#define PA_AUGMENT_QUANTILES 1025
+int pa_augment_params_check(const pa_augment_params* host, int32_t n, int32_t n_src);
+/* the table q: q[j] = the standard normal quantile at j / 1024 (fp64, rounded once) for 0 < j < 1024; q[0] = -q[1024] chosen so
+ * that the outermost cells keep the normal's second moment over their probability 1 / 1024. out_host: float32[1025]. */
+int pa_augment_quantiles(float* out_host);
+int pa_augment_crops(pa_engine* e, const uint8_t* src_dev, int32_t n_src, const pa_augment_params* params_dev, int32_t n,
+                     int32_t out_format, void* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ SOURCES = [
     ("misc.hip", []),
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("crop_sized.hip", ["-ffp-contract=off"]),
+    ("augment.hip", ["-ffp-contract=off"]),
     ("detect.hip", ["-ffp-contract=off"]),
     ("conv_rows.hip", []),
     ("lstm.hip", []),

@@ -133,6 +133,18 @@ class pa_train_stats(C.Structure):
     _fields_ = [("loss", C.c_float), ("valid", C.c_int32), ("correct", C.c_int32), ("pad", C.c_int32)]
 
 
+class pa_augment_params(C.Structure):
+    _fields_ = [("src", C.c_int32), ("flip", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float), ("blur_k", C.c_int32),
+                ("hue_shift", C.c_float), ("sat_shift", C.c_float), ("val_shift", C.c_float), ("noise_sigma", C.c_float),
+                ("pixel_drop_thr", C.c_uint32), ("n_holes", C.c_int32), ("holes", C.c_uint8 * 16), ("channel_mask", C.c_int32),
+                ("xmap", C.c_uint8 * 128), ("ymap", C.c_uint8 * 128), ("key", C.c_uint64)]
+
+
+PA_AUGMENT_U8 = 0
+PA_AUGMENT_MODEL = 1
+PA_AUGMENT_QUANTILES = 1025
+
+
 class pa_kernel_stat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 48),
@@ -298,6 +310,9 @@ SYMBOLS = [
     ("pa_wino4_weight_floats", C.c_size_t, [C.c_int32, C.c_int32]),
     ("pa_wino4_transform_weights", C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     ("pa_wino4_conv3x3", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 10 + [_P, C.c_size_t, _P]),
+    ("pa_augment_params_check", C.c_int, [_P, C.c_int32, C.c_int32]),
+    ("pa_augment_quantiles", C.c_int, [_P]),
+    ("pa_augment_crops", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
 ]
 
 _lib = None

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 import yaml
 
-from . import constants
+from . import augment, constants
 from .anim_ontology import MOVE_TO_CLASS_ID
 from .cnn_action_detector import CNNActionDetector
 from .dataset_utils import action_sample_from_frame_middle_out
@@ -602,15 +602,24 @@ class AIRunner:
         return out
 
     def fit_head(self, actions=None, ground_truth_csv: str = None, epochs: int = 1, batch_size: int = 64, seed: int = 0, lines=None,
-                 first_frame: int = 0):
+                 first_frame: int = 0, synth_difficulty: int = 0, raise_difficulty: bool = False):
         """Fine-tunes the model's temporal head on the open clip (``head_trainer.HeadTrainer``; the model is built with
         ``freeze_encoder=True``): the clip runs ONCE as ``run_action_recognition`` runs it, its per-crop features are taken from
         the engine's cache (``pa_features_export``), and every epoch is a seeded permutation of the labelled (frame, fighter)
         windows in minibatches of ``batch_size`` -- windows from the runner's own sampler and ``frame_delta``, centre labels from
         ``label_table`` (ground truth as in ``evaluate``; unlabelled frames are left out). The head's weights change in place in
         the model's engine; the clip's cached results are dropped, so the next ``run_action_recognition`` / ``evaluate`` runs
-        the trained model. One read per epoch. -> ``[{"epoch", "loss", "accuracy", "windows"}, ...]`` (each step's loss is taken
-        before its update)."""
+        the trained model. One read per epoch. -> ``[{"epoch", "loss", "accuracy", "windows", "synth_difficulty"}, ...]`` (each
+        step's loss is taken before its update).
+
+        ``synth_difficulty`` 1 or 2 trains on AUGMENTED crops, as the reference's dataset does (``augment.py``):
+        the clip still runs once, for boxes and crops; its crops are held on the device as one
+        ``uint8[(max_frames - 1) * F, 128, 128, 3]``, and every minibatch is a fresh ``augment.sample_params(B * S, level, rng,
+        src=rows of the batch's windows)``, one ``pa_augment_crops`` straight into the model's layout, ``pa_backbone_windows``
+        and the trainer's step -- what ``CNNActionDetector.training_step`` does with a batch. No window is seen twice with
+        the same pixels. ``raise_difficulty=True`` applies the reference's ``training_epoch_end`` rule
+        (``cnn_action_detector.py:118-129``): when the mean of an epoch's per-step accuracies passes 0.85 the level goes up by
+        one, to 2 at most. With ``synth_difficulty=0`` and ``raise_difficulty=False`` (the defaults) nothing of this runs."""
         from .ult_action_dataset import label_table, load_ground_truth_labels
 
         if actions is not None and ground_truth_csv is not None:
@@ -629,12 +638,17 @@ class AIRunner:
         self.model.train()                      # (NotImplementedError unless freeze_encoder=True)
         trainer = self.model.configure_optimizers()
         if batch_size > trainer.max_batch:
+            # (the trainer's capacity is the one limit: pa_backbone_windows takes any number of crops, max_crops at a time)
             raise ValueError(f"fit_head: batch_size above {trainer.max_batch}")
+        level = int(synth_difficulty)
+        if level != synth_difficulty or not 0 <= level <= augment.MAX_LEVEL:
+            raise ValueError(f"fit_head: synth_difficulty is 0, 1 or {augment.MAX_LEVEL}, got {synth_difficulty!r}")
+        augmented = level > 0 or bool(raise_difficulty)
         try:
-            self._run_clip()
+            res = self._run_clip()
             ceng = self._clip_engine
             n, F = self.max_frames, ceng.F
-            feats = ceng.features_export(0, n)                                       # [n, F, 1024], rows (frame - 1) * F + slot
+            feats = None if augmented else ceng.features_export(0, n)                # [n, F, 1024], rows (frame - 1) * F + slot
             idx = np.argwhere(table != -100)                                         # (frame - 1, slot) of every labelled window
             if len(idx) == 0:
                 raise ValueError("fit_head: the ground truth labels no frame of this clip")
@@ -645,12 +659,33 @@ class AIRunner:
             rng = np.random.default_rng(seed)
             history = []
             trainer.epoch_stats()   # a fresh epoch
+            if augmented:
+                eng, S = self.model.engine, self.num_frames_per_sample
+                crops = torch.from_numpy(np.ascontiguousarray(res["crops_rgb"][: n - 1]).reshape(-1, 128, 128, 3)).to(eng.device)
+                x = torch.empty((batch_size * S, 3, 128, 128), dtype=torch.float32, device=eng.device)
+                step_feats = torch.empty((batch_size * S, 1024), dtype=torch.float32, device=eng.device)
+                rows = torch.arange(batch_size * S, dtype=torch.int32, device=eng.device)
             for epoch in range(epochs):
                 order = rng.permutation(len(idx))
+                step_stats = []
                 for b0 in range(0, len(order), batch_size):
                     sel = order[b0:b0 + batch_size]
-                    trainer.step(feats, wins[sel], labels[sel])
-                history.append(dict(epoch=epoch, **trainer.epoch_stats()))
+                    if not augmented:
+                        trainer.step(feats, wins[sel], labels[sel])
+                        continue
+                    k = len(sel) * S
+                    if level:
+                        params = augment.sample_params(k, level, rng, src=wins[sel].ravel())
+                    else:   # (raise_difficulty from level 0: the plain crops through the same path)
+                        params = augment.identity_params(k, src=wins[sel].ravel())
+                    augment.augment_crops(eng, crops, params, "model", out=x[:k])
+                    eng._check(eng._lib.pa_backbone_windows(eng._h, x.data_ptr(), k, step_feats.data_ptr(), eng._stream()))
+                    step_stats.append(trainer.step(step_feats[:k], rows[:k].view(len(sel), S), labels[sel]))
+                history.append(dict(epoch=epoch, **trainer.epoch_stats(), synth_difficulty=level))
+                if raise_difficulty:
+                    st = torch.stack(step_stats).cpu().numpy()   # per step: [1] labelled windows, [2] of them predicted right
+                    if float(np.mean(st[:, 2] / np.maximum(st[:, 1], 1))) > augment.RAISE_ACCURACY and level < augment.MAX_LEVEL:
+                        level += 1
         finally:
             self.model.eval()
         self._results = None   # predictions of the untrained head

@@ -44,14 +44,7 @@ struct DropSite {
     float scale;         // 1 / (1 - p)
 };
 
-__host__ __device__ __forceinline__ uint32_t et_mix(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
+__host__ __device__ __forceinline__ uint32_t et_mix(uint32_t x) { return hash_mix(x); }   // train_common.h
 
 // the mask value of element i: 1 / (1 - p) where it is kept, 0 where it is dropped
 __device__ __forceinline__ float et_keep(const DropSite& s, uint32_t i) {

@@ -128,6 +128,7 @@ struct pa_engine {
     size_t t_stride = 0;
     int32_t* status_tmp = nullptr;
     int32_t* fallback = nullptr;  // [1 + max_crops]: count, then crop indices
+    AugmentTables* aug_tabs = nullptr;  // pa_augment_crops: the normal quantiles, OpenCV's two HSV division tables, k / 255 (augment.hip)
     // two-way interleave of the backbone (two half batches on two streams; knobs.interleave: measured +0.5 % only -- kernels of two
     // streams do not overlap usefully -- and kept as a knob)
     hipStream_t side = nullptr;
@@ -1098,6 +1099,12 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     ALLOC(e->hop, (size_t)NC * PA_HOP_BLOCKS_MAX * PA_HOP_BLOCK_BYTES, true);  // 302 KB a crop
     ALLOC(e->t1, (size_t)NC * e->t_stride, false);
     ALLOC(e->t2, (size_t)NC * e->t_stride, false);
+    {
+        AugmentTables at;
+        augment_tables_host(&at);
+        ALLOC(e->aug_tabs, (size_t)1, false);
+        HIPCHK(e, hipMemcpy(e->aug_tabs, &at, sizeof(at), hipMemcpyHostToDevice));
+    }
 #undef ALLOC
     HIPCHK(e, hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
@@ -1274,6 +1281,18 @@ int pa_square_crops(pa_engine* e, const uint8_t* frames, int32_t n, int32_t heig
     if (n > e->cfg.max_batch_frames || height > e->cfg.max_frame_height || width > e->cfg.max_frame_width)
         return fail(e, PA_ERR_CAPACITY, "pa_square_crops: frames exceed engine capacity");
     return run_preprocess(e, frames, n, height, width, boxes, padding, swap_rb, crops, nullptr, status, (hipStream_t)stream);
+}
+
+int pa_augment_crops(pa_engine* e, const uint8_t* src_dev, int32_t n_src, const pa_augment_params* params_dev, int32_t n,
+                     int32_t out_format, void* out_dev, void* stream) {
+    if (!e || !src_dev || !params_dev || !out_dev || n < 1 || n_src < 1 || (out_format != PA_AUGMENT_U8 && out_format != PA_AUGMENT_MODEL))
+        return fail(e, PA_ERR_INVALID_ARG, "pa_augment_crops: bad argument");
+    if (((uintptr_t)src_dev | (uintptr_t)out_dev) & 15 || (uintptr_t)params_dev & 7)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_augment_crops: src and out must be 16-byte aligned, params 8-byte aligned");
+    if (!e->aug_tabs) return fail(e, PA_ERR_INVALID_ARG, "pa_augment_crops: the engine has no tables");
+    ProfScope ps(e, (hipStream_t)stream, "augment", 0.0, (double)n * 49152.0 * (out_format == PA_AUGMENT_MODEL ? 5.0 : 2.0));
+    HIPCHK(e, launch_augment(src_dev, n_src, params_dev, n, out_format, out_dev, e->aug_tabs, (hipStream_t)stream));
+    return PA_OK;
 }
 
 int pa_square_crops_sized(pa_engine* e, const uint8_t* frames, int32_t n, int32_t height, int32_t width, const double* boxes,

@@ -542,4 +542,19 @@ size_t head_tensor_floats(int S, int A);
 hipError_t launch_head_train_step(const HeadTrainParams& p, const AdamScalars& ak, hipStream_t s);
 hipError_t launch_head_export(const HeadTensors& src, int S, int A, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// augmentation of 128 x 128 crops (augment.hip; pa_augment_crops of include/playaid_hip.h)
+// ---------------------------------------------------------------------------
+// the constant tables one launch copies into LDS: built once on the host in fp64 (augment_tables_host), held by the engine
+struct AugmentTables {
+    float q[1028];        // 1025 normal quantiles (pa_augment_quantiles), padded to 16 bytes
+    int32_t sdiv[256];    // OpenCV's RGB -> HSV: round((255 << 12) / v)
+    int32_t hdiv[256];    // ... round((180 << 12) / (6 diff))
+    float unit[256];      // (float)k / 255.f
+};
+void augment_tables_host(AugmentTables* t);
+// params: device, pa_augment_params[n]; out_format 0 = uint8 [n][128][128][3], 1 = float32 [n][3][128][128]
+hipError_t launch_augment(const uint8_t* src, int n_src, const void* params, int n, int out_format, void* out,
+                          const AugmentTables* tabs_dev, hipStream_t s);
+
 }  // namespace pa

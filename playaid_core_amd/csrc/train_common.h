@@ -13,6 +13,19 @@ namespace pa {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));   // the accumulator of v_mfma_f32_32x32x2_f32
 
+// ---- the counter-based hash -------------------------------------------------------------------------------------------------
+// `mix` of include/playaid_hip.h: the encoder trainer's dropout masks (encoder_train.hip) and the augmentation's noise and pixel
+// dropout (augment.hip) are r = mix(mix(i ^ key) + key) of an element index i -- a function of (key, i) alone.
+__host__ __device__ __forceinline__ uint32_t hash_mix(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+__host__ __device__ __forceinline__ uint32_t hash_element(uint32_t key, uint32_t i) { return hash_mix(hash_mix(i ^ key) + key); }
+
 // ---- the loss ---------------------------------------------------------------------------------------------------------------
 // A label outside [0, A) counts as ignored (-100 is the only such value a checked caller passes).
 

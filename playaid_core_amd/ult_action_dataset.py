@@ -10,9 +10,13 @@ runner has open, with the crops cut ON THE DEVICE by the engine's crop path (``p
 the same sampler with the runner's own range (frames are 1-indexed crop files, ``ai_runner.py:438-439``). Its batches are what
 ``CNNActionDetector.forward`` takes (``cnn_action_detector.py:86-92``).
 
+``synth_difficulty`` 1 or 2 passes every crop of an item through the reference's ``augment_char_crop`` at that level
+(``ult_action_dataset.py:305-330``), on the device: ``augment.py``, DESIGN.md 5.14.
+
 Not built, by scope (training only): the random choice of (fighter, action, frame), the frame-delta
-choice, ``synth_difficulty`` augmentation, the synthetic-stage compositing of the "simple" split, ``preceding_actions`` (the
-reference's own loop over them is empty: ``range(a, a)``, ``ult_action_dataset.py:284-286``).
+choice, the synthetic-stage compositing of the "simple" split (``augment_synth_char_crop``, ``get_synth``: it needs the
+character renders), ``preceding_actions`` (the reference's own loop over them is empty: ``range(a, a)``,
+``ult_action_dataset.py:284-286``).
 
 For scoring (``metrics.py``, ``AIRunner.evaluate``): ``load_ground_truth_labels`` reads a hand-labelled clip's CSV as the
 reference does (``ult_action_dataset.py:512-559``) and ``label_table`` turns action strings -- per-fighter lists or that CSV's
@@ -27,7 +31,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import constants
+from . import augment, constants
 from .anim_ontology import MOVE_TO_CLASS_ID
 from .dataset_utils import action_sample_from_frame_middle_out
 
@@ -99,7 +103,7 @@ class ClipWindowDataset:
     ``AIRunner.run_action_recognition``'s two loops, ``ai_runner.py:493-520``)."""
 
     def __init__(self, runner, actions: Optional[Sequence[Sequence[str]]] = None, animations: Optional[List[str]] = None,
-                 crop_size: int = 128):
+                 crop_size: int = 128, synth_difficulty: int = 0, seed: int = 0):
         """``runner``: an ``AIRunner`` (its clip, label repair, crop mode and sampler settings are used as they are).
         ``actions[p][f - 1]``: the ground-truth action string of fighter slot p in frame f (what the reference reads from the
         frame's label file, ``ult_action_dataset.py:340-343``), or None: every frame is labelled ``Undefined``.
@@ -107,7 +111,12 @@ class ClipWindowDataset:
         ``crop_size`` (``UltActionRecogDataset(crop_size=...)``; 16..512): 128 hands out the runner's own crops, as ever. With
         any other size the S crops of an item are cut from the clip's FRAMES by ``Engine.square_crops(output_size=crop_size)``
         with the runner's repaired boxes at the engine's crop padding (RGB, no JPEG write / read: that stage is 128 x 128) --
-        so the clip needs frames, and a clip that holds only crop files raises ValueError."""
+        so the clip needs frames, and a clip that holds only crop files raises ValueError.
+        ``synth_difficulty`` (``UltActionRecogDataset(synth_difficulty=...)``; 0, 1 or 2): with 1 or 2 the S crops of an item go
+        through ``augment.augment_crops`` at that level, each with its own draw as in the reference's loop; the draw of item
+        ``idx`` in epoch ``e`` (``set_epoch``) is a pure function of ``(seed, e, idx)``. The augmentation is the 128 x 128
+        kernel: with another ``crop_size`` it raises ValueError (DESIGN.md 5.8c has the sized crops, 5.14 the augmentation). 0
+        leaves every item as it is without the argument."""
         self.runner = runner
         self.animations = list(animations) if animations is not None else list(MOVE_TO_CLASS_ID.keys())
         self.characters = list(constants.CHAR_LIST)
@@ -117,6 +126,9 @@ class ClipWindowDataset:
         if self.crop_size != crop_size or not 16 <= self.crop_size <= 512:
             raise ValueError(f"crop_size must be an integer in 16..512, got {crop_size!r}")
         self._sized_boxes = None
+        self.synth_difficulty = self._check_level(synth_difficulty)
+        self.seed, self.epoch = int(seed), 0
+        self._crops_dev = None   # (the clip's results it was made from, the crops as one device tensor [(max_frames - 1) * F, 128, 128, 3])
         if self.crop_size != 128 and (runner.clip.frames.shape[1] == 0 or runner.clip.frames.shape[2] == 0):
             raise ValueError(f"crop_size={self.crop_size}: crops of another size than 128 are cut from the clip's frames, and this "
                              "clip holds crop files only: frames are needed")
@@ -127,6 +139,34 @@ class ClipWindowDataset:
 
     def __len__(self):
         return (self.runner.max_frames - 1) * len(self.runner.fighters)
+
+    def _check_level(self, level) -> int:
+        if level not in range(augment.MAX_LEVEL + 1):
+            raise ValueError(f"synth_difficulty is 0, 1 or {augment.MAX_LEVEL}, got {level!r}")
+        if level and self.crop_size != 128:
+            raise ValueError(f"synth_difficulty={level} with crop_size={self.crop_size}: the augmentation is built for 128 x 128 crops only "
+                             "(DESIGN.md 5.8c: crops of other sizes; 5.14: the augmentation)")
+        return int(level)
+
+    def set_epoch(self, epoch: int):
+        """The epoch the augmentation's draws are keyed by (with ``seed`` and the item's index)."""
+        self.epoch = int(epoch)
+
+    def make_synth_more_challenging(self):
+        """``UltActionRecogDataset.make_synth_more_challenging`` (``ult_action_dataset.py:561-564``): one level up, 2 at most."""
+        if self.synth_difficulty < augment.MAX_LEVEL:
+            self.synth_difficulty = self._check_level(self.synth_difficulty + 1)
+
+    def _augmented(self, res, idx: int, p: int, frame_nums):
+        """The item's S crops through ``augment_char_crop`` at the dataset's level: one launch, one read."""
+        eng = self.runner._clip_engine
+        if self._crops_dev is None or self._crops_dev[0] is not res:
+            crops = np.ascontiguousarray(res["crops_rgb"][: self.runner.max_frames - 1])
+            self._crops_dev = (res, torch.from_numpy(crops.reshape(-1, 128, 128, 3)).to(eng.device), crops.shape[1])
+        _, crops_dev, F = self._crops_dev
+        rng = np.random.default_rng([self.seed, self.epoch, idx])
+        params = augment.sample_params(len(frame_nums), self.synth_difficulty, rng, src=[(f - 1) * F + p for f in frame_nums])
+        return list(augment.augment_crops(eng, crops_dev, params, "uint8").cpu().numpy())
 
     def _action_id(self, action: str) -> int:
         return _action_id(self.animations, action)
@@ -143,7 +183,10 @@ class ClipWindowDataset:
         )
         if self.crop_size == 128:
             res = self.runner._run_clip()  # the clip's crops, cut once on the device and cached by the runner
-            frames = [res["crops_rgb"][f - 1, p] for f in frame_nums]
+            if self.synth_difficulty:
+                frames = self._augmented(res, idx, p, frame_nums)
+            else:
+                frames = [res["crops_rgb"][f - 1, p] for f in frame_nums]
         else:
             frames = self._cut_sized(p, frame_nums)
         actions = [self.actions[p][f - 1] if self.actions is not None else "Undefined" for f in frame_nums]
