@@ -1,6 +1,7 @@
 // The ResNet-18 engine's decisions as plain host code: its environment knobs in one table, what follows from them, and which
 // kernel form, tile, K split and branch placement one convolution launch takes (pa_api.hip's run_conv launches what plan_conv
-// returns). No HIP, no pointers: tests/helpers/engine_plan_table.cpp compiles this header with the host compiler alone.
+// returns). The rows it plans from: engine_table.h. No HIP, no pointers: tests/helpers/engine_plan_table.cpp compiles both headers with
+// the host compiler alone.
 #pragma once
 #include "gemm_tile.h"
 

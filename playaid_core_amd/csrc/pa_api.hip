@@ -4,7 +4,7 @@
 // in the enqueue calls.
 #include "../../include/playaid_hip.h"
 #include "conv_rows.h"
-#include "engine_plan.h"
+#include "engine_table.h"   // the layer table, over engine_plan.h
 #include "train_common.h"   // adam_scalars, adam_config_ok, TrainerCore
 
 #include <algorithm>
@@ -19,9 +19,10 @@ using namespace pa;
 
 namespace {
 
+static_assert(FEATURE_STRIDE == PA_FEATURE_STRIDE, "engine_table.h pads the fc to the cached feature rows' width");
 constexpr int WINO_TICKETS = 4096;   // tiles of one Winograd launch that may use split K (more: no split)
 
-// A row of the layer table: what engine_plan.h plans from, plus its buffers and weights
+// A row of the layer table (engine_table.h): what engine_plan.h plans from, plus its buffers and weights
 struct ConvLayer : LayerDesc {
     std::string name;
     float* in = nullptr;
@@ -71,13 +72,14 @@ struct pa_engine {
     std::vector<char> ready;
     // device memory (all freed in pa_destroy)
     std::vector<void*> allocs;
-    // every folded / re-laid-out weight tensor lives in ONE device arena at offsets that depend only on
-    // (S, A, compute_dtype): a rank that received the arena over RCCL adopts it with one device copy
-    // (pa_create_from_arena) instead of folding the blob again
+    // every folded / re-laid-out weight tensor lives in ONE device arena at offsets that depend only on what the layer table and the
+    // entries' sizes depend on: S, A, compute_dtype, the per-process knobs (EngineKnobs' first part) and whether max_crops reaches knobs.wino_f4_min (layer
+    // 4's F(4x4) filters). A rank that received the arena over RCCL from an engine equal in all of these adopts it with one device
+    // copy (pa_create_from_arena) instead of folding the blob again. (The size check of adopt mode sees the offsets only: the Winograd
+    // filters' order inside their entry also follows ConvLayer::wino_bn, which wino_pick_bn takes from max_crops)
     uint8_t* arena = nullptr;
     size_t arena_cap = 0, arena_used = 0;
     std::vector<uint8_t> arena_stage;  // host mirror while pa_create folds (empty in adopt mode and afterwards)
-    bool adopt = false;
     int32_t* dev_errors = nullptr;  // [4] device-side error counters ([0] = scatter ids outside the clip, [1] = crop images that did not fit)
     int32_t* savebox_rects = nullptr;  // [max_crops][4] scratch of pa_save_one_box_crops
     double* clean_g6 = nullptr;        // scratch of pa_clean_detections: the detection table through '%g' (grown on demand)
@@ -181,85 +183,62 @@ int dev_alloc(pa_engine* e, T** ptr, size_t count, bool zero) {
     return PA_OK;
 }
 
-// Bump-allocate `bytes` in the weight arena (256-byte aligned) and, unless the arena is being adopted,
-// stage the host data for the single upload at the end of pa_create.
-int arena_put(pa_engine* e, void** dst, const void* host, size_t bytes) {
-    const size_t off = (e->arena_used + 255) & ~(size_t)255;
+// Place `n` elements of T in the weight arena (256-byte aligned bump): *dst gets their device address, in both modes of create.
+// *stage: where pa_create writes them on the host for the single upload at its end (zeroed), nullptr when the arena is adopted
+template <typename T, typename D>
+int arena_place(pa_engine* e, D** dst, size_t n, T** stage) {
+    const size_t off = (e->arena_used + 255) & ~(size_t)255, bytes = n * sizeof(T);
     if (off + bytes > e->arena_cap) return fail(e, PA_ERR_BAD_WEIGHTS, "weight arena overflow");
     e->arena_used = off + bytes;
-    *dst = e->arena + off;
-    if (!e->adopt) memcpy(e->arena_stage.data() + off, host, bytes);
+    *dst = reinterpret_cast<D*>(e->arena + off);
+    *stage = e->arena_stage.empty() ? nullptr : reinterpret_cast<T*>(e->arena_stage.data() + off);
     return PA_OK;
 }
 
-int upload(pa_engine* e, float** dst, const std::vector<float>& host) {
-    return arena_put(e, reinterpret_cast<void**>(dst), host.data(), host.size() * sizeof(float));
+// ... n floats, the first n_host of them from `host` and the rest zero
+int put(pa_engine* e, float** dst, size_t n, const float* host, size_t n_host) {
+    float* s;
+    const int rc = arena_place(e, dst, n, &s);
+    if (!rc && s) memcpy(s, host, n_host * sizeof(float));
+    return rc;
+}
+int put(pa_engine* e, float** dst, size_t n, const float* host) { return put(e, dst, n, host, n); }
+
+// ... as bf16 (round to nearest even): weights of the bf16 conv path; the device pointer keeps the float* type of ConvLayer::wgt,
+// the kernels reinterpret it.
+int put_bf16(pa_engine* e, float** dst, size_t n, const float* host) {
+    uint16_t* s;
+    const int rc = arena_place(e, dst, n, &s);
+    for (size_t i = 0; !rc && s && i < n; ++i) s[i] = bf16_rne(host[i]);
+    return rc;
 }
 
-// fp32 -> bf16 (round to nearest even) weights of the bf16 conv path; the device pointer keeps
-// the float* type of ConvLayer::wgt, the kernels reinterpret it.
-int upload_bf16(pa_engine* e, float** dst, const std::vector<float>& host) {
-    std::vector<uint16_t> h(host.size());
-    if (!e->adopt)
-        for (size_t i = 0; i < host.size(); ++i) h[i] = bf16_rne(host[i]);
-    return arena_put(e, reinterpret_cast<void**>(dst), h.data(), h.size() * sizeof(uint16_t));
+// ... fp32 [cout][ktot] as three bf16 slices per weight in psgemm.hip's stage-image order (PA_DTYPE_EMULATED_F32)
+int put_split(pa_engine* e, unsigned short** dst, const float* host, int cout, int ktot) {
+    const size_t n = psgemm_weight_elems(cout, ktot, false);
+    if (n == 0) return PA_ERR_INVALID_ARG;
+    unsigned short* s;
+    const int rc = arena_place(e, dst, n, &s);
+    if (!rc && s) psgemm_pack_weights(host, cout, ktot, false, s);
+    return rc;
 }
 
-// fp32 [cout][ktot] -> three bf16 slices per weight in psgemm.hip's stage-image order (PA_DTYPE_EMULATED_F32)
-int upload_split(pa_engine* e, unsigned short** dst, const std::vector<float>& host, int cout, int ktot, bool residual) {
-    std::vector<unsigned short> h(psgemm_weight_elems(cout, ktot, residual), 0);
-    if (h.empty()) return PA_ERR_INVALID_ARG;
-    if (!e->adopt) psgemm_pack_weights(host.data(), cout, ktot, residual, h.data());
-    return arena_put(e, reinterpret_cast<void**>(dst), h.data(), h.size() * sizeof(unsigned short));
-}
-
-// --- weight blob walking -----------------------------------------------------
+// --- weight blob walking (pa_create only) --------------------------------------
 struct BlobReader {
     const float* base;
     size_t pos, limit;  // in floats
-    bool dry;  // adopting a prepared arena: only the sizes matter, nothing returned by take() is read
     const float* take(size_t n) {
         if (pos + n > limit) return nullptr;
-        const float* r = dry ? base : base + pos;
+        const float* r = base + pos;
         pos += n;
         return r;
     }
 };
 
-size_t blob_float_count(int S, int A) {
-    size_t n = 0;
-    auto conv = [&](int co, int ci, int k) { n += (size_t)co * ci * k * k; };
-    auto bn = [&](int c) { n += 4 * (size_t)c; };
-    conv(64, 3, 7);
-    bn(64);
-    int cin = 64;
-    const int widths[4] = {64, 128, 256, 512};
-    for (int li = 0; li < 4; ++li) {
-        const int co = widths[li];
-        for (int b = 0; b < 2; ++b) {
-            const int ci = b == 0 ? cin : co;
-            conv(co, ci, 3);
-            bn(co);
-            conv(co, co, 3);
-            bn(co);
-            if (b == 0 && li > 0) {
-                conv(co, ci, 1);
-                bn(co);
-            }
-        }
-        cin = co;
-    }
-    n += 1000 * 512 + 1000;
-    n += (size_t)512 * 1000 * S + 512;
-    n += 128 * 512 + 128;
-    n += (size_t)A * 128 + A;
-    return n;
-}
-
 // Fold eval-mode BatchNorm (eps 1e-5) into conv weights in fp64 and re-lay-out
 // OIHW -> [cout][tap][chunk] (tap = ky*kw_taps + kx, channels innermost, zero
 // padded to `chunk`). The 7x7 stem uses tap = ky and chunk = 8 px * 4 ch.
-bool fold_conv(BlobReader& br, const ConvLayer& L, std::vector<float>& w_out, std::vector<float>& b_out) {
+bool fold_conv(BlobReader& br, const LayerDesc& L, std::vector<float>& w_out, std::vector<float>& b_out) {
     const size_t wn = (size_t)L.cout * L.cin * L.kh * L.kw;
     const float* w = br.take(wn);
     const float* gamma = br.take(L.cout);
@@ -270,7 +249,6 @@ bool fold_conv(BlobReader& br, const ConvLayer& L, std::vector<float>& w_out, st
     const int ktot = L.taps * L.chunk;
     w_out.assign((size_t)L.cout * ktot, 0.f);
     b_out.assign(L.cout, 0.f);
-    if (br.dry) return true;
     const bool stem = (L.kh == 7);
     for (int co = 0; co < L.cout; ++co) {
         const double scale = (double)gamma[co] / std::sqrt((double)var[co] + 1e-5);
@@ -734,15 +712,21 @@ const char* pa_status_string(int status) {
 
 const char* pa_last_error(const pa_engine* e) { return e ? e->last_error.c_str() : "null engine"; }
 
-size_t pa_weight_blob_bytes(int S, int A) { return 8 * sizeof(int32_t) + blob_float_count(S, A) * sizeof(float); }
+// (the blob is the same for every knob, dtype and batch: any table counts it)
+size_t pa_weight_blob_bytes(int S, int A) { return 8 * sizeof(int32_t) + blob_floats(engine_table(EngineKnobs(), DT_F32, 1), S, A) * sizeof(float); }
 
 }  // extern "C"
 
 namespace {
 
-// pa_create (blob != nullptr: fold the Lightning tensors) and pa_create_from_arena (arena_dev != nullptr:
-// adopt a prepared weight arena of `src_bytes` bytes) share everything but the source of the weights.
-int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const void* arena_dev, pa_engine** out) {
+// ---- the steps of create_impl, in its order ------------------------------------------------------------------------------------
+
+#define ALLOC(ptr, count, zero)                                                     \
+    do {                                                                            \
+        if (int rc__ = dev_alloc(e, &(ptr), (size_t)(count), zero)) return rc__;    \
+    } while (0)
+
+int check_create_args(const pa_config* cfg, const void* blob, size_t src_bytes, const void* arena_dev, pa_engine** out) {
     if (!cfg || (!blob && !arena_dev) || !out) return PA_ERR_INVALID_ARG;
     *out = nullptr;
     if (cfg->abi_version != PA_ABI_VERSION) return PA_ERR_INVALID_ARG;
@@ -754,41 +738,30 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     const int32_t* hdr = reinterpret_cast<const int32_t*>(blob);
     if (blob && (src_bytes != pa_weight_blob_bytes(S, A) || hdr[0] != PA_WEIGHT_MAGIC || hdr[1] != 1 || hdr[2] != S || hdr[3] != A))
         return PA_ERR_BAD_WEIGHTS;
-    pa_engine* e = new pa_engine();
-    e->cfg = *cfg;
-    e->bf16 = cfg->compute_dtype == PA_DTYPE_BF16;
-    e->emu = cfg->compute_dtype == PA_DTYPE_EMULATED_F32;
-    e->dtype = e->bf16 ? DT_BF16 : e->emu ? DT_EMULATED_F32 : DT_F32;
-    e->adopt = blob == nullptr;
-    e->knobs = engine_knobs();  // the per-create knobs as the environment has them now
-    const EngineKnobs& K = e->knobs;
-    *out = e;  // handed back even on failure so the caller can read pa_last_error, then pa_destroy
-    {
-        int ndev = 0;
-        const hipError_t derr = hipGetDeviceCount(&ndev);
-        if (derr != hipSuccess || ndev <= 0 || cfg->device_id < 0 || cfg->device_id >= ndev)
-            return fail(e, PA_ERR_NO_DEVICE,
-                        std::string("hipGetDeviceCount: ") + hipGetErrorString(derr) + ", devices=" + std::to_string(ndev) +
-                            ", requested device " + std::to_string(cfg->device_id));
-    }
-    HIPCHK(e, hipSetDevice(cfg->device_id));
-    HIPCHK(e, preprocess_init_device());
-    const int NC = cfg->max_batch_frames * F;
-    e->max_crops = NC;
-    e->cache_rows = cfg->max_clip_frames * F;
-    int rc;
-#define ALLOC(ptr, count, zero)                         \
-    do {                                                \
-        rc = dev_alloc(e, &(ptr), (size_t)(count), zero); \
-        if (rc != PA_OK) return rc;                     \
-    } while (0)
+    return PA_OK;
+}
 
+int select_device(pa_engine* e) {
+    int ndev = 0;
+    const hipError_t derr = hipGetDeviceCount(&ndev);
+    if (derr != hipSuccess || ndev <= 0 || e->cfg.device_id < 0 || e->cfg.device_id >= ndev)
+        return fail(e, PA_ERR_NO_DEVICE,
+                    std::string("hipGetDeviceCount: ") + hipGetErrorString(derr) + ", devices=" + std::to_string(ndev) +
+                        ", requested device " + std::to_string(e->cfg.device_id));
+    HIPCHK(e, hipSetDevice(e->cfg.device_id));
+    HIPCHK(e, preprocess_init_device());
+    return PA_OK;
+}
+
+// model input, stem and pool outputs, features, cache and the small per-crop tables (the layers' own buffers: wire_layers)
+int alloc_activations(pa_engine* e) {
+    const int NC = e->max_crops;
     ALLOC(e->x0_slot[0], (size_t)NC * 134 * 134 * 4, true);
     ALLOC(e->x0_slot[1], (size_t)NC * 134 * 134 * 4, true);
     e->x0 = e->x0_slot[0];
     // PA_STEM_INT=0: every producer writes k / 255 and the fp32 stem runs, as before the integer form (A/B runs). The unfused stems
     // of PA_STEM_POOL=0 / PA_STEM_IGEMM=1 have no integer form and switch it off too.
-    e->stem_int = engine_forms(K, e->dtype).stem_int;
+    e->stem_int = engine_forms(e->knobs, e->dtype).stem_int;
     if (e->stem_int) {
         ALLOC(e->xi_slot[0], (size_t)NC * 134 * 134 * 4, true);
         ALLOC(e->xi_slot[1], (size_t)NC * 134 * 134 * 4, true);
@@ -805,283 +778,209 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     ALLOC(e->cache, (size_t)e->cache_rows * PA_FEATURE_STRIDE, true);
     ALLOC(e->cache_status, (size_t)e->cache_rows, true);
     ALLOC(e->h1, (size_t)NC * 512, true);
-    ALLOC(e->gather, (size_t)NC * S, true);
+    ALLOC(e->gather, (size_t)NC * e->cfg.sequence_length, true);
     ALLOC(e->status_tmp, (size_t)NC, true);
     ALLOC(e->dev_errors, 4, true);
     // scratch of pa_clean_detections, sized for the longest clip and the widest detection table (max_det <= 8): the enqueue-only
     // call never allocates for a table the engine was made for (a longer one still grows it, behind a device synchronisation)
-    e->clean_g6_cap = (size_t)cfg->max_clip_frames * 8 * 6;
+    e->clean_g6_cap = (size_t)e->cfg.max_clip_frames * 8 * 6;
     ALLOC(e->clean_g6, e->clean_g6_cap, false);
+    return PA_OK;
+}
 
-    // ---- layer table + weights --------------------------------------------
-    // arena capacity: the folded tensors are the blob's plus zero padding (stem K 147 -> 224, fc and
-    // Conv1d 1000 -> 1024) and 256-byte alignment per tensor; 1.25x + 1 MiB covers every (S, A)
-    // (+ 16 / 9 of the 3x3 filters once more: the Winograd layout of the fp32 stride-1 3x3 layers, kept beside the direct one)
-    // (+ 36 / 9 of layer 4's three stride-1 filters where F(4x4, 3x3) taken apart can engage: engine_plan.h's wino4_layer)
-    e->arena_cap = pa_weight_blob_bytes(S, A) / 4 * 13 + (1u << 20);
-    if (e->dtype != DT_BF16 && K.wino && K.wino_f4 && NC >= K.wino_f4_min) e->arena_cap += 3 * (wino4_weight_floats(512, 512) * sizeof(float) + 256);
-    {
-        void* ar = nullptr;
-        HIPCHK(e, hipMalloc(&ar, e->arena_cap));
-        e->allocs.push_back(ar);
-        e->arena = reinterpret_cast<uint8_t*>(ar);
-    }
-    if (!e->adopt) e->arena_stage.assign(e->arena_cap, 0);
-    static const float dry_source[1] = {0.f};  // adopt mode: take() only has to return non-null
-    const float* blob_f = e->adopt ? dry_source : reinterpret_cast<const float*>(hdr + 8);
-    BlobReader br{blob_f, 0, blob_float_count(S, A), e->adopt};
-    std::vector<float> keep_w, keep_b;  // host copy of the last conv added with keep=true (not uploaded yet)
-    // a Winograd layer on a 4 x 4 map: its filters once more as the 36 GEMM images of F(4x4, 3x3) taken apart (wino4.hip), beside the
-    // F(2x2) image, which serves the batches below the threshold and PA_WINO_F4=0 at run time
-    auto add_wino4 = [&](ConvLayer& L, const std::vector<float>& w) -> int {
-        if (!wino4_layer(K, e->dtype, L, NC)) return PA_OK;
-        L.wino4 = true;
-        std::vector<float> u4(wino4_weight_floats(L.cin, L.cout), 0.f);
-        if (!br.dry) wino4_transform_weights(w.data(), L.cin, L.cout, u4.data());
-        return upload(e, &L.wino4_wgt, u4);
-    };
-    auto add_conv = [&](const std::string& name, int cin, int cout, int k, int stride, int in_hw, float* in, float* outb,
-                        float* residual, int relu, bool keep = false) -> int {
+// The weight arena, and in fold mode its zeroed host mirror. Capacity: the folded tensors are the blob's plus zero padding (stem K
+// 147 -> 224, fc and Conv1d 1000 -> 1024) and 256-byte alignment per tensor; 1.25x + 1 MiB covers every (S, A)
+// (+ 16 / 9 of the 3x3 filters once more: the Winograd layout of the fp32 stride-1 3x3 layers, kept beside the direct one)
+// (+ 36 / 9 of layer 4's three stride-1 filters where F(4x4, 3x3) taken apart can engage: engine_plan.h's wino4_layer)
+int alloc_arena(pa_engine* e, bool fold) {
+    const EngineKnobs& K = e->knobs;
+    e->arena_cap = pa_weight_blob_bytes(e->cfg.sequence_length, e->cfg.num_actions) / 4 * 13 + (1u << 20);
+    if (e->dtype != DT_BF16 && K.wino && K.wino_f4 && e->max_crops >= K.wino_f4_min) e->arena_cap += 3 * (wino4_weight_floats(512, 512) * sizeof(float) + 256);
+    void* ar = nullptr;
+    HIPCHK(e, hipMalloc(&ar, e->arena_cap));
+    e->allocs.push_back(ar);
+    e->arena = reinterpret_cast<uint8_t*>(ar);
+    if (fold) e->arena_stage.assign(e->arena_cap, 0);
+    return PA_OK;
+}
+
+// The table's rows (engine_table.h) as pa_engine::convs / fc, each with its buffers: per layer three zero-bordered activation
+// buffers the four convs rotate through, and the stored 1x1/2 branch where block-0 conv2 adds one
+int wire_layers(pa_engine* e, const std::vector<TableRow>& rows) {
+    for (const TableRow& r : rows) {
         ConvLayer L;
-        static_cast<LayerDesc&>(L) = conv_desc(K, e->dtype, NC, cin, cout, k, stride, in_hw, residual != nullptr);
-        L.name = name;
-        L.in = in;
-        L.out = outb;
-        L.residual = residual;
-        L.relu = relu;
-        std::vector<float> w, b;
-        if (!fold_conv(br, L, w, b)) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at " + name);
-        int r2 = PA_OK;
-        if (keep) {
-            keep_w.swap(w);
-            keep_b.swap(b);
-        } else {
-            r2 = (e->bf16 && k == 3) ? upload_bf16(e, &L.wgt, w) : upload(e, &L.wgt, w);
-            if (r2) return r2;
-            if (wino_layer(K, e->dtype, L)) {
-                L.wino = true;
-                L.wino_bn = wino_pick_bn(cout, (long long)NC * (L.out_hw / 4) * (L.out_hw / 4), cin);
-                std::vector<float> ug(wino_weight_floats(cin, cout), 0.f);
-                if (!br.dry) wino_transform_weights(w.data(), cin, cout, L.wino_bn, ug.data());
-                r2 = upload(e, &L.wino_wgt, ug);
-                if (r2) return r2;
-                if ((r2 = add_wino4(L, w))) return r2;
-            }
-            // PA_DTYPE_EMULATED_F32: the stride-2 3x3 openers of layers 2-4 on psgemm.hip (the stride-1 3x3 layers keep their exact
-            // Winograd kernel: per layer the two measure the same, profiles/r06_pgemm_split_layers.txt)
-            L.split = e->emu && k == 3 && stride == 2 && cin % 32 == 0;
-            if (L.split && (r2 = upload_split(e, &L.split_wgt, w, cout, 9 * cin, false))) return r2;
-            if (e->bf16 && k == 7 && (r2 = upload_bf16(e, &e->stem_wgt_bf16, w))) return r2;
-            r2 = upload(e, &L.bias, b);
-            if (r2) return r2;
-        }
-        e->convs.push_back(L);
-        return PA_OK;
-    };
-
-    rc = add_conv("conv1", 3, 64, 7, 2, 128, e->x0, e->c1, nullptr, 1);
-    if (rc) return rc;
-    {
-        const int widths[4] = {64, 128, 256, 512};
-        const int hw_in[4] = {32, 32, 16, 8};
-        float* cur = e->p1;
-        int cin = 64;
-        for (int li = 0; li < 4; ++li) {
-            const int co = widths[li];
-            const int stride = li == 0 ? 1 : 2;
-            const int hw_out = hw_in[li] / stride;
-            const size_t buf = (size_t)NC * (hw_out + 2) * (hw_out + 2) * co;
-            float *mid, *outA, *outB;
-            ALLOC(mid, buf, true);
-            ALLOC(outA, buf, true);
-            ALLOC(outB, buf, true);
-            const std::string pre = "layer" + std::to_string(li + 1);
-            // block 0 (blob order: conv1, bn1, conv2, bn2, downsample)
-            rc = add_conv(pre + ".0.conv1", cin, co, 3, stride, hw_in[li], cur, mid, nullptr, 1);
-            if (rc) return rc;
-            if (li == 0) {
-                rc = add_conv(pre + ".0.conv2", co, co, 3, 1, hw_out, mid, outA, cur, 1);
-                if (rc) return rc;
-            } else {
-                // conv2 and the 1x1/2 downsample of the block input are ONE implicit GEMM:
-                //   out = relu( [W2' | Wd'] . [im2col3x3(mid) ; x(2y,2x)] + (b2' + bd') )
-                // (K = 9*co + cin): no separate downsample launch, no residual tensor.
-                rc = add_conv(pre + ".0.conv2", co, co, 3, 1, hw_out, mid, outA, nullptr, 1, /*keep=*/true);
-                if (rc) return rc;
-                ConvLayer D;  // only used to fold the downsample weights
-                D.name = pre + ".0.downsample";
-                D.cin = cin; D.cout = co; D.kh = D.kw = 1; D.taps = 1; D.kw_taps = 1; D.chunk = cin;
-                std::vector<float> wd, bd;
-                if (!fold_conv(br, D, wd, bd)) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at " + D.name);
-                ConvLayer& L = e->convs.back();
-                const int k_main = 9 * co, k_all = k_main + cin;
-                std::vector<float> wf((size_t)co * k_all), bf(co);
-                for (int o = 0; o < co; ++o) {
-                    memcpy(&wf[(size_t)o * k_all], &keep_w[(size_t)o * k_main], sizeof(float) * k_main);
-                    memcpy(&wf[(size_t)o * k_all + k_main], &wd[(size_t)o * cin], sizeof(float) * cin);
-                    bf[o] = (float)((double)keep_b[o] + (double)bd[o]);
-                }
-                L.ds.src = cur;
-                L.branch.c = cin;
-                L.branch.hw = hw_in[li];
-                L.branch.stride = stride;
-                if (e->bf16) {
-                    rc = upload_bf16(e, &L.wgt, keep_w);  // [co][9 co]: the 3x3 alone
-                    if (rc) return rc;
-                    rc = upload_bf16(e, &L.ds.wgt, wd);   // [co][cin]
-                    if (rc) return rc;
-                    ALLOC(L.ds.out, buf, true);
-                } else {
-                    rc = upload(e, &L.wgt, wf);
-                    if (rc) return rc;
-                    // the same layer in Winograd form: the 3x3 alone on wino.hip, the 1x1/2 branch as a small GEMM of its own whose
-                    // result the 3x3 adds as its residual (PA_WINO >= 1 and the map sizes the kernel is faster on; else the fused
-                    // implicit GEMM above)
-                    if (K.wino_ds && wino_layer(K, e->dtype, L)) {
-                        L.wino = true;
-                        L.wino_bn = wino_pick_bn(co, (long long)NC * (hw_out / 4) * (hw_out / 4), co);
-                        std::vector<float> ug(wino_weight_floats(co, co), 0.f);
-                        if (!br.dry) wino_transform_weights(keep_w.data(), co, co, L.wino_bn, ug.data());
-                        rc = upload(e, &L.wino_wgt, ug);
-                        if (rc) return rc;
-                        if ((rc = add_wino4(L, keep_w))) return rc;
-                        rc = upload(e, &L.ds.wgt, wd);   // [co][cin] fp32
-                        if (rc) return rc;
-                        L.branch.split = e->emu;
-                        if (e->emu && (rc = upload_split(e, &L.ds.split_wgt, wd, co, cin, false))) return rc;
-                        ALLOC(L.ds.out, buf, true);
-                    }
-                }
-                // Where the branch is computed (engine_plan.h). bf16, PA_BF16_DS_FUSE=0: its own GEMM (round 2-3), for A/B runs. The exact
-                // path: the block's stride-2 opener computes it on its centre tap (pigemm.hip's pgemm_branch_kernel) and this layer adds
-                // ds.out without a launch (headline +1.7 %, profiles/opener_branch_parent_ab.md; results are bit-identical either way).
-                // PA_F32_DS_FUSE=0: the branch as its own GEMM (A/B); PA_DS_SIDE=1 and PA_S2_PGEMM=0 keep the separate GEMM too
-                ConvLayer& C1 = e->convs[e->convs.size() - 2];  // the block's stride-2 opener
-                L.branch.place = place_branch(K, e->dtype, C1, L, C1.in == cur, li);
-                if (L.branch.place == BRANCH_OPENER || L.branch.place == BRANCH_OPENER_PROBE) {
-                    C1.carries = L.branch.place;
-                    C1.carries_of = (int)e->convs.size() - 1;
-                }
-                rc = upload(e, &L.bias, bf);
-                if (rc) return rc;
-                L.k_alg += cin;
-            }
-            rc = add_conv(pre + ".1.conv1", co, co, 3, 1, hw_out, outA, mid, nullptr, 1);
-            if (rc) return rc;
-            rc = add_conv(pre + ".1.conv2", co, co, 3, 1, hw_out, mid, outB, outA, 1);
-            if (rc) return rc;
-            cur = outB;
-            cin = co;
-        }
-        e->layer4_out = cur;
+        static_cast<LayerDesc&>(L) = r.d;
+        L.name = r.name;
+        L.carries_of = r.carries_of;
+        if (r.kind == ROW_FC) e->fc = L;
+        else e->convs.push_back(L);
     }
-    {  // fc 512 -> 1000 (N padded to 1024 with zero rows so cached rows are 1024 wide)
-        const float* w = br.take((size_t)1000 * 512);
-        const float* b = br.take(1000);
-        if (!w || !b) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at fc");
-        std::vector<float> wp((size_t)PA_FEATURE_STRIDE * 512, 0.f), bp(PA_FEATURE_STRIDE, 0.f);
-        if (!br.dry) {
-            memcpy(wp.data(), w, sizeof(float) * 1000 * 512);
-            memcpy(bp.data(), b, sizeof(float) * 1000);
+    e->convs[0].in = e->x0;
+    e->convs[0].out = e->c1;
+    float* cur = e->p1;
+    for (int li = 0; li < 4; ++li) {
+        ConvLayer* c = &e->convs[1 + 4 * li];  // conv1, conv2 of block 0; conv1, conv2 of block 1
+        const size_t buf = (size_t)e->max_crops * (c[0].out_hw + 2) * (c[0].out_hw + 2) * c[0].cout;
+        float *mid, *outA, *outB;
+        ALLOC(mid, buf, true);
+        ALLOC(outA, buf, true);
+        ALLOC(outB, buf, true);
+        c[0].in = cur; c[0].out = mid;
+        c[1].in = mid; c[1].out = outA;
+        if (rows[2 + 4 * li].kind == ROW_CONV2_DS) {
+            c[1].ds.src = cur;
+            if (c[1].branch.place != BRANCH_SECOND_K) ALLOC(c[1].ds.out, buf, true);
+        } else {
+            c[1].residual = cur;
         }
-        ConvLayer& L = e->fc;
-        static_cast<LayerDesc&>(L) = fc_desc(K, PA_FEATURE_STRIDE);
-        L.name = "fc";
-        L.in = e->pooled; L.out = nullptr; L.residual = nullptr;
-        rc = upload(e, &L.wgt, wp);
-        if (rc) return rc;
-        rc = upload(e, &L.bias, bp);
-        if (rc) return rc;
+        c[2].in = outA; c[2].out = mid;
+        c[3].in = mid; c[3].out = outB; c[3].residual = outA;
+        cur = outB;
+    }
+    e->layer4_out = cur;
+    e->fc.in = e->pooled;
+    return PA_OK;
+}
+
+// The arena entries of one conv row, in the arena's order; br: fold mode, the blob at this row (nullptr: adopt mode, sizes only)
+int place_conv(pa_engine* e, ConvLayer& L, RowKind kind, BlobReader* br) {
+    const int cin = L.cin, co = L.cout, ktot = L.taps * L.chunk, cb = L.branch.c;
+    const bool ds = kind == ROW_CONV2_DS, bf = e->bf16 && L.kh == 3;
+    std::vector<float> w, b, wd, bd;  // fold mode: the conv, and the 1x1/2 downsample behind it, BatchNorm folded
+    if (br && !fold_conv(*br, L, w, b)) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at " + L.name);
+    if (br && ds) {
+        LayerDesc D;
+        D.cin = cb; D.cout = co; D.kh = D.kw = 1; D.taps = 1; D.kw_taps = 1; D.chunk = cb;
+        if (!fold_conv(*br, D, wd, bd)) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at " + L.name.substr(0, L.name.rfind('.')) + ".downsample");
+        for (int o = 0; o < co; ++o) b[o] = (float)((double)b[o] + (double)bd[o]);
+    }
+    int rc;
+    float* s;
+    if (bf) {   // bf16: the 3x3 alone, the branch always a matrix of its own
+        if ((rc = put_bf16(e, &L.wgt, (size_t)co * ktot, w.data()))) return rc;
+        if (ds && (rc = put_bf16(e, &L.ds.wgt, (size_t)co * cb, wd.data()))) return rc;
+    } else if (ds) {   // [W2 | Wd]: the branch as extra K
+        if ((rc = arena_place(e, &L.wgt, (size_t)co * (ktot + cb), &s))) return rc;
+        for (int o = 0; s && o < co; ++o) {
+            memcpy(s + (size_t)o * (ktot + cb), &w[(size_t)o * ktot], sizeof(float) * ktot);
+            memcpy(s + (size_t)o * (ktot + cb) + ktot, &wd[(size_t)o * cb], sizeof(float) * cb);
+        }
+    } else if ((rc = put(e, &L.wgt, (size_t)co * ktot, w.data()))) {
+        return rc;
+    }
+    if (L.wino) {
+        L.wino_bn = wino_pick_bn(co, (long long)e->max_crops * (L.out_hw / 4) * (L.out_hw / 4), cin);
+        if ((rc = arena_place(e, &L.wino_wgt, wino_weight_floats(cin, co), &s))) return rc;
+        if (s) wino_transform_weights(w.data(), cin, co, L.wino_bn, s);
+        // on a 4 x 4 map once more as the 36 GEMM images of F(4x4, 3x3) taken apart (wino4.hip), beside the F(2x2) image, which serves
+        // the batches below the threshold and PA_WINO_F4=0 at run time
+        if (L.wino4) {
+            if ((rc = arena_place(e, &L.wino4_wgt, wino4_weight_floats(cin, co), &s))) return rc;
+            if (s) wino4_transform_weights(w.data(), cin, co, s);
+        }
+        // block-0 conv2 in Winograd form: the 1x1/2 branch is a small GEMM of its own whose result the 3x3 adds as its residual
+        if (ds && (rc = put(e, &L.ds.wgt, (size_t)co * cb, wd.data()))) return rc;
+        if (ds && L.branch.split && (rc = put_split(e, &L.ds.split_wgt, wd.data(), co, cb))) return rc;
+    }
+    if (L.split && (rc = put_split(e, &L.split_wgt, w.data(), co, ktot))) return rc;
+    if (e->bf16 && L.kh == 7 && (rc = put_bf16(e, &e->stem_wgt_bf16, (size_t)co * ktot, w.data()))) return rc;
+    return put(e, &L.bias, co, b.data());
+}
+
+// Every arena entry, in the arena's order: the conv rows, the fc, the temporal head. Each entry's size follows from the table and
+// (S, A) and is placed in both modes; only fold mode (br != nullptr) reads the blob and fills the host stage
+int place_weights(pa_engine* e, const std::vector<TableRow>& rows, BlobReader* br) {
+    const int S = e->cfg.sequence_length, A = e->cfg.num_actions;
+    int rc;
+    float* s;
+    for (size_t i = 0; i < e->convs.size(); ++i)
+        if ((rc = place_conv(e, e->convs[i], rows[i].kind, br))) return rc;
+    {  // fc 512 -> 1000 (N padded to 1024 with zero rows so cached rows are 1024 wide)
+        const float *w = nullptr, *b = nullptr;
+        if (br && (!(w = br->take((size_t)1000 * 512)) || !(b = br->take(1000)))) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at fc");
+        if ((rc = put(e, &e->fc.wgt, (size_t)PA_FEATURE_STRIDE * 512, w, (size_t)1000 * 512))) return rc;
+        if ((rc = put(e, &e->fc.bias, PA_FEATURE_STRIDE, b, 1000))) return rc;
     }
     {  // Conv1d(1000 -> 512, k=S): [512][1000][S] -> [512][S][1024]
-        const float* w = br.take((size_t)512 * 1000 * S);
-        const float* b = br.take(512);
-        if (!w || !b) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at cnn1d");
-        std::vector<float> wp((size_t)512 * S * PA_FEATURE_STRIDE, 0.f);
-        for (int o = 0; o < 512 && !br.dry; ++o)
+        const float *w = nullptr, *b = nullptr;
+        if (br && (!(w = br->take((size_t)512 * 1000 * S)) || !(b = br->take(512)))) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob too short at cnn1d");
+        if ((rc = arena_place(e, &e->w1d, (size_t)512 * S * PA_FEATURE_STRIDE, &s))) return rc;
+        for (int o = 0; s && o < 512; ++o)
             for (int c = 0; c < 1000; ++c)
-                for (int t = 0; t < S; ++t)
-                    wp[((size_t)o * S + t) * PA_FEATURE_STRIDE + c] = w[((size_t)o * 1000 + c) * S + t];
-        rc = upload(e, &e->w1d, wp);
-        if (rc) return rc;
-        rc = upload(e, &e->b1d, br.dry ? std::vector<float>(512) : std::vector<float>(b, b + 512));
-        if (rc) return rc;
-        choose_tile(NC, 512, S * 32, &e->head_tile, &e->head_splitk);
-        // 16 tiles x 224 k-steps: 16 splits of 14 steps beat 32 of 7 (26.2 vs 28.6 us incl. the reduce)
-        if (e->head_splitk > 16) e->head_splitk = 16;
-        if (K.head_splitk) e->head_splitk = K.head_splitk;
+                for (int t = 0; t < S; ++t) s[((size_t)o * S + t) * PA_FEATURE_STRIDE + c] = w[((size_t)o * 1000 + c) * S + t];
+        if ((rc = put(e, &e->b1d, 512, b))) return rc;
     }
-    {
-        const float* w2 = br.take(128 * 512);
-        const float* b2 = br.take(128);
-        const float* w3 = br.take((size_t)A * 128);
-        const float* b3 = br.take(A);
-        if (!w2 || !b2 || !w3 || !b3 || br.pos != br.limit) return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob size mismatch at classifier");
-        // head_mlp_kernel reads both matrices k-major (lanes = outputs): w2 -> [512][128], w3 -> [128][64]
-        std::vector<float> w2t((size_t)512 * 128), w3t((size_t)128 * 64, 0.f);
-        for (int o = 0; o < 128 && !br.dry; ++o)
-            for (int k = 0; k < 512; ++k) w2t[(size_t)k * 128 + o] = w2[(size_t)o * 512 + k];
-        for (int a = 0; a < A && !br.dry; ++a)
-            for (int k = 0; k < 128; ++k) w3t[(size_t)k * 64 + a] = w3[(size_t)a * 128 + k];
-        if ((rc = upload(e, &e->w2, w2t))) return rc;
-        if ((rc = upload(e, &e->b2, br.dry ? std::vector<float>(128) : std::vector<float>(b2, b2 + 128)))) return rc;
-        if ((rc = upload(e, &e->w3, w3t))) return rc;
-        if ((rc = upload(e, &e->b3, br.dry ? std::vector<float>(A) : std::vector<float>(b3, b3 + A)))) return rc;
+    {  // head_mlp_kernel reads both matrices k-major (lanes = outputs): w2 -> [512][128], w3 -> [128][64]
+        const float *w2 = nullptr, *b2 = nullptr, *w3 = nullptr, *b3 = nullptr;
+        if (br && (!(w2 = br->take(128 * 512)) || !(b2 = br->take(128)) || !(w3 = br->take((size_t)A * 128)) || !(b3 = br->take(A)) || br->pos != br->limit))
+            return fail(e, PA_ERR_BAD_WEIGHTS, "weight blob size mismatch at classifier");
+        if ((rc = arena_place(e, &e->w2, (size_t)512 * 128, &s))) return rc;
+        for (int o = 0; s && o < 128; ++o)
+            for (int k = 0; k < 512; ++k) s[(size_t)k * 128 + o] = w2[(size_t)o * 512 + k];
+        if ((rc = put(e, &e->b2, 128, b2))) return rc;
+        if ((rc = arena_place(e, &e->w3, (size_t)128 * 64, &s))) return rc;
+        for (int a = 0; s && a < A; ++a)
+            for (int k = 0; k < 128; ++k) s[(size_t)k * 64 + a] = w3[(size_t)a * 128 + k];
+        if ((rc = put(e, &e->b3, A, b3))) return rc;
     }
-    // the arena is complete: one host-to-device copy (fold mode) or one device copy (adopt mode)
-    if (e->adopt) {
+    return PA_OK;
+}
+
+// The arena is laid out: one host-to-device copy of the stage (fold mode) or one device copy of the prepared arena (adopt mode)
+int load_arena(pa_engine* e, const void* arena_dev, size_t src_bytes) {
+    if (arena_dev) {
         if (src_bytes != e->arena_used) return fail(e, PA_ERR_BAD_WEIGHTS, "weight arena size does not match this configuration");
         HIPCHK(e, hipMemcpy(e->arena, arena_dev, e->arena_used, hipMemcpyDeviceToDevice));
     } else {
         HIPCHK(e, hipMemcpy(e->arena, e->arena_stage.data(), e->arena_used, hipMemcpyHostToDevice));
         std::vector<uint8_t>().swap(e->arena_stage);
     }
-    if (e->stem_int) {
-        // the integer stem's three bf16 slices, from the folded fp32 stem weights as they lie in the arena (so a folded and an adopted
-        // arena give the same slices and the arena keeps its size and layout): s0 = bf16(w), s1 = bf16(w - s0), s2 = bf16(w - s0 - s1),
-        // round to nearest even each, the splitting of pack_stage_weights
-        const size_t nw = (size_t)64 * 224;
-        std::vector<float> w(nw);
-        HIPCHK(e, hipMemcpy(w.data(), e->convs[0].wgt, nw * sizeof(float), hipMemcpyDeviceToHost));
-        std::vector<uint16_t> sl(3 * nw);
-        for (size_t i = 0; i < nw; ++i) {
-            float x = w[i];
-            for (int k = 0; k < 3; ++k) {
-                const uint16_t hq = bf16_rne(x);
-                sl[k * nw + i] = hq;
-                const uint32_t u = (uint32_t)hq << 16;
-                float f;
-                memcpy(&f, &u, 4);
-                x -= f;
-            }
+    return PA_OK;
+}
+
+// The integer stem's three bf16 slices, from the folded fp32 stem weights as they lie in the arena (so a folded and an adopted
+// arena give the same slices and the arena keeps its size and layout): s0 = bf16(w), s1 = bf16(w - s0), s2 = bf16(w - s0 - s1),
+// round to nearest even each, the splitting of pack_stage_weights
+int make_stem_slices(pa_engine* e) {
+    if (!e->stem_int) return PA_OK;
+    const size_t nw = (size_t)64 * 224;
+    std::vector<float> w(nw);
+    HIPCHK(e, hipMemcpy(w.data(), e->convs[0].wgt, nw * sizeof(float), hipMemcpyDeviceToHost));
+    std::vector<uint16_t> sl(3 * nw);
+    for (size_t i = 0; i < nw; ++i) {
+        float x = w[i];
+        for (int k = 0; k < 3; ++k) {
+            const uint16_t hq = bf16_rne(x);
+            sl[k * nw + i] = hq;
+            const uint32_t u = (uint32_t)hq << 16;
+            float f;
+            memcpy(&f, &u, 4);
+            x -= f;
         }
-        ALLOC(e->stem_wgt_int, 3 * nw, false);
-        HIPCHK(e, hipMemcpy(e->stem_wgt_int, sl.data(), sl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
-    // split-K slabs: the largest splitk*M*N over all layers
-    {
-        size_t need = 0;
-        for (const ConvLayer& L : e->convs)
-            if (L.splitk > 1) need = std::max(need, (size_t)L.splitk * NC * L.out_hw * L.out_hw * L.cout);
-        if (e->fc.splitk > 1) need = std::max(need, (size_t)e->fc.splitk * NC * PA_FEATURE_STRIDE);
-        if (e->head_splitk > 1) need = std::max(need, (size_t)e->head_splitk * NC * 512);
-        // the Winograd kernel's split-K scratch (wino.hip): at most one launch's worth of partial output tiles -- a grid of 256
-        // eight-wave (512 four-wave) workgroups x 32 floats per thread -- and a ticket per tile
-        bool any_wino = false;
-        for (const ConvLayer& L : e->convs) any_wino = any_wino || L.wino_wgt;
-        if (any_wino) {
-            need = std::max(need, (size_t)256 * 512 * 32);
-            ALLOC(e->wino_tickets, (size_t)2 * WINO_TICKETS, true);
-        }
-        // V and M of F(4x4, 3x3) taken apart (wino4.hip)
-        for (const ConvLayer& L : e->convs)
-            if (L.wino4_wgt) e->wino4_region = std::max(e->wino4_region, (size_t)36 * wino4_rows(NC) * (L.cin + L.cout));
-        if (e->wino4_region) ALLOC(e->wino4_scratch, e->wino4_region * (K.interleave ? 2 : 1), false);
-        need *= 2;  // one region per interleaved half batch
-        e->slab_floats = need;
-        ALLOC(e->slab, need, false);
+    ALLOC(e->stem_wgt_int, 3 * nw, false);
+    HIPCHK(e, hipMemcpy(e->stem_wgt_int, sl.data(), sl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    return PA_OK;
+}
+
+// The split-K slab (engine_table.h's slab_floats), the Winograd kernel's tickets -- one per tile -- and V and M of F(4x4, 3x3)
+// taken apart (wino4.hip)
+int alloc_slab(pa_engine* e, const std::vector<TableRow>& rows) {
+    bool any_wino = false;
+    for (const ConvLayer& L : e->convs) {
+        any_wino = any_wino || L.wino;
+        if (L.wino4) e->wino4_region = std::max(e->wino4_region, (size_t)36 * wino4_rows(e->max_crops) * (L.cin + L.cout));
     }
-    // preprocess scratch
+    if (any_wino) ALLOC(e->wino_tickets, (size_t)2 * WINO_TICKETS, true);
+    if (e->wino4_region) ALLOC(e->wino4_scratch, e->wino4_region * (e->knobs.interleave ? 2 : 1), false);
+    e->slab_floats = slab_floats(rows, e->knobs, e->max_crops, e->cfg.sequence_length);
+    ALLOC(e->slab, e->slab_floats, false);
+    return PA_OK;
+}
+
+int alloc_crop_scratch(pa_engine* e) {
+    const pa_config* cfg = &e->cfg;
+    const int NC = e->max_crops;
     e->coef_dim = std::max(cfg->max_frame_height, cfg->max_frame_width);
     // per-crop scratch of the resamplers: a whole frame slice, and at least the runner-input branch's worst
     // case (INTER_AREA result of 448 rows + the 128 rows behind the vertical pass, 128 px x 3 B each)
@@ -1099,13 +998,15 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     ALLOC(e->hop, (size_t)NC * PA_HOP_BLOCKS_MAX * PA_HOP_BLOCK_BYTES, true);  // 302 KB a crop
     ALLOC(e->t1, (size_t)NC * e->t_stride, false);
     ALLOC(e->t2, (size_t)NC * e->t_stride, false);
-    {
-        AugmentTables at;
-        augment_tables_host(&at);
-        ALLOC(e->aug_tabs, (size_t)1, false);
-        HIPCHK(e, hipMemcpy(e->aug_tabs, &at, sizeof(at), hipMemcpyHostToDevice));
-    }
+    AugmentTables at;
+    augment_tables_host(&at);
+    ALLOC(e->aug_tabs, (size_t)1, false);
+    HIPCHK(e, hipMemcpy(e->aug_tabs, &at, sizeof(at), hipMemcpyHostToDevice));
+    return PA_OK;
+}
 #undef ALLOC
+
+int create_streams(pa_engine* e) {
     HIPCHK(e, hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
@@ -1113,6 +1014,40 @@ int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const 
     HIPCHK(e, hipEventCreateWithFlags(&e->ev_ds_join, hipEventDisableTiming));
     HIPCHK(e, hipDeviceSynchronize());
     return PA_OK;
+}
+
+// pa_create (blob != nullptr: fold the Lightning tensors) and pa_create_from_arena (arena_dev != nullptr:
+// adopt a prepared weight arena of `src_bytes` bytes) share everything but the source of the weights.
+int create_impl(const pa_config* cfg, const void* blob, size_t src_bytes, const void* arena_dev, pa_engine** out) {
+    int rc = check_create_args(cfg, blob, src_bytes, arena_dev, out);
+    if (rc) return rc;
+    pa_engine* e = new pa_engine();
+    e->cfg = *cfg;
+    e->bf16 = cfg->compute_dtype == PA_DTYPE_BF16;
+    e->emu = cfg->compute_dtype == PA_DTYPE_EMULATED_F32;
+    e->dtype = e->bf16 ? DT_BF16 : e->emu ? DT_EMULATED_F32 : DT_F32;
+    e->knobs = engine_knobs();  // the per-create knobs as the environment has them now
+    e->max_crops = cfg->max_batch_frames * cfg->num_fighters;
+    e->cache_rows = cfg->max_clip_frames * cfg->num_fighters;
+    *out = e;  // handed back even on failure so the caller can read pa_last_error, then pa_destroy
+    const std::vector<TableRow> rows = engine_table(e->knobs, e->dtype, e->max_crops);
+    if ((rc = select_device(e))) return rc;
+    if ((rc = alloc_activations(e))) return rc;
+    if ((rc = alloc_arena(e, blob != nullptr))) return rc;
+    if ((rc = wire_layers(e, rows))) return rc;
+    head_plan(e->knobs, e->max_crops, cfg->sequence_length, &e->head_tile, &e->head_splitk);
+    if (blob) {   // fold: the tensors behind the blob's header, all of them
+        BlobReader br{reinterpret_cast<const float*>(blob) + 8, 0, blob_floats(rows, cfg->sequence_length, cfg->num_actions)};
+        rc = place_weights(e, rows, &br);
+    } else {
+        rc = place_weights(e, rows, nullptr);
+    }
+    if (rc) return rc;
+    if ((rc = load_arena(e, arena_dev, src_bytes))) return rc;
+    if ((rc = make_stem_slices(e))) return rc;
+    if ((rc = alloc_slab(e, rows))) return rc;
+    if ((rc = alloc_crop_scratch(e))) return rc;
+    return create_streams(e);
 }
 
 }  // namespace

@@ -1,12 +1,13 @@
 """What the ResNet-18 engine plans for each layer (csrc/engine_plan.h: the knob table, plan_conv), without a GPU.
 
-tests/helpers/engine_plan_table.cpp includes the header, builds the seventeen-conv table + fc the way ``create_impl`` does and prints
-one line per (dtype, max crops, crops, layer); knob settings are arguments, so nothing here touches this process's environment. It
-is compiled with the host C++ compiler alone ($CXX, else g++): no hipcc, no GPU.
+tests/helpers/engine_plan_table.cpp prints the seventeen-conv table + fc that ``pa_create`` itself builds (csrc/engine_table.h: the
+rows, the split-K slab and the weight blob's float count are the engine's own, not a copy), one line per (dtype, max crops, crops,
+layer); knob settings are arguments, so nothing here touches this process's environment. It is compiled with the host C++ compiler
+alone ($CXX, else g++): no hipcc, no GPU.
 
 The expected values are written out by hand from the rules themselves -- ``choose_tile`` / ``im2col_tile`` (transcribed here as
-``choose_tile``), the order of forms and ``create_impl``'s placement of the 1x1/2 branches -- never taken from
-``plan_conv``'s output. They are also what tests/helpers/opener_branch_worker.py and tests/test_backbone_layers.py say their batch
+``choose_tile``), the order of forms, ``wino4_layer``'s rule and the table's placement of the 1x1/2 branches -- never
+taken from ``plan_conv``'s output. They are also what tests/helpers/opener_branch_worker.py and tests/test_backbone_layers.py say their batch
 sizes reach.
 """
 import os
@@ -58,11 +59,12 @@ def table(tmp_path_factory):
                 f = dict(x.split("=", 1) for x in fields)
                 if kind == "forms":
                     forms[f["dtype"]] = f
-                else:
+                elif kind == "plan":
                     plans[(f["dtype"], int(f["max_crops"]), int(f["crops"]), f["layer"])] = f
             cache[key] = (plans, forms)
         return cache[key]
 
+    run.exe = exe
     return run
 
 
@@ -71,6 +73,7 @@ def rows(plans, dtype, max_crops, crops):
 
 
 F32_CASES = [f"f32:128:{n}" for n in (1, 5, 35, 64, 128)]
+LAYER4_STRIDE1 = ["layer4.0.conv2", "layer4.1.conv1", "layer4.1.conv2"]   # the 4 x 4 maps: F(4x4, 3x3) from 64 crops per launch
 
 
 def test_f32_openers_at_default_knobs(table):
@@ -111,13 +114,46 @@ def test_f32_default_any_batch(table):
         assert len(r) == 18
         for name in STRIDE1:
             assert r[name]["form"] == "wino", (n, name)
-            assert float(r[name]["flops_executed"]) == float(r[name]["flops"]) * 4.0 / 9.0
+            f4 = name in LAYER4_STRIDE1 and n >= 64
+            assert r[name]["wino_f4"] == str(int(f4)), (n, name)
+            assert float(r[name]["flops_executed"]) == float(r[name]["flops"]) * (1.0 / 4.0 if f4 else 4.0 / 9.0), (n, name)
         for l, name in zip((2, 3, 4), BLOCK0_CONV2):
             assert r[name]["branch"] in ("stored", "gemm_before") and r[name]["place"] != "second_k"
             assert int(r[name]["ktot"]) == 9 * WIDTH[l]   # no second K source
             assert float(r[name]["flops"]) == 2.0 * n * OUT_HW[l] ** 2 * WIDTH[l] * 9 * WIDTH[l]
         assert (r["fc"]["form"], r["fc"]["tile"], r["fc"]["splitk"]) == ("im2col", "64x64", "4")
         assert r["conv1"]["form"] == "im2col"   # (the generic stem: only PA_STEM_IGEMM=1 launches it)
+
+
+def test_f4_filters_per_case(table):
+    """LayerDesc::wino4 by wino4_layer's rule: an exact dtype, a Winograd layer on a 4 x 4 map, PA_WINO_F4, and an engine whose full
+    batch reaches the threshold of 64 crops."""
+    def have(case, *knobs):
+        return sorted(k[3] for k, v in table([case], *knobs)[0].items() if v["wino4"] == "1")
+
+    assert have("f32:128:128") == LAYER4_STRIDE1
+    assert have("f32:128:1") == LAYER4_STRIDE1       # the filters belong to the engine, not to the launch
+    assert have("emulated_f32:128:128") == LAYER4_STRIDE1
+    assert have("f32:32:32") == []
+    assert have("f32:128:128", "PA_WINO_F4=0") == []
+    assert have("bf16:128:128") == []
+    assert all(v["wino_f4"] == "0" for case in ("f32:32:32", "bf16:128:128", "f32:128:1") for v in table([case])[0].values())
+    assert all(v["wino_f4"] == "0" for v in table(["f32:128:128"], "PA_WINO_F4=0")[0].values())
+
+
+@pytest.mark.parametrize("S,A", [(1, 1), (5, 7), (15, 64)])
+def test_blob_float_count(table, S, A):
+    """The table's count of the weight blob against Python's own statement of it and against ResNet-18 counted by hand: 11 689 512
+    parameters (the 1000-way fc included) + running mean and variance of 4 800 BatchNorm channels = 11 699 112."""
+    import math
+
+    from playaid_core_amd.weights import blob_key_order
+
+    out = subprocess.run([table.exe, f"blob:{S}:{A}"], check=True, capture_output=True, text=True).stdout.splitlines()
+    got = [dict(x.split("=", 1) for x in line.split()[1:]) for line in out if line.startswith("blob ")]
+    assert len(got) == 1 and (got[0]["S"], got[0]["A"]) == (str(S), str(A))
+    assert int(got[0]["floats"]) == sum(math.prod(shape) for _, shape in blob_key_order(S, A))
+    assert int(got[0]["floats"]) == 11_699_112 + 512 * 1000 * S + 512 + 128 * 512 + 128 + 128 * A + A
 
 
 def test_knob_precedence_f32(table):

@@ -198,17 +198,22 @@ def plan_table(tmp_path_factory):
     cxx = os.environ.get("CXX") or "g++"
     if not shutil.which(cxx.split()[0]):
         pytest.skip(f"no host C++ compiler ({cxx})")
-    exe = str(tmp_path_factory.mktemp("wino4_plan") / "wino4_plan_table")
-    subprocess.run(cxx.split() + ["-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "helpers", "wino4_plan_table.cpp")], check=True)
+    exe = str(tmp_path_factory.mktemp("wino4_plan") / "engine_plan_table")
+    subprocess.run(cxx.split() + ["-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "helpers", "engine_plan_table.cpp")], check=True)
 
     def run(*args):
+        """The knobs line and the rows of the four layers' second blocks (layerN.1.conv1: cin = cout = 64 .. 512 on maps of 32 .. 4)
+        of the engine's own table; has_f4_filters: LayerDesc::wino4."""
         env = {k: v for k, v in os.environ.items() if not k.startswith("PA_")}
         out = subprocess.run([exe, *args], check=True, capture_output=True, text=True, env=env).stdout.splitlines()
         knobs = dict(x.split("=", 1) for x in out[0].split()[1:])
         plans = {}
         for line in out[1:]:
-            f = dict(x.split("=", 1) for x in line.split()[1:])
-            plans[(f["dtype"], int(f["max_crops"]), int(f["crops"]), f["layer"])] = f
+            kind, *fields = line.split()
+            f = dict(x.split("=", 1) for x in fields)
+            if kind == "plan" and f["layer"].endswith(".1.conv1"):
+                f["has_f4_filters"] = f["wino4"]
+                plans[(f["dtype"], int(f["max_crops"]), int(f["crops"]), f["layer"])] = f
         return knobs, plans
 
     return run
