@@ -4,6 +4,7 @@
 #include "gemm_tile.h"   // GemmTile
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "crop_math.h"  // CropPlan, AreaTabPacked (behind the HIP runtime: its device functions use __mul24)
 
 namespace pa {
 
@@ -231,10 +232,7 @@ hipError_t launch_wino4_conv3x3(const Wino4Params& p, hipStream_t s);
 // ---------------------------------------------------------------------------
 // crop preprocessing (preprocess.hip)
 // ---------------------------------------------------------------------------
-#define PA_KSIZE_MAX 15
-// Plan-internal crop status (never reported): a (d x 0) slice that ImageOps.pad turns into a black d x d canvas
-// without resizing. The kernels treat it as a failed crop (all-zero pixels); the plan reports PA_CROP_OK.
-#define PA_CROP_BLANK 0x100
+// CropPlan, AreaTabPacked, PA_KSIZE_MAX and PA_CROP_BLANK: crop_math.h (included above; the host compiler reads it too)
 // Stage buffers of crop_fused_kernel; + 2176 B of INTER_AREA tables = 80000 B: two 512-thread
 // workgroups per CU (16 waves). Measured ladder of this choice (64 x 1080p step, kernel alone):
 // 256 threads / 50944 B (3 per CU) 0.189 ms -> 512 threads / 46592 B 0.169 -> 512 threads / 77824 B
@@ -242,37 +240,6 @@ hipError_t launch_wino4_conv3x3(const Wino4Params& p, hipStream_t s);
 // 8-row sub-bands (the 7-tap vertical support makes 4-row sub-bands recompute 1.7x of the horizontal
 // pass, 8-row ones 1.35x).
 #define PA_FUSED_LDS_BYTES 77824
-
-struct CropPlan {
-    int32_t status;
-    int32_t frame;
-    int32_t sx0, sy0, sw, sh;  // slice of the frame
-    int32_t d;                 // square side
-    int32_t rw, rh;            // size after ImageOps.contain
-    int32_t px, py;            // paste offset inside the d x d canvas
-    int32_t need_h, need_v;    // bicubic passes
-    int32_t ksize_h, ksize_v;
-    int32_t out_h;             // INTER_AREA destination height (width is 128)
-    int32_t area_mode;         // 0 copy, 1 fast 2x2, 2 fast integer, 3 general
-    int32_t iscale_x, iscale_y;
-    int32_t fused_rb;          // output rows per LDS sub-band of the fused kernel (8/4/2/1), 0 = multi-kernel fallback
-    int32_t mfma_v;            // the fused kernel's vertical pass runs on the int8 matrix instruction (B1 transposed in LDS)
-    // the horizontal pass runs on it as well (only with mfma_v), from the crop's operand in PreprocParams::hop. 1: B0 is
-    // staged as the frame's aligned dwords and the operand's tap positions carry the slice's byte misalignment h_mis;
-    // 2 (PA_CROP_MFMA_H=2, the A/B row of the staging alone): B0 is staged re-aligned as for the vector form, h_mis = 0
-    int32_t mfma_h, h_mis;
-    double scale_x, scale_y;
-    // Pillow coefficient tables of the two bicubic passes ([out][2 + PA_KSIZE_MAX]): the engine's cache of the
-    // (2 * (d / 2) + 2 * padding -> d) pairs, or this crop's own rows of PreprocParams::coef for any other pair
-    const int32_t* coef_h;
-    const int32_t* coef_v;
-};
-
-// One entry of cv::computeResizeAreaTab per destination column / row of a crop (plan kernel -> fused kernel)
-struct AreaTabPacked {
-    uint32_t bits;  // s_first | n_mid << 16 | has_first << 24 | has_last << 25
-    float a_first, a_mid, a_last;
-};
 
 // The horizontal matrix form's operand (crop_hop_kernel -> crop_fused_kernel): per crop PA_HOP_BLOCKS_MAX blocks of 10
 // output pixels (30 byte columns of the 32 the instruction has), PA_HOP_BLOCK_BYTES each: six 1 KB fragments -- digit

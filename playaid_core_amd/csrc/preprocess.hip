@@ -24,6 +24,14 @@
 // kernel's two bicubic passes, on the int8 matrix instruction). Five small kernels keep every
 // size general (any box, any frame): a fused LDS kernel for crops whose bands fit 48 KB,
 // a multi-pass fallback over global scratch for the rest.
+//
+// Where the pieces live: the reference arithmetic itself -- the plan's geometry, the INTER_AREA branch and pixel, Pillow's
+// tables and output values, the matrix forms' digits -- is crop_math.h's, once each and host-compilable; what needs
+// PreprocParams (slice / intermediates / tables of a crop, the two global-memory passes, the plan kernels' head and tail)
+// is crop_common.h's, shared with crop_sized.hip. This file holds the 128 path's kernels -- plan (its sub-band and
+// matrix-form search), operand builder, fallback, the fused kernel as stage functions (cf_*) under its band loop (the
+// vector form of its horizontal pass alone stays inline: see there) -- and the
+// runner-input, rectangle, box-projection and window-upload kernels.
 #include "crop_common.h"
 #ifdef PA_STAMP_BUILD
 #include <cstdio>
@@ -80,8 +88,6 @@ __device__ __forceinline__ BandRows band_rows(const CropPlan& pl, int r0, int r1
     }
     return b;
 }
-
-__device__ __forceinline__ int kk_dbg(const int32_t* row, int t) { return row[2 + t]; }
 
 __device__ __forceinline__ int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
@@ -162,114 +168,7 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
     const int crop = blockIdx.x;
     if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
-    CropPlan pl;
-    pl.status = PA_CROP_OK;
-    pl.frame = p.src_frame ? p.src_frame[crop] : crop / p.fighters;
-    pl.sx0 = pl.sy0 = pl.sw = pl.sh = 0;
-    pl.d = pl.rw = pl.rh = pl.px = pl.py = 0;
-    pl.need_h = pl.need_v = pl.ksize_h = pl.ksize_v = 0;
-    pl.out_h = 0;
-    pl.area_mode = 0;
-    pl.iscale_x = pl.iscale_y = 1;
-    pl.fused_rb = 0;
-    pl.mfma_v = 0;
-    pl.mfma_h = pl.h_mis = 0;
-    pl.coef_h = pl.coef_v = nullptr;
-    pl.scale_x = pl.scale_y = 1.0;
-    const double* b = p.boxes + (size_t)crop * 4;
-    const int W = p.width, H = p.height, pad = p.padding;
-    if (!p.windows && (unsigned)pl.frame >= (unsigned)p.n_src) {  // a source index outside the frame buffer: never dereferenced
-        pl.frame = 0;
-        pl.status = PA_CROP_BAD_FRAME;
-    }
-    int cx, cy, cw, ch;
-    // YoloCrop.yolo_pixels (fighter.py:305-314)
-    if (pl.status == PA_CROP_OK && (!to_int_checked(b[0] * W, &cx) || !to_int_checked(b[1] * H, &cy) ||
-                                    !to_int_checked(b[2] * W, &cw) || !to_int_checked(b[3] * H, &ch))) {
-        pl.status = PA_CROP_BAD_BOX;
-    }
-    if (pl.status == PA_CROP_OK) {
-        const int d = cw > ch ? cw : ch;
-        pl.d = d;
-        if (d <= 0 || d > 16384) pl.status = PA_CROP_BAD_BOX;
-    }
-    if (pl.status == PA_CROP_OK) {
-        const int d = pl.d;
-        const int half = d / 2;  // int(square_dim / 2)
-        int y0 = cy - half - pad, y1 = cy + half + pad, x0 = cx - half - pad, x1 = cx + half + pad;
-        y0 = y0 > 0 ? y0 : 0;
-        x0 = x0 > 0 ? x0 : 0;
-        y1 = y1 < H ? y1 : H;
-        x1 = x1 < W ? x1 : W;
-        np_slice(y0, y1, H, &pl.sy0, &pl.sh);
-        np_slice(x0, x1, W, &pl.sx0, &pl.sw);
-        if (pl.sh != d || pl.sw != d) {
-            // ImageOps.pad(raw_crop, (d, d), color="black")
-            if (pl.sh == 0 || pl.sw == 0) {
-                // Pillow's contain size of a (sh x 0) slice is (0, d): equal to the source size when sh == d, so
-                // ImageOps.pad skips the resize and returns the black d x d canvas (the reference's crop is all zero);
-                // any other empty slice raises (ValueError -> (False, None), or ZeroDivisionError for sh == 0)
-                pl.status = (pl.sw == 0 && pl.sh == d) ? PA_CROP_BLANK : PA_CROP_EMPTY;
-            } else {
-                int rw = d, rh = d;
-                const double im_ratio = (double)pl.sw / (double)pl.sh;
-                if (im_ratio != 1.0) {
-                    if (im_ratio > 1.0) {
-                        const int nh = (int)rint((double)pl.sh / (double)pl.sw * (double)d);
-                        if (nh != d) rh = nh;
-                    } else {
-                        const int nw = (int)rint((double)pl.sw / (double)pl.sh * (double)d);
-                        if (nw != d) rw = nw;
-                    }
-                }
-                if (rw <= 0 || rh <= 0) {
-                    pl.status = PA_CROP_EMPTY;
-                } else {
-                    pl.rw = rw;
-                    pl.rh = rh;
-                    pl.need_h = rw != pl.sw;
-                    pl.need_v = rh != pl.sh;
-                    if (rw != d)
-                        pl.px = (int)rint((double)(d - rw) * 0.5);
-                    else if (rh != d)
-                        pl.py = (int)rint((double)(d - rh) * 0.5);
-                    if (pl.need_h) pl.ksize_h = bicubic_ksize(pl.sw, rw);
-                    if (pl.need_v) pl.ksize_v = bicubic_ksize(pl.sh, rh);
-                    if (pl.ksize_h > PA_KSIZE_MAX || pl.ksize_v > PA_KSIZE_MAX) pl.status = PA_CROP_FILTER_TOO_WIDE;
-                    if ((size_t)pl.sh * rw * 3 > p.t_stride || (size_t)rh * rw * 3 > p.t_stride || rw > p.coef_dim ||
-                        rh > p.coef_dim)
-                        pl.status = PA_CROP_FILTER_TOO_WIDE;
-                }
-            }
-        } else {
-            pl.rw = pl.rh = d;
-        }
-    }
-    if (pl.status == PA_CROP_OK) {
-        const int d = pl.d;
-        {
-            // imutils.resize(width=128): dim = (128, int(h * (128 / float(w))))
-            const double r = 128.0 / (double)d;
-            pl.out_h = (int)((double)d * r);
-            const double inv_sx = 128.0 / (double)d;
-            const double inv_sy = (double)pl.out_h / (double)d;
-            pl.scale_x = 1.0 / inv_sx;
-            pl.scale_y = 1.0 / inv_sy;
-            if (pl.scale_x < 1.0 || pl.scale_y < 1.0) {
-                // source smaller than 128 px: cv::resize emulates INTER_AREA with its fixed-point
-                // bilinear resizer (area_pixel mode 4); rare, served by the fallback kernel only
-                pl.area_mode = 4;
-            } else if (d == PA_CROP && pl.out_h == PA_CROP) {
-                pl.area_mode = 0;
-            } else {
-                pl.iscale_x = (int)rint(pl.scale_x);  // saturate_cast<int>(double) == cvRound
-                pl.iscale_y = (int)rint(pl.scale_y);
-                const bool fast = fabs(pl.scale_x - pl.iscale_x) < 2.220446049250313e-16 &&
-                                  fabs(pl.scale_y - pl.iscale_y) < 2.220446049250313e-16;
-                pl.area_mode = fast ? ((pl.iscale_x == 2 && pl.iscale_y == 2) ? 1 : 2) : 3;
-            }
-        }
-    }
+    CropPlan pl = crop_plan_geometry(p, crop, PA_CROP);  // (every lane: cheap, identical)
     if (p.ablate & 16) pl.fused_rb = 2;
     if (pl.status == PA_CROP_OK && pl.area_mode != 4 && !(p.ablate & 16)) {
         // largest sub-band height whose LDS stages fit the fused kernel's budget. At each height the matrix form of the
@@ -330,20 +229,8 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
             const int slot = atomicAdd(p.fallback_count, 1);
             p.fallback_list[slot] = crop;
         }
-        // coefficient tables: a pass (2 * (d / 2) + 2 * padding -> d) -- the slice of every crop the frame edge does not
-        // clip (fighter.py:334-343: centre -/+ int(d / 2) -/+ padding) -- reads the engine's cache; any other pair is
-        // computed below into this crop's own rows
-        for (int axis = 0; axis < 2; ++axis) {
-            const int in_size = axis ? pl.sh : pl.sw, out_size = axis ? pl.rh : pl.rw;
-            const bool cached = p.coef_cache && in_size == 2 * (out_size / 2) + 2 * p.coef_cache_pad && out_size >= 1 &&
-                                out_size <= p.coef_cache_dmax;
-            const int32_t* tab = cached ? p.coef_cache + (size_t)out_size * (out_size - 1) / 2 * COEF_ROW
-                                        : p.coef + (size_t)(crop * 2 + axis) * p.coef_dim * COEF_ROW;
-            if (axis) pl.coef_v = tab; else pl.coef_h = tab;
-        }
-        p.plans[crop] = pl;
+        crop_plan_publish(p, crop, pl);
         plan_sh = pl;
-        if (p.status) p.status[crop] = pl.status == PA_CROP_BLANK ? PA_CROP_OK : pl.status;
     }
     }
     __syncthreads();
@@ -358,14 +245,7 @@ __global__ __launch_bounds__(256) void crop_plan_kernel(const PreprocParams p) {
         else if (t - PA_CROP < pl.out_h) q = area_pack(area_tab(t - PA_CROP, pl.scale_y, pl.d));
         p.area_tabs[(size_t)crop * 2 * PA_CROP + t] = q;
     }
-    // Pillow precompute_coeffs + normalize_coeffs_8bpc for the passes the cache does not hold (one thread per output coordinate)
-    for (int axis = 0; axis < 2; ++axis) {
-        if (!(axis ? pl.need_v : pl.need_h)) continue;
-        const int in_size = axis ? pl.sh : pl.sw, out_size = axis ? pl.rh : pl.rw;
-        int32_t* own = p.coef + (size_t)(crop * 2 + axis) * p.coef_dim * COEF_ROW;
-        if ((axis ? pl.coef_v : pl.coef_h) != own) continue;
-        for (int xx = threadIdx.x; xx < out_size; xx += 256) bicubic_coef_row(in_size, out_size, xx, own + (size_t)xx * COEF_ROW);
-    }
+    crop_plan_fill_tables(p, crop, pl);
 }
 
 // The engine's coefficient cache: table d = the pass (2 * (d / 2) + 2 * padding -> d), at row d * (d - 1) / 2.
@@ -405,11 +285,7 @@ __global__ __launch_bounds__(256) void crop_hop_kernel(const PreprocParams p) {
         if (e == 32) {
             v = (h_mis + 3 * coef[(size_t)x0 * COEF_ROW]) & ~3;
         } else if (e < 3 * PA_HOP_PIXELS && x0 + e / 3 < rw) {
-            const int32_t* row = coef + (size_t)(x0 + e / 3) * COEF_ROW;
-            const int cnt = row[1];
-            int ksum = 0;
-            for (int t = 0; t < 7; ++t) ksum += t < cnt ? row[2 + t] : 0;
-            v = 128 * ksum + (1 << (PRECISION_BITS - 1));
+            v = coef_row_constant(coef + (size_t)(x0 + e / 3) * COEF_ROW);
         }
         reinterpret_cast<int32_t*>(ob0 + (size_t)u * PA_HOP_BLOCK_BYTES + 6 * 1024)[e] = v;
     }
@@ -433,8 +309,8 @@ __global__ __launch_bounds__(256) void crop_hop_kernel(const PreprocParams p) {
         const int first = h_mis + 3 * xmin0[u];
         const int kidx = (first & 3) + 3 * (xmin[u] + t - xmin0[u]) + c;
         if (t < cnt[u] && kidx >= 0 && kidx < PA_HOP_WINDOW) {  // (the plan checked the window; never write outside the block)
-            const int d0 = (int)(int8_t)(k[u] & 0xff), k1 = (k[u] - d0) >> 8;
-            const int d1 = (int)(int8_t)(k1 & 0xff), d2 = (k1 - d1) >> 8;
+            int d0, d1, d2;
+            coef_digits(k[u], &d0, &d1, &d2);
             // fragment (digit, half window): lane = (window byte's 16-byte quarter & 1) * 32 + column, its byte kidx & 15
             uint8_t* o = ob0 + (size_t)u * PA_HOP_BLOCK_BYTES + (kidx >> 5) * 1024 + (((kidx >> 4) & 1) * 32 + n) * 16 + (kidx & 15);
             o[0 * 2048] = (uint8_t)d2;
@@ -460,69 +336,7 @@ __device__ __forceinline__ uint32_t clip8_pk4(int a, int b, int c, int d) {
 // walks the compact list the plan kernel built and runs the three passes of a crop back to
 // back (workgroup barrier + fence between them), so the common case -- empty list -- costs
 // one tiny launch.
-// ImagingResampleHorizontal_8bpc over the slice rows: t1[y][xx][c].
-__device__ void fallback_h(const PreprocParams& p, int crop, const CropPlan& pl) {
-    if (!pl.need_h) return;
-    const int total = pl.sh * pl.rw;
-    size_t src_pitch;
-    const uint8_t* src = slice_ptr(p, crop, pl, &src_pitch);
-    uint8_t* dst = p.t1 + (size_t)crop * p.t_stride;
-    const int32_t* coef = pl.coef_h;
-    for (int i = threadIdx.x; i < total; i += blockDim.x) {
-        const int y = i / pl.rw;
-        const int xx = i - y * pl.rw;
-        const int32_t* row = coef + (size_t)xx * COEF_ROW;
-        const int xmin = row[0], cnt = row[1];
-        const uint8_t* s = src + (size_t)y * src_pitch + (size_t)xmin * 3;
-        int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-        for (int x = 0; x < cnt; ++x) {
-            const int k = row[2 + x];
-            a0 += __mul24((int)s[3 * x + 0], k);  // u8 x 22-bit fixed point: fits v_mad_i32_i24
-            a1 += __mul24((int)s[3 * x + 1], k);
-            a2 += __mul24((int)s[3 * x + 2], k);
-        }
-        uint8_t* o = dst + (size_t)i * 3;
-        o[0] = (uint8_t)clip8(a0);
-        o[1] = (uint8_t)clip8(a1);
-        o[2] = (uint8_t)clip8(a2);
-    }
-}
-
-// ImagingResampleVertical_8bpc: t2[yy][x][c] from t1 (or the slice when no horizontal pass ran).
-__device__ void fallback_v(const PreprocParams& p, int crop, const CropPlan& pl) {
-    if (!pl.need_v) return;
-    const int total = pl.rh * pl.rw;
-    const uint8_t* src;
-    size_t src_pitch;
-    if (pl.need_h) {
-        src = p.t1 + (size_t)crop * p.t_stride;
-        src_pitch = (size_t)pl.rw * 3;
-    } else {
-        src = slice_ptr(p, crop, pl, &src_pitch);
-    }
-    uint8_t* dst = p.t2 + (size_t)crop * p.t_stride;
-    const int32_t* coef = pl.coef_v;
-    for (int i = threadIdx.x; i < total; i += blockDim.x) {
-        const int yy = i / pl.rw;
-        const int x = i - yy * pl.rw;
-        const int32_t* row = coef + (size_t)yy * COEF_ROW;
-        const int ymin = row[0], cnt = row[1];
-        const uint8_t* s = src + (size_t)ymin * src_pitch + (size_t)x * 3;
-        int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-        for (int y = 0; y < cnt; ++y) {
-            const int k = row[2 + y];
-            a0 += __mul24((int)s[0], k);
-            a1 += __mul24((int)s[1], k);
-            a2 += __mul24((int)s[2], k);
-            s += src_pitch;
-        }
-        uint8_t* o = dst + (size_t)i * 3;
-        o[0] = (uint8_t)clip8(a0);
-        o[1] = (uint8_t)clip8(a1);
-        o[2] = (uint8_t)clip8(a2);
-    }
-}
-
+// The two bicubic passes are crop_common.h's (crop_pass_h / crop_pass_v), shared with crop_sized.hip.
 // channel swap + u8 crop + zero-bordered NHWC4 model input for pixel i of `crop`: k / 255 as fp32 or bf16, or the integers k as bf16
 __device__ __forceinline__ void write_crop_pixel(const PreprocParams& p, int crop, int i, int o0, int o1, int o2) {
     if (p.swap_rb) {
@@ -558,21 +372,12 @@ __device__ __forceinline__ void write_crop_pixel(const PreprocParams& p, int cro
 
 // INTER_AREA from the global-memory intermediates, final black pad to 128 rows.
 __device__ void fallback_area(const PreprocParams& p, int crop, const CropPlan& pl) {
-    Canvas cv;
-    cv.px = pl.px; cv.py = pl.py; cv.rw = pl.rw; cv.rh = pl.rh;
-    if (pl.need_v) {
-        cv.src = p.t2 + (size_t)crop * p.t_stride;
-        cv.pitch = (size_t)pl.rw * 3;
-    } else if (pl.need_h) {
-        cv.src = p.t1 + (size_t)crop * p.t_stride;
-        cv.pitch = (size_t)pl.rw * 3;
-    } else {
-        cv.src = slice_ptr(p, crop, pl, &cv.pitch);
-    }
+    const Canvas cv = crop_canvas(p, crop, pl);
+    const AreaGeom g = area_geom(pl, PA_CROP);
     for (int i = threadIdx.x; i < PA_CROP * PA_CROP; i += blockDim.x) {
         const int dy = i >> 7, dx = i & 127;
         int o0 = 0, o1 = 0, o2 = 0;
-        if (dy < pl.out_h) area_pixel(pl, cv, dy, dx, o0, o1, o2);
+        if (dy < pl.out_h) area_pixel(g, cv, dy, dx, o0, o1, o2);
         write_crop_pixel(p, crop, i, o0, o1, o2);
     }
 }
@@ -583,10 +388,10 @@ __device__ void crop_fallback_body(const PreprocParams& p, int band) {
     for (int fb = band; fb < count; fb += gridDim.x) {
         const int crop = p.fallback_list[fb];
         const CropPlan pl = p.plans[crop];
-        fallback_h(p, crop, pl);
+        crop_pass_h(p, crop, pl, threadIdx.x, blockDim.x);
         __threadfence();
         __syncthreads();
-        fallback_v(p, crop, pl);
+        crop_pass_v(p, crop, pl, threadIdx.x, blockDim.x);
         __threadfence();
         __syncthreads();
         fallback_area(p, crop, pl);
@@ -645,6 +450,355 @@ constexpr int CF_NT = 512;         // threads of a crop_fused_kernel workgroup
 constexpr int CF_NW = CF_NT / 64;   // its waves
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+// One 32 x 32 tile of exact bicubic sums on the int8 matrix instruction, for both passes: the pixels (offset to p - 128) as
+// NA A fragments of 32 K values each, the coefficients' base-256 digits (crop_math.h: coef_digits) as B fragments b[3][NA],
+// digit 2 first, cst the lane's column constant (coef_row_constant). Horner over the digits in one accumulator tile:
+// ((D_2 << 8) + D_1 << 8) + D_0 + constant, the constant added with the middle digit (wrapping int32 arithmetic; the total
+// itself fits).
+template <int NA>
+__device__ __forceinline__ i32x16 mfma_digits_tile(const i32x4* a, const i32x4* b, int cst) {
+    i32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {  // digit 2, 1, 0
+#pragma unroll
+        for (int h = 0; h < NA; ++h) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[h], b[NA * j + h], acc, 0, 0, 0);
+        if (j < 2) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = (int)(((uint32_t)acc[e] << 8) + (j == 1 ? (uint32_t)cst : 0u));
+        }
+    }
+    return acc;
+}
+
+// ---- stage 0: slice rows [ty0, ty0 + n0) -> B0 (aligned dwords) ------------------------------------------------------
+// wave w takes rows w, w+8, ...; its lanes take consecutive dwords of the row, four
+// independent 256-byte segments in flight per iteration (the loop is latency-bound).
+// Aligned copy, for the matrix-form horizontal pass: the frame's own aligned dwords, one load each -- the rows share the
+// misalignment h_mis (row pitch a multiple of 4) and the pass's operand places its taps behind it. The first
+// and last dword of a row are whole dwords that hold a byte of the slice, so they lie inside the frame buffer.
+__device__ __forceinline__ void cf_stage_aligned(const uint8_t* slice, size_t frame_pitch, int row_dwords, int ty0, int n0, int p0, int wave,
+                                                 int lane) {
+    for (int y = wave; y < n0; y += CF_NW) {
+        const uintptr_t ga = (uintptr_t)(slice + (size_t)(ty0 + y) * frame_pitch);
+        const uint32_t* g4 = reinterpret_cast<const uint32_t*>(ga & ~(uintptr_t)3);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + y * p0);
+        for (int j0 = 0; j0 < row_dwords; j0 += 256) {
+            uint32_t v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + lane + 64 * u;
+                v[u] = j < row_dwords ? g4[j] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + lane + 64 * u;
+                if (j < row_dwords) dst[j] = v[u];
+            }
+        }
+    }
+}
+
+// Re-aligning copy (v_alignbyte): every LDS row starts on the slice row's first byte
+__device__ __forceinline__ void cf_stage_realign(const uint8_t* slice, size_t frame_pitch, int sw, int ty0, int n0, int p0, int wave, int lane) {
+    const int row_dwords = (sw * 3 + 3) >> 2;
+    const int row_bytes = sw * 3;
+    for (int y = wave; y < n0; y += CF_NW) {
+        const uintptr_t ga = (uintptr_t)(slice + (size_t)(ty0 + y) * frame_pitch);
+        const uint32_t* g4 = reinterpret_cast<const uint32_t*>(ga & ~(uintptr_t)3);
+        const uint32_t sh = (uint32_t)(ga & 3);  // wave-uniform misalignment of this row
+        uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + y * p0);
+        for (int j0 = 0; j0 < row_dwords; j0 += 256) {
+            uint32_t lo[4], hi[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + lane + 64 * u;
+                lo[u] = j < row_dwords ? g4[j] : 0u;
+                // the next dword is only dereferenced when the row really straddles it
+                hi[u] = (sh && j < row_dwords && 4 * (j + 1) < (int)sh + row_bytes) ? g4[j + 1] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + lane + 64 * u;
+                if (j < row_dwords) dst[j] = __builtin_amdgcn_alignbyte(hi[u], lo[u], sh);
+            }
+        }
+    }
+}
+
+// ---- the matrix-form vertical pass's coefficient operand ----------------------------------------------------------------
+// once per workgroup and sub-band, over zeros (the band outside the taps): thread = (resized row, tap).
+// k = d0 + 256 d1 + 65536 d2 with d0, d1 in [-128, 127]; digit plane j holds d_j at [row][first tap + t]
+__device__ __forceinline__ void cf_v_operand(const int32_t* coef_v, const BandRows b, const BandLds L, int tid) {
+    const int n = tid >> 3, t = tid & 7;
+    if (tid < CF_MFMA_N * 8 && n < b.ry1 - b.ry0) {
+        const int32_t* row = coef_v + (uint32_t)(b.ry0 + n) * (uint32_t)COEF_ROW;  // (scalar base + 32-bit lane offset)
+        const int rel = row[0] - b.ty0 + t;
+        if (t < row[1] && t < 7 && rel >= 0 && rel < CF_MFMA_K) {
+            int d0, d1, d2;
+            coef_digits(row[2 + t], &d0, &d1, &d2);
+            uint8_t* c = pa_smem + L.offc + n * CF_MFMA_K + rel;
+            c[0] = (uint8_t)d0;
+            c[CF_MFMA_N * CF_MFMA_K] = (uint8_t)d1;
+            c[2 * CF_MFMA_N * CF_MFMA_K] = (uint8_t)d2;
+        }
+    }
+}
+
+// ---- stage H: B0 -> B1 -------------------------------------------------------------------------------------------------
+// Matrix form: B1[source row m][output byte column] of a block of PA_HOP_PIXELS output pixels = the block's
+// 64-byte window of row m x the crop's operand (crop_hop_kernel), digit by digit as in the vertical pass
+// below. A = 32 source rows x 64 window bytes: a lane (row lane & 31, half lane >> 5) reads bytes
+// 16 half .. + 15 of each 32-byte step of its row from B0, - 128 = one XOR per dword; rows past the band's
+// end repeat its last row, window bytes past the row's end meet zero digits. B = the operand's fragments,
+// straight from global memory (L2: the crop's 16 workgroups share them), column lane & 31, the same bytes.
+// Result register 4g + e of a lane is source row 8g + 4 (lane >> 5) + e of column lane & 31: a register
+// group is one dword of the transposed B1 the vertical pass reads. A wave takes every eighth block.
+__device__ __forceinline__ void cf_h_mfma(const uint8_t* hop, int rw, const BandLds L, int n0, int wave, int lane) {
+    const int n = lane & 31, half = lane >> 5;
+    const int nb = (rw + PA_HOP_PIXELS - 1) / PA_HOP_PIXELS, rw3 = rw * 3;
+    const int arow = (n < n0 ? n : n0 - 1) * L.p0 + half * 16;
+    // The window bases of all of this wave's blocks come in one load before the loop (lane i: its i-th block), and
+    // a block's six fragments and constants are requested together ahead of the reads of B0 -- a tile would
+    // otherwise wait for L2 four times in a row (base -> B0 address, then fragment pair by fragment pair).
+    int wb_all = 0;
+    if (wave + CF_NW * lane < nb)
+        wb_all = reinterpret_cast<const int32_t*>(hop + (size_t)(wave + CF_NW * lane) * PA_HOP_BLOCK_BYTES + 6 * 1024)[32];
+    int it = 0;
+    for (int blk = wave; blk < nb; blk += CF_NW, ++it) {
+        const uint8_t* ob = hop + (size_t)blk * PA_HOP_BLOCK_BYTES;
+        i32x4 bf[6];
+#pragma unroll
+        for (int f = 0; f < 6; ++f) bf[f] = (reinterpret_cast<const i32x4*>(ob) + lane)[f * 64];
+        const int cst = reinterpret_cast<const int32_t*>(ob + 6 * 1024)[n];
+        int wbase = __builtin_amdgcn_readlane(wb_all, it);
+        // (the builder wrote a dword offset inside the row; clamped all the same, so that a read never leaves LDS)
+        wbase = wbase < 0 ? 0 : (wbase > L.p0 ? L.p0 : wbase) & ~3;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + arow + wbase);
+        i32x4 a[2];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            a[0][q] = (int)(src[q] ^ 0x80808080u);
+            a[1][q] = (int)(src[8 + q] ^ 0x80808080u);
+        }
+        const i32x16 acc = mfma_digits_tile<2>(a, bf, cst);
+        const int col = blk * (3 * PA_HOP_PIXELS) + n;
+        if (n < 3 * PA_HOP_PIXELS && col < rw3) {
+            uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off1 + col * L.pt + (col >> 3) * L.skew + half * 4);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                if (8 * g + 4 * half < L.pt) dst[2 * g] = clip8_pk4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        }
+    }
+}
+
+// ---- stage V: (B1 | B0) -> B2 ------------------------------------------------------------------------------------------
+// Matrix form: B2[resized row n][byte column] = clip8((2^21 + sum_k B1[k][column] * coef[n][k]) >> 22) as three
+// int8 products D_j = (B1 - 128) x digit_j, one v_mfma_i32_32x32x32_i8 each: A = 32 byte
+// columns x 32 source rows (a lane: its column's 16 consecutive rows from the transposed B1, -128 = one XOR per
+// dword), B = the digit plane, 32 source rows x 32 resized rows (a lane: resized row lane & 31, the same 16 source
+// rows as its A fragment, so the order of k inside the instruction does not matter). With the resized row's
+// constant 2^21 + 128 * sum(coef), the exact int32 sum Pillow accumulates is D_0 + (D_1 << 8) + (D_2 << 16) + constant.
+// A wave takes every eighth 32-column block; the B fragments stay in registers over its blocks.
+__device__ __forceinline__ void cf_v_mfma(const int32_t* coef_v, int rw, const BandRows b, const BandLds L, int wave, int lane) {
+    const int n = lane & 31, hk = (lane >> 5) * 16, n2 = b.ry1 - b.ry0;
+    const int nblk = (rw * 3 + 31) >> 5;
+    const uint8_t* cop = pa_smem + L.offc + n * CF_MFMA_K + hk;  // + j * CF_MFMA_N * CF_MFMA_K: digit plane j
+    i32x4 bop[3];  // digit 2, 1, 0
+#pragma unroll
+    for (int j = 0; j < 3; ++j) bop[j] = *reinterpret_cast<const i32x4*>(cop + (2 - j) * CF_MFMA_N * CF_MFMA_K);
+    int cst = 0;
+    if (n < n2) cst = coef_row_constant(coef_v + (uint32_t)(b.ry0 + n) * (uint32_t)COEF_ROW);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off2 + n * L.p1 + (lane >> 5) * 4);
+    for (int blk = wave; blk < nblk; blk += CF_NW) {
+        const int col = blk * 32 + n;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + L.off1 + col * L.pt + (col >> 3) * L.skew + hk);
+        i32x4 a;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = (int)(src[q] ^ 0x80808080u);
+        const i32x16 acc = mfma_digits_tile<1>(&a, bop, cst);
+        // result register 4g + e of a lane: byte column 32 blk + 8g + 4 (lane >> 5) + e of resized row lane & 31,
+        // so a register group is one dword of B2's row (whose pitch holds the whole last block)
+        if (n < n2) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) dst[blk * 8 + 2 * g] = clip8_pk4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        }
+    }
+}
+
+// hipcc 7.2 fuses "two (x >> 22) clamped to u8, packed" into v_ashr_pk_u8_i32
+// and then ORs its result as if bits 16..31 were zero; on gfx950 they are not,
+// which corrupted bytes 2 and 3 of every dword. The empty asm keeps the four
+// clamped values opaque so the pack is plain shifts and ORs.
+__device__ __forceinline__ uint32_t clip8_x4(int a0, int a1, int a2, int a3) {
+    uint32_t c0 = clip8(a0), c1 = clip8(a1), c2 = clip8(a2), c3 = clip8(a3);
+    asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
+    return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+}
+
+// Vector form: wave w takes output rows w, w+8, ...: the row's coefficients are wave-uniform (loaded
+// once), each lane produces 4 bytes from one ds_read_b32 per tap row.
+__device__ __forceinline__ void cf_v_vector(const int32_t* coef_v, int rw, int ksize_v, const BandRows b, const BandLds L, int in_base, int in_pitch,
+                                            int wave, int lane) {
+    const int n2 = b.ry1 - b.ry0;
+    const int row_dwords = (rw * 3 + 3) >> 2;
+    const uint32_t* lds32 = reinterpret_cast<const uint32_t*>(pa_smem);
+    const int pitch_dw = in_pitch >> 2;
+    for (int yy = wave; yy < n2; yy += CF_NW) {
+        const int32_t* row = coef_v + (size_t)(b.ry0 + yy) * COEF_ROW;
+        const int ymin = row[0], cnt = row[1];
+        const int s0 = (in_base >> 2) + (ymin - b.ty0) * pitch_dw;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off2 + yy * L.p1);
+        if (ksize_v <= 7) {
+            // common case: 7 taps fully unrolled (a 15-way unroll spilled the coefficient
+            // array to scratch); taps beyond cnt have zero coefficients and re-read the
+            // last valid row
+            int k[7];
+#pragma unroll
+            for (int t = 0; t < 7; ++t) k[t] = t < cnt ? row[2 + t] : 0;
+            for (int j0 = 0; j0 < row_dwords; j0 += 256) {
+                // four independent dwords per lane: 28 LDS reads in flight
+                int acc[4][4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc[u][c] = 1 << (PRECISION_BITS - 1);
+#pragma unroll
+                for (int t = 0; t < 7; ++t) {
+                    const int tr = t < cnt ? t : cnt - 1;
+                    uint32_t v[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int j = j0 + lane + 64 * u;
+                        v[u] = lds32[s0 + tr * pitch_dw + (j < row_dwords ? j : row_dwords - 1)];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        acc[u][0] += __mul24((int)(v[u] & 0xff), k[t]);
+                        acc[u][1] += __mul24((int)((v[u] >> 8) & 0xff), k[t]);
+                        acc[u][2] += __mul24((int)((v[u] >> 16) & 0xff), k[t]);
+                        acc[u][3] += __mul24((int)(v[u] >> 24), k[t]);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = j0 + lane + 64 * u;
+                    const uint32_t packed = clip8_x4(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
+                    if (j < row_dwords) dst[j] = packed;
+                }
+            }
+        } else {
+            for (int j = lane; j < row_dwords; j += 64) {
+                int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
+                for (int t = 0; t < cnt; ++t) {
+                    const uint32_t v = lds32[s0 + t * pitch_dw + j];
+                    const int kt = row[2 + t];
+                    a0 += __mul24((int)(v & 0xff), kt);
+                    a1 += __mul24((int)((v >> 8) & 0xff), kt);
+                    a2 += __mul24((int)((v >> 16) & 0xff), kt);
+                    a3 += __mul24((int)(v >> 24), kt);
+                }
+                dst[j] = clip8_x4(a0, a1, a2, a3);
+            }
+        }
+    }
+}
+
+// ---- stage A: INTER_AREA + pad + outputs -------------------------------------------------------------------------------
+// Fractional INTER_AREA, the common case, from the plan kernel's tables in LDS. Same fp32 operation order as
+// area_pixel(); taps that fall on the black canvas add +0.0f in the
+// reference order, so clipping the tap ranges to the pasted region is
+// exact. One (unaligned) 32-bit LDS read fetches the three channels.
+// Table entries as plain scalars (passing the structs by reference made
+// hipcc keep them in scratch memory); cv.ry0 .. is the sub-band's window of resized rows.
+__device__ __forceinline__ void cf_area_frac(const AreaTabPacked qx, const AreaTabPacked qy, const LdsCanvas cv, int rh, int& o0, int& o1, int& o2) {
+    const int x_first = (int)(qx.bits & 0xffff), x_mid = (int)((qx.bits >> 16) & 0xff);
+    const int x_hf = (int)((qx.bits >> 24) & 1), x_n = x_hf + x_mid + (int)((qx.bits >> 25) & 1);
+    const int y_first = (int)(qy.bits & 0xffff), y_mid = (int)((qy.bits >> 16) & 0xff);
+    const int y_hf = (int)((qy.bits >> 24) & 1), y_n = y_hf + y_mid + (int)((qy.bits >> 25) & 1);
+#define PA_ALPHA_X(K) ((K) < x_hf ? qx.a_first : ((K) < x_hf + x_mid ? qx.a_mid : qx.a_last))
+#define PA_ALPHA_Y(J) ((J) < y_hf ? qy.a_first : ((J) < y_hf + y_mid ? qy.a_mid : qy.a_last))
+    int k_lo = cv.px - x_first, k_hi = cv.px + cv.rw - x_first;
+    k_lo = k_lo > 0 ? k_lo : 0;
+    k_hi = k_hi < x_n ? k_hi : x_n;
+    int j_lo = cv.py - y_first, j_hi = cv.py + rh - y_first;
+    j_lo = j_lo > 0 ? j_lo : 0;
+    j_hi = j_hi < y_n ? j_hi : y_n;
+    float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f;
+    const int col0 = (x_first + k_lo - cv.px) * 3;
+    const int nk = k_hi - k_lo;
+    if (nk <= 6) {
+        // <= 6 taps x 3 channels = <= 18 bytes per row: six aligned dwords cover them
+        // at any alignment; funnel-shifted, every byte sits at a static position
+        float al[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) al[k] = k < nk ? PA_ALPHA_X(k_lo + k) : 0.f;
+        for (int j = j_lo; j < j_hi; ++j) {
+            const float beta = PA_ALPHA_Y(j);
+            const int o = cv.base + (y_first + j - cv.py - cv.ry0) * cv.pitch + col0;
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + (o & ~3));
+            const uint32_t shb = (uint32_t)(o & 3);
+            uint32_t w[6], r[5];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) w[q] = src[q];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) r[q] = __builtin_amdgcn_alignbyte(w[q + 1], w[q], shb);
+            float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                if (k < nk) {
+                    const int q0 = 3 * k, q1 = 3 * k + 1, q2 = 3 * k + 2;
+                    b0 = b0 + (float)((r[q0 >> 2] >> (8 * (q0 & 3))) & 0xff) * al[k];
+                    b1 = b1 + (float)((r[q1 >> 2] >> (8 * (q1 & 3))) & 0xff) * al[k];
+                    b2 = b2 + (float)((r[q2 >> 2] >> (8 * (q2 & 3))) & 0xff) * al[k];
+                }
+            }
+            sum0 = sum0 + beta * b0;
+            sum1 = sum1 + beta * b1;
+            sum2 = sum2 + beta * b2;
+        }
+    } else {
+        for (int j = j_lo; j < j_hi; ++j) {
+            const float beta = PA_ALPHA_Y(j);
+            int o = cv.base + (y_first + j - cv.py - cv.ry0) * cv.pitch + col0;
+            float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+            for (int k = k_lo; k < k_hi; ++k) {
+                const float alpha = PA_ALPHA_X(k);
+                b0 = b0 + (float)pa_smem[o] * alpha;
+                b1 = b1 + (float)pa_smem[o + 1] * alpha;
+                b2 = b2 + (float)pa_smem[o + 2] * alpha;
+                o += 3;
+            }
+            sum0 = sum0 + beta * b0;
+            sum1 = sum1 + beta * b1;
+            sum2 = sum2 + beta * b2;
+        }
+    }
+#undef PA_ALPHA_X
+#undef PA_ALPHA_Y
+    o0 = cv_saturate_u8(sum0);
+    o1 = cv_saturate_u8(sum1);
+    o2 = cv_saturate_u8(sum2);
+}
+
+// The sub-band's rb output rows from r0 on: INTER_AREA from the canvas in LDS, the black pad below out_h, the outputs
+__device__ __forceinline__ void cf_area(const PreprocParams& p, int crop, const CropPlan& pl, const LdsCanvas cv, const AreaTabPacked* tabs, int band0,
+                                        int r0, int rb, int tid) {
+    const AreaGeom g = area_geom(pl, PA_CROP);
+    for (int i = tid; i < rb * PA_CROP; i += CF_NT) {
+        const int dy = r0 + (i >> 7), dx = i & 127;
+        int o0 = 0, o1 = 0, o2 = 0;
+        if (dy < pl.out_h) {
+            if (pl.area_mode == 3) cf_area_frac(tabs[dx], tabs[PA_CROP + dy - band0], cv, pl.rh, o0, o1, o2);
+            else area_pixel(g, cv, dy, dx, o0, o1, o2);
+        }
+        write_crop_pixel(p, crop, dy * PA_CROP + dx, o0, o1, o2);
+    }
+}
+
+// The kernel: the band loop, the barriers and the choice of forms.
 __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParams p) {
 #ifdef PA_STAMP_BUILD
     const unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
@@ -693,145 +847,26 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
     for (int r0 = band0; r0 < band0 + 8; r0 += rb) {
         const BandRows b = band_rows(pl, r0, r0 + rb);
         const BandLds L = band_lds(pl, b);
-        const int n0 = b.ty1 - b.ty0, n2 = b.ry1 - b.ry0;
-        // ---- stage 0: slice rows -> B0 (aligned dwords) ----------------------
-        // wave w takes rows w, w+4, ...; its lanes take consecutive dwords of the row, four
-        // independent 256-byte segments in flight per iteration (the loop is latency-bound).
-        if (pl.mfma_h == 1 && !(p.ablate & 1)) {
-            // matrix-form horizontal pass: the frame's own aligned dwords, one load each -- the rows share the
-            // misalignment h_mis (row pitch a multiple of 4) and the pass's operand places its taps behind it. The first
-            // and last dword of a row are whole dwords that hold a byte of the slice, so they lie inside the frame buffer.
-            const int row_dwords = (pl.h_mis + pl.sw * 3 + 3) >> 2;
-            for (int y = wave; y < n0; y += CF_NW) {
-                const uintptr_t ga = (uintptr_t)(slice + (size_t)(b.ty0 + y) * frame_pitch);
-                const uint32_t* g4 = reinterpret_cast<const uint32_t*>(ga & ~(uintptr_t)3);
-                uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + y * L.p0);
-                for (int j0 = 0; j0 < row_dwords; j0 += 256) {
-                    uint32_t v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int j = j0 + lane + 64 * u;
-                        v[u] = j < row_dwords ? g4[j] : 0u;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int j = j0 + lane + 64 * u;
-                        if (j < row_dwords) dst[j] = v[u];
-                    }
-                }
-            }
-        } else if (!(p.ablate & 1)) {
-            const int row_dwords = (pl.sw * 3 + 3) >> 2;
-            const int row_bytes = pl.sw * 3;
-            for (int y = wave; y < n0; y += CF_NW) {
-                const uintptr_t ga = (uintptr_t)(slice + (size_t)(b.ty0 + y) * frame_pitch);
-                const uint32_t* g4 = reinterpret_cast<const uint32_t*>(ga & ~(uintptr_t)3);
-                const uint32_t sh = (uint32_t)(ga & 3);  // wave-uniform misalignment of this row
-                uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + y * L.p0);
-                for (int j0 = 0; j0 < row_dwords; j0 += 256) {
-                    uint32_t lo[4], hi[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int j = j0 + lane + 64 * u;
-                        lo[u] = j < row_dwords ? g4[j] : 0u;
-                        // the next dword is only dereferenced when the row really straddles it
-                        hi[u] = (sh && j < row_dwords && 4 * (j + 1) < (int)sh + row_bytes) ? g4[j + 1] : 0u;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int j = j0 + lane + 64 * u;
-                        if (j < row_dwords) dst[j] = __builtin_amdgcn_alignbyte(hi[u], lo[u], sh);
-                    }
-                }
-            }
-        }
-        // (matrix-form vertical pass, L.pt != 0: its coefficient operand starts as zeros -- the band outside the taps)
-        const bool mfma_v = L.pt != 0;
-        if (mfma_v) {
+        const int n0 = b.ty1 - b.ty0;
+        const bool mfma_v = L.pt != 0;  // matrix-form vertical pass
+        if (pl.mfma_h == 1 && !(p.ablate & 1)) cf_stage_aligned(slice, frame_pitch, (pl.h_mis + pl.sw * 3 + 3) >> 2, b.ty0, n0, L.p0, wave, lane);
+        else if (!(p.ablate & 1)) cf_stage_realign(slice, frame_pitch, pl.sw, b.ty0, n0, L.p0, wave, lane);
+        if (mfma_v) {  // its coefficient operand starts as zeros
             uint32_t* cz = reinterpret_cast<uint32_t*>(pa_smem + L.offc);
             for (int i = tid; i < 3 * CF_MFMA_N * CF_MFMA_K / 4; i += CF_NT) cz[i] = 0u;
         }
         __syncthreads();
-        // ---- stage H: B0 -> B1 ----------------------------------------------
         int in_base = 0, in_pitch = L.p0;
         if (pl.need_h && !(p.ablate & 2)) {
-            if (mfma_v && tid < CF_MFMA_N * 8) {
-                // the vertical pass's coefficient operand, once per workgroup and sub-band: thread = (resized row, tap).
-                // k = d0 + 256 d1 + 65536 d2 with d0, d1 in [-128, 127]; digit plane j holds d_j at [row][first tap + t]
-                const int n = tid >> 3, t = tid & 7;
-                if (n < n2) {
-                    const int32_t* row = coef_v + (uint32_t)(b.ry0 + n) * (uint32_t)COEF_ROW;  // (scalar base + 32-bit lane offset)
-                    const int rel = row[0] - b.ty0 + t;
-                    if (t < row[1] && t < 7 && rel >= 0 && rel < CF_MFMA_K) {
-                        const int k = row[2 + t];
-                        const int d0 = (int)(int8_t)(k & 0xff), k1 = (k - d0) >> 8;
-                        const int d1 = (int)(int8_t)(k1 & 0xff), d2 = (k1 - d1) >> 8;
-                        uint8_t* c = pa_smem + L.offc + n * CF_MFMA_K + rel;
-                        c[0] = (uint8_t)d0;
-                        c[CF_MFMA_N * CF_MFMA_K] = (uint8_t)d1;
-                        c[2 * CF_MFMA_N * CF_MFMA_K] = (uint8_t)d2;
-                    }
-                }
-            }
-            if (pl.mfma_h && n0 > 0) {
-                // Matrix form: B1[source row m][output byte column] of a block of PA_HOP_PIXELS output pixels = the block's
-                // 64-byte window of row m x the crop's operand (crop_hop_kernel), digit by digit as in the vertical pass
-                // below. A = 32 source rows x 64 window bytes: a lane (row lane & 31, half lane >> 5) reads bytes
-                // 16 half .. + 15 of each 32-byte step of its row from B0, - 128 = one XOR per dword; rows past the band's
-                // end repeat its last row, window bytes past the row's end meet zero digits. B = the operand's fragments,
-                // straight from global memory (L2: the crop's 16 workgroups share them), column lane & 31, the same bytes.
-                // Result register 4g + e of a lane is source row 8g + 4 (lane >> 5) + e of column lane & 31: a register
-                // group is one dword of the transposed B1 the vertical pass reads. A wave takes every eighth block.
-                const int n = lane & 31, half = lane >> 5;
-                const int nb = (pl.rw + PA_HOP_PIXELS - 1) / PA_HOP_PIXELS, rw3 = pl.rw * 3;
-                const uint8_t* hop = p.hop + (size_t)crop * PA_HOP_BLOCKS_MAX * PA_HOP_BLOCK_BYTES;
-                const int arow = (n < n0 ? n : n0 - 1) * L.p0 + half * 16;
-                // The window bases of all of this wave's blocks come in one load before the loop (lane i: its i-th block), and
-                // a block's six fragments and constants are requested together ahead of the reads of B0 -- a tile would
-                // otherwise wait for L2 four times in a row (base -> B0 address, then fragment pair by fragment pair).
-                int wb_all = 0;
-                if (wave + CF_NW * lane < nb)
-                    wb_all = reinterpret_cast<const int32_t*>(hop + (size_t)(wave + CF_NW * lane) * PA_HOP_BLOCK_BYTES + 6 * 1024)[32];
-                int it = 0;
-                for (int blk = wave; blk < nb; blk += CF_NW, ++it) {
-                    const uint8_t* ob = hop + (size_t)blk * PA_HOP_BLOCK_BYTES;
-                    i32x4 bf[6];
-#pragma unroll
-                    for (int f = 0; f < 6; ++f) bf[f] = (reinterpret_cast<const i32x4*>(ob) + lane)[f * 64];
-                    const int cst = reinterpret_cast<const int32_t*>(ob + 6 * 1024)[n];
-                    int wbase = __builtin_amdgcn_readlane(wb_all, it);
-                    // (the builder wrote a dword offset inside the row; clamped all the same, so that a read never leaves LDS)
-                    wbase = wbase < 0 ? 0 : (wbase > L.p0 ? L.p0 : wbase) & ~3;
-                    const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + arow + wbase);
-                    i32x4 a0, a1;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        a0[q] = (int)(src[q] ^ 0x80808080u);
-                        a1[q] = (int)(src[8 + q] ^ 0x80808080u);
-                    }
-                    i32x16 acc;
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc[e] = 0;
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {  // digit 2, 1, 0
-                        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, bf[2 * j], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, bf[2 * j + 1], acc, 0, 0, 0);
-                        if (j < 2) {
-#pragma unroll
-                            for (int e = 0; e < 16; ++e) acc[e] = (int)(((uint32_t)acc[e] << 8) + (j == 1 ? (uint32_t)cst : 0u));
-                        }
-                    }
-                    const int col = blk * (3 * PA_HOP_PIXELS) + n;
-                    if (n < 3 * PA_HOP_PIXELS && col < rw3) {
-                        uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off1 + col * L.pt + (col >> 3) * L.skew + half * 4);
-#pragma unroll
-                        for (int g = 0; g < 4; ++g)
-                            if (8 * g + 4 * half < L.pt) dst[2 * g] = clip8_pk4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
-                    }
-                }
-            }
-            // vector form: work item = (output column, chunk of 4 rows): the column's <= 15 coefficients are
-            // fetched once per item and reused for its rows; ~6 items per thread keeps all 256
+            if (mfma_v) cf_v_operand(coef_v, b, L, tid);
+            if (pl.mfma_h && n0 > 0) cf_h_mfma(p.hop + (size_t)crop * PA_HOP_BLOCKS_MAX * PA_HOP_BLOCK_BYTES, pl.rw, L, n0, wave, lane);
+            // Vector form of stage H, the one stage left inline, its wide-filter branch with its own copy of the sum:
+            // as a stage function (or as per-item functions under this loop, or with bicubic_acc in the wide branch)
+            // the object kept 128 VGPRs and no scratch, but the allocation moved everywhere and the crop stage of
+            // crops that take the MATRIX forms -- which never run this code -- went from 0.0977 to 0.1038 ms per 64
+            // 1080p frames (profiles/crop_shared_parent_ab.md).
+            // Work item = (output column, chunk of 4 rows): the column's <= 15 coefficients are
+            // fetched once per item and reused for its rows; ~6 items per thread keeps all 512
             // threads busy (one item per column would leave the second pass 3/4 empty).
             const int chunks = (n0 + 3) >> 2;
             const int items = pl.mfma_h ? 0 : chunks * pl.rw;
@@ -925,138 +960,10 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
             in_base = L.off1;
             in_pitch = L.p1;
             __syncthreads();
-#ifdef PA_EXTRA_SYNC
-            __threadfence_block();
-            __syncthreads();
-            __builtin_amdgcn_s_sleep(100);
-            __syncthreads();
-#endif
         }
-        // ---- stage V: (B1 | B0) -> B2 ------------------------------------------
-        // wave w takes output rows w, w+4, ...: the row's coefficients are wave-uniform (loaded
-        // once), each lane produces 4 bytes from one ds_read_b32 per tap row.
-        if (mfma_v) {
-            // Matrix form: B2[resized row n][byte column] = clip8((2^21 + sum_k B1[k][column] * coef[n][k]) >> 22) as three
-            // int8 products D_j = (B1 - 128) x digit_j, one v_mfma_i32_32x32x32_i8 each: A = 32 byte
-            // columns x 32 source rows (a lane: its column's 16 consecutive rows from the transposed B1, -128 = one XOR per
-            // dword), B = the digit plane, 32 source rows x 32 resized rows (a lane: resized row lane & 31, the same 16 source
-            // rows as its A fragment, so the order of k inside the instruction does not matter). With the resized row's
-            // constant 2^21 + 128 * sum(coef), the exact int32 sum Pillow accumulates is D_0 + (D_1 << 8) + (D_2 << 16) + constant.
-            // A wave takes every eighth 32-column block; the B fragments stay in registers over its blocks.
-            const int n = lane & 31, hk = (lane >> 5) * 16;
-            const int nblk = (pl.rw * 3 + 31) >> 5;
-            const uint8_t* cop = pa_smem + L.offc + n * CF_MFMA_K + hk;  // + j * CF_MFMA_N * CF_MFMA_K: digit plane j
-            i32x4 bop[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) bop[j] = *reinterpret_cast<const i32x4*>(cop + j * CF_MFMA_N * CF_MFMA_K);
-            int cst = 0;
-            if (n < n2) {
-                const int32_t* row = coef_v + (uint32_t)(b.ry0 + n) * (uint32_t)COEF_ROW;
-                const int cnt = row[1];
-                int ksum = 0;
-#pragma unroll
-                for (int t = 0; t < 7; ++t) ksum += t < cnt ? row[2 + t] : 0;
-                cst = 128 * ksum + (1 << (PRECISION_BITS - 1));
-            }
-            uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off2 + n * L.p1 + (lane >> 5) * 4);
-            for (int blk = wave; blk < nblk; blk += CF_NW) {
-                const int col = blk * 32 + n;
-                const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + L.off1 + col * L.pt + (col >> 3) * L.skew + hk);
-                i32x4 a;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) a[q] = (int)(src[q] ^ 0x80808080u);
-                // Horner over the digits, in one accumulator tile: ((D_2 << 8) + D_1 << 8) + D_0 + constant (wrapping int32
-                // arithmetic; the total itself fits)
-                i32x16 acc;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[e] = 0;
-#pragma unroll
-                for (int j = 2; j >= 0; --j) {
-                    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bop[j], acc, 0, 0, 0);
-                    if (j) {
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[e] = (int)(((uint32_t)acc[e] << 8) + (j == 1 ? (uint32_t)cst : 0u));
-                    }
-                }
-                // result register 4g + e of a lane: byte column 32 blk + 8g + 4 (lane >> 5) + e of resized row lane & 31,
-                // so a register group is one dword of B2's row (whose pitch holds the whole last block)
-                if (n < n2) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) dst[blk * 8 + 2 * g] = clip8_pk4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
-                }
-            }
-            in_base = L.off2;
-            in_pitch = L.p1;
-            __syncthreads();
-        } else if (pl.need_v && !(p.ablate & 4)) {
-            const int row_dwords = (pl.rw * 3 + 3) >> 2;
-            const uint32_t* lds32 = reinterpret_cast<const uint32_t*>(pa_smem);
-            const int pitch_dw = in_pitch >> 2;
-            for (int yy = wave; yy < n2; yy += CF_NW) {
-                const int32_t* row = coef_v + (size_t)(b.ry0 + yy) * COEF_ROW;
-                const int ymin = row[0], cnt = row[1];
-                const int s0 = (in_base >> 2) + (ymin - b.ty0) * pitch_dw;
-                uint32_t* dst = reinterpret_cast<uint32_t*>(pa_smem + L.off2 + yy * L.p1);
-                if (pl.ksize_v <= 7) {
-                    // common case: 7 taps fully unrolled (a 15-way unroll spilled the coefficient
-                    // array to scratch); taps beyond cnt have zero coefficients and re-read the
-                    // last valid row
-                    int k[7];
-#pragma unroll
-                    for (int t = 0; t < 7; ++t) k[t] = t < cnt ? row[2 + t] : 0;
-                    for (int j0 = 0; j0 < row_dwords; j0 += 256) {
-                        // four independent dwords per lane: 28 LDS reads in flight
-                        int acc[4][4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) acc[u][c] = 1 << (PRECISION_BITS - 1);
-#pragma unroll
-                        for (int t = 0; t < 7; ++t) {
-                            const int tr = t < cnt ? t : cnt - 1;
-                            uint32_t v[4];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                const int j = j0 + lane + 64 * u;
-                                v[u] = lds32[s0 + tr * pitch_dw + (j < row_dwords ? j : row_dwords - 1)];
-                            }
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) {
-                                acc[u][0] += __mul24((int)(v[u] & 0xff), k[t]);
-                                acc[u][1] += __mul24((int)((v[u] >> 8) & 0xff), k[t]);
-                                acc[u][2] += __mul24((int)((v[u] >> 16) & 0xff), k[t]);
-                                acc[u][3] += __mul24((int)(v[u] >> 24), k[t]);
-                            }
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int j = j0 + lane + 64 * u;
-                            // hipcc 7.2 fuses "two (x >> 22) clamped to u8, packed" into v_ashr_pk_u8_i32
-                            // and then ORs its result as if bits 16..31 were zero; on gfx950 they are not,
-                            // which corrupted bytes 2 and 3 of every dword. The empty asm keeps the four
-                            // clamped values opaque so the pack is plain shifts and ORs.
-                            uint32_t c0 = clip8(acc[u][0]), c1 = clip8(acc[u][1]), c2 = clip8(acc[u][2]), c3 = clip8(acc[u][3]);
-                            asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
-                            if (j < row_dwords) dst[j] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
-                        }
-                    }
-                } else {
-                    for (int j = lane; j < row_dwords; j += 64) {
-                        int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0, a3 = a0;
-                        for (int t = 0; t < cnt; ++t) {
-                            const uint32_t v = lds32[s0 + t * pitch_dw + j];
-                            const int kt = row[2 + t];
-                            a0 += __mul24((int)(v & 0xff), kt);
-                            a1 += __mul24((int)((v >> 8) & 0xff), kt);
-                            a2 += __mul24((int)((v >> 16) & 0xff), kt);
-                            a3 += __mul24((int)(v >> 24), kt);
-                        }
-                        uint32_t c0 = clip8(a0), c1 = clip8(a1), c2 = clip8(a2), c3 = clip8(a3);
-                        asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
-                        dst[j] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
-                    }
-                }
-            }
+        if (mfma_v || (pl.need_v && !(p.ablate & 4))) {
+            if (mfma_v) cf_v_mfma(coef_v, pl.rw, b, L, wave, lane);
+            else cf_v_vector(coef_v, pl.rw, pl.ksize_v, b, L, in_base, in_pitch, wave, lane);
             in_base = L.off2;
             in_pitch = L.p1;
             __syncthreads();
@@ -1073,98 +980,13 @@ __global__ __launch_bounds__(CF_NT, 4) void crop_fused_kernel(const PreprocParam
             for (int i = tid; i < L.total; i += CF_NT) p.dbg[256 + i] = pa_smem[i];
         }
 #endif
-        // ---- stage A: INTER_AREA + pad + outputs --------------------------------
         if (!(p.ablate & 8)) {
             LdsCanvas cv;
             cv.base = in_base;
             cv.pitch = in_pitch;
             cv.px = pl.px; cv.py = pl.py; cv.rw = pl.rw;
             cv.ry0 = b.ry0; cv.ry1 = b.ry1;
-            for (int i = tid; i < rb * PA_CROP; i += CF_NT) {
-                const int dy = r0 + (i >> 7), dx = i & 127;
-                int o0 = 0, o1 = 0, o2 = 0;
-                if (dy < pl.out_h) {
-                    if (pl.area_mode == 3) {
-                        // fractional INTER_AREA, the common case. Same fp32 operation order as
-                        // area_pixel(); taps that fall on the black canvas add +0.0f in the
-                        // reference order, so clipping the tap ranges to the pasted region is
-                        // exact. One (unaligned) 32-bit LDS read fetches the three channels.
-                        // table entries as plain scalars (passing the structs by reference made
-                        // hipcc keep them in scratch memory)
-                        const AreaTabPacked qx = tabs[dx], qy = tabs[PA_CROP + dy - band0];
-                        const int x_first = (int)(qx.bits & 0xffff), x_mid = (int)((qx.bits >> 16) & 0xff);
-                        const int x_hf = (int)((qx.bits >> 24) & 1), x_n = x_hf + x_mid + (int)((qx.bits >> 25) & 1);
-                        const int y_first = (int)(qy.bits & 0xffff), y_mid = (int)((qy.bits >> 16) & 0xff);
-                        const int y_hf = (int)((qy.bits >> 24) & 1), y_n = y_hf + y_mid + (int)((qy.bits >> 25) & 1);
-#define PA_ALPHA_X(K) ((K) < x_hf ? qx.a_first : ((K) < x_hf + x_mid ? qx.a_mid : qx.a_last))
-#define PA_ALPHA_Y(J) ((J) < y_hf ? qy.a_first : ((J) < y_hf + y_mid ? qy.a_mid : qy.a_last))
-                        int k_lo = pl.px - x_first, k_hi = pl.px + pl.rw - x_first;
-                        k_lo = k_lo > 0 ? k_lo : 0;
-                        k_hi = k_hi < x_n ? k_hi : x_n;
-                        int j_lo = pl.py - y_first, j_hi = pl.py + pl.rh - y_first;
-                        j_lo = j_lo > 0 ? j_lo : 0;
-                        j_hi = j_hi < y_n ? j_hi : y_n;
-                        float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f;
-                        const int col0 = (x_first + k_lo - pl.px) * 3;
-                        const int nk = k_hi - k_lo;
-                        if (nk <= 6) {
-                            // <= 6 taps x 3 channels = <= 18 bytes per row: six aligned dwords cover them
-                            // at any alignment; funnel-shifted, every byte sits at a static position
-                            float al[6];
-#pragma unroll
-                            for (int k = 0; k < 6; ++k) al[k] = k < nk ? PA_ALPHA_X(k_lo + k) : 0.f;
-                            for (int j = j_lo; j < j_hi; ++j) {
-                                const float beta = PA_ALPHA_Y(j);
-                                const int o = in_base + (y_first + j - pl.py - b.ry0) * in_pitch + col0;
-                                const uint32_t* src = reinterpret_cast<const uint32_t*>(pa_smem + (o & ~3));
-                                const uint32_t shb = (uint32_t)(o & 3);
-                                uint32_t w[6], r[5];
-#pragma unroll
-                                for (int q = 0; q < 6; ++q) w[q] = src[q];
-#pragma unroll
-                                for (int q = 0; q < 5; ++q) r[q] = __builtin_amdgcn_alignbyte(w[q + 1], w[q], shb);
-                                float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-#pragma unroll
-                                for (int k = 0; k < 6; ++k) {
-                                    if (k < nk) {
-                                        const int q0 = 3 * k, q1 = 3 * k + 1, q2 = 3 * k + 2;
-                                        b0 = b0 + (float)((r[q0 >> 2] >> (8 * (q0 & 3))) & 0xff) * al[k];
-                                        b1 = b1 + (float)((r[q1 >> 2] >> (8 * (q1 & 3))) & 0xff) * al[k];
-                                        b2 = b2 + (float)((r[q2 >> 2] >> (8 * (q2 & 3))) & 0xff) * al[k];
-                                    }
-                                }
-                                sum0 = sum0 + beta * b0;
-                                sum1 = sum1 + beta * b1;
-                                sum2 = sum2 + beta * b2;
-                            }
-                        } else {
-                            for (int j = j_lo; j < j_hi; ++j) {
-                                const float beta = PA_ALPHA_Y(j);
-                                int o = in_base + (y_first + j - pl.py - b.ry0) * in_pitch + col0;
-                                float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-                                for (int k = k_lo; k < k_hi; ++k) {
-                                    const float alpha = PA_ALPHA_X(k);
-                                    b0 = b0 + (float)pa_smem[o] * alpha;
-                                    b1 = b1 + (float)pa_smem[o + 1] * alpha;
-                                    b2 = b2 + (float)pa_smem[o + 2] * alpha;
-                                    o += 3;
-                                }
-                                sum0 = sum0 + beta * b0;
-                                sum1 = sum1 + beta * b1;
-                                sum2 = sum2 + beta * b2;
-                            }
-                        }
-#undef PA_ALPHA_X
-#undef PA_ALPHA_Y
-                        o0 = cv_saturate_u8(sum0);
-                        o1 = cv_saturate_u8(sum1);
-                        o2 = cv_saturate_u8(sum2);
-                    } else {
-                        area_pixel(pl, cv, dy, dx, o0, o1, o2);
-                    }
-                }
-                write_crop_pixel(p, crop, dy * PA_CROP + dx, o0, o1, o2);
-            }
+            cf_area(p, crop, pl, cv, tabs, band0, r0, rb, tid);
         }
         __syncthreads();  // the next sub-band reuses the LDS stages
 #ifdef PA_STAMP_BUILD
@@ -1240,165 +1062,20 @@ hipError_t launch_project_boxes(const double* log, double* boxes, int32_t n, hip
 // passes over L2-resident scratch (t1: INTER_AREA result, t2: after the horizontal bicubic pass, then
 // t1's second half: after the vertical pass), coefficient tables in LDS. Same integer / IEEE arithmetic
 // as the fused path (shared helpers above), bit-exact against oracle/yolo_crop.runner_input_from_crop.
-struct RunnerInPlan {
-    int status;
-    int sw, sh;          // source image
-    int ow, oh;          // INTER_AREA destination width (128 for runner inputs) and height
-    int mode;            // 0 copy, 1 2x2, 2 integer, 3 general, 4 enlarging (bilinear emulation)
-    int isx, isy;
-    double scale_x, scale_y;
-    int rw, rh, px, py;  // ImageOps.pad: size after contain, paste offset (rw == 128 && rh == 128: no pad step)
-    int need_h, need_v;
-};
-
-struct WhCanvas {  // plain [rows][cols][3] bytes
-    const uint8_t* src;
-    int pitch;
-    __device__ __forceinline__ void load(int y, int x, int& c0, int& c1, int& c2) const {
-        const uint8_t* s = src + (size_t)y * pitch + x * 3;
-        c0 = s[0]; c1 = s[1]; c2 = s[2];
-    }
-};
-
-// One destination pixel of cv::resize(INTER_AREA) from an sw x sh image to ow x oh (area_pixel() with
-// separate axes; the source is a plain image, no paste window).
-__device__ __forceinline__ void area_pixel_wh(const RunnerInPlan& pl, const WhCanvas& cv, int dy, int dx, int& o0, int& o1, int& o2) {
-    if (pl.mode == 0) {
-        cv.load(dy, dx, o0, o1, o2);
-    } else if (pl.mode == 1) {
-        int s0 = 2, s1 = 2, s2 = 2;
-        for (int yy = 0; yy < 2; ++yy)
-            for (int xx = 0; xx < 2; ++xx) {
-                int c0, c1, c2;
-                cv.load(dy * 2 + yy, dx * 2 + xx, c0, c1, c2);
-                s0 += c0; s1 += c1; s2 += c2;
-            }
-        o0 = s0 >> 2; o1 = s1 >> 2; o2 = s2 >> 2;
-    } else if (pl.mode == 2) {
-        int s0 = 0, s1 = 0, s2 = 0;
-        for (int yy = 0; yy < pl.isy; ++yy)
-            for (int xx = 0; xx < pl.isx; ++xx) {
-                int c0, c1, c2;
-                cv.load(dy * pl.isy + yy, dx * pl.isx + xx, c0, c1, c2);
-                s0 += c0; s1 += c1; s2 += c2;
-            }
-        const float scale = 1.f / (float)(pl.isx * pl.isy);
-        o0 = cv_saturate_u8((float)s0 * scale);
-        o1 = cv_saturate_u8((float)s1 * scale);
-        o2 = cv_saturate_u8((float)s2 * scale);
-    } else if (pl.mode == 4) {
-        // cv::resize's 8-bit bilinear resizer with area-mode coefficients (see area_pixel())
-        const double inv_x = (double)pl.ow / (double)pl.sw, inv_y = (double)pl.oh / (double)pl.sh;
-        int sx = (int)floor((double)dx * pl.scale_x);
-        float fx = (float)((double)(dx + 1) - (double)(sx + 1) * inv_x);
-        fx = fx <= 0.f ? 0.f : fx - floorf(fx);
-        const bool plain = sx + 1 >= pl.sw;
-        if (sx >= pl.sw - 1) {
-            fx = 0.f;
-            sx = pl.sw - 1;
-        }
-        const int a0 = (int)rintf((1.f - fx) * 2048.f), a1 = (int)rintf(fx * 2048.f);
-        const int sy = (int)floor((double)dy * pl.scale_y);
-        float fy = (float)((double)(dy + 1) - (double)(sy + 1) * inv_y);
-        fy = fy <= 0.f ? 0.f : fy - floorf(fy);
-        const int b0 = (int)rintf((1.f - fy) * 2048.f), b1 = (int)rintf(fy * 2048.f);
-        const int r0 = sy < pl.sh - 1 ? sy : pl.sh - 1;
-        const int r1 = sy + 1 < pl.sh - 1 ? sy + 1 : pl.sh - 1;
-        int h0[3], h1[3];
-        int c0, c1, c2, e0 = 0, e1 = 0, e2 = 0;
-        cv.load(r0, sx, c0, c1, c2);
-        if (!plain) cv.load(r0, sx + 1, e0, e1, e2);
-        h0[0] = plain ? c0 * 2048 : c0 * a0 + e0 * a1;
-        h0[1] = plain ? c1 * 2048 : c1 * a0 + e1 * a1;
-        h0[2] = plain ? c2 * 2048 : c2 * a0 + e2 * a1;
-        cv.load(r1, sx, c0, c1, c2);
-        if (!plain) cv.load(r1, sx + 1, e0, e1, e2);
-        h1[0] = plain ? c0 * 2048 : c0 * a0 + e0 * a1;
-        h1[1] = plain ? c1 * 2048 : c1 * a0 + e1 * a1;
-        h1[2] = plain ? c2 * 2048 : c2 * a0 + e2 * a1;
-        o0 = ((((b0 * (h0[0] >> 4)) >> 16) + ((b1 * (h1[0] >> 4)) >> 16) + 2) >> 2) & 0xff;
-        o1 = ((((b0 * (h0[1] >> 4)) >> 16) + ((b1 * (h1[1] >> 4)) >> 16) + 2) >> 2) & 0xff;
-        o2 = ((((b0 * (h0[2] >> 4)) >> 16) + ((b1 * (h1[2] >> 4)) >> 16) + 2) >> 2) & 0xff;
-    } else {
-        const AreaTab tx = area_tab(dx, pl.scale_x, pl.sw);
-        const AreaTab ty = area_tab(dy, pl.scale_y, pl.sh);
-        float sum0 = 0.f, sum1 = 0.f, sum2 = 0.f;
-        for (int j = 0; j < ty.n; ++j) {
-            const float beta = area_alpha(ty, j);
-            float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-            for (int k = 0; k < tx.n; ++k) {
-                const float alpha = area_alpha(tx, k);
-                int c0, c1, c2;
-                cv.load(ty.s_first + j, tx.s_first + k, c0, c1, c2);
-                b0 = b0 + (float)c0 * alpha;
-                b1 = b1 + (float)c1 * alpha;
-                b2 = b2 + (float)c2 * alpha;
-            }
-            sum0 = sum0 + beta * b0;
-            sum1 = sum1 + beta * b1;
-            sum2 = sum2 + beta * b2;
-        }
-        o0 = cv_saturate_u8(sum0);
-        o1 = cv_saturate_u8(sum1);
-        o2 = cv_saturate_u8(sum2);
-    }
-}
+// The plan (RunnerInPlan, runner_in_plan) and the pixel of the last step (runner_in_pixel) are crop_math.h's.
 
 // What get_action_recognition_input_for_frame does to one crop image (ai_runner.py:446-459), decided once per image: the
-// INTER_AREA destination, the branch of cv::resize it takes, ImageOps.pad's contain size / paste offset / bicubic passes.
-__device__ void runner_plan(const RunnerInParams& q, int crop, RunnerInPlan& pl, long long& off) {
-    pl.status = PA_CROP_OK;
+// descriptor's bounds here, then the INTER_AREA destination, the branch of cv::resize it takes, ImageOps.pad's contain
+// size / paste offset / bicubic passes.
+__device__ RunnerInPlan runner_plan(const RunnerInParams& q, int crop, long long& off) {
     off = q.desc[crop].offset;
-    pl.sh = q.desc[crop].height;
-    pl.sw = q.desc[crop].width;
-    pl.ow = PA_CROP; pl.oh = 0; pl.mode = 0; pl.isx = pl.isy = 1; pl.scale_x = pl.scale_y = 1.0;
-    pl.rw = pl.rh = PA_CROP; pl.px = pl.py = 0; pl.need_h = pl.need_v = 0;
-    if (pl.sh < 1 || pl.sw < 1 || pl.sh > q.max_h || pl.sw > q.max_w || off < 0 ||
-        off + (long long)pl.sh * pl.sw * 3 > q.images_bytes)
-        pl.status = PA_CROP_BAD_BOX;
-    if (pl.status == PA_CROP_OK) {
-        // imutils.resize(width=128): dim = (128, int(h * (128 / float(w))))
-        const double r = 128.0 / (double)pl.sw;
-        const double ohd = (double)pl.sh * r;
-        pl.oh = ohd < 2.0e9 ? (int)ohd : 0;
-        if (pl.oh < 1) pl.status = PA_CROP_EMPTY;  // cv2.resize raises for an empty destination
+    const int sh = q.desc[crop].height, sw = q.desc[crop].width;
+    if (sh < 1 || sw < 1 || sh > q.max_h || sw > q.max_w || off < 0 || off + (long long)sh * sw * 3 > q.images_bytes) {
+        RunnerInPlan bad = {};
+        bad.status = PA_CROP_BAD_BOX;
+        return bad;
     }
-    if (pl.status == PA_CROP_OK) {
-        const double inv_sx = 128.0 / (double)pl.sw, inv_sy = (double)pl.oh / (double)pl.sh;
-        pl.scale_x = 1.0 / inv_sx;
-        pl.scale_y = 1.0 / inv_sy;
-        if (pl.sw == PA_CROP && pl.sh == pl.oh) {
-            pl.mode = 0;
-        } else if (pl.scale_x < 1.0 || pl.scale_y < 1.0) {
-            pl.mode = 4;
-        } else {
-            pl.isx = (int)rint(pl.scale_x);
-            pl.isy = (int)rint(pl.scale_y);
-            const bool fast = fabs(pl.scale_x - pl.isx) < 2.220446049250313e-16 && fabs(pl.scale_y - pl.isy) < 2.220446049250313e-16;
-            pl.mode = fast ? ((pl.isx == 2 && pl.isy == 2) ? 1 : 2) : 3;
-        }
-        if (pl.oh != PA_CROP) {
-            // ImageOps.pad(img 128 x oh, (128, 128)): contain keeps the aspect ratio (ImageOps.py)
-            const double im_ratio = 128.0 / (double)pl.oh;
-            if (im_ratio > 1.0) {
-                const int nh = (int)rint((double)pl.oh / 128.0 * 128.0);
-                if (nh != PA_CROP) pl.rh = nh;
-            } else {
-                const int nw = (int)rint(128.0 / (double)pl.oh * 128.0);
-                if (nw != PA_CROP) pl.rw = nw;
-            }
-            if (pl.rw < 1 || pl.rh < 1) pl.status = PA_CROP_EMPTY;
-            pl.need_h = pl.rw != PA_CROP;
-            pl.need_v = pl.rh != pl.oh;
-            if (pl.rw != PA_CROP)
-                pl.px = (int)rint((double)(PA_CROP - pl.rw) * 0.5);
-            else if (pl.rh != PA_CROP)
-                pl.py = (int)rint((double)(PA_CROP - pl.rh) * 0.5);
-            if ((pl.need_h && bicubic_ksize(PA_CROP, pl.rw) > PA_KSIZE_MAX) || (pl.need_v && bicubic_ksize(pl.oh, pl.rh) > PA_KSIZE_MAX))
-                pl.status = PA_CROP_FILTER_TOO_WIDE;
-        }
-        if ((size_t)(pl.oh + (pl.need_v ? pl.rh : 0)) * PA_CROP * 3 > q.t_stride) pl.status = PA_CROP_FILTER_TOO_WIDE;  // scratch
-    }
+    return runner_in_plan(sw, sh, q.t_stride);
 }
 
 // The three steps of a runner input as three launches over (image, part) grids -- INTER_AREA | Pillow's horizontal pass | its
@@ -1418,9 +1095,9 @@ __global__ __launch_bounds__(256) void runner_input_stage_kernel(const RunnerInP
     out.crops_u8 = q.inputs_u8;
     out.crops_f32 = q.inputs_f32;
     out.crops_f32_is_bf16 = q.inputs_f32_is_bf16;
-    RunnerInPlan pl;
     long long off;
-    runner_plan(q, crop, pl, off);
+    const RunnerInPlan pl = runner_plan(q, crop, off);
+    const int oh = pl.area.oh;
     if (STAGE == 0 && part == 0 && tid == 0 && q.status) q.status[crop] = pl.status;
     if (pl.status != PA_CROP_OK) {
         if (STAGE == 2)
@@ -1432,11 +1109,11 @@ __global__ __launch_bounds__(256) void runner_input_stage_kernel(const RunnerInP
     if (STAGE == 0) {
         WhCanvas cv;
         cv.src = q.images + off;
-        cv.pitch = pl.sw * 3;
-        for (int i = i0; i < pl.oh * PA_CROP; i += istep) {
+        cv.pitch = pl.area.sw * 3;
+        for (int i = i0; i < oh * PA_CROP; i += istep) {
             const int dy = i >> 7, dx = i & 127;
             int o0, o1, o2;
-            area_pixel_wh(pl, cv, dy, dx, o0, o1, o2);
+            area_pixel(pl.area, cv, dy, dx, o0, o1, o2);
             uint8_t* o = A + (size_t)i * 3;
             o[0] = (uint8_t)o0; o[1] = (uint8_t)o1; o[2] = (uint8_t)o2;
         }
@@ -1446,52 +1123,18 @@ __global__ __launch_bounds__(256) void runner_input_stage_kernel(const RunnerInP
         if (!pl.need_h) return;
         if (tid < pl.rw) bicubic_coef_row(PA_CROP, pl.rw, tid, coef[tid]);  // (fp64, one output coordinate per thread)
         __syncthreads();
-        for (int i = i0; i < pl.oh * pl.rw; i += istep) {
-            const int y = i / pl.rw, xx = i - y * pl.rw;
-            const int32_t* row = coef[xx];
-            const uint8_t* sp = A + ((size_t)y * PA_CROP + row[0]) * 3;
-            int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-            for (int t = 0; t < row[1]; ++t) {
-                const int k = row[2 + t];
-                a0 += __mul24((int)sp[3 * t + 0], k);
-                a1 += __mul24((int)sp[3 * t + 1], k);
-                a2 += __mul24((int)sp[3 * t + 2], k);
-            }
-            uint8_t* o = B + (size_t)i * 3;
-            o[0] = (uint8_t)clip8(a0); o[1] = (uint8_t)clip8(a1); o[2] = (uint8_t)clip8(a2);
-        }
+        bicubic_pass_h(coef[0], A, (size_t)PA_CROP * 3, oh, pl.rw, B, i0, istep);
         return;
     }
     // STAGE 2: ImagingResampleVertical_8bpc for the canvas pixels that need it, paste on the black 128 x 128 canvas, channel
     // swap, u8 + model input
-    const uint8_t* cur = pl.need_h ? B : A;
-    const int cur_w = pl.need_h ? pl.rw : PA_CROP;
-    const int cur_h = pl.need_v ? pl.rh : pl.oh;
     if (pl.need_v) {
-        if (tid < pl.rh) bicubic_coef_row(pl.oh, pl.rh, tid, coef[tid]);
+        if (tid < pl.rh) bicubic_coef_row(oh, pl.rh, tid, coef[tid]);
         __syncthreads();
     }
     for (int i = i0; i < PA_CROP * PA_CROP; i += istep) {
-        const int y = (i >> 7) - pl.py, x = (i & 127) - pl.px;
-        int o0 = 0, o1 = 0, o2 = 0;
-        if ((unsigned)y < (unsigned)cur_h && (unsigned)x < (unsigned)cur_w) {
-            if (pl.need_v) {
-                const int32_t* row = coef[y];
-                const uint8_t* sp = cur + ((size_t)row[0] * cur_w + x) * 3;
-                int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-                for (int t = 0; t < row[1]; ++t) {
-                    const int k = row[2 + t];
-                    a0 += __mul24((int)sp[0], k);
-                    a1 += __mul24((int)sp[1], k);
-                    a2 += __mul24((int)sp[2], k);
-                    sp += (size_t)cur_w * 3;
-                }
-                o0 = clip8(a0); o1 = clip8(a1); o2 = clip8(a2);
-            } else {
-                const uint8_t* sp = cur + ((size_t)y * cur_w + x) * 3;
-                o0 = sp[0]; o1 = sp[1]; o2 = sp[2];
-            }
-        }
+        int o0, o1, o2;
+        runner_in_pixel(pl, pl.need_h ? B : A, coef[0], i, o0, o1, o2);
         write_crop_pixel(out, crop, i, o0, o1, o2);
     }
 }
@@ -1568,39 +1211,19 @@ hipError_t launch_slice_upload(const uint8_t* frames_host, long long frames_byte
 // YoloCrop.crop_img (fighter.py:316-321) + imutils.resize(width = out_w) (= cv2.resize INTER_AREA to
 // (out_w, int(h * (out_w / float(w)))), imutils 0.5.4) for up to four fixed pixel rectangles per frame: the damage
 // HUD crops of AIRunner.run_damage_detection (ai_runner.py:556-571, damage_crop_to_percent :114). One workgroup per
-// (rectangle, frame), one thread per destination pixel, every INTER_AREA branch of area_pixel_wh (the HUD boxes are
+// (rectangle, frame), one thread per destination pixel, every INTER_AREA branch of area_pixel (the HUD boxes are
 // ENLARGED at 720p / 1080p: OpenCV's bilinear emulation). Channel order is kept (BGR in, BGR out).
 __global__ __launch_bounds__(256) void rect_resize_kernel(const RectResizeParams q) {
     const int r = blockIdx.x, f = blockIdx.y;
-    RunnerInPlan pl;
-    pl.status = PA_CROP_OK;
-    pl.sw = q.x2[r] - q.x1[r];
-    pl.sh = q.y2[r] - q.y1[r];
-    pl.ow = q.out_w;
-    pl.oh = q.out_h[r];
-    pl.rw = pl.rh = pl.px = pl.py = pl.need_h = pl.need_v = 0;
-    pl.isx = pl.isy = 1;
-    const double inv_sx = (double)pl.ow / (double)pl.sw, inv_sy = (double)pl.oh / (double)pl.sh;
-    pl.scale_x = 1.0 / inv_sx;
-    pl.scale_y = 1.0 / inv_sy;
-    if (pl.sw == pl.ow && pl.sh == pl.oh) {
-        pl.mode = 0;
-    } else if (pl.scale_x < 1.0 || pl.scale_y < 1.0) {
-        pl.mode = 4;
-    } else {
-        pl.isx = (int)rint(pl.scale_x);
-        pl.isy = (int)rint(pl.scale_y);
-        const bool fast = fabs(pl.scale_x - pl.isx) < 2.220446049250313e-16 && fabs(pl.scale_y - pl.isy) < 2.220446049250313e-16;
-        pl.mode = fast ? ((pl.isx == 2 && pl.isy == 2) ? 1 : 2) : 3;
-    }
+    const AreaGeom g = area_branch(q.x2[r] - q.x1[r], q.y2[r] - q.y1[r], q.out_w, q.out_h[r]);
     WhCanvas cv;
     cv.pitch = q.width * 3;
     cv.src = q.frames + ((size_t)f * q.height + q.y1[r]) * q.width * 3 + (size_t)q.x1[r] * 3;
     uint8_t* dst = q.out + ((size_t)f * q.n_rects + r) * q.out_h_cap * q.out_w * 3;
-    for (int i = threadIdx.x; i < pl.oh * pl.ow; i += 256) {
-        const int dy = i / pl.ow, dx = i - dy * pl.ow;
+    for (int i = threadIdx.x; i < g.oh * g.ow; i += 256) {
+        const int dy = i / g.ow, dx = i - dy * g.ow;
         int o0, o1, o2;
-        area_pixel_wh(pl, cv, dy, dx, o0, o1, o2);
+        area_pixel(g, cv, dy, dx, o0, o1, o2);
         uint8_t* o = dst + (size_t)i * 3;
         o[0] = (uint8_t)o0; o[1] = (uint8_t)o1; o[2] = (uint8_t)o2;
     }

@@ -61,6 +61,19 @@ def test_runner_inputs_on_gpu_bit_exact(engine):
 
 
 @pytest.mark.gpu
+def test_non_square_sources_take_every_area_branch(engine):
+    """One crop image per branch of cv2.resize(INTER_AREA) to width 128 with sw != sh -- 128 x 96 copy, 256 x 200 2 x 2, 384 x 300
+    integer, 200 x 150 fractional, 64 x 48 enlarging -- in one call: the shared ``area_pixel`` with separate source width and
+    height on the device, whatever branches the committed vectors take."""
+    rng = np.random.default_rng(5)
+    imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in [(96, 128), (200, 256), (300, 384), (150, 200), (48, 64)]]
+    got, status = engine.runner_inputs(imgs)
+    assert (status == 0).all(), status
+    for im, g in zip(imgs, got):
+        assert np.array_equal(g, yolo_crop.runner_input_from_crop(im)), im.shape
+
+
+@pytest.mark.gpu
 def test_clip_from_crop_images_equals_clip_from_frames(engine):
     """A clip handed over as crop images (the reference's crops/<Fighter>/<video>_<n>.jpg after decoding)
     gives the labels of the same clip handed over as frames + boxes: the images are the BGR square
