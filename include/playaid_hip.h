@@ -1279,6 +1279,70 @@ int pa_augment_quantiles(float* out_host);
 int pa_augment_crops(pa_engine* e, const uint8_t* src_dev, int32_t n_src, const pa_augment_params* params_dev, int32_t n,
                      int32_t out_format, void* out_dev, void* stream);
 
+/* Appended (the version stays 15): the reference's synthetic training frames -- load_and_augment_frame_to_stage_crop at
+ * synth_difficulty 0 (ult_action_dataset.py:97-136), which get_synth and simple_dataset call once per frame -- as ONE launch
+ * for n output frames from images that were uploaded once (csrc/synth_composite.hip). A bank holds images on
+ * the device: PA_SYNTH_SPRITES the character renders as RGBA (cv2 reads BGRA; the loader swaps once, which commutes with a
+ * per-channel resample), PA_SYNTH_STAGES the stage pictures as RGB. Output frame i with square side D = dim:
+ *   1 stage crop     stage[stage_y : stage_y + D, stage_x : stage_x + D] of stage image params[i].stage
+ *   2 sprite size    the sprite is h x w; imutils.resize in double precision: h > w: (ow, oh) = ((int)(w * (D / (double)h)), D),
+ *                    else (ow, oh) = (D, (int)(h * (D / (double)w)))
+ *   3 resample       cv2.resize(sprite, (ow, oh), INTER_AREA) of all four channels, each a plain channel (no premultiplication),
+ *                    by the branch cv::resize takes: equal sizes copy; either axis enlarging -> the 8-bit bilinear resizer with
+ *                    area-mode coefficients (11-bit weights, (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2);
+ *                    both scales integers -> box sums ((s + 2) >> 2 for 2 x 2, else cvRound((float)s * (1.f / (float)area)));
+ *                    else computeResizeAreaTab's weights in fp32: per source row the horizontal sum in table order, multiply
+ *                    then add, then the vertical sum of beta * row the same way, then cvRound (ties to even) and saturate
+ *   4 paste          Image.paste(sprite, (px, py), sprite): px = (D - ow) / 2 + paste_dx, py = (D - oh) / 2 + paste_dy, clipped
+ *                    to the canvas; per covered pixel and channel c of R, G, B, with a the resampled alpha:
+ *                    t = s_c * a + d_c * (255 - a) + 128; out_c = ((t >> 8) + t) >> 8   (Pillow's paste_mask_RGBA)
+ *   5 output         PA_SYNTH_U8 -> uint8[n][D][D][3]; PA_SYNTH_MODEL (D = 128 only) -> float32[n][3][128][128] with value
+ *                    (float)byte / 255.f, the input of pa_backbone_windows / pa_infer_windows
+ * synth_dataset.composite_reference is the numpy twin.
+ *
+ * pa_synth_bank_create: images_host[k] points at image k's packed rows (heights[k] x widths[k] x 4 bytes for sprites, x 3 for
+ * stages). Validated on the host before any device call -- n >= 1, sprite sides 1..PA_SYNTH_SPRITE_MAX, stage sides
+ * 1..PA_SYNTH_STAGE_MAX, no sprite so thin that step 2 gives it an empty size (ow or oh 0, for which cv2.resize raises) at
+ * every dim; PA_ERR_INVALID_ARG and a message otherwise -- then packed, each image 16-byte aligned, behind a descriptor table
+ * into one device allocation and uploaded once. A sprite whose longer side is at most 32 times the shorter has ow, oh >= 1
+ * at every dim >= 32; a thinner one only from some larger dim on, and pa_synth_params_check and pa_synth_composite return
+ * PA_ERR_INVALID_ARG for a dim below the largest such bound of the bank's sprites. With e NULL the bank holds the sizes alone
+ * (no device allocation): pa_synth_params_check takes it, pa_synth_composite refuses it. PA_ERR_CAPACITY: the host has no
+ * memory for the packed copy (as large as the bank); PA_ERR_HIP: the device allocation or the upload failed. The kernel trusts the descriptors because only the library writes them. A bank is
+ * independent of the launches that read it: a later producer of sprites can hand pa_synth_composite a bank of its own.
+ *
+ * The kernel is defined for ANY parameter bytes: sprite and stage are clamped into their banks, the stage origin into
+ * [0, W - D] x [0, H - D], the paste offsets to +-PA_SYNTH_PASTE_MAX; the reserved words are not read.
+ * pa_synth_params_check (host only, no device call) returns PA_ERR_INVALID_ARG for anything of that kind, for a non-zero
+ * reserved word, for a dim outside PA_SYNTH_DIM_MIN..PA_SYNTH_DIM_MAX and for a record whose stage is smaller than dim.
+ *
+ * pa_synth_composite: params on the device (8-byte aligned), n 1..65535, dim PA_SYNTH_DIM_MIN..PA_SYNTH_DIM_MAX, out 16-byte
+ * aligned, PA_SYNTH_MODEL only with dim == 128, every stage of the bank at least dim x dim. PA_ERR_INVALID_ARG otherwise.
+ * Enqueue only; nothing is read back. */
+typedef struct pa_synth_bank pa_synth_bank;
+typedef struct pa_synth_params {
+    int32_t sprite;              /* image of the sprite bank */
+    int32_t stage;               /* image of the stage bank */
+    int32_t stage_x, stage_y;    /* origin of the D x D stage crop */
+    int32_t paste_dx, paste_dy;  /* added to the centred paste position */
+    int32_t reserved[2];         /* zero */
+} pa_synth_params;
+#define PA_SYNTH_SPRITES 0
+#define PA_SYNTH_STAGES 1
+#define PA_SYNTH_U8 0
+#define PA_SYNTH_MODEL 1
+#define PA_SYNTH_DIM_MIN 32
+#define PA_SYNTH_DIM_MAX 256
+#define PA_SYNTH_SPRITE_MAX 1024
+#define PA_SYNTH_STAGE_MAX 4096
+#define PA_SYNTH_PASTE_MAX 4096
+int pa_synth_bank_create(pa_engine* e, int32_t kind, const uint8_t* const* images_host, const int32_t* widths, const int32_t* heights,
+                         int32_t n, pa_synth_bank** out);
+void pa_synth_bank_destroy(pa_synth_bank* bank);
+int pa_synth_params_check(const pa_synth_params* host, int32_t n, const pa_synth_bank* sprites, const pa_synth_bank* stages, int32_t dim);
+int pa_synth_composite(pa_engine* e, const pa_synth_bank* sprites, const pa_synth_bank* stages, const pa_synth_params* params_dev,
+                       int32_t n, int32_t dim, int32_t out_format, void* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

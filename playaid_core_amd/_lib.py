@@ -145,6 +145,22 @@ PA_AUGMENT_MODEL = 1
 PA_AUGMENT_QUANTILES = 1025
 
 
+class pa_synth_params(C.Structure):
+    _fields_ = [("sprite", C.c_int32), ("stage", C.c_int32), ("stage_x", C.c_int32), ("stage_y", C.c_int32),
+                ("paste_dx", C.c_int32), ("paste_dy", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+PA_SYNTH_SPRITES = 0
+PA_SYNTH_STAGES = 1
+PA_SYNTH_U8 = 0
+PA_SYNTH_MODEL = 1
+PA_SYNTH_DIM_MIN = 32
+PA_SYNTH_DIM_MAX = 256
+PA_SYNTH_SPRITE_MAX = 1024
+PA_SYNTH_STAGE_MAX = 4096
+PA_SYNTH_PASTE_MAX = 4096
+
+
 class pa_kernel_stat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 48),
@@ -313,6 +329,10 @@ SYMBOLS = [
     ("pa_augment_params_check", C.c_int, [_P, C.c_int32, C.c_int32]),
     ("pa_augment_quantiles", C.c_int, [_P]),
     ("pa_augment_crops", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("pa_synth_bank_create", C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(_P)]),
+    ("pa_synth_bank_destroy", None, [_P]),
+    ("pa_synth_params_check", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32]),
+    ("pa_synth_composite", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
 ]
 
 _lib = None

@@ -5,6 +5,7 @@
 #include "../../include/playaid_hip.h"
 #include "conv_rows.h"
 #include "engine_table.h"   // the layer table, over engine_plan.h
+#include "synth_math.h"     // SynthDesc
 #include "train_common.h"   // adam_scalars, adam_config_ok, TrainerCore
 
 #include <algorithm>
@@ -2154,6 +2155,137 @@ int pa_annotate_frames(pa_annot* h, const uint8_t* frames_in, int32_t n, int32_t
     if (pa::launch_annotate(p, s) != hipSuccess) return PA_ERR_HIP;
     h->used[slot] = true;
     if (hipEventRecord(h->done[slot], s) != hipSuccess) return PA_ERR_HIP;
+    return PA_OK;
+}
+
+// ---- synthetic training frames (synth_composite.hip) ----------------------------------------------------------------------------
+
+struct pa_synth_bank {
+    int kind = 0;
+    std::vector<SynthDesc> descs;   // the host's copy of the table: what the argument checks read
+    int min_w = 0, min_h = 0;
+    int dim_min = PA_SYNTH_DIM_MIN;   // sprites: the smallest dim at which every image resizes to at least 1 x 1
+    unsigned char* dev = nullptr;   // [descriptor table, padded to 16 bytes][images]; nullptr: a bank made without an engine
+    size_t table_bytes = 0;
+};
+
+int pa_synth_bank_create(pa_engine* e, int32_t kind, const uint8_t* const* images_host, const int32_t* widths, const int32_t* heights,
+                         int32_t n, pa_synth_bank** out) {
+    if (!out) return PA_ERR_INVALID_ARG;
+    *out = nullptr;
+    pa_synth_bank* b = nullptr;
+    try {   // (the table, the messages and the host copy of the whole bank allocate: no exception may cross the C ABI)
+        if ((kind != PA_SYNTH_SPRITES && kind != PA_SYNTH_STAGES) || !images_host || !widths || !heights || n < 1)
+            return fail(e, PA_ERR_INVALID_ARG, "pa_synth_bank_create: kind is PA_SYNTH_SPRITES or PA_SYNTH_STAGES, n at least 1, no null array");
+        const int side_max = kind == PA_SYNTH_SPRITES ? PA_SYNTH_SPRITE_MAX : PA_SYNTH_STAGE_MAX;
+        const size_t px_bytes = kind == PA_SYNTH_SPRITES ? 4 : 3;
+        std::vector<SynthDesc> descs((size_t)n);
+        size_t total = 0;
+        int min_w = side_max, min_h = side_max, dim_min = PA_SYNTH_DIM_MIN;
+        for (int32_t k = 0; k < n; ++k) {
+            const int w = widths[k], h = heights[k];
+            const std::string which = "pa_synth_bank_create: image " + std::to_string(k) + " (" + std::to_string(h) + " x " + std::to_string(w) + ")";
+            if (!images_host[k]) return fail(e, PA_ERR_INVALID_ARG, which + " has no pixels");
+            if (w < 1 || h < 1 || w > side_max || h > side_max)
+                return fail(e, PA_ERR_INVALID_ARG, which + ": sides are 1.." + std::to_string(side_max));
+            if (kind == PA_SYNTH_SPRITES) {
+                const int d = synth_dim_min(w, h);
+                if (d > PA_SYNTH_DIM_MAX) return fail(e, PA_ERR_INVALID_ARG, which + ": too thin, no dim resizes it to at least 1 x 1");
+                dim_min = std::max(dim_min, d);
+            }
+            descs[k].offset = total;
+            descs[k].w = w;
+            descs[k].h = h;
+            total += ((size_t)w * h * px_bytes + 15) & ~(size_t)15;
+            min_w = std::min(min_w, w);
+            min_h = std::min(min_h, h);
+        }
+        b = new pa_synth_bank();
+        b->kind = kind;
+        b->descs = descs;
+        b->min_w = min_w;
+        b->min_h = min_h;
+        b->dim_min = dim_min;
+        b->table_bytes = ((size_t)n * sizeof(SynthDesc) + 15) & ~(size_t)15;
+        if (e) {   // (without an engine: the table alone, for pa_synth_params_check)
+            std::vector<unsigned char> stage(b->table_bytes + total, 0);
+            std::memcpy(stage.data(), descs.data(), (size_t)n * sizeof(SynthDesc));
+            for (int32_t k = 0; k < n; ++k)
+                std::memcpy(stage.data() + b->table_bytes + descs[k].offset, images_host[k], (size_t)descs[k].w * descs[k].h * px_bytes);
+            void* p = nullptr;
+            hipError_t err = hipMalloc(&p, stage.size());
+            if (err == hipSuccess) {
+                b->dev = static_cast<unsigned char*>(p);
+                err = hipMemcpy(p, stage.data(), stage.size(), hipMemcpyHostToDevice);
+            }
+            if (err != hipSuccess) {
+                pa_synth_bank_destroy(b);
+                b = nullptr;
+                return fail(e, PA_ERR_HIP, std::string("pa_synth_bank_create: ") + hipGetErrorString(err));
+            }
+        }
+        *out = b;
+        return PA_OK;
+    } catch (const std::exception&) {
+        pa_synth_bank_destroy(b);
+        if (e) e->last_error.clear();   // (no allocation on this path)
+        return PA_ERR_CAPACITY;         // out of host memory
+    }
+}
+
+void pa_synth_bank_destroy(pa_synth_bank* b) {
+    if (!b) return;
+    if (b->dev) (void)hipFree(b->dev);
+    delete b;
+}
+
+int pa_synth_params_check(const pa_synth_params* host, int32_t n, const pa_synth_bank* sprites, const pa_synth_bank* stages, int32_t dim) {
+    if (!host || n < 1 || !sprites || !stages || sprites->kind != PA_SYNTH_SPRITES || stages->kind != PA_SYNTH_STAGES ||
+        dim < PA_SYNTH_DIM_MIN || dim > PA_SYNTH_DIM_MAX || dim < sprites->dim_min)
+        return PA_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < n; ++i) {
+        const pa_synth_params& p = host[i];
+        if (p.sprite < 0 || p.sprite >= (int32_t)sprites->descs.size() || p.stage < 0 || p.stage >= (int32_t)stages->descs.size())
+            return PA_ERR_INVALID_ARG;
+        const SynthDesc& g = stages->descs[(size_t)p.stage];
+        if (g.w < dim || g.h < dim || p.stage_x < 0 || p.stage_x > g.w - dim || p.stage_y < 0 || p.stage_y > g.h - dim) return PA_ERR_INVALID_ARG;
+        if (p.paste_dx < -PA_SYNTH_PASTE_MAX || p.paste_dx > PA_SYNTH_PASTE_MAX || p.paste_dy < -PA_SYNTH_PASTE_MAX || p.paste_dy > PA_SYNTH_PASTE_MAX)
+            return PA_ERR_INVALID_ARG;
+        if (p.reserved[0] != 0 || p.reserved[1] != 0) return PA_ERR_INVALID_ARG;
+    }
+    return PA_OK;
+}
+
+int pa_synth_composite(pa_engine* e, const pa_synth_bank* sprites, const pa_synth_bank* stages, const pa_synth_params* params_dev,
+                       int32_t n, int32_t dim, int32_t out_format, void* out_dev, void* stream) {
+    if (!e || !sprites || !stages || !params_dev || !out_dev || n < 1 || n > 65535 || sprites->kind != PA_SYNTH_SPRITES ||
+        stages->kind != PA_SYNTH_STAGES || (out_format != PA_SYNTH_U8 && out_format != PA_SYNTH_MODEL))
+        return fail(e, PA_ERR_INVALID_ARG, "pa_synth_composite: bad argument");
+    if (!sprites->dev || !stages->dev) return fail(e, PA_ERR_INVALID_ARG, "pa_synth_composite: a bank that was made without an engine has no pixels");
+    if (dim < PA_SYNTH_DIM_MIN || dim > PA_SYNTH_DIM_MAX || (out_format == PA_SYNTH_MODEL && dim != PA_CROP))
+        return fail(e, PA_ERR_INVALID_ARG, "pa_synth_composite: dim is " + std::to_string(PA_SYNTH_DIM_MIN) + ".." + std::to_string(PA_SYNTH_DIM_MAX) +
+                                               ", and 128 for PA_SYNTH_MODEL");
+    if ((uintptr_t)out_dev & 15 || (uintptr_t)params_dev & 7)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_synth_composite: out must be 16-byte aligned, params 8-byte aligned");
+    if (stages->min_w < dim || stages->min_h < dim) return fail(e, PA_ERR_INVALID_ARG, "pa_synth_composite: a stage of the bank is smaller than dim");
+    if (dim < sprites->dim_min)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_synth_composite: a sprite of the bank is too thin for this dim (it resizes to an empty image below dim " +
+                                               std::to_string(sprites->dim_min) + ")");
+    if (!e->aug_tabs) return fail(e, PA_ERR_INVALID_ARG, "pa_synth_composite: the engine has no tables");
+    SynthArgs a;
+    a.sprite_px = sprites->dev + sprites->table_bytes;
+    a.sprite_desc = reinterpret_cast<const SynthDesc*>(sprites->dev);
+    a.n_sprites = (int)sprites->descs.size();
+    a.stage_px = stages->dev + stages->table_bytes;
+    a.stage_desc = reinterpret_cast<const SynthDesc*>(stages->dev);
+    a.n_stages = (int)stages->descs.size();
+    a.params = params_dev;
+    a.n = n, a.dim = dim, a.out_format = out_format;
+    a.out = out_dev;
+    a.unit = e->aug_tabs->unit;
+    const double px = (double)n * dim * dim;
+    ProfScope ps(e, (hipStream_t)stream, "synth_composite", 0.0, px * (out_format == PA_SYNTH_MODEL ? 15.0 : 6.0));
+    HIPCHK(e, launch_synth_composite(a, (hipStream_t)stream));
     return PA_OK;
 }
 

@@ -524,4 +524,22 @@ void augment_tables_host(AugmentTables* t);
 hipError_t launch_augment(const uint8_t* src, int n_src, const void* params, int n, int out_format, void* out,
                           const AugmentTables* tabs_dev, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// synthetic training frames: a sprite resampled and pasted over a stage crop (synth_composite.hip; pa_synth_composite)
+// ---------------------------------------------------------------------------
+struct SynthDesc;   // synth_math.h
+struct SynthArgs {
+    const uint8_t* sprite_px;        // the sprite bank's first pixel (RGBA images, each 16-byte aligned)
+    const SynthDesc* sprite_desc;
+    int n_sprites;
+    const uint8_t* stage_px;         // the stage bank's (RGB)
+    const SynthDesc* stage_desc;
+    int n_stages;
+    const pa_synth_params* params;   // device, [n]
+    int n, dim, out_format;
+    void* out;                       // PA_SYNTH_U8: uint8 [n][dim][dim][3]; PA_SYNTH_MODEL: float32 [n][3][128][128]
+    const float* unit;               // AugmentTables::unit on the device: (float)k / 255.f
+};
+hipError_t launch_synth_composite(const SynthArgs& a, hipStream_t s);
+
 }  // namespace pa

@@ -13,9 +13,13 @@ the same sampler with the runner's own range (frames are 1-indexed crop files, `
 ``synth_difficulty`` 1 or 2 passes every crop of an item through the reference's ``augment_char_crop`` at that level
 (``ult_action_dataset.py:305-330``), on the device: ``augment.py``, DESIGN.md 5.14.
 
+The synthetic windows of the reference's dataset (``get_synth``, ``simple_dataset``: character renders resized and pasted over
+stage crops) are ``synth_dataset.SynthWindowDataset``, composed on the device from uploaded renders (``synth_dataset.py``,
+DESIGN.md 5.15).
+
 Not built, by scope (training only): the random choice of (fighter, action, frame), the frame-delta
-choice, the synthetic-stage compositing of the "simple" split (``augment_synth_char_crop``, ``get_synth``: it needs the
-character renders), ``preceding_actions`` (the reference's own loop over them is empty: ``range(a, a)``,
+choice, ``augment_synth_char_crop`` (the augmentation of the RGBA render BEFORE it is pasted, which ``synth_difficulty`` 1 / 2
+adds to the synthetic windows), ``preceding_actions`` (the reference's own loop over them is empty: ``range(a, a)``,
 ``ult_action_dataset.py:284-286``).
 
 For scoring (``metrics.py``, ``AIRunner.evaluate``): ``load_ground_truth_labels`` reads a hand-labelled clip's CSV as the
