@@ -1343,6 +1343,81 @@ int pa_synth_params_check(const pa_synth_params* host, int32_t n, const pa_synth
 int pa_synth_composite(pa_engine* e, const pa_synth_bank* sprites, const pa_synth_bank* stages, const pa_synth_params* params_dev,
                        int32_t n, int32_t dim, int32_t out_format, void* out_dev, void* stream);
 
+/* Appended (the version stays 15): the reference's augmentation of a character render BEFORE the paste, augment_synth_char_crop
+ * (dataset_utils.py:255-378, output_size = 128), which load_and_augment_frame_to_stage_crop runs on every render when
+ * synth_difficulty is 1 or 2 (csrc/sprite_augment.hip). Output sprite i reads the h x w RGBA image
+ * params[i].src of a PA_SYNTH_SPRITES bank and is written, as 128 x 128 RGBA, into slot i of a bank made by
+ * pa_sprite_bank_create, which pa_synth_composite then takes like any other sprite bank:
+ *   a resize to width 128   imutils.resize(width=128): cv2.resize(INTER_AREA) to 128 x h1, h1 = (int)(h * (128 / (double)w)), all
+ *                           four channels plain channels, by the branch cv::resize takes (step 3 of pa_synth_composite)
+ *   b ImageOps.pad          to (128, 128), transparent. h1 == 128: unchanged. h1 < 128: pasted (copied, no mask) at row
+ *                           rint((128 - h1) * 0.5) (Python's round: ties to even). h1 > 128: Image.resize((w2, 128), BICUBIC),
+ *                           w2 = rint(128 / (double)h1 * 128), as Pillow does it for RGBA -- every pixel to premultiplied RGBa
+ *                           (c' = MULDIV255(c, a): t = c * a + 128, ((t >> 8) + t) >> 8; alpha kept), the horizontal then the
+ *                           vertical 8-bit pass over all four channels (22-bit coefficients of precompute_coeffs, the sum starts
+ *                           at 2^21, >> 22, clipped to 0..255), back to RGBA (alpha 0 or 255: unchanged, else
+ *                           min(255, 255 * c / a), integer division) -- pasted at column rint((128 - w2) * 0.5)
+ *   c shrink                new_scale != 0 (96..127): cv2.resize(INTER_AREA) to new_scale x new_scale, then ImageOps.expand with a
+ *                           transparent border of 128 - new_scale: a canvas of side C = 256 - new_scale. Otherwise C = 128
+ *   d the Compose           on the C x C canvas, RGB as the image and alpha as the mask. The image takes stages 1..8 of
+ *                           pa_augment_crops with C for 128 wherever a size enters: the flip reads column C - 1 - u, the blur's
+ *                           border reflects about C - 1, the stream positions are v * C + u, holes are squares of side
+ *                           S = min(96, C / 3) at (holes[2 j], holes[2 j + 1]) = (x, y). Then output pixel (x, y) of the
+ *                           O x O result (O = 128 when sized_crop != 0, else C) is the image's value at (xmap[x], ymap[y])
+ *                           (Downscale then RandomSizedCrop, both nearest, composed by the host). The mask takes the flip, 0 at
+ *                           dropped pixels and inside holes, nothing of the other stages, and is gathered at (axmap[x], aymap[y])
+ *                           (RandomSizedCrop alone)
+ *   e resize to width 128   O == 128: unchanged; else cv2.resize(INTER_AREA) of the four channels from C x C to 128 x 128
+ * sprite_augment.augment_sprites_reference is the numpy twin.
+ *
+ * The kernel is defined for ANY parameter bytes: src is clamped into the bank, the floats are read as pa_augment_crops reads
+ * them, n_holes is clamped to 0..2, channel_mask is taken & 7, a blur_k other than 2 or 3 and a new_scale outside 96..127 are
+ * 0, sized_crop and flip count as 0 / 1, map entries are clamped to C - 1 (entries from O on are not read), holes are
+ * comparisons. pa_sprite_aug_params_check (host only, no device call) returns PA_ERR_INVALID_ARG for anything of that kind and
+ * for values outside the reference's limits: alpha outside [0.8, 1.2], beta outside [-0.2, 0.6], hue outside [-256, 256], sat
+ * outside [-67, 67], val outside [-10, 10], a noise_sigma that is neither 0 nor in [sqrt(427.63), sqrt(500)], a pixel_drop_thr
+ * that is neither 0 nor PA_SPRITE_DROP_THR (probability 0.1), a hole beyond C - S, channel_mask outside 0..6, a non-zero
+ * reserved word. It also checks the bank: PA_ERR_INVALID_ARG when a render is so flat that h1 < 1 (cv2.resize raises),
+ * PA_ERR_CAPACITY when one is so tall that h1 > PA_SPRITE_H1_MAX = 448 (step b's filter then has more than PA_KSIZE_MAX = 15
+ * taps, and its intermediate outgrows the scratch): every render with h <= 3.5 w is taken.
+ *
+ * pa_sprite_bank_create: a PA_SYNTH_SPRITES bank of n (1..65535) slots of 128 x 128 whose descriptors the library writes and
+ * whose pixels only pa_sprite_augment writes (zero until then), with the kernel's scratch behind them (524288 bytes for each of
+ * min(n, 256) workgroups). With e NULL the bank holds the sizes alone. pa_synth_bank_destroy frees it.
+ * pa_sprite_augment: params on the device (8-byte aligned), n 1..slots of out_bank, sprites a bank with pixels that is not
+ * out_bank; the bank-level limits above are refused here too, on the host. PA_ERR_INVALID_ARG / PA_ERR_CAPACITY otherwise.
+ * Launches on one out_bank must be stream-ordered with each other and with the pa_synth_composite calls that read it. Enqueue
+ * only; nothing is read back. */
+typedef struct pa_sprite_aug_params {
+    int32_t src;                 /* image of the sprite bank */
+    int32_t flip;
+    float alpha, beta;
+    int32_t blur_k;
+    float hue_shift, sat_shift, val_shift;
+    float noise_sigma;
+    uint32_t pixel_drop_thr;
+    int32_t n_holes;
+    uint8_t holes[4];            /* (x, y) of up to two holes */
+    int32_t channel_mask;
+    int32_t new_scale;           /* 0: no shrink */
+    int32_t sized_crop;          /* != 0: the maps have 128 entries (RandomSizedCrop fired), else C */
+    int32_t reserved;            /* zero */
+    uint8_t xmap[160], ymap[160];    /* the image's gather */
+    uint8_t axmap[160], aymap[160];  /* the mask's */
+    uint64_t key;
+} pa_sprite_aug_params;          /* 712 bytes */
+#define PA_SPRITE_DROP_THR 429496729u
+#define PA_SPRITE_H1_MAX 448
+#define PA_SPRITE_CANVAS_MAX 160
+int pa_sprite_aug_params_check(const pa_sprite_aug_params* host, int32_t n, const pa_synth_bank* sprites);
+int pa_sprite_bank_create(pa_engine* e, int32_t n, pa_synth_bank** out);
+int pa_sprite_augment(pa_engine* e, const pa_synth_bank* sprites, const pa_sprite_aug_params* params_dev, int32_t n,
+                      pa_synth_bank* out_bank, void* stream);
+/* Slots first .. first + n - 1 of a bank of pa_sprite_bank_create as uint8[n][128][128][4] (RGBA) in host memory, for tests and
+ * for looking at what a level does: a copy behind the work already enqueued on `stream`, which the call waits for.
+ * PA_ERR_INVALID_ARG for a bank of another kind or without pixels, or a range outside the slots. */
+int pa_sprite_bank_read(pa_engine* e, const pa_synth_bank* bank, int32_t first, int32_t n, uint8_t* out_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,19 @@ PA_SYNTH_STAGE_MAX = 4096
 PA_SYNTH_PASTE_MAX = 4096
 
 
+class pa_sprite_aug_params(C.Structure):
+    _fields_ = [("src", C.c_int32), ("flip", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float), ("blur_k", C.c_int32),
+                ("hue_shift", C.c_float), ("sat_shift", C.c_float), ("val_shift", C.c_float), ("noise_sigma", C.c_float),
+                ("pixel_drop_thr", C.c_uint32), ("n_holes", C.c_int32), ("holes", C.c_uint8 * 4), ("channel_mask", C.c_int32),
+                ("new_scale", C.c_int32), ("sized_crop", C.c_int32), ("reserved", C.c_int32), ("xmap", C.c_uint8 * 160),
+                ("ymap", C.c_uint8 * 160), ("axmap", C.c_uint8 * 160), ("aymap", C.c_uint8 * 160), ("key", C.c_uint64)]
+
+
+PA_SPRITE_DROP_THR = 429496729
+PA_SPRITE_H1_MAX = 448
+PA_SPRITE_CANVAS_MAX = 160
+
+
 class pa_kernel_stat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 48),
@@ -333,6 +346,10 @@ SYMBOLS = [
     ("pa_synth_bank_destroy", None, [_P]),
     ("pa_synth_params_check", C.c_int, [_P, C.c_int32, _P, _P, C.c_int32]),
     ("pa_synth_composite", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    ("pa_sprite_aug_params_check", C.c_int, [_P, C.c_int32, _P]),
+    ("pa_sprite_bank_create", C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
+    ("pa_sprite_augment", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    ("pa_sprite_bank_read", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
 ]
 
 _lib = None

@@ -343,18 +343,24 @@ def _hsv_shift(a: np.ndarray, lut_h, lut_s, lut_v) -> np.ndarray:
     return np.clip(np.rint(out * f32(255.0)), 0, 255).astype(np.uint8)
 
 
+def box_blur(a: np.ndarray, k: int) -> np.ndarray:
+    """``cv2.blur(a, (k, k))`` of uint8[h, w, 3] for k = 2 or 3: the window starts at -1 (OpenCV's anchor k / 2), the border is
+    reflect-101, the sum is divided by k * k to nearest, ties to even."""
+    h, w = a.shape[:2]
+    pad = np.pad(a.astype(np.int64), ((1, 1), (1, 1), (0, 0)), mode="reflect")
+    s = sum(pad[dy:dy + h, dx:dx + w] for dy in range(k) for dx in range(k))
+    if k == 2:
+        q, rem = s >> 2, s & 3
+        return (q + ((rem == 3) | ((rem == 2) & ((q & 1) == 1)))).astype(np.uint8)
+    return ((2 * s + 9) // 18).astype(np.uint8)
+
+
 def _augment_one(img: np.ndarray, p) -> np.ndarray:
     lut_bc, lut_h, lut_s, lut_v = _tables(p)
     a = lut_bc[img[:, ::-1] if p["flip"] else img]                                        # 1, 2
     k = int(p["blur_k"])
     if k:                                                                                  # 3
-        pad = np.pad(a.astype(np.int64), ((1, 1), (1, 1), (0, 0)), mode="reflect")         # reflect-101; the window starts at -1
-        s = sum(pad[dy:dy + SIZE, dx:dx + SIZE] for dy in range(k) for dx in range(k))
-        if k == 2:
-            q, rem = s >> 2, s & 3
-            a = (q + ((rem == 3) | ((rem == 2) & ((q & 1) == 1)))).astype(np.uint8)
-        else:
-            a = ((2 * s + 9) // 18).astype(np.uint8)
+        a = box_blur(a, k)
     if p["hue_shift"] != 0 or p["sat_shift"] != 0 or p["val_shift"] != 0:                  # 4
         a = _hsv_shift(a, lut_h, lut_s, lut_v)
     pos = np.arange(SIZE * SIZE, dtype=np.int64).reshape(SIZE, SIZE)                       # v * 128 + u

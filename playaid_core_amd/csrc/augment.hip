@@ -16,8 +16,7 @@
 // Memory safety for ANY parameter bytes: src is clamped, map entries are masked with & 127, hole tests are comparisons (no
 // address is formed from a hole), every table index is a byte. Compiled with -ffp-contract=off (_build.py): the fp32 stages
 // must not have their multiplies and adds fused.
-#include "pa_kernels.h"
-#include "train_common.h"   // hash_mix, hash_element; include/playaid_hip.h
+#include "augment_math.h"   // the stages' arithmetic, shared with sprite_augment.hip; include/playaid_hip.h
 
 #include <cmath>
 
@@ -36,20 +35,6 @@ struct alignas(16) AugLds {
 };
 static_assert(sizeof(AugLds) <= 64 * 1024, "one workgroup's LDS");
 static_assert(sizeof(pa_augment_params) == 328 && sizeof(pa_augment_params) % 4 == 0 && sizeof(AugmentTables) % 16 == 0, "copied in words");
-
-// a float of the parameter block as the kernel uses it: its identity value when it is not finite, else clamped
-__host__ __device__ __forceinline__ float aug_sane(float x, float ident, float lo, float hi) {
-    if (!(fabsf(x) <= 3.4028235e38f)) return ident;
-    return fminf(fmaxf(x, lo), hi);
-}
-
-__device__ __forceinline__ int aug_reflect(int i) {   // BORDER_REFLECT_101 on 0..127, for i in -1..128
-    return i < 0 ? -i : (i > 127 ? 254 - i : i);
-}
-
-__device__ __forceinline__ uint8_t aug_byte(float t) {   // trunc(clip(t, 0, 255))
-    return (uint8_t)(int)fminf(fmaxf(t, 0.f), 255.f);
-}
 
 __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(const uint8_t* __restrict__ src, int n_src,
                                                               const pa_augment_params* __restrict__ params, int out_format,
@@ -79,22 +64,10 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(const uint8_t* __r
     const uint32_t thr = L.prm.pixel_drop_thr;
     const int n_holes = min(max(L.prm.n_holes, 0), 8);
     const int cmask = L.prm.channel_mask & 7;
-    uint32_t k0 = hash_mix((uint32_t)L.prm.key + 0x9e3779b9u);
-    k0 = hash_mix(k0 ^ (uint32_t)(L.prm.key >> 32));
-    const uint32_t k_noise = hash_mix(k0 ^ (1u * 0x85ebca6bu));
-    const uint32_t k_drop = hash_mix(k0 ^ (2u * 0x85ebca6bu));
+    uint32_t k_noise, k_drop;
+    aug_stream_keys(L.prm.key, &k_noise, &k_drop);
 
-    if (tid < 256) {
-        const float bo = beta * 255.f;
-        L.lut_bc[tid] = aug_byte((float)tid * alpha + bo);
-        const double t = (double)tid + (double)hue;
-        double r = t - floor(t * (1.0 / 180.0)) * 180.0;   // (k + shift) mod 180 in [0, 180): the quotient may be one off, the two
-        if (r < 0.0) r += 180.0;                            // corrections are exact
-        if (r >= 180.0) r -= 180.0;
-        L.lut_h[tid] = (uint8_t)(int)r;
-        L.lut_s[tid] = (uint8_t)(int)fmin(fmax((double)tid + (double)sat, 0.0), 255.0);
-        L.lut_v[tid] = (uint8_t)(int)fmin(fmax((double)tid + (double)val, 0.0), 255.0);
-    }
+    if (tid < 256) aug_lut_entry(tid, alpha, beta, hue, sat, val, L.lut_bc, L.lut_h, L.lut_s, L.lut_v);
     __syncthreads();
 
     {
@@ -137,72 +110,19 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(const uint8_t* __r
             } else {
                 int s0 = 0, s1 = 0, s2 = 0;
                 for (int dy = 0; dy < blur; ++dy) {
-                    const int vy = aug_reflect(v - 1 + dy);
+                    const int vy = aug_reflect(v - 1 + dy, 128);
                     for (int dx = 0; dx < blur; ++dx) {
-                        const uint8_t* p = &L.img[vy * AUG_ROW + aug_reflect(u - 1 + dx) * 3];
+                        const uint8_t* p = &L.img[vy * AUG_ROW + aug_reflect(u - 1 + dx, 128) * 3];
                         s0 += p[0]; s1 += p[1]; s2 += p[2];
                     }
                 }
-                const int s[3] = {s0, s1, s2};
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (blur == 2) {   // s / 4 to nearest, ties to even
-                        const int q = s[k] >> 2, rem = s[k] & 3;
-                        c[k] = q + ((rem == 3 || (rem == 2 && (q & 1))) ? 1 : 0);
-                    } else {           // s / 9 to nearest (no ties: 9 is odd)
-                        c[k] = (2 * s[k] + 9) / 18;
-                    }
-                }
+                c[0] = aug_blur_round(s0, blur); c[1] = aug_blur_round(s1, blur); c[2] = aug_blur_round(s2, blur);
             }
-            if (hsv_on) {
-                const int r = c[0], g = c[1], b = c[2];
-                const int vmax = max(r, max(g, b)), vmin = min(r, min(g, b));
-                const int diff = vmax - vmin;
-                const int vr = vmax == r ? -1 : 0, vg = vmax == g ? -1 : 0;
-                const int s8 = ((diff * L.tabs.sdiv[vmax] + (1 << 11)) >> 12) & 255;
-                int h = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + (~vg & (r - g + 4 * diff))));
-                h = (h * L.tabs.hdiv[diff] + (1 << 11)) >> 12;
-                h += h < 0 ? 180 : 0;
-                h = min(max(h, 0), 255);
-                const int H = L.lut_h[h], S = L.lut_s[s8], V = L.lut_v[vmax];
-                const float vf = (float)V * (1.f / 255.f), sf = (float)S * (1.f / 255.f);
-                float rf = vf, gf = vf, bf = vf;
-                if (S != 0) {
-                    float hf = (float)H * (6.f / 180.f);
-                    int sector = (int)hf;   // hf >= 0: the floor
-                    hf -= (float)sector;
-                    if ((unsigned)sector >= 6u) {
-                        sector = 0;
-                        hf = 0.f;
-                    }
-                    const float t1 = vf * (1.f - sf);
-                    const float t2 = vf * (1.f - sf * hf);
-                    const float t3 = vf * (1.f - sf * (1.f - hf));
-                    // OpenCV's sector table, (b, g, r) of tab[] = {v, t1, t2, t3}: {1,3,0} {1,0,2} {3,0,1} {0,2,1} {0,1,3} {2,1,0}
-                    switch (sector) {
-                        case 0: bf = t1; gf = t3; rf = vf; break;
-                        case 1: bf = t1; gf = vf; rf = t2; break;
-                        case 2: bf = t3; gf = vf; rf = t1; break;
-                        case 3: bf = vf; gf = t2; rf = t1; break;
-                        case 4: bf = vf; gf = t1; rf = t3; break;
-                        default: bf = t2; gf = t1; rf = vf; break;
-                    }
-                }
-                c[0] = (int)fminf(fmaxf(rintf(rf * 255.f), 0.f), 255.f);
-                c[1] = (int)fminf(fmaxf(rintf(gf * 255.f), 0.f), 255.f);
-                c[2] = (int)fminf(fmaxf(rintf(bf * 255.f), 0.f), 255.f);
-            }
+            if (hsv_on) aug_hsv_pixel(c, L.tabs, L.lut_h, L.lut_s, L.lut_v);
             const uint32_t pos = (uint32_t)(v * 128 + u);
             if (sigma > 0.f) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const uint32_t r = hash_element(k_noise, pos * 3u + (uint32_t)k);
-                    const int cell = (int)(r >> 22);
-                    const float f = (float)(r & 0x3fffffu) * (1.f / 4194304.f);
-                    const float q0 = L.tabs.q[cell];
-                    const float z = q0 + f * (L.tabs.q[cell + 1] - q0);
-                    c[k] = aug_byte((float)c[k] + sigma * z);
-                }
+                for (int k = 0; k < 3; ++k) c[k] = aug_noise_byte(c[k], sigma, k_noise, pos * 3u + (uint32_t)k, L.tabs.q);
             }
             bool zero = thr != 0u && hash_element(k_drop, pos) < thr;
             for (int hole = 0; hole < n_holes; ++hole)

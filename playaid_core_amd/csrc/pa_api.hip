@@ -5,7 +5,7 @@
 #include "../../include/playaid_hip.h"
 #include "conv_rows.h"
 #include "engine_table.h"   // the layer table, over engine_plan.h
-#include "synth_math.h"     // SynthDesc
+#include "synth_math.h"     // SynthDesc, runner_in_plan
 #include "train_common.h"   // adam_scalars, adam_config_ok, TrainerCore
 
 #include <algorithm>
@@ -2167,6 +2167,9 @@ struct pa_synth_bank {
     int dim_min = PA_SYNTH_DIM_MIN;   // sprites: the smallest dim at which every image resizes to at least 1 x 1
     unsigned char* dev = nullptr;   // [descriptor table, padded to 16 bytes][images]; nullptr: a bank made without an engine
     size_t table_bytes = 0;
+    unsigned char* scratch = nullptr;   // pa_sprite_bank_create: the augmentation kernel's, [scratch_groups][SPRITE_SCRATCH_BYTES]
+    int scratch_groups = 0;
+    bool slots = false;                 // ... and its images are slots that pa_sprite_augment writes
 };
 
 int pa_synth_bank_create(pa_engine* e, int32_t kind, const uint8_t* const* images_host, const int32_t* widths, const int32_t* heights,
@@ -2236,6 +2239,7 @@ int pa_synth_bank_create(pa_engine* e, int32_t kind, const uint8_t* const* image
 void pa_synth_bank_destroy(pa_synth_bank* b) {
     if (!b) return;
     if (b->dev) (void)hipFree(b->dev);
+    if (b->scratch) (void)hipFree(b->scratch);
     delete b;
 }
 
@@ -2286,6 +2290,134 @@ int pa_synth_composite(pa_engine* e, const pa_synth_bank* sprites, const pa_synt
     const double px = (double)n * dim * dim;
     ProfScope ps(e, (hipStream_t)stream, "synth_composite", 0.0, px * (out_format == PA_SYNTH_MODEL ? 15.0 : 6.0));
     HIPCHK(e, launch_synth_composite(a, (hipStream_t)stream));
+    return PA_OK;
+}
+
+// ---- augmentation of the renders before the paste (sprite_augment.hip) -----------------------------------------------------------
+
+// The bank-level limits of pa_sprite_augment: PA_OK, PA_ERR_INVALID_ARG for a render whose resize to width 128 is empty (cv2.resize
+// raises; so does Pillow for an empty contain size, which h1 <= PA_SPRITE_H1_MAX rules out), PA_ERR_CAPACITY for one taller than that.
+static int sprite_bank_limits(const pa_synth_bank* sprites, int* which) {
+    for (size_t k = 0; k < sprites->descs.size(); ++k) {
+        const RunnerInPlan in = runner_in_plan(sprites->descs[k].w, sprites->descs[k].h, (size_t)1 << 30);
+        *which = (int)k;
+        if (in.status == PA_CROP_EMPTY || in.area.oh < 1) return PA_ERR_INVALID_ARG;
+        if (in.status != PA_CROP_OK || in.area.oh > PA_SPRITE_H1_MAX) return PA_ERR_CAPACITY;
+    }
+    return PA_OK;
+}
+
+int pa_sprite_aug_params_check(const pa_sprite_aug_params* host, int32_t n, const pa_synth_bank* sprites) {
+    if (!host || n < 1 || !sprites || sprites->kind != PA_SYNTH_SPRITES) return PA_ERR_INVALID_ARG;
+    int which = 0;
+    const int rc = sprite_bank_limits(sprites, &which);
+    if (rc != PA_OK) return rc;
+    auto in = [](float x, float lo, float hi) { return x >= lo && x <= hi; };   // false for NaN
+    for (int32_t i = 0; i < n; ++i) {
+        const pa_sprite_aug_params& p = host[i];
+        if (p.src < 0 || p.src >= (int32_t)sprites->descs.size() || (p.flip != 0 && p.flip != 1)) return PA_ERR_INVALID_ARG;
+        if (!in(p.alpha, 0.8f, 1.2f) || !in(p.beta, -0.2f, 0.6f)) return PA_ERR_INVALID_ARG;
+        if (p.blur_k != 0 && p.blur_k != 2 && p.blur_k != 3) return PA_ERR_INVALID_ARG;
+        if (!in(p.hue_shift, -256.f, 256.f) || !in(p.sat_shift, -67.f, 67.f) || !in(p.val_shift, -10.f, 10.f)) return PA_ERR_INVALID_ARG;
+        if (p.noise_sigma != 0.f && !in(p.noise_sigma, 20.679216f, 22.360680f)) return PA_ERR_INVALID_ARG;   // sqrt(427.63), sqrt(500) as floats
+        if (p.pixel_drop_thr != 0u && p.pixel_drop_thr != PA_SPRITE_DROP_THR) return PA_ERR_INVALID_ARG;
+        if (p.new_scale != 0 && (p.new_scale < 96 || p.new_scale > 127)) return PA_ERR_INVALID_ARG;
+        if ((p.sized_crop != 0 && p.sized_crop != 1) || p.reserved != 0) return PA_ERR_INVALID_ARG;
+        const int C = p.new_scale ? 256 - p.new_scale : 128, O = p.sized_crop ? 128 : C;
+        const int S = std::min(96, C / 3);
+        if (p.n_holes < 0 || p.n_holes > 2 || p.channel_mask < 0 || p.channel_mask > 6) return PA_ERR_INVALID_ARG;
+        for (int h = 0; h < 2 * p.n_holes; ++h)
+            if (p.holes[h] > C - S) return PA_ERR_INVALID_ARG;
+        for (int k = 0; k < O; ++k)
+            if (p.xmap[k] >= C || p.ymap[k] >= C || p.axmap[k] >= C || p.aymap[k] >= C) return PA_ERR_INVALID_ARG;
+    }
+    return PA_OK;
+}
+
+int pa_sprite_bank_create(pa_engine* e, int32_t n, pa_synth_bank** out) {
+    if (!out) return PA_ERR_INVALID_ARG;
+    *out = nullptr;
+    pa_synth_bank* b = nullptr;
+    try {
+        if (n < 1 || n > 65535) return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_bank_create: n is 1..65535");
+        b = new pa_synth_bank();
+        b->kind = PA_SYNTH_SPRITES;
+        b->slots = true;
+        b->descs.resize((size_t)n);
+        for (int32_t k = 0; k < n; ++k) {
+            b->descs[(size_t)k].offset = (uint64_t)k * (PA_CROP * PA_CROP * 4);
+            b->descs[(size_t)k].w = b->descs[(size_t)k].h = PA_CROP;
+        }
+        b->min_w = b->min_h = PA_CROP;
+        b->table_bytes = ((size_t)n * sizeof(SynthDesc) + 15) & ~(size_t)15;
+        if (e) {
+            const size_t bytes = b->table_bytes + (size_t)n * (PA_CROP * PA_CROP * 4);
+            b->scratch_groups = std::min((int)n, SPRITE_WORKGROUPS_MAX);
+            void* p = nullptr;
+            hipError_t err = hipMalloc(&p, bytes);
+            if (err == hipSuccess) {
+                b->dev = static_cast<unsigned char*>(p);
+                err = hipMemset(p, 0, bytes);
+            }
+            if (err == hipSuccess) err = hipMemcpy(p, b->descs.data(), (size_t)n * sizeof(SynthDesc), hipMemcpyHostToDevice);
+            if (err == hipSuccess) {
+                err = hipMalloc(&p, (size_t)b->scratch_groups * SPRITE_SCRATCH_BYTES);
+                if (err == hipSuccess) b->scratch = static_cast<unsigned char*>(p);
+            }
+            if (err != hipSuccess) {
+                pa_synth_bank_destroy(b);
+                b = nullptr;
+                return fail(e, PA_ERR_HIP, std::string("pa_sprite_bank_create: ") + hipGetErrorString(err));
+            }
+        }
+        *out = b;
+        return PA_OK;
+    } catch (const std::exception&) {
+        pa_synth_bank_destroy(b);
+        if (e) e->last_error.clear();
+        return PA_ERR_CAPACITY;
+    }
+}
+
+int pa_sprite_augment(pa_engine* e, const pa_synth_bank* sprites, const pa_sprite_aug_params* params_dev, int32_t n, pa_synth_bank* out_bank,
+                      void* stream) {
+    if (!e || !sprites || !params_dev || !out_bank || n < 1 || sprites->kind != PA_SYNTH_SPRITES || (uintptr_t)params_dev & 7)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_augment: bad argument (params 8-byte aligned, n at least 1)");
+    if (!out_bank->slots || !out_bank->dev || !out_bank->scratch || out_bank == sprites)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_augment: out_bank is a bank of pa_sprite_bank_create, made with an engine, and not the source");
+    if (!sprites->dev) return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_augment: a bank that was made without an engine has no pixels");
+    if (n > (int32_t)out_bank->descs.size())
+        return fail(e, PA_ERR_CAPACITY, "pa_sprite_augment: n is beyond out_bank's " + std::to_string(out_bank->descs.size()) + " slots");
+    int which = 0;
+    const int rc = sprite_bank_limits(sprites, &which);
+    if (rc != PA_OK) {
+        const SynthDesc& d = sprites->descs[(size_t)which];
+        return fail(e, rc, "pa_sprite_augment: sprite " + std::to_string(which) + " (" + std::to_string(d.h) + " x " + std::to_string(d.w) +
+                               (rc == PA_ERR_CAPACITY ? "): resized to width 128 it is taller than " + std::to_string(PA_SPRITE_H1_MAX) + " (h <= 3.5 w is always taken)"
+                                                      : "): resized to width 128 it is empty"));
+    }
+    if (!e->aug_tabs) return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_augment: the engine has no tables");
+    SpriteAugArgs a;
+    a.sprite_px = sprites->dev + sprites->table_bytes;
+    a.sprite_desc = reinterpret_cast<const SynthDesc*>(sprites->dev);
+    a.n_sprites = (int)sprites->descs.size();
+    a.params = params_dev;
+    a.n = n;
+    a.out_px = out_bank->dev + out_bank->table_bytes;
+    a.scratch = out_bank->scratch;
+    a.workgroups = std::min((int)n, out_bank->scratch_groups);
+    a.tabs = e->aug_tabs;
+    ProfScope ps(e, (hipStream_t)stream, "sprite_augment", 0.0, (double)n * 65536.0 * 8.0);
+    HIPCHK(e, launch_sprite_augment(a, (hipStream_t)stream));
+    return PA_OK;
+}
+
+int pa_sprite_bank_read(pa_engine* e, const pa_synth_bank* bank, int32_t first, int32_t n, uint8_t* out_host, void* stream) {
+    if (!e || !bank || !out_host || !bank->slots || !bank->dev || first < 0 || n < 1 || (int64_t)first + n > (int64_t)bank->descs.size())
+        return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_bank_read: a bank of pa_sprite_bank_create with pixels, and a range inside its slots");
+    const size_t slot = (size_t)PA_CROP * PA_CROP * 4;
+    HIPCHK(e, hipMemcpyAsync(out_host, bank->dev + bank->table_bytes + (size_t)first * slot, (size_t)n * slot, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     return PA_OK;
 }
 

@@ -542,4 +542,25 @@ struct SynthArgs {
 };
 hipError_t launch_synth_composite(const SynthArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// augmentation of character renders before the paste (sprite_augment.hip; pa_sprite_augment)
+// ---------------------------------------------------------------------------
+// one workgroup's scratch: [128 x h1 resize, later the chain's C x C output][horizontal bicubic pass, later the C x C canvas]
+// [128 x 128 canvas], dwords
+constexpr size_t SPRITE_SCRATCH_R0 = 128 * PA_SPRITE_H1_MAX * 4, SPRITE_SCRATCH_R1 = 128 * PA_SPRITE_H1_MAX * 4, SPRITE_SCRATCH_R2 = 128 * 128 * 4;
+constexpr size_t SPRITE_SCRATCH_BYTES = SPRITE_SCRATCH_R0 + SPRITE_SCRATCH_R1 + SPRITE_SCRATCH_R2;
+constexpr int SPRITE_WORKGROUPS_MAX = 256;
+struct SpriteAugArgs {
+    const uint8_t* sprite_px;        // the source bank's first pixel
+    const SynthDesc* sprite_desc;
+    int n_sprites;
+    const pa_sprite_aug_params* params;   // device, [n]
+    int n;
+    uint8_t* out_px;                 // the output bank's first pixel: slot i at i * 65536
+    uint8_t* scratch;                // [workgroups][SPRITE_SCRATCH_BYTES]
+    int workgroups;
+    const AugmentTables* tabs;
+};
+hipError_t launch_sprite_augment(const SpriteAugArgs& a, hipStream_t s);
+
 }  // namespace pa

@@ -16,9 +16,10 @@ backbone's input layout; no frame exists on the host.
   (DESIGN.md 5.15 lists what is unverified);
 * ``SynthWindowDataset`` hands out the reference's 4-tuple per item and whole batches in the model layout from one launch.
 
-``synth_difficulty`` 1 / 2 is NOT built: it needs ``augment_synth_char_crop`` (``dataset_utils.py``), whose RGBA chain runs on
-the sprite BEFORE the paste. ``pa_synth_composite`` takes its sprites from a bank handle so that such a stage can hand it a
-bank of its own outputs.
+``augment_synth_char_crop`` (``dataset_utils.py``), the RGBA chain the reference runs on the sprite BEFORE the paste when
+``synth_difficulty`` is 1 or 2, is ``sprite_augment.py``: one launch from the sprite bank into a bank of augmented 128 x 128
+sprites, which ``pa_synth_composite`` takes through the same bank handle. ``SynthWindowDataset(sprite_augment=level,
+paste_jitter=40)`` is the reference's level; the argument ``synth_difficulty`` itself still raises (it may become sugar for the pair).
 
 The order of the draws in ``sample_synth`` is fixed (scalars, from one ``numpy.random.Generator``; ``choice(seq)`` stands for
 ``seq[integers(0, len(seq))]``):
@@ -497,14 +498,20 @@ class SynthWindowDataset:
     def __init__(self, engine, sprites: SpriteBank, stages: StageBank, animations: Optional[Sequence[str]] = None,
                  characters: Optional[Sequence[str]] = None, num_samples: int = 1024, num_frames_per_sample: int = 7,
                  img_dimension: int = 128, randomize_stage_background: bool = False, move_stage_background: bool = False,
-                 paste_jitter: int = 0, seed: int = 0, synth_difficulty: int = 0):
+                 paste_jitter: int = 0, seed: int = 0, synth_difficulty: int = 0, sprite_augment=None):
         """``animations``: the action list the labels index (default: the ontology's, as ``ClipWindowDataset``);
         ``characters``: the list the character label indexes (default: the bank's characters). ``paste_jitter``: the reference
-        uses 40 when ``synth_difficulty`` is on. ``synth_difficulty`` other than 0 raises: see the module docstring."""
+        uses 40 when ``synth_difficulty`` is on. ``sprite_augment``: None, or 1 / 2 / a dict of ``augment_synth_char_crop``'s
+        probabilities (``sprite_augment.sample_sprite_params``): every frame's render goes through that function, with its own
+        draw from the item's generator AFTER the draws of ``sample_synth`` (so None gives the same windows as before), in one
+        ``pa_sprite_augment`` launch per item or batch ahead of the one composite launch. ``synth_difficulty`` other than 0
+        raises: see the module docstring."""
         if synth_difficulty:
-            raise NotImplementedError("synth_difficulty 1 / 2 needs augment_synth_char_crop (dataset_utils.py), which resizes, pads, "
-                                      "shrinks and augments the RGBA sprite BEFORE the paste: not built. paste_jitter=40 gives that "
-                                      "level's paste offsets alone.")
+            raise NotImplementedError("synth_difficulty 1 / 2 is augment_synth_char_crop (dataset_utils.py) on the sprite BEFORE the "
+                                      "paste plus paste offsets of +-40: pass sprite_augment=level, paste_jitter=40, which together "
+                                      "are the reference's level.")
+        self.sprite_augment = self._check_sprite_augment(sprite_augment)
+        self._aug_bank = None
         if animations is None:
             from .anim_ontology import MOVE_TO_CLASS_ID
 
@@ -528,18 +535,64 @@ class SynthWindowDataset:
         """The epoch the draws are keyed by (with ``seed`` and the item's index)."""
         self.epoch = int(epoch)
 
-    def sample(self, idx: int):
-        """``sample_synth`` for item ``idx``: the draw alone, nothing on the device."""
+    @staticmethod
+    def _check_sprite_augment(level):
+        from . import sprite_augment as sa
+
+        if level is None or isinstance(level, dict) or (not isinstance(level, bool) and level in sa.SPRITE_LEVELS):
+            if isinstance(level, dict):
+                sa.sample_sprite_params(1, level, np.random.default_rng(0))   # (ValueError for an unknown key)
+            return level
+        raise ValueError(f"sprite_augment is None, one of {sorted(sa.SPRITE_LEVELS)} or a dict, got {level!r}")
+
+    def make_synth_more_challenging(self):
+        """``UltActionRecogDataset.make_synth_more_challenging`` (``ult_action_dataset.py:561-564``) for the sprite augmentation: an
+        integer level (None counts as 0) goes one up, 2 at most; a dict stays as it is."""
+        from . import sprite_augment as sa
+
+        if not isinstance(self.sprite_augment, dict):
+            self.sprite_augment = min((self.sprite_augment or 0) + 1, sa.MAX_LEVEL)
+
+    def _draw(self, idx: int):
         if not 0 <= idx < len(self):
             raise IndexError(idx)
         rng = np.random.default_rng([self.seed, self.epoch, int(idx)])
-        return sample_synth(rng, self.sprites.tree, self.animations, self.characters, self.num_frames_per_sample, self.img_dimension,
+        draw = sample_synth(rng, self.sprites.tree, self.animations, self.characters, self.num_frames_per_sample, self.img_dimension,
                             self.stages.shapes, self.randomize_stage_background, self.move_stage_background, self.paste_jitter)
+        aug = None
+        if self.sprite_augment is not None:
+            from . import sprite_augment as sa
 
-    def _item(self, params, char_label, actions, frame_paths):
+            aug = sa.sample_sprite_params(len(draw[0]), self.sprite_augment, rng, src=draw[0]["sprite"])
+        return draw, aug
+
+    def sample(self, idx: int):
+        """``sample_synth`` for item ``idx``: the draw alone, nothing on the device."""
+        return self._draw(idx)[0]
+
+    def sample_sprite_augment(self, idx: int):
+        """The ``pa_sprite_aug_params`` records of item ``idx``'s S frames (None without ``sprite_augment``): drawn from the item's
+        generator after ``sample``'s draws; record k reads the render ``sample(idx)[0]["sprite"][k]``."""
+        return self._draw(idx)[1]
+
+    def _composite(self, params, aug, out_format):
+        """The frames of ``params``; with ``aug`` (one record per frame) every render is augmented into a bank of ``len(params)``
+        slots first and frame k pastes slot k."""
+        if aug is None:
+            return composite(self.engine, self.sprites, self.stages, params, self.img_dimension, out_format)
+        from . import sprite_augment as sa
+
+        if self._aug_bank is None or len(self._aug_bank) < len(params):   # kept: the launches on it are ordered by the engine's stream
+            self._aug_bank = sa.AugmentedSpriteBank(self.engine, len(params))
+        bank = sa.augment_sprites(self.engine, self.sprites, aug, out=self._aug_bank)
+        params = params.copy()
+        params["sprite"] = np.arange(len(params))
+        return composite(self.engine, bank, self.stages, params, self.img_dimension, out_format)
+
+    def _item(self, params, char_label, actions, frame_paths, aug=None):
         import torch
 
-        frames = composite(self.engine, self.sprites, self.stages, params, self.img_dimension, "uint8").cpu()
+        frames = self._composite(params, aug, "uint8").cpu()
         return (frames.permute(0, 3, 1, 2).float() / 255.0, torch.tensor(char_label),
                 torch.tensor([self.animations.index(a) for a in actions]),
                 {"char": self.characters[char_label], "frames": list(frames.numpy()), "frame_paths": frame_paths, "actions": actions})
@@ -547,8 +600,8 @@ class SynthWindowDataset:
     def __getitem__(self, idx: int):
         """The reference's 4-tuple (``ult_action_dataset.py:676-689``): ``frames[S, 3, D, D].float() / 255``,
         ``tensor(char_label)``, ``tensor(anim_label[S])`` and a dict with ``char``, ``frames``, ``frame_paths``, ``actions``."""
-        params, char_label, actions, _ = self.sample(idx)
-        return self._item(params, char_label, actions, [self.sprites.paths[int(k)] for k in params["sprite"]])
+        (params, char_label, actions, _), aug = self._draw(idx)
+        return self._item(params, char_label, actions, [self.sprites.paths[int(k)] for k in params["sprite"]], aug)
 
     def simple_item(self, idx: int, frames: Sequence):
         """``simple_dataset``'s fixed-frame form (``ult_action_dataset.py:373-427``): the bank's images ``frames`` over stage 0
@@ -585,9 +638,11 @@ class SynthWindowDataset:
 
         S = self.num_frames_per_sample
         for i0 in range(0, len(self), batch_size):
-            draws = [self.sample(i) for i in range(i0, min(i0 + batch_size, len(self)))]
+            both = [self._draw(i) for i in range(i0, min(i0 + batch_size, len(self)))]
+            draws = [b[0] for b in both]
             params = np.concatenate([d[0] for d in draws])
-            x = composite(self.engine, self.sprites, self.stages, params, self.img_dimension, "model")
+            aug = np.concatenate([b[1] for b in both]) if self.sprite_augment is not None else None
+            x = self._composite(params, aug, "model")
             dev = self.engine.device
             yield (x.view(len(draws), S, 3, self.img_dimension, self.img_dimension),
                    torch.tensor([d[1] for d in draws], device=dev),

@@ -15,11 +15,11 @@ the same sampler with the runner's own range (frames are 1-indexed crop files, `
 
 The synthetic windows of the reference's dataset (``get_synth``, ``simple_dataset``: character renders resized and pasted over
 stage crops) are ``synth_dataset.SynthWindowDataset``, composed on the device from uploaded renders (``synth_dataset.py``,
-DESIGN.md 5.15).
+DESIGN.md 5.15); ``augment_synth_char_crop``, the augmentation of the RGBA render BEFORE it is pasted that ``synth_difficulty``
+1 / 2 adds to them, is ``sprite_augment.py``.
 
 Not built, by scope (training only): the random choice of (fighter, action, frame), the frame-delta
-choice, ``augment_synth_char_crop`` (the augmentation of the RGBA render BEFORE it is pasted, which ``synth_difficulty`` 1 / 2
-adds to the synthetic windows), ``preceding_actions`` (the reference's own loop over them is empty: ``range(a, a)``,
+choice, ``preceding_actions`` (the reference's own loop over them is empty: ``range(a, a)``,
 ``ult_action_dataset.py:284-286``).
 
 For scoring (``metrics.py``, ``AIRunner.evaluate``): ``load_ground_truth_labels`` reads a hand-labelled clip's CSV as the
