@@ -1418,6 +1418,18 @@ int pa_sprite_augment(pa_engine* e, const pa_synth_bank* sprites, const pa_sprit
  * PA_ERR_INVALID_ARG for a bank of another kind or without pixels, or a range outside the slots. */
 int pa_sprite_bank_read(pa_engine* e, const pa_synth_bank* bank, int32_t first, int32_t n, uint8_t* out_host, void* stream);
 
+/* Appended (the version stays 15): pa_wino_conv3x3 with the workgroup's shape as one more argument, for parity tests and
+ * measurements of single layers. PA_WINO_WG_BY_BN: the launch pa_wino_conv3x3 makes (eight waves over 16 sub-blocks x 64 channels, or
+ * four over 16 x 32, as `bn` says). PA_WINO_WG_2X2: four waves as two tile groups by two channel groups -- 8 sub-blocks (128 pixels)
+ * x 64 channels, one workgroup per CU; it reads the `bn` = 64 filter layout and nothing else. Neither splits K: per lane the
+ * arithmetic is the same in both, so the two give the same bits. PA_ERR_INVALID_ARG for another shape value, for PA_WINO_WG_2X2
+ * with `bn` != 64, and for whatever pa_wino_conv3x3 refuses. Enqueue only. */
+#define PA_WINO_WG_BY_BN 0
+#define PA_WINO_WG_2X2 1
+int pa_wino_conv3x3_shape(const float* x, const float* ug, const float* bias, const float* residual, float* out, int32_t n,
+                          int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride,
+                          int32_t out_px_stride, int32_t out_pad, int32_t act, int32_t res_after, int32_t shape, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -350,6 +350,7 @@ SYMBOLS = [
     ("pa_sprite_bank_create", C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
     ("pa_sprite_augment", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     ("pa_sprite_bank_read", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    ("pa_wino_conv3x3_shape", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 12 + [_P]),
 ]
 
 _lib = None

@@ -4,6 +4,7 @@
 // the host compiler alone.
 #pragma once
 #include "gemm_tile.h"
+#include "wino_shape.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -32,6 +33,8 @@ struct EngineKnobs {
     int wino_ds = 1;        // PA_WINO_DS=0: block-0 conv2 of layers 2-4 stays one implicit GEMM with the branch as its second K source
     int wino_f4 = 1;        // PA_WINO_F4=0: the Winograd layers on 4 x 4 maps stay on the fused F(2x2) kernel at every batch
     int wino_f4_min = WINO_F4_MIN_CROPS;  // PA_WINO_F4_MIN: ... below this many crops per launch
+    int wino_l3_shape = -1; // PA_WINO_L3_SHAPE=0..3: the launches of the Winograd layers on 8 x 8 maps (layer 3) as this WinoShape (wino_shape.h) at
+                            // every batch -- 0 split K, 1 unsplit eight waves, 2 unsplit four waves of 32 channels, 3 unsplit 2 x 2 waves; unset: the rule's own
     int bf16_ds_fuse = 1;   // PA_BF16_DS_FUSE: the bf16 openers carry their block's branch; 0: its own GEMM, 2: own GEMM, the opener's tile as if fused
     int f32_ds_fuse = 1;    // PA_F32_DS_FUSE=0: the exact openers do not carry their block's branch
     // -- read at every pa_create / pa_create_from_arena --
@@ -70,6 +73,7 @@ inline EngineKnobs engine_knobs() {
         k.wino_ds = env_int("PA_WINO_DS", k.wino_ds);
         k.wino_f4 = env_int("PA_WINO_F4", k.wino_f4);
         k.wino_f4_min = env_int("PA_WINO_F4_MIN", k.wino_f4_min);
+        k.wino_l3_shape = env_int("PA_WINO_L3_SHAPE", k.wino_l3_shape);
         k.bf16_ds_fuse = env_int("PA_BF16_DS_FUSE", k.bf16_ds_fuse);
         k.f32_ds_fuse = env_int("PA_F32_DS_FUSE", k.f32_ds_fuse);
         return k;
@@ -208,6 +212,12 @@ inline bool wino_layer(const EngineKnobs& k, ComputeDtype dt, const LayerDesc& L
 // 5.1d), if the engine's full batch reaches the threshold at all. PA_WINO_F4=0: never (A/B)
 inline bool wino4_layer(const EngineKnobs& k, ComputeDtype dt, const LayerDesc& L, int max_crops) {
     return wino_layer(k, dt, L) && k.wino_f4 && L.out_hw == 4 && L.in_hw == 4 && L.cin % 64 == 0 && L.cout % 64 == 0 && max_crops >= k.wino_f4_min;
+}
+
+// How the launches of Winograd layer L are shaped in an engine of `max_crops` crops (wino_shape.h): decided at create, from the
+// layer's geometry, max_crops and the per-process knobs alone, so that every engine of one shape in a process decides alike
+inline WinoLayerShape wino_layer_shape(const EngineKnobs& k, const LayerDesc& L, int max_crops) {
+    return wino_layer_shape(k.wino_l3_shape, L.cin, L.cout, L.out_hw, max_crops, wino_bn_force());
 }
 
 // Can `opener` compute the branch that `conv2` adds? Same input, same output shape, padding and chunk, tile not pinned;

@@ -31,7 +31,8 @@ struct ConvLayer : LayerDesc {
     float* residual = nullptr;
     float* wgt = nullptr;   // device [cout][taps*chunk]; block-0 conv2 of layers 2-4, fp32: [W2 | Wd], the branch as extra K read from `ds.src`
     float* wino_wgt = nullptr;  // LayerDesc::wino: the filters in wino.hip's layout
-    int wino_bn = 0;            // ... laid out for workgroups of this many output channels (wino_pick_bn at the full batch)
+    int wino_bn = 0;            // ... laid out for workgroups of this many output channels (wino_layer_shape at the full batch)
+    WinoShape wino_shape = WINO_SHAPE_SPLIT;  // ... and how its launches are shaped: with the split-K scratch, or unsplit on one of three workgroups
     float* wino4_wgt = nullptr; // LayerDesc::wino4: the filters as wino4.hip's 36 GEMM images
     float* bias = nullptr;  // device [cout]
     unsigned short* split_wgt = nullptr;  // LayerDesc::split: three bf16 slices per weight in psgemm.hip's stage-image order
@@ -77,7 +78,7 @@ struct pa_engine {
     // entries' sizes depend on: S, A, compute_dtype, the per-process knobs (EngineKnobs' first part) and whether max_crops reaches knobs.wino_f4_min (layer
     // 4's F(4x4) filters). A rank that received the arena over RCCL from an engine equal in all of these adopts it with one device
     // copy (pa_create_from_arena) instead of folding the blob again. (The size check of adopt mode sees the offsets only: the Winograd
-    // filters' order inside their entry also follows ConvLayer::wino_bn, which wino_pick_bn takes from max_crops)
+    // filters' order inside their entry also follows ConvLayer::wino_bn, which wino_layer_shape takes from max_crops)
     uint8_t* arena = nullptr;
     size_t arena_cap = 0, arena_used = 0;
     std::vector<uint8_t> arena_stage;  // host mirror while pa_create folds (empty in adopt mode and afterwards)
@@ -422,7 +423,8 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
             pe = launch_wino4_conv3x3(q, s);
         } else if (P.form == CONV_WINO) {
             WinoParams q = wino_params(p, ncrops, L.out_hw, L.out_hw, L.cin, L.wino_wgt, L.wino_bn);
-            if (e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
+            q.tg2 = L.wino_shape == WINO_SHAPE_TG2;
+            if (L.wino_shape == WINO_SHAPE_SPLIT && e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
                 q.slab = e->slab + slab_off;
                 q.slab_floats = e->slab_floats > slab_off ? std::min(e->slab_floats - slab_off, e->slab_floats / 2) : 0;
                 q.tickets = reinterpret_cast<int32_t*>(e->wino_tickets) + (slab_off ? WINO_TICKETS : 0);
@@ -870,7 +872,9 @@ int place_conv(pa_engine* e, ConvLayer& L, RowKind kind, BlobReader* br) {
         return rc;
     }
     if (L.wino) {
-        L.wino_bn = wino_pick_bn(co, (long long)e->max_crops * (L.out_hw / 4) * (L.out_hw / 4), cin);
+        const WinoLayerShape ws = wino_layer_shape(e->knobs, L, e->max_crops);
+        L.wino_bn = ws.bn;
+        L.wino_shape = ws.shape;
         if ((rc = arena_place(e, &L.wino_wgt, wino_weight_floats(cin, co), &s))) return rc;
         if (s) wino_transform_weights(w.data(), cin, co, L.wino_bn, s);
         // on a 4 x 4 map once more as the 36 GEMM images of F(4x4, 3x3) taken apart (wino4.hip), beside the F(2x2) image, which serves

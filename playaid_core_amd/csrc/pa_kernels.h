@@ -196,6 +196,7 @@ struct WinoParams {
     int32_t* tickets;
     int32_t tickets_cap, ksplit;
     int32_t tiles_m, xcd_gm, xcd_gn;   // set by the launcher: pixel tiles; the 8 XCDs as a gm x gn grid over (pixel, channel) tiles, 0 = launch order
+    int32_t tg2;   // 0: the workgroup bn implies; 1: four waves as 2 tile groups x 2 channel groups (bn == 64), 8 sub-blocks each, never split
 };
 size_t wino_weight_floats(int cin, int cout);
 // output channels per workgroup = per stage image of the filter layout (64 | 32); cin_split > 0: the caller launches with split-K

@@ -17,6 +17,8 @@
 // whose sides are multiples of four.
 //   workgroup = 8 waves: 4 tile groups (16 sub-blocks = 256 pixels) x 2 channel groups (64 channels), one to a CU
 //            or 4 waves: 4 tile groups x 32 channels, two to a CU: 32-channel layers, and layers too small for the first form
+//            or 4 waves: 2 tile groups (8 sub-blocks) x 2 channel groups (64 channels), one to a CU, a wave per SIMD: the unsplit
+//               shape between the two for a layer whose 16-sub-block tiles fill half the chip (WinoParams::tg2, wino_shape.h)
 //               (8 waves as 8 tile groups x 32 channels: the first shape of the 32-channel layers, kept behind PA_WINO_SMALL32=0)
 //   Where even that leaves CUs without work the launcher splits K (ksplit workgroups per tile, see the epilogue).
 // K loop over chunks of 8 input channels. A stage of the LDS ring holds, for one chunk,
@@ -49,6 +51,7 @@
 // (layers 3-4 at 64-128 crops) the input channels are summed in a different grouping at different batch sizes and an image's
 // values move by fp32 rounding (bounded at 2e-5 by tests/test_wino.py::test_wino_split_k_results_move_by_rounding_only_across_batch_sizes).
 #include "tile_common.h"
+#include "wino_shape.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -216,9 +219,10 @@ __device__ __forceinline__ void wino_chunk(const lds_f* ul, const lds_f* pl, f32
 
 // NST: stages of the LDS ring (3 where they fit: the DMA of chunk c + 2 is issued during chunk c, so the wait in front of a
 // barrier is for copies issued a whole chunk earlier)
-// (four-wave workgroups: two per CU -- without the bound hipcc spreads the kernel over 330 registers and one fits)
+// (four-wave workgroups of 32 channels: two per CU -- without the bound hipcc spreads the kernel over 330 registers and one fits;
+// four waves as 2 tile groups x 2 channel groups hold 84 KB of LDS: one per CU, a wave per SIMD with all its registers)
 template <int TGN, int NCG, int NST, int ABL>
-__global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 ? 2 : 1) void wino3x3_kernel(const WinoParams p) {
+__global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 && NCG == 1 ? 2 : 1) void wino3x3_kernel(const WinoParams p) {
     using G = WinoGeo<TGN, NCG>;
     constexpr int NW = G::NW;
     constexpr int KU = G::U_INSTR / NW;               // filter DMA instructions per wave and chunk
@@ -517,23 +521,9 @@ size_t wino_weight_floats(int cin, int cout) { return (size_t)16 * cin * cout; }
 
 // [cout][ky][kx][cin] (BatchNorm folded) -> the stage images the kernel copies: [cout / BN][cin / 8][16][BN / 16][16][8]
 // with G g G^T evaluated in fp64 and rounded once
-// Output channels per workgroup (= per stage image of the filter layout) for a layer of `cout` channels and `n_sb` 4x4-pixel
-// sub-blocks per launch: 64 (eight waves: 4 tile groups x 2 channel groups) where that fills the chip; 32 -- four waves, two
-// workgroups per CU -- where 64-channel workgroups would leave CUs idle (ResNet-18's layer 3 at 128 crops: 128 workgroups of 64
-// channels take 81 us, 256 of 32 channels 65; the detector's 12 x 20 map at 64 frames has 240 and keeps 64: 83 against 121 us)
-// and for layers of 32 channels. PA_WINO_BN=32|64 forces it (A/B).
-int wino_pick_bn(int cout, long long n_sb, int cin_split) {
-    static const int force = getenv("PA_WINO_BN") ? atoi(getenv("PA_WINO_BN")) : 0;
-    if (cout % 64) return 32;
-    if (force == 32 || force == 64) return force;
-    long long wg64 = ((n_sb + 15) / 16) * (cout / 64);
-    // a caller with split-K scratch (cin_split = the layer's input channels): the launcher multiplies the grid by up to the
-    // largest power of two that leaves eight chunks per split -- 64-channel workgroups x 4 beat 32-channel ones x 4 on
-    // ResNet-18's layers 3 / 4 (52-54 against 55 us, 56 against 61 us at 128 crops)
-    if (cin_split > 0)
-        for (int k2 = 2; k2 <= 8 && (cin_split / 8) % k2 == 0 && (cin_split / 8) / k2 >= 8 && wg64 * 2 <= 256; k2 *= 2) wg64 *= 2;
-    return wg64 < 192 ? 32 : 64;
-}
+// Output channels per workgroup of a layer's filter layout: the rule is host code of its own (wino_shape.h). PA_WINO_BN=32|64
+// forces it (A/B).
+int wino_pick_bn(int cout, long long n_sb, int cin_split) { return wino_pick_bn_rule(cout, n_sb, cin_split, wino_bn_force()); }
 
 void wino_transform_weights(const float* w, int cin, int cout, int bn, float* ug) {
     const int gi_n = bn / 16, n_chunks = cin / 8;
@@ -580,16 +570,22 @@ hipError_t launch_wino3x3(const WinoParams& p_in, hipStream_t s) {
     // (PA_WINO_SMALL32=0: that form, A/B)
     static const int small32 = getenv("PA_WINO_SMALL32") ? atoi(getenv("PA_WINO_SMALL32")) : 1;
     const bool small_wg = bn == 32 && (p.cout % 64 == 0 || small32);
-    const int nsb = bn == 64 ? 16 : (small_wg ? 16 : 32);
+    // tg2: four waves as 2 tile groups x 2 channel groups -- 8 sub-blocks x 64 channels over the full K, the unsplit shape of a
+    // layer whose 16-sub-block tiles leave half the chip empty (ResNet-18's layer 3 at 128 crops: 256 workgroups, one per CU).
+    // It reads the 64-channel filter layout and never splits.
+    if (p.tg2 != 0 && p.tg2 != 1) return hipErrorInvalidValue;
+    const bool tg2 = p.tg2 == 1;
+    if (tg2 && bn != 64) return hipErrorInvalidValue;
+    const int nsb = tg2 ? 8 : (bn == 64 ? 16 : (small_wg ? 16 : 32));
     p.tiles_n = p.cout / bn;
     const int tiles_m = (p.n_sb + nsb - 1) / nsb;
     // split K where the tiles alone leave CUs without a workgroup (ResNet-18's layers 3 and 4 at 128 crops: 256 four-wave / 64
     // eight-wave workgroups): the largest power of two that keeps >= 8 chunks per split and the grid within one workgroup of
     // eight waves (two of four) per CU; needs the caller's scratch (slab, tickets). PA_WINO_KS=1 turns it off, n forces n.
     static const int ks_force = getenv("PA_WINO_KS") ? atoi(getenv("PA_WINO_KS")) : 0;
-    const int n_tiles = tiles_m * p.tiles_n, threads = (bn == 64 || !small_wg) ? 512 : 256;
+    const int n_tiles = tiles_m * p.tiles_n, threads = tg2 ? 256 : ((bn == 64 || !small_wg) ? 512 : 256);
     int ks = 1;
-    if (p.slab && p.tickets && n_tiles <= p.tickets_cap) {
+    if (!tg2 && p.slab && p.tickets && n_tiles <= p.tickets_cap) {
         const int target = threads == 512 ? 256 : 512;
         for (int k2 = 2; k2 <= 8; k2 *= 2)
             if ((p.cin / 8) % k2 == 0 && (p.cin / 8) / k2 >= 8 && n_tiles * k2 <= target && (size_t)n_tiles * k2 * 32 * threads <= p.slab_floats &&
@@ -621,7 +617,8 @@ hipError_t launch_wino3x3(const WinoParams& p_in, hipStream_t s) {
     static const int abl = getenv("PA_WINO_ABL") ? atoi(getenv("PA_WINO_ABL")) : 0;
     static const int nst = getenv("PA_WINO_STAGES") ? atoi(getenv("PA_WINO_STAGES")) : 2;  // 3: a three-stage ring (A/B: 62.3 against 61.5 us on layer 1, 95.2 against 92.1 on the 24 x 40 map -- the prologue then waits behind two chunks of copies)
 #define WN_LAUNCH(ABL_)                                                                                        \
-    if (bn == 64 && nst == 3) hipLaunchKernelGGL((wino3x3_kernel<4, 2, 3, ABL_>), dim3(grid), dim3(512), 0, s, p);    \
+    if (tg2) hipLaunchKernelGGL((wino3x3_kernel<2, 2, 2, ABL_>), dim3(grid), dim3(256), 0, s, p);                     \
+    else if (bn == 64 && nst == 3)hipLaunchKernelGGL((wino3x3_kernel<4, 2, 3, ABL_>), dim3(grid), dim3(512), 0, s, p);    \
     else if (bn == 64) hipLaunchKernelGGL((wino3x3_kernel<4, 2, 2, ABL_>), dim3(grid), dim3(512), 0, s, p);           \
     else if (small_wg) hipLaunchKernelGGL((wino3x3_kernel<4, 1, 2, ABL_>), dim3(grid), dim3(256), 0, s, p);           \
     else hipLaunchKernelGGL((wino3x3_kernel<8, 1, 2, ABL_>), dim3(grid), dim3(512), 0, s, p)
@@ -645,7 +642,7 @@ hipError_t launch_wino3x3(const WinoParams& p_in, hipStream_t s) {
             static int calls = 0;
             static unsigned long long* dev = nullptr;
             const char* sf = getenv("PA_WINO_STAMP_FILE");
-            const int nw = bn == 64 ? 8 : (small_wg ? 4 : 8);
+            const int nw = threads / 64;
             const bool now = sf && calls++ == (getenv("PA_WINO_STAMP_CALL") ? atoi(getenv("PA_WINO_STAMP_CALL")) : 0);
             const size_t words = (size_t)grid * nw * 64;
             if (now) {
@@ -699,9 +696,11 @@ int pa_wino_transform_weights(const float* w_host, int32_t cin, int32_t cout, in
 
 static int wino_conv3x3_impl(const float* x, const float* ug, const float* bias, const float* residual, float* out, int32_t n, int32_t height,
                              int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad,
-                             int32_t act, int32_t res_after, float* slab, size_t slab_floats, int32_t* tickets, int32_t n_tickets, void* stream) {
+                             int32_t act, int32_t res_after, float* slab, size_t slab_floats, int32_t* tickets, int32_t n_tickets, void* stream,
+                             int32_t tg2 = 0) {
     if (!x || !ug || !out || n < 1 || out_pad < 0 || act < 0 || act > 2) return PA_ERR_INVALID_ARG;
     pa::WinoParams p{};
+    p.tg2 = tg2;
     p.slab = slab; p.slab_floats = slab_floats; p.tickets = tickets; p.tickets_cap = n_tickets;
     p.act = x; p.wgt = ug; p.bias = bias; p.residual = residual; p.out = out;
     p.n_img = n; p.height = height; p.width = width; p.cin = cin; p.cout = cout; p.bn = bn;
@@ -731,6 +730,14 @@ int pa_wino_conv3x3_splitk(const float* x, const float* ug, const float* bias, c
     if (!slab || !tickets || n_tickets < 1 || (reinterpret_cast<unsigned long long>(slab) & 15ull)) return PA_ERR_INVALID_ARG;
     return wino_conv3x3_impl(x, ug, bias, residual, out, n, height, width, cin, cout, bn, in_px_stride, out_px_stride, out_pad, act, res_after, slab,
                              slab_floats, tickets, n_tickets, stream);
+}
+
+int pa_wino_conv3x3_shape(const float* x, const float* ug, const float* bias, const float* residual, float* out, int32_t n, int32_t height,
+                          int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad,
+                          int32_t act, int32_t res_after, int32_t shape, void* stream) {
+    if (shape != PA_WINO_WG_BY_BN && shape != PA_WINO_WG_2X2) return PA_ERR_INVALID_ARG;
+    return wino_conv3x3_impl(x, ug, bias, residual, out, n, height, width, cin, cout, bn, in_px_stride, out_px_stride, out_pad, act, res_after, nullptr, 0,
+                             nullptr, 0, stream, shape == PA_WINO_WG_2X2 ? 1 : 0);
 }
 
 }  // extern "C"

@@ -40,6 +40,9 @@ def transform_weights(w_oihw: np.ndarray, bn: int = 0) -> np.ndarray:
     return ug
 
 
+WG_BY_BN, WG_2X2 = 0, 1   # PA_WINO_WG_*: the workgroup shapes of ``pa_wino_conv3x3_shape``
+
+
 class SplitKScratch:
     """Device scratch of ``pa_wino_conv3x3_splitk``: the slab the partial output tiles meet in (16 MB covers every launch) and the
     tickets (zero between launches). Launches that share one belong on one stream."""
@@ -50,10 +53,12 @@ class SplitKScratch:
 
 
 def conv3x3(x_pad: torch.Tensor, ug: torch.Tensor, cin: int, cout: int, bias=None, residual=None, out=None, out_pad: int = 1,
-            act: int = 0, res_after: bool = False, out_px_stride: int = None, bn: int = 0, split_k: SplitKScratch = None) -> torch.Tensor:
+            act: int = 0, res_after: bool = False, out_px_stride: int = None, bn: int = 0, split_k: SplitKScratch = None,
+            shape: int = None) -> torch.Tensor:
     """x_pad float32[n, H + 2, W + 2, C >= cin] (device, zero border) -> out float32[n, H + 2 out_pad, W + 2 out_pad, C'] (interior
     written, border untouched). Enqueues on the current stream. ``split_k``: scratch that lets the launcher split the input
-    channels over several workgroups per tile where the tiles alone would not fill the chip."""
+    channels over several workgroups per tile where the tiles alone would not fill the chip. ``shape`` (``WG_BY_BN`` | ``WG_2X2``):
+    through ``pa_wino_conv3x3_shape``, unsplit, on the workgroup shape named."""
     lib = _lib.load()
     if x_pad.dtype != torch.float32 or not x_pad.is_cuda or not x_pad.is_contiguous() or x_pad.dim() != 4:
         raise ValueError("x_pad: contiguous float32[n, H + 2, W + 2, C] on the device")
@@ -66,7 +71,11 @@ def conv3x3(x_pad: torch.Tensor, ug: torch.Tensor, cin: int, cout: int, bias=Non
     stream = C.c_void_p(torch.cuda.current_stream(x_pad.device).cuda_stream)
     args = (ptr(x_pad), ptr(ug), ptr(bias), ptr(residual), ptr(out), n, h, w, cin, cout, bn or (64 if cout % 64 == 0 else 32), cs, out.shape[3], out_pad,
             int(act), int(bool(res_after)))
-    if split_k is None:
+    if shape is not None:
+        if split_k is not None:
+            raise ValueError("shape and split_k exclude each other")
+        rc = lib.pa_wino_conv3x3_shape(*args, int(shape), stream)
+    elif split_k is None:
         rc = lib.pa_wino_conv3x3(*args, stream)
     else:
         rc = lib.pa_wino_conv3x3_splitk(*args, ptr(split_k.slab), split_k.slab.numel(), ptr(split_k.tickets), split_k.tickets.numel(), stream)
