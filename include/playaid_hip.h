@@ -1430,6 +1430,92 @@ int pa_wino_conv3x3_shape(const float* x, const float* ug, const float* bias, co
                           int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride,
                           int32_t out_px_stride, int32_t out_pad, int32_t act, int32_t res_after, int32_t shape, void* stream);
 
+/* Appended (the version stays 15): the detector's own synthetic training images, composite_chars_onto_stage of
+ * gen_synth_char_detection.py:190-262 -- one to four renders, each resized to a random width, augmented, and pasted over a WHOLE
+ * stage picture -- as two more launches around pa_sprite_augment (csrc/sprite_resize.hip, csrc/scene_composite.hip, DESIGN.md
+ * 5.17): pa_sprite_resize -> pa_sprite_augment -> pa_scene_composite -> pa_jpegenc_encode, and no frame on the host.
+ *
+ * pa_sprite_resize: output i is Image.resize((out_w, out_h)) of the h x w RGBA render params[i].src of a PA_SYNTH_SPRITES bank,
+ * as the installed Pillow does it for mode RGBA with its default filter, BICUBIC:
+ *   (out_w, out_h) == (w, h)   a copy (no premultiplication: the round trip below is not the identity)
+ *   otherwise                  every pixel to premultiplied RGBa (c' = MULDIV255(c, a): t = c * a + 128, ((t >> 8) + t) >> 8; alpha
+ *                              kept); when out_w != w the horizontal 8-bit pass, then when out_h != h the vertical one, each over
+ *                              all four channels (precompute_coeffs + normalize_coeffs_8bpc: support 2 * max(in / out, 1), the
+ *                              weights summed in tap order in double precision, each divided by the sum, scaled by 2^22 and
+ *                              rounded half away from zero; a value is 2^21 + the sum of u8 * coefficient, >> 22, clipped to
+ *                              0..255) -- a pass whose size does not change is skipped, not run with scale 1; back to RGBA (alpha
+ *                              0 or 255: unchanged, else min(255, 255 * c / a), integer division)
+ * Resampling the four channels as plain channels gives other bytes. detect_composite.resize_sprites_reference is the numpy twin.
+ * Limits: any render of the bank (sides up to PA_SYNTH_SPRITE_MAX), out_w 1..PA_SPRITE_RESIZE_W_MAX, out_h
+ * 1..PA_SPRITE_RESIZE_H_MAX (the reference draws widths 50..150 and pa_sprite_augment takes heights up to 3.5 widths). A row of
+ * a pass in -> out has at most min(ceil(2 * max(in / out, 1)) * 2 + 1, in) taps -- 83 for 1024 -> 50, 1024 for 1024 -> 1 -- and
+ * the kernel keeps one pass's table, out rows of that many, in LDS: at most PA_SPRITE_RESIZE_COEFS = 4 * 1024 + 3 * 560
+ * coefficients (ksize <= 4 in / out + 3). PA_KSIZE_MAX = 15 of the crop stage and of pa_sprite_augment's pad step is another
+ * matter and stays.
+ *
+ * pa_sprite_resize_bank_create: a PA_SYNTH_SPRITES bank of n (1..65535) slots of up to max_w x max_h (1..PA_SPRITE_RESIZE_W_MAX,
+ * 1..PA_SPRITE_RESIZE_H_MAX; PA_ERR_INVALID_ARG and a message otherwise), each max_w * max_h * 4 bytes rounded up to 16; slot i's
+ * descriptor is 1 x 1 (a transparent pixel) until a call fills it. Behind the slots: the records' device copy, and the kernel's
+ * scratch (the horizontal pass's output, PA_SYNTH_SPRITE_MAX rows of max_w pixels, for each of min(n, 256) workgroups). With e
+ * NULL the bank holds the sizes alone. pa_synth_bank_destroy frees it; pa_sprite_augment and pa_synth_composite read it like
+ * any other sprite bank. Nothing is allocated per call.
+ * pa_sprite_resize: params on the HOST, n 1..slots of out_bank, sprites a bank with pixels that is not out_bank. The call
+ * writes the descriptors of slots 0..n-1: the host's copy (what pa_sprite_aug_params_check and the launches' argument checks
+ * read) at once, the device's copy by the kernel itself, stream-ordered with the pixels. The records travel through a pinned
+ * staging area of the bank (the call waits for the previous call's copy out of it, not for its kernel). PA_ERR_INVALID_ARG /
+ * PA_ERR_CAPACITY (n beyond the slots) and a message otherwise. Calls on one out_bank must be stream-ordered with each other
+ * and with the launches that read it. Enqueue only.
+ * The kernel is defined for ANY parameter bytes: src is clamped into the bank, out_w to 1..max_w, out_h to 1..max_h of the
+ * output bank, every source coordinate is clamped where the address is formed; the reserved word is not read.
+ * pa_sprite_resize_params_check (host only, no device call) returns PA_ERR_INVALID_ARG for a src outside the bank, a size
+ * below 1 or a non-zero reserved word, PA_ERR_CAPACITY for a size beyond the output bank's slots.
+ * pa_sprite_resize_bank_read: slot `slot` as uint8[h][w][4] of its current host descriptor into out_host (capacity bytes), behind
+ * the work enqueued on `stream`, which the call waits for; for tests. */
+typedef struct pa_sprite_resize_params {
+    int32_t src;                 /* image of the sprite bank */
+    int32_t out_w, out_h;
+    int32_t reserved;            /* zero */
+} pa_sprite_resize_params;
+#define PA_SPRITE_RESIZE_W_MAX 160
+#define PA_SPRITE_RESIZE_H_MAX 560
+#define PA_SPRITE_RESIZE_COEFS 5776
+int pa_sprite_resize_params_check(const pa_sprite_resize_params* host, int32_t n, const pa_synth_bank* sprites, const pa_synth_bank* out_bank);
+int pa_sprite_resize_bank_create(pa_engine* e, int32_t n, int32_t max_w, int32_t max_h, pa_synth_bank** out);
+int pa_sprite_resize(pa_engine* e, const pa_synth_bank* sprites, const pa_sprite_resize_params* params_host, int32_t n,
+                     pa_synth_bank* out_bank, void* stream);
+int pa_sprite_resize_bank_read(pa_engine* e, const pa_synth_bank* bank, int32_t slot, uint8_t* out_host, size_t capacity, void* stream);
+
+/* pa_scene_composite: scene i is the whole picture params[i].stage of a PA_SYNTH_STAGES bank (RGB, W x H) with n_sprites (0..4)
+ * 128 x 128 RGBA slots of a pa_sprite_bank_create bank pasted over it in order, sprite k with its top-left corner at
+ * (sprites[k].x, sprites[k].y) through its own alpha -- Image.paste(char, (x, y), char): per covered pixel and channel c of R, G, B,
+ * t = s_c * a + d_c * (255 - a) + 128; out_c = ((t >> 8) + t) >> 8, where d is the picture with the earlier sprites already
+ * in it -- clipped to the picture; x and y may be negative or beyond it. detect_composite.compose_scenes_reference is the twin.
+ * Output: the scenes as packed uint8[H][W][3] RGB in `images`, scene i at the sum of the earlier scenes' sizes, each rounded up
+ * to 16 bytes, and desc[i] = {offset, H, W}: the pair pa_jpegenc_encode(bgr = 0) takes as it is. Stages of different sizes may
+ * share a call. A scene that does not fit images_capacity (padding included) gets height = width = 0, for which the encoder
+ * writes an empty entry, and none of its bytes is written; so do the scenes behind it.
+ * The kernel is defined for ANY parameter bytes: stage and slot are clamped into their banks, n_sprites to 0..4, x and y to
+ * +-PA_SYNTH_PASTE_MAX, and a sprite's pixel is addressed only where both of its coordinates are 0..127; the reserved words are
+ * not read. pa_scene_params_check (host only) returns PA_ERR_INVALID_ARG for anything of that kind and for a non-zero reserved
+ * word (the entries from n_sprites on must be zero as well).
+ * pa_scene_composite: params and desc on the device (8-byte aligned), images 16-byte aligned, n 1..65535, sprites a bank of
+ * 128 x 128 slots with pixels. PA_ERR_INVALID_ARG and a message otherwise. Two launches (the layout: one small workgroup; the
+ * scenes), enqueue only. */
+#define PA_SCENE_SPRITES_MAX 4
+typedef struct pa_scene_sprite {
+    int32_t slot;                /* slot of the sprite bank */
+    int32_t x, y;                /* where its top-left corner goes in the picture */
+} pa_scene_sprite;
+typedef struct pa_scene_params {
+    int32_t stage;               /* image of the stage bank */
+    int32_t n_sprites;           /* 0..4 */
+    pa_scene_sprite sprites[PA_SCENE_SPRITES_MAX];
+    int32_t reserved[2];         /* zero */
+} pa_scene_params;               /* 64 bytes */
+int pa_scene_params_check(const pa_scene_params* host, int32_t n, const pa_synth_bank* sprites, const pa_synth_bank* stages);
+int pa_scene_composite(pa_engine* e, const pa_synth_bank* sprites, const pa_synth_bank* stages, const pa_scene_params* params_dev,
+                       int32_t n, uint8_t* images_dev, size_t images_capacity, pa_crop_image* desc_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

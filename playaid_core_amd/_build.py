@@ -36,6 +36,8 @@ SOURCES = [
     ("augment.hip", ["-ffp-contract=off"]),
     ("synth_composite.hip", ["-ffp-contract=off"]),
     ("sprite_augment.hip", ["-ffp-contract=off"]),
+    ("sprite_resize.hip", ["-ffp-contract=off"]),
+    ("scene_composite.hip", ["-ffp-contract=off"]),
     ("detect.hip", ["-ffp-contract=off"]),
     ("conv_rows.hip", []),
     ("lstm.hip", []),
@@ -65,7 +67,7 @@ def _newer(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = os.environ.get("HIPCC", "hipcc")
-    headers = [os.path.join(CSRC, "pa_kernels.h"), os.path.join(CSRC, "gemm_tile.h"), os.path.join(CSRC, "engine_plan.h"), os.path.join(CSRC, "engine_table.h"), os.path.join(CSRC, "wino_shape.h"),os.path.join(CSRC, "conv_rows.h"), os.path.join(CSRC, "pgemm_common.h"), os.path.join(CSRC, "tile_common.h"), os.path.join(CSRC, "crop_common.h"), os.path.join(CSRC, "crop_math.h"), os.path.join(CSRC, "synth_math.h"), os.path.join(CSRC, "augment_math.h"), os.path.join(CSRC, "jpeg_dct.h"), os.path.join(CSRC, "jpeg_entropy.h"), os.path.join(CSRC, "train_common.h"), os.path.join(CSRC, "lstm_handle.h"), os.path.join(CSRC, "encoder_handle.h"), os.path.join(HERE, "..", "include", "playaid_hip.h")]
+    headers = [os.path.join(CSRC, "pa_kernels.h"), os.path.join(CSRC, "gemm_tile.h"), os.path.join(CSRC, "engine_plan.h"), os.path.join(CSRC, "engine_table.h"), os.path.join(CSRC, "wino_shape.h"),os.path.join(CSRC, "conv_rows.h"), os.path.join(CSRC, "pgemm_common.h"), os.path.join(CSRC, "tile_common.h"), os.path.join(CSRC, "crop_common.h"), os.path.join(CSRC, "crop_math.h"), os.path.join(CSRC, "synth_math.h"), os.path.join(CSRC, "scene_math.h"), os.path.join(CSRC, "augment_math.h"), os.path.join(CSRC, "jpeg_dct.h"), os.path.join(CSRC, "jpeg_entropy.h"), os.path.join(CSRC, "train_common.h"), os.path.join(CSRC, "lstm_handle.h"), os.path.join(CSRC, "encoder_handle.h"), os.path.join(HERE, "..", "include", "playaid_hip.h")]
     objs = []
     rebuilt = False
     for src, extra in SOURCES:

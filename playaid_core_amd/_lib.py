@@ -174,6 +174,25 @@ PA_SPRITE_H1_MAX = 448
 PA_SPRITE_CANVAS_MAX = 160
 
 
+class pa_sprite_resize_params(C.Structure):
+    _fields_ = [("src", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("reserved", C.c_int32)]
+
+
+PA_SPRITE_RESIZE_W_MAX = 160
+PA_SPRITE_RESIZE_H_MAX = 560
+PA_SPRITE_RESIZE_COEFS = 5776
+PA_SCENE_SPRITES_MAX = 4
+
+
+class pa_scene_sprite(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+class pa_scene_params(C.Structure):
+    _fields_ = [("stage", C.c_int32), ("n_sprites", C.c_int32), ("sprites", pa_scene_sprite * PA_SCENE_SPRITES_MAX),
+                ("reserved", C.c_int32 * 2)]
+
+
 class pa_kernel_stat(C.Structure):
     _fields_ = [
         ("name", C.c_char * 48),
@@ -351,6 +370,12 @@ SYMBOLS = [
     ("pa_sprite_augment", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     ("pa_sprite_bank_read", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("pa_wino_conv3x3_shape", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 12 + [_P]),
+    ("pa_sprite_resize_params_check", C.c_int, [_P, C.c_int32, _P, _P]),
+    ("pa_sprite_resize_bank_create", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    ("pa_sprite_resize", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
+    ("pa_sprite_resize_bank_read", C.c_int, [_P, _P, C.c_int32, _P, C.c_size_t, _P]),
+    ("pa_scene_params_check", C.c_int, [_P, C.c_int32, _P, _P]),
+    ("pa_scene_composite", C.c_int, [_P, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P]),
 ]
 
 _lib = None

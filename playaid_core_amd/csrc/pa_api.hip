@@ -6,6 +6,7 @@
 #include "conv_rows.h"
 #include "engine_table.h"   // the layer table, over engine_plan.h
 #include "synth_math.h"     // SynthDesc, runner_in_plan
+#include "scene_math.h"     // resize_read, scene_read, scene_bytes_padded
 #include "train_common.h"   // adam_scalars, adam_config_ok, TrainerCore
 
 #include <algorithm>
@@ -2174,6 +2175,13 @@ struct pa_synth_bank {
     unsigned char* scratch = nullptr;   // pa_sprite_bank_create: the augmentation kernel's, [scratch_groups][SPRITE_SCRATCH_BYTES]
     int scratch_groups = 0;
     bool slots = false;                 // ... and its images are slots that pa_sprite_augment writes
+    // pa_sprite_resize_bank_create: slots of up to slot_w x slot_h that pa_sprite_resize writes, descriptors included
+    int slot_w = 0, slot_h = 0;
+    size_t slot_bytes = 0;
+    pa_sprite_resize_params* params_dev = nullptr;      // [slots], behind the pixels in `dev`
+    pa_sprite_resize_params* params_pinned = nullptr;   // [slots]: where a call's records wait for their copy
+    hipEvent_t staged = nullptr;                        // ... recorded behind that copy
+    bool staged_pending = false;
 };
 
 int pa_synth_bank_create(pa_engine* e, int32_t kind, const uint8_t* const* images_host, const int32_t* widths, const int32_t* heights,
@@ -2244,6 +2252,11 @@ void pa_synth_bank_destroy(pa_synth_bank* b) {
     if (!b) return;
     if (b->dev) (void)hipFree(b->dev);
     if (b->scratch) (void)hipFree(b->scratch);
+    if (b->staged) {
+        if (b->staged_pending) (void)hipEventSynchronize(b->staged);
+        (void)hipEventDestroy(b->staged);
+    }
+    if (b->params_pinned) (void)hipHostFree(b->params_pinned);
     delete b;
 }
 
@@ -2422,6 +2435,175 @@ int pa_sprite_bank_read(pa_engine* e, const pa_synth_bank* bank, int32_t first, 
     const size_t slot = (size_t)PA_CROP * PA_CROP * 4;
     HIPCHK(e, hipMemcpyAsync(out_host, bank->dev + bank->table_bytes + (size_t)first * slot, (size_t)n * slot, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return PA_OK;
+}
+
+// ---- the detector's synthetic training images (sprite_resize.hip, scene_composite.hip) ------------------------------------------
+
+int pa_sprite_resize_params_check(const pa_sprite_resize_params* host, int32_t n, const pa_synth_bank* sprites, const pa_synth_bank* out_bank) {
+    if (!host || n < 1 || !sprites || !out_bank || sprites->kind != PA_SYNTH_SPRITES || out_bank->slot_w < 1 || sprites == out_bank)
+        return PA_ERR_INVALID_ARG;
+    if (n > (int32_t)out_bank->descs.size()) return PA_ERR_CAPACITY;
+    for (int32_t i = 0; i < n; ++i) {
+        const pa_sprite_resize_params& p = host[i];
+        if (p.src < 0 || p.src >= (int32_t)sprites->descs.size() || p.out_w < 1 || p.out_h < 1 || p.reserved != 0) return PA_ERR_INVALID_ARG;
+        if (p.out_w > out_bank->slot_w || p.out_h > out_bank->slot_h) return PA_ERR_CAPACITY;
+    }
+    return PA_OK;
+}
+
+int pa_sprite_resize_bank_create(pa_engine* e, int32_t n, int32_t max_w, int32_t max_h, pa_synth_bank** out) {
+    if (!out) return PA_ERR_INVALID_ARG;
+    *out = nullptr;
+    pa_synth_bank* b = nullptr;
+    try {
+        if (n < 1 || n > 65535 || max_w < 1 || max_w > PA_SPRITE_RESIZE_W_MAX || max_h < 1 || max_h > PA_SPRITE_RESIZE_H_MAX)
+            return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_resize_bank_create: n is 1..65535, max_w 1.." + std::to_string(PA_SPRITE_RESIZE_W_MAX) +
+                                                   ", max_h 1.." + std::to_string(PA_SPRITE_RESIZE_H_MAX));
+        b = new pa_synth_bank();
+        b->kind = PA_SYNTH_SPRITES;
+        b->slot_w = max_w;
+        b->slot_h = max_h;
+        b->slot_bytes = ((size_t)max_w * max_h * 4 + 15) & ~(size_t)15;
+        b->descs.resize((size_t)n);
+        for (int32_t k = 0; k < n; ++k) {
+            b->descs[(size_t)k].offset = (uint64_t)k * b->slot_bytes;
+            b->descs[(size_t)k].w = b->descs[(size_t)k].h = 1;   // a transparent pixel until a call fills the slot
+        }
+        b->min_w = b->min_h = 1;
+        b->table_bytes = ((size_t)n * sizeof(SynthDesc) + 15) & ~(size_t)15;
+        if (e) {
+            const size_t px_bytes = (size_t)n * b->slot_bytes;
+            const size_t bytes = b->table_bytes + px_bytes + (size_t)n * sizeof(pa_sprite_resize_params);
+            b->scratch_groups = std::min((int)n, RESIZE_WORKGROUPS_MAX);
+            void* p = nullptr;
+            hipError_t err = hipMalloc(&p, bytes);
+            if (err == hipSuccess) {
+                b->dev = static_cast<unsigned char*>(p);
+                b->params_dev = reinterpret_cast<pa_sprite_resize_params*>(b->dev + b->table_bytes + px_bytes);
+                err = hipMemset(p, 0, bytes);
+            }
+            if (err == hipSuccess) err = hipMemcpy(p, b->descs.data(), (size_t)n * sizeof(SynthDesc), hipMemcpyHostToDevice);
+            if (err == hipSuccess) {
+                err = hipMalloc(&p, (size_t)b->scratch_groups * PA_SYNTH_SPRITE_MAX * (size_t)max_w * 4);
+                if (err == hipSuccess) b->scratch = static_cast<unsigned char*>(p);
+            }
+            if (err == hipSuccess) {
+                err = hipHostMalloc(&p, (size_t)n * sizeof(pa_sprite_resize_params), hipHostMallocDefault);
+                if (err == hipSuccess) b->params_pinned = static_cast<pa_sprite_resize_params*>(p);
+            }
+            if (err == hipSuccess) err = hipEventCreateWithFlags(&b->staged, hipEventDisableTiming);
+            if (err != hipSuccess) {
+                pa_synth_bank_destroy(b);
+                b = nullptr;
+                return fail(e, PA_ERR_HIP, std::string("pa_sprite_resize_bank_create: ") + hipGetErrorString(err));
+            }
+        }
+        *out = b;
+        return PA_OK;
+    } catch (const std::exception&) {
+        pa_synth_bank_destroy(b);
+        if (e) e->last_error.clear();
+        return PA_ERR_CAPACITY;
+    }
+}
+
+int pa_sprite_resize(pa_engine* e, const pa_synth_bank* sprites, const pa_sprite_resize_params* params_host, int32_t n, pa_synth_bank* out_bank,
+                     void* stream) {
+    if (!e || !sprites || !params_host || !out_bank || n < 1 || sprites->kind != PA_SYNTH_SPRITES)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_resize: bad argument (params on the host, n at least 1)");
+    if (out_bank->slot_w < 1 || !out_bank->dev || !out_bank->scratch || !out_bank->params_pinned || out_bank == sprites)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_resize: out_bank is a bank of pa_sprite_resize_bank_create, made with an engine, and not the source");
+    if (!sprites->dev) return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_resize: a bank that was made without an engine has no pixels");
+    if (n > (int32_t)out_bank->descs.size())
+        return fail(e, PA_ERR_CAPACITY, "pa_sprite_resize: n is beyond out_bank's " + std::to_string(out_bank->descs.size()) + " slots");
+    hipStream_t s = (hipStream_t)stream;
+    if (out_bank->staged_pending) {   // the previous call's copy out of the staging area (not its kernel)
+        HIPCHK(e, hipEventSynchronize(out_bank->staged));
+        out_bank->staged_pending = false;
+    }
+    std::memcpy(out_bank->params_pinned, params_host, (size_t)n * sizeof(pa_sprite_resize_params));
+    HIPCHK(e, hipMemcpyAsync(out_bank->params_dev, out_bank->params_pinned, (size_t)n * sizeof(pa_sprite_resize_params), hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipEventRecord(out_bank->staged, s));
+    out_bank->staged_pending = true;
+    for (int32_t i = 0; i < n; ++i) {   // the host's copy of what the kernel writes into the device's table
+        const ResizeRead r = resize_read(params_host[i], (int)sprites->descs.size(), out_bank->slot_w, out_bank->slot_h);
+        out_bank->descs[(size_t)i].w = r.ow;
+        out_bank->descs[(size_t)i].h = r.oh;
+    }
+    SpriteResizeArgs a;
+    a.sprite_px = sprites->dev + sprites->table_bytes;
+    a.sprite_desc = reinterpret_cast<const SynthDesc*>(sprites->dev);
+    a.n_sprites = (int)sprites->descs.size();
+    a.params = out_bank->params_dev;
+    a.n = n;
+    a.out_desc = reinterpret_cast<SynthDesc*>(out_bank->dev);
+    a.out_px = out_bank->dev + out_bank->table_bytes;
+    a.slot_bytes = out_bank->slot_bytes;
+    a.max_w = out_bank->slot_w;
+    a.max_h = out_bank->slot_h;
+    a.scratch = out_bank->scratch;
+    a.workgroups = std::min((int)n, out_bank->scratch_groups);
+    ProfScope ps(e, s, "sprite_resize", 0.0, 0.0);
+    HIPCHK(e, launch_sprite_resize(a, s));
+    return PA_OK;
+}
+
+int pa_sprite_resize_bank_read(pa_engine* e, const pa_synth_bank* bank, int32_t slot, uint8_t* out_host, size_t capacity, void* stream) {
+    if (!e || !bank || !out_host || bank->slot_w < 1 || !bank->dev || slot < 0 || slot >= (int32_t)bank->descs.size())
+        return fail(e, PA_ERR_INVALID_ARG, "pa_sprite_resize_bank_read: a bank of pa_sprite_resize_bank_create with pixels, and one of its slots");
+    const SynthDesc& d = bank->descs[(size_t)slot];
+    const size_t bytes = (size_t)d.w * d.h * 4;
+    if (capacity < bytes) return fail(e, PA_ERR_CAPACITY, "pa_sprite_resize_bank_read: the slot holds " + std::to_string(bytes) + " bytes");
+    HIPCHK(e, hipMemcpyAsync(out_host, bank->dev + bank->table_bytes + d.offset, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
+    return PA_OK;
+}
+
+int pa_scene_params_check(const pa_scene_params* host, int32_t n, const pa_synth_bank* sprites, const pa_synth_bank* stages) {
+    if (!host || n < 1 || !sprites || !stages || !sprites->slots || stages->kind != PA_SYNTH_STAGES) return PA_ERR_INVALID_ARG;
+    for (int32_t i = 0; i < n; ++i) {
+        const pa_scene_params& p = host[i];
+        if (p.stage < 0 || p.stage >= (int32_t)stages->descs.size() || p.n_sprites < 0 || p.n_sprites > PA_SCENE_SPRITES_MAX) return PA_ERR_INVALID_ARG;
+        if (p.reserved[0] != 0 || p.reserved[1] != 0) return PA_ERR_INVALID_ARG;
+        for (int k = 0; k < PA_SCENE_SPRITES_MAX; ++k) {
+            const pa_scene_sprite& q = p.sprites[k];
+            if (k >= p.n_sprites) {
+                if (q.slot != 0 || q.x != 0 || q.y != 0) return PA_ERR_INVALID_ARG;
+                continue;
+            }
+            if (q.slot < 0 || q.slot >= (int32_t)sprites->descs.size()) return PA_ERR_INVALID_ARG;
+            if (q.x < -PA_SYNTH_PASTE_MAX || q.x > PA_SYNTH_PASTE_MAX || q.y < -PA_SYNTH_PASTE_MAX || q.y > PA_SYNTH_PASTE_MAX) return PA_ERR_INVALID_ARG;
+        }
+    }
+    return PA_OK;
+}
+
+int pa_scene_composite(pa_engine* e, const pa_synth_bank* sprites, const pa_synth_bank* stages, const pa_scene_params* params_dev, int32_t n,
+                       uint8_t* images_dev, size_t images_capacity, pa_crop_image* desc_dev, void* stream) {
+    if (!e || !sprites || !stages || !params_dev || !images_dev || !desc_dev || n < 1 || n > 65535 || stages->kind != PA_SYNTH_STAGES)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_scene_composite: bad argument (n is 1..65535, stages a PA_SYNTH_STAGES bank)");
+    if (!sprites->slots) return fail(e, PA_ERR_INVALID_ARG, "pa_scene_composite: sprites is a bank of pa_sprite_bank_create (128 x 128 slots)");
+    if (!sprites->dev || !stages->dev) return fail(e, PA_ERR_INVALID_ARG, "pa_scene_composite: a bank that was made without an engine has no pixels");
+    if ((uintptr_t)images_dev & 15 || (uintptr_t)params_dev & 7 || (uintptr_t)desc_dev & 7)
+        return fail(e, PA_ERR_INVALID_ARG, "pa_scene_composite: images must be 16-byte aligned, params and desc 8-byte aligned");
+    uint64_t largest = 0;
+    for (const SynthDesc& d : stages->descs) largest = std::max(largest, scene_bytes_padded(d.w, d.h));
+    SceneArgs a;
+    a.sprite_px = sprites->dev + sprites->table_bytes;
+    a.n_slots = (int)sprites->descs.size();
+    a.stage_px = stages->dev + stages->table_bytes;
+    a.stage_desc = reinterpret_cast<const SynthDesc*>(stages->dev);
+    a.n_stages = (int)stages->descs.size();
+    a.params = params_dev;
+    a.n = n;
+    a.images = images_dev;
+    a.images_capacity = images_capacity;
+    a.desc = desc_dev;
+    const uint64_t per_group = 16u * 256u * 4u;   // scene_composite.hip: SCENE_THREADS x SCENE_PIECES pieces of 16 bytes
+    a.groups_x = (int)((largest + per_group - 1) / per_group);
+    ProfScope ps(e, (hipStream_t)stream, "scene_composite", 0.0, 2.0 * (double)n * (double)largest);
+    HIPCHK(e, launch_scene_composite(a, (hipStream_t)stream));
     return PA_OK;
 }
 

@@ -564,4 +564,38 @@ struct SpriteAugArgs {
 };
 hipError_t launch_sprite_augment(const SpriteAugArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// the detector's synthetic training images (sprite_resize.hip, scene_composite.hip; pa_sprite_resize, pa_scene_composite)
+// ---------------------------------------------------------------------------
+constexpr int RESIZE_WORKGROUPS_MAX = 256;
+struct SpriteResizeArgs {
+    const uint8_t* sprite_px;        // the source bank's first pixel
+    const SynthDesc* sprite_desc;
+    int n_sprites;
+    const pa_sprite_resize_params* params;   // device, [n]
+    int n;
+    SynthDesc* out_desc;             // the output bank's descriptor table: entries 0..n-1 are written
+    uint8_t* out_px;                 // its first pixel: slot i at i * slot_bytes
+    size_t slot_bytes;
+    int max_w, max_h;                // a slot's capacity
+    uint8_t* scratch;                // [workgroups][PA_SYNTH_SPRITE_MAX * max_w] dwords: the horizontal pass's output
+    int workgroups;
+};
+hipError_t launch_sprite_resize(const SpriteResizeArgs& a, hipStream_t s);
+
+struct SceneArgs {
+    const uint8_t* sprite_px;        // a bank of 128 x 128 RGBA slots
+    int n_slots;
+    const uint8_t* stage_px;         // the stage bank's first pixel (RGB images, each 16-byte aligned and padded to 16)
+    const SynthDesc* stage_desc;
+    int n_stages;
+    const pa_scene_params* params;   // device, [n]
+    int n;
+    uint8_t* images;                 // 16-byte aligned
+    size_t images_capacity;
+    pa_crop_image* desc;             // device, [n]: written by the layout launch, read by the scenes'
+    int groups_x;                    // workgroups per scene, sized by the bank's largest stage
+};
+hipError_t launch_scene_composite(const SceneArgs& a, hipStream_t s);
+
 }  // namespace pa
