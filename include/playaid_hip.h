@@ -1430,6 +1430,18 @@ int pa_wino_conv3x3_shape(const float* x, const float* ug, const float* bias, co
                           int32_t height, int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride,
                           int32_t out_px_stride, int32_t out_pad, int32_t act, int32_t res_after, int32_t shape, void* stream);
 
+/* Appended (the version stays 15): pa_wino_conv3x3 with the launch width `wg` (output channels per workgroup: 32 | 64) beside the
+ * filter layout's `bn`, which must be 64. wg == 64 is the launch pa_wino_conv3x3 makes (pa_wino_conv3x3_splitk where `slab` and
+ * `tickets` are given; both null: no scratch). wg == 32 is the one new combination: four-wave workgroups of 16 sub-blocks x 32
+ * channels, two to a CU, each copying its half of the 64-channel filter images -- per lane the same instructions on the same values
+ * as the eight-wave workgroup, so the same bits. It never splits K: PA_ERR_INVALID_ARG where scratch is handed in with it, for
+ * `bn` != 64 (the 32-channel layout has its own launch and nothing to halve), for another `wg`, and for whatever pa_wino_conv3x3 /
+ * _splitk refuse. Enqueue only. */
+int pa_wino_conv3x3_wg(const float* x, const float* ug, const float* bias, const float* residual, float* out, int32_t n, int32_t height,
+                       int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride, int32_t out_px_stride,
+                       int32_t out_pad, int32_t act, int32_t res_after, int32_t wg, float* slab, size_t slab_floats, int32_t* tickets,
+                       int32_t n_tickets, void* stream);
+
 /* Appended (the version stays 15): the detector's own synthetic training images, composite_chars_onto_stage of
  * gen_synth_char_detection.py:190-262 -- one to four renders, each resized to a random width, augmented, and pasted over a WHOLE
  * stage picture -- as two more launches around pa_sprite_augment (csrc/sprite_resize.hip, csrc/scene_composite.hip, DESIGN.md

@@ -370,6 +370,7 @@ SYMBOLS = [
     ("pa_sprite_augment", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     ("pa_sprite_bank_read", C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     ("pa_wino_conv3x3_shape", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 12 + [_P]),
+    ("pa_wino_conv3x3_wg", C.c_int, [_P, _P, _P, _P, _P] + [C.c_int32] * 12 + [_P, C.c_size_t, _P, C.c_int32, _P]),
     ("pa_sprite_resize_params_check", C.c_int, [_P, C.c_int32, _P, _P]),
     ("pa_sprite_resize_bank_create", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
     ("pa_sprite_resize", C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),

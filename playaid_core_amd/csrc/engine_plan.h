@@ -35,6 +35,9 @@ struct EngineKnobs {
     int wino_f4_min = WINO_F4_MIN_CROPS;  // PA_WINO_F4_MIN: ... below this many crops per launch
     int wino_l3_shape = -1; // PA_WINO_L3_SHAPE=0..3: the launches of the Winograd layers on 8 x 8 maps (layer 3) as this WinoShape (wino_shape.h) at
                             // every batch -- 0 split K, 1 unsplit eight waves, 2 unsplit four waves of 32 channels, 3 unsplit 2 x 2 waves; unset: the rule's own
+    int wino_wg = 0;        // PA_WINO_WG=32|64: the launch width (output channels per workgroup) of the Winograd layers that run unsplit on a 64-channel
+                            // filter layout (layers 1 and 2; wino_shape.h); unset: the rule's own
+    int wino_wg_hw = 0;     // PA_WINO_WG_HW: ... forced only on maps of this width (32: layer 1, 16: layer 2); 0: on every open layer
     int bf16_ds_fuse = 1;   // PA_BF16_DS_FUSE: the bf16 openers carry their block's branch; 0: its own GEMM, 2: own GEMM, the opener's tile as if fused
     int f32_ds_fuse = 1;    // PA_F32_DS_FUSE=0: the exact openers do not carry their block's branch
     // -- read at every pa_create / pa_create_from_arena --
@@ -74,6 +77,8 @@ inline EngineKnobs engine_knobs() {
         k.wino_f4 = env_int("PA_WINO_F4", k.wino_f4);
         k.wino_f4_min = env_int("PA_WINO_F4_MIN", k.wino_f4_min);
         k.wino_l3_shape = env_int("PA_WINO_L3_SHAPE", k.wino_l3_shape);
+        k.wino_wg = env_int("PA_WINO_WG", k.wino_wg);
+        k.wino_wg_hw = env_int("PA_WINO_WG_HW", k.wino_wg_hw);
         k.bf16_ds_fuse = env_int("PA_BF16_DS_FUSE", k.bf16_ds_fuse);
         k.f32_ds_fuse = env_int("PA_F32_DS_FUSE", k.f32_ds_fuse);
         return k;
@@ -218,6 +223,12 @@ inline bool wino4_layer(const EngineKnobs& k, ComputeDtype dt, const LayerDesc& 
 // layer's geometry, max_crops and the per-process knobs alone, so that every engine of one shape in a process decides alike
 inline WinoLayerShape wino_layer_shape(const EngineKnobs& k, const LayerDesc& L, int max_crops) {
     return wino_layer_shape(k.wino_l3_shape, L.cin, L.cout, L.out_hw, max_crops, wino_bn_force());
+}
+
+// ... and their width: the output channels per workgroup of its launches at the full batch (ws.bn unless the layer is open for the
+// choice); a launch of fewer crops checks wino_wg_launch_open for itself
+inline int wino_layer_wg(const EngineKnobs& k, const LayerDesc& L, int max_crops) {
+    return wino_layer_wg(k.wino_wg, k.wino_wg_hw, wino_layer_shape(k, L, max_crops), L.cin, L.cout, L.out_hw, max_crops, wino_ks_force());
 }
 
 // Can `opener` compute the branch that `conv2` adds? Same input, same output shape, padding and chunk, tile not pinned;

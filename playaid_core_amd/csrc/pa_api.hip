@@ -34,6 +34,7 @@ struct ConvLayer : LayerDesc {
     float* wino_wgt = nullptr;  // LayerDesc::wino: the filters in wino.hip's layout
     int wino_bn = 0;            // ... laid out for workgroups of this many output channels (wino_layer_shape at the full batch)
     WinoShape wino_shape = WINO_SHAPE_SPLIT;  // ... and how its launches are shaped: with the split-K scratch, or unsplit on one of three workgroups
+    int wino_wg = 0;            // ... and how many output channels a workgroup of them takes: wino_bn, or 32 beside wino_bn == 64 (wino_layer_wg)
     float* wino4_wgt = nullptr; // LayerDesc::wino4: the filters as wino4.hip's 36 GEMM images
     float* bias = nullptr;  // device [cout]
     unsigned short* split_wgt = nullptr;  // LayerDesc::split: three bf16 slices per weight in psgemm.hip's stage-image order
@@ -425,7 +426,10 @@ int run_conv(pa_engine* e, const ConvLayer& L, int crop0, int ncrops, size_t sla
         } else if (P.form == CONV_WINO) {
             WinoParams q = wino_params(p, ncrops, L.out_hw, L.out_hw, L.cin, L.wino_wgt, L.wino_bn);
             q.tg2 = L.wino_shape == WINO_SHAPE_TG2;
-            if (L.wino_shape == WINO_SHAPE_SPLIT && e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
+            // width 32 beside a 64-channel layout where this launch cannot split; a launch of few crops that can keeps its split
+            const bool wg32 = L.wino_bn == 64 && wino_launch_wg(L.wino_wg, L.wino_bn, L.cin, L.cout, L.out_hw, ncrops, wino_ks_force()) == 32;
+            if (wg32) q.wg = 32;
+            if (!wg32 && L.wino_shape == WINO_SHAPE_SPLIT && e->wino_tickets && e->slab) {   // split-K scratch: this half batch's region
                 q.slab = e->slab + slab_off;
                 q.slab_floats = e->slab_floats > slab_off ? std::min(e->slab_floats - slab_off, e->slab_floats / 2) : 0;
                 q.tickets = reinterpret_cast<int32_t*>(e->wino_tickets) + (slab_off ? WINO_TICKETS : 0);
@@ -876,6 +880,7 @@ int place_conv(pa_engine* e, ConvLayer& L, RowKind kind, BlobReader* br) {
         const WinoLayerShape ws = wino_layer_shape(e->knobs, L, e->max_crops);
         L.wino_bn = ws.bn;
         L.wino_shape = ws.shape;
+        L.wino_wg = wino_layer_wg(e->knobs, L, e->max_crops);
         if ((rc = arena_place(e, &L.wino_wgt, wino_weight_floats(cin, co), &s))) return rc;
         if (s) wino_transform_weights(w.data(), cin, co, L.wino_bn, s);
         // on a 4 x 4 map once more as the 36 GEMM images of F(4x4, 3x3) taken apart (wino4.hip), beside the F(2x2) image, which serves

@@ -197,6 +197,8 @@ struct WinoParams {
     int32_t tickets_cap, ksplit;
     int32_t tiles_m, xcd_gm, xcd_gn;   // set by the launcher: pixel tiles; the 8 XCDs as a gm x gn grid over (pixel, channel) tiles, 0 = launch order
     int32_t tg2;   // 0: the workgroup bn implies; 1: four waves as 2 tile groups x 2 channel groups (bn == 64), 8 sub-blocks each, never split
+    int32_t wg;    // output channels per workgroup of THIS launch, beside the layout's bn: 0 = the layout's own; named only with bn == 64: 64 = its own
+                   // again, 32 = four waves of 16 sub-blocks x 32 channels on the 64-channel filter images, two to a CU, never split (no scratch)
 };
 size_t wino_weight_floats(int cin, int cout);
 // output channels per workgroup = per stage image of the filter layout (64 | 32); cin_split > 0: the caller launches with split-K

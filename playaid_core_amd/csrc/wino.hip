@@ -17,6 +17,7 @@
 // whose sides are multiples of four.
 //   workgroup = 8 waves: 4 tile groups (16 sub-blocks = 256 pixels) x 2 channel groups (64 channels), one to a CU
 //            or 4 waves: 4 tile groups x 32 channels, two to a CU: 32-channel layers, and layers too small for the first form
+//               (WIDE: the same workgroup on a filter image laid out for 64 channels, of which it copies its half -- WinoParams::wg)
 //            or 4 waves: 2 tile groups (8 sub-blocks) x 2 channel groups (64 channels), one to a CU, a wave per SIMD: the unsplit
 //               shape between the two for a layer whose 16-sub-block tiles fill half the chip (WinoParams::tg2, wino_shape.h)
 //               (8 waves as 8 tile groups x 32 channels: the first shape of the 32-channel layers, kept behind PA_WINO_SMALL32=0)
@@ -221,9 +222,15 @@ __device__ __forceinline__ void wino_chunk(const lds_f* ul, const lds_f* pl, f32
 // barrier is for copies issued a whole chunk earlier)
 // (four-wave workgroups of 32 channels: two per CU -- without the bound hipcc spreads the kernel over 330 registers and one fits;
 // four waves as 2 tile groups x 2 channel groups hold 84 KB of LDS: one per CU, a wave per SIMD with all its registers)
-template <int TGN, int NCG, int NST, int ABL>
+// WIDE: a 32-channel workgroup on the filter layout of 64-channel ones. A chunk's image is [16 positions][BN / 16][16 ch][8 cin]: in
+// the 64-channel image the 32 channels of a workgroup are one contiguous 1 KB run per position -- exactly one DMA instruction of the
+// 32-channel form -- at a pitch of 2 KB, the upper half 1 KB further on. Only the source offsets of the filter copies and the image a
+// channel tile belongs to differ; the stage in LDS, and with it every operand read and every sum, is the 32-channel form's.
+template <int TGN, int NCG, int NST, int ABL, bool WIDE = false>
 __global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 && NCG == 1 ? 2 : 1) void wino3x3_kernel(const WinoParams p) {
     using G = WinoGeo<TGN, NCG>;
+    static_assert(!WIDE || G::BN == 32, "WIDE: one DMA instruction per position");
+    constexpr int UW = WIDE ? 2 : 1;                  // workgroups that share one filter image
     constexpr int NW = G::NW;
     constexpr int KU = G::U_INSTR / NW;               // filter DMA instructions per wave and chunk
     constexpr int KPI = (G::P_INSTR + NW - 1) / NW;   // patch DMA instructions per wave and chunk
@@ -270,13 +277,13 @@ __global__ __launch_bounds__(64 * TGN * NCG, TGN * NCG == 4 && NCG == 1 ? 2 : 1)
 #define WN_STAMP(K) if ((ABL & 8) && clk && (K) < 63) clk[K] = __builtin_amdgcn_s_memtime()
 
     const i32x4 act_rsrc = wn_rsrc(p.act), wgt_rsrc = wn_rsrc(p.wgt);
-    const int u_soff0 = (tile_n * (p.cin >> 3) + chunk0) * G::U_FLOATS * 4;
+    const int u_soff0 = ((tile_n / UW) * (p.cin >> 3) + chunk0) * (UW * G::U_FLOATS * 4) + (tile_n % UW) * 1024;
     // DMA instruction K (0 .. KD - 1) of chunk C into stage (UL, PL): first the wave's share of the filter image (a straight
     // copy), then of the patch. Patch instructions past the stage's last (P_INSTR is not always a multiple of the wave count)
     // repeat the wave's previous one -- the same bytes to the same place -- so that every wave issues KD per chunk and one
     // counted wait serves all.
     int pvoff[KPI], pdst[KPI];
-#define WN_ISSUE_U(UL, C, K) wn_blds16(wgt_rsrc, (((K) * NW + wave) * 64 + lane) * 16, u_soff0 + (C) * (G::U_FLOATS * 4), (UL) + ((K) * NW + wave) * 256)
+#define WN_ISSUE_U(UL, C, K) wn_blds16(wgt_rsrc, (((K) * NW + wave) * (64 * UW) + lane) * 16, u_soff0 + (C) * (UW * G::U_FLOATS * 4), (UL) + ((K) * NW + wave) * 256)
 #define WN_ISSUE_P(PL, C, J) wn_blds16(act_rsrc, pvoff[J], (C) * 32, (PL) + pdst[J])
 #define WN_ISSUE_ALL(UL, PL, C)                                                                  \
     {                                                                                            \
@@ -576,16 +583,25 @@ hipError_t launch_wino3x3(const WinoParams& p_in, hipStream_t s) {
     if (p.tg2 != 0 && p.tg2 != 1) return hipErrorInvalidValue;
     const bool tg2 = p.tg2 == 1;
     if (tg2 && bn != 64) return hipErrorInvalidValue;
+    // wg: the launch width beside the layout's bn (0: what bn implies). 32 on a 64-channel layout is the one combination that is
+    // not the layout's own: the four-wave workgroup of 16 sub-blocks x 32 channels, two to a CU, copying its half of each filter
+    // image (WIDE) -- twice the workgroups of the eight-wave form at half its LDS, so that another stream's kernels fit beside it.
+    // It never splits K: a caller with scratch has to decide first. A width is named only beside a 64-channel layout (64: that
+    // layout's own launch); every other layout is launched with wg = 0.
+    if (p.wg != 0 && p.wg != 32 && p.wg != 64) return hipErrorInvalidValue;
+    if (p.wg != 0 && bn != 64) return hipErrorInvalidValue;
+    const bool wide = p.wg == 32;
+    if (wide && (tg2 || p.slab || p.tickets)) return hipErrorInvalidValue;
     const int nsb = tg2 ? 8 : (bn == 64 ? 16 : (small_wg ? 16 : 32));
-    p.tiles_n = p.cout / bn;
+    p.tiles_n = p.cout / (wide ? 32 : bn);
     const int tiles_m = (p.n_sb + nsb - 1) / nsb;
     // split K where the tiles alone leave CUs without a workgroup (ResNet-18's layers 3 and 4 at 128 crops: 256 four-wave / 64
     // eight-wave workgroups): the largest power of two that keeps >= 8 chunks per split and the grid within one workgroup of
     // eight waves (two of four) per CU; needs the caller's scratch (slab, tickets). PA_WINO_KS=1 turns it off, n forces n.
-    static const int ks_force = getenv("PA_WINO_KS") ? atoi(getenv("PA_WINO_KS")) : 0;
-    const int n_tiles = tiles_m * p.tiles_n, threads = tg2 ? 256 : ((bn == 64 || !small_wg) ? 512 : 256);
+    const int ks_force = wino_ks_force();
+    const int n_tiles = tiles_m * p.tiles_n, threads = tg2 || wide ? 256 : ((bn == 64 || !small_wg) ? 512 : 256);
     int ks = 1;
-    if (!tg2 && p.slab && p.tickets && n_tiles <= p.tickets_cap) {
+    if (!tg2 && !wide && p.slab && p.tickets && n_tiles <= p.tickets_cap) {
         const int target = threads == 512 ? 256 : 512;
         for (int k2 = 2; k2 <= 8; k2 *= 2)
             if ((p.cin / 8) % k2 == 0 && (p.cin / 8) / k2 >= 8 && n_tiles * k2 <= target && (size_t)n_tiles * k2 * 32 * threads <= p.slab_floats &&
@@ -618,6 +634,7 @@ hipError_t launch_wino3x3(const WinoParams& p_in, hipStream_t s) {
     static const int nst = getenv("PA_WINO_STAGES") ? atoi(getenv("PA_WINO_STAGES")) : 2;  // 3: a three-stage ring (A/B: 62.3 against 61.5 us on layer 1, 95.2 against 92.1 on the 24 x 40 map -- the prologue then waits behind two chunks of copies)
 #define WN_LAUNCH(ABL_)                                                                                        \
     if (tg2) hipLaunchKernelGGL((wino3x3_kernel<2, 2, 2, ABL_>), dim3(grid), dim3(256), 0, s, p);                     \
+    else if (wide) hipLaunchKernelGGL((wino3x3_kernel<4, 1, 2, ABL_, true>), dim3(grid), dim3(256), 0, s, p);         \
     else if (bn == 64 && nst == 3)hipLaunchKernelGGL((wino3x3_kernel<4, 2, 3, ABL_>), dim3(grid), dim3(512), 0, s, p);    \
     else if (bn == 64) hipLaunchKernelGGL((wino3x3_kernel<4, 2, 2, ABL_>), dim3(grid), dim3(512), 0, s, p);           \
     else if (small_wg) hipLaunchKernelGGL((wino3x3_kernel<4, 1, 2, ABL_>), dim3(grid), dim3(256), 0, s, p);           \
@@ -697,10 +714,11 @@ int pa_wino_transform_weights(const float* w_host, int32_t cin, int32_t cout, in
 static int wino_conv3x3_impl(const float* x, const float* ug, const float* bias, const float* residual, float* out, int32_t n, int32_t height,
                              int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad,
                              int32_t act, int32_t res_after, float* slab, size_t slab_floats, int32_t* tickets, int32_t n_tickets, void* stream,
-                             int32_t tg2 = 0) {
+                             int32_t tg2 = 0, int32_t wg = 0) {
     if (!x || !ug || !out || n < 1 || out_pad < 0 || act < 0 || act > 2) return PA_ERR_INVALID_ARG;
     pa::WinoParams p{};
     p.tg2 = tg2;
+    p.wg = wg;
     p.slab = slab; p.slab_floats = slab_floats; p.tickets = tickets; p.tickets_cap = n_tickets;
     p.act = x; p.wgt = ug; p.bias = bias; p.residual = residual; p.out = out;
     p.n_img = n; p.height = height; p.width = width; p.cin = cin; p.cout = cout; p.bn = bn;
@@ -738,6 +756,15 @@ int pa_wino_conv3x3_shape(const float* x, const float* ug, const float* bias, co
     if (shape != PA_WINO_WG_BY_BN && shape != PA_WINO_WG_2X2) return PA_ERR_INVALID_ARG;
     return wino_conv3x3_impl(x, ug, bias, residual, out, n, height, width, cin, cout, bn, in_px_stride, out_px_stride, out_pad, act, res_after, nullptr, 0,
                              nullptr, 0, stream, shape == PA_WINO_WG_2X2 ? 1 : 0);
+}
+
+int pa_wino_conv3x3_wg(const float* x, const float* ug, const float* bias, const float* residual, float* out, int32_t n, int32_t height,
+                       int32_t width, int32_t cin, int32_t cout, int32_t bn, int32_t in_px_stride, int32_t out_px_stride, int32_t out_pad, int32_t act,
+                       int32_t res_after, int32_t wg, float* slab, size_t slab_floats, int32_t* tickets, int32_t n_tickets, void* stream) {
+    if (wg != 32 && wg != 64) return PA_ERR_INVALID_ARG;
+    if ((slab || tickets) && (!slab || !tickets || n_tickets < 1 || (reinterpret_cast<unsigned long long>(slab) & 15ull))) return PA_ERR_INVALID_ARG;
+    return wino_conv3x3_impl(x, ug, bias, residual, out, n, height, width, cin, cout, bn, in_px_stride, out_px_stride, out_pad, act, res_after, slab,
+                             slab_floats, tickets, n_tickets, stream, 0, wg);
 }
 
 }  // extern "C"

@@ -96,4 +96,62 @@ inline WinoLayerShape wino_layer_shape(int knob, int cin, int cout, int out_hw, 
     }
 }
 
+// ---- the launch width of the many-tile layers -----------------------------------------------------------------------------------
+// A layer on the 64-channel filter layout that runs unsplit (tiles enough) has two workgroups to choose from: eight waves over 16
+// sub-blocks x 64 channels (104 KB of LDS: one to a CU, nothing of another stream beside it), or four waves over 16 sub-blocks x 32
+// channels, two to a CU at 72 KB each, reading the same layout (wino.hip's WIDE kernel). Per lane both execute the same instructions
+// on the same values: the choice never changes a bit of the result, only who else fits on the CU meanwhile.
+
+// PA_WINO_KS as the launcher reads it (0: unset; 1: it never splits K). Read once per process.
+inline int wino_ks_force() {
+    static const int force = getenv("PA_WINO_KS") ? atoi(getenv("PA_WINO_KS")) : 0;
+    return force;
+}
+
+// Can a launch over n_sb sub-blocks run on width 32 beside a 64-channel layout? Only where the launcher, handed the split-K scratch,
+// would not split (the width takes no scratch, and a split sum is another fp32 sum): the layer's 64-channel tiles times every
+// split its K allows exceed the chip, or PA_WINO_KS=1.
+inline bool wino_wg_launch_open(int cin, int cout, long long n_sb, int ks_force) {
+    if (cout % 64) return false;
+    return ks_force == 1 || wino_split64(wino_shape_workgroups(WINO_SHAPE_UNSPLIT8, n_sb, cout), cin) == 1;
+}
+
+// Which layers the width is open for: stride-1 3x3 layers under WINO_SHAPE_SPLIT (the launcher's own rule) on a 64-channel layout
+// that run unsplit at the engine's full batch, on maps of at least 16 x 16 -- ResNet-18's layers 1 and 2. The 8 x 8 maps have
+// PA_WINO_L3_SHAPE; the 4 x 4 maps split, or run as F(4x4) taken apart.
+inline bool wino_wg_open(WinoLayerShape ws, int cin, int cout, int out_hw, long long n_sb, int ks_force) {
+    return ws.shape == WINO_SHAPE_SPLIT && ws.bn == 64 && out_hw >= 16 && wino_wg_launch_open(cin, cout, n_sb, ks_force);
+}
+
+// Unset knob: width 32 exactly where it was measured to win on two lanes by the project's bar (profiles/wino_wg_width_parent_ab.md),
+// 64 elsewhere:
+//   * engines of 96 to 128 crops, where layers 1 and 2 are both open: measured at both ends, +1.9 % at 96 crops and +1.4 % at 128
+//     (layer 2 alone +1.3 % at 128; layer 1 alone stayed under the bar at both, +0.7 % and +1.1 %, and is taken with layer 2, the
+//     pair being the best median of the three);
+//   * a layer whose eight-wave workgroups are exactly one per CU (WINO_WG_ONE_PER_CU of them): layer 1 at 64 crops, +2.6 %.
+// Layer 1 at 80 crops measured +0.7 %, under the bar, and keeps 64; engines above 128 crops were not measured and keep 64.
+constexpr long long WINO_WG_ONE_PER_CU = 256;
+constexpr int WINO_WG_CROPS_LO = 96, WINO_WG_CROPS_HI = 128;
+inline int wino_wg_default(int cout, int out_hw, long long n_sb) {
+    const long long crops = n_sb / ((out_hw / 4) * (out_hw / 4));
+    if (wino_shape_workgroups(WINO_SHAPE_UNSPLIT8, n_sb, cout) == WINO_WG_ONE_PER_CU) return 32;
+    return crops >= WINO_WG_CROPS_LO && crops <= WINO_WG_CROPS_HI ? 32 : 64;
+}
+
+// knobs: PA_WINO_WG (32 | 64 = that width for every open layer at every max_crops; anything else = unset) and PA_WINO_WG_HW (a map
+// width: the knob forces only the open layers on maps of that width -- 32 = layer 1, 16 = layer 2 -- the others keep the rule; 0 = all)
+inline int wino_layer_wg(int knob, int knob_hw, WinoLayerShape ws, int cin, int cout, int out_hw, int max_crops, int ks_force) {
+    const long long n_sb = (long long)max_crops * (out_hw / 4) * (out_hw / 4);
+    if (!wino_wg_open(ws, cin, cout, out_hw, n_sb, ks_force)) return ws.bn;
+    if ((knob == 32 || knob == 64) && (knob_hw == 0 || knob_hw == out_hw)) return knob;
+    return wino_wg_default(cout, out_hw, n_sb);
+}
+
+// The width of ONE launch of `ncrops` crops of a layer whose width at the full batch is layer_wg on a layout of bn channels: a launch
+// of few crops that the launcher could split keeps the eight-wave workgroups and its split, as before the width existed
+inline int wino_launch_wg(int layer_wg, int bn, int cin, int cout, int out_hw, int ncrops, int ks_force) {
+    const long long n_sb = (long long)ncrops * (out_hw / 4) * (out_hw / 4);
+    return layer_wg == 32 && bn == 64 && wino_wg_launch_open(cin, cout, n_sb, ks_force) ? 32 : bn;
+}
+
 }  // namespace pa

@@ -54,11 +54,13 @@ class SplitKScratch:
 
 def conv3x3(x_pad: torch.Tensor, ug: torch.Tensor, cin: int, cout: int, bias=None, residual=None, out=None, out_pad: int = 1,
             act: int = 0, res_after: bool = False, out_px_stride: int = None, bn: int = 0, split_k: SplitKScratch = None,
-            shape: int = None) -> torch.Tensor:
+            shape: int = None, wg: int = None) -> torch.Tensor:
     """x_pad float32[n, H + 2, W + 2, C >= cin] (device, zero border) -> out float32[n, H + 2 out_pad, W + 2 out_pad, C'] (interior
     written, border untouched). Enqueues on the current stream. ``split_k``: scratch that lets the launcher split the input
     channels over several workgroups per tile where the tiles alone would not fill the chip. ``shape`` (``WG_BY_BN`` | ``WG_2X2``):
-    through ``pa_wino_conv3x3_shape``, unsplit, on the workgroup shape named."""
+    through ``pa_wino_conv3x3_shape``, unsplit, on the workgroup shape named. ``wg`` (32 | 64): through ``pa_wino_conv3x3_wg``, the
+    output channels per workgroup of this launch beside a 64-channel filter layout (``bn=64``) -- 32 runs four-wave workgroups on
+    the layout as it is, bit for bit the eight-wave result, and takes no ``split_k``."""
     lib = _lib.load()
     if x_pad.dtype != torch.float32 or not x_pad.is_cuda or not x_pad.is_contiguous() or x_pad.dim() != 4:
         raise ValueError("x_pad: contiguous float32[n, H + 2, W + 2, C] on the device")
@@ -71,7 +73,12 @@ def conv3x3(x_pad: torch.Tensor, ug: torch.Tensor, cin: int, cout: int, bias=Non
     stream = C.c_void_p(torch.cuda.current_stream(x_pad.device).cuda_stream)
     args = (ptr(x_pad), ptr(ug), ptr(bias), ptr(residual), ptr(out), n, h, w, cin, cout, bn or (64 if cout % 64 == 0 else 32), cs, out.shape[3], out_pad,
             int(act), int(bool(res_after)))
-    if shape is not None:
+    if wg is not None:
+        if shape is not None:
+            raise ValueError("shape and wg exclude each other")
+        sk = (ptr(split_k.slab), split_k.slab.numel(), ptr(split_k.tickets), split_k.tickets.numel()) if split_k is not None else (C.c_void_p(0), 0, C.c_void_p(0), 0)
+        rc = lib.pa_wino_conv3x3_wg(*args, int(wg), *sk, stream)
+    elif shape is not None:
         if split_k is not None:
             raise ValueError("shape and split_k exclude each other")
         rc = lib.pa_wino_conv3x3_shape(*args, int(shape), stream)
